@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- headline benchmark of the MI355X LZ4 block engine.
 
-    python bench.py --gpus N --steps K --warmup W [--workload decompress|compress|roundtrip|random256k|text]
+    python bench.py --gpus N --steps K --warmup W [--workload decompress|compress|roundtrip|random256k|text] [--dump-outputs DIR]
 
 One "step" = one pass of the hot path over one batch of input resident in HBM.  Default workload (N=1)
 is BASELINE.json configs[1]: decompress-only, 64 KiB blocks, 4 GiB lzsynth(16, 2048) stream of
@@ -25,6 +25,12 @@ compute+gather rates, the gather's own rate against the root's xGMI links and `r
 BASELINE config 4 (64 GiB over 8 GPUs) is 8 GiB per GPU: `--workload roundtrip --blocks 131072` runs that share
 (131 072 blocks of 64 KiB compressed, compacted and decoded in one call each); rehearsed at N = 1
 (profiles/r05_bench_roundtrip_8GiB.json).  At N = 8 the root's verification decodes 8 x that in one call.
+
+`--dump-outputs DIR` writes what the last timed step handed its caller -- decoded bytes and per-block results, and/or
+the compacted stream with its offsets and per-block lengths -- to DIR/<name>.npy (N > 1: DIR/<name>_rank<r>.npy), as
+float32 (bytes) or float64 (integers), before anything else runs on those buffers.  At most DUMP_LIMIT bytes in all:
+an array over its share is a sample at indices drawn from DUMP_SEED, the same for the same arguments.  The inputs are
+the generator's seeded blocks, so two builds run with the same arguments can be compared array for array.
 """
 import argparse
 import json
@@ -39,6 +45,8 @@ sys.path.insert(0, os.path.join(ROOT, "streamly-lz4_amd"))
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 
 HBM_PEAK_GBPS = 8000.0   # MI355X_MICROARCH.md: HBM3E 8 TB/s spec (6.29 TB/s measured copy)
+DUMP_LIMIT = 64 * 10 ** 6   # --dump-outputs: bytes in all (over all ranks)
+DUMP_SEED = 20261015
 
 WORKLOADS = {
     # name: (kind, block_len, n_blocks_per_gpu, accel, timed phase)
@@ -48,6 +56,29 @@ WORKLOADS = {
     "random256k": ("random", 262144, 16384, 400, "roundtrip"),  # configs[4] per-GPU share
     "text": ("text", 65536, 65536, 1, "decompress"),
 }
+
+
+def dump_outputs(out_dir, arrays, rank, world):
+    """--dump-outputs: arrays = [(name, device tensor, numpy dtype)].  Small arrays go out whole; the rest share what is
+    left of this rank's part of DUMP_LIMIT, each as a sorted sample of distinct indices drawn from DUMP_SEED."""
+    import numpy as np
+    import torch
+    os.makedirs(out_dir, exist_ok=True)
+    suffix = "_rank%d" % rank if world > 1 else ""
+    left = DUMP_LIMIT // world
+    todo = sorted(arrays, key=lambda a: a[1].numel() * np.dtype(a[2]).itemsize)
+    for i, (name, t, dt) in enumerate(todo):
+        item = np.dtype(dt).itemsize
+        share = left // (len(todo) - i) - 1024                      # (room for the .npy header)
+        n = t.numel()
+        if n * item <= share:
+            a = t.cpu().numpy().astype(dt)
+        else:
+            idx = np.sort(np.random.default_rng(DUMP_SEED).choice(n, size=share // item, replace=False))
+            a = t[torch.from_numpy(idx).to(t.device)].cpu().numpy().astype(dt)
+        path = os.path.join(out_dir, name + suffix + ".npy")
+        np.save(path, a)
+        left -= os.path.getsize(path)
 
 
 def canterbury_large(n_bytes):
@@ -341,9 +372,12 @@ def one_stream_bench(args, torch, S, dist, eng, dev, rank, world, red_dev, kind,
     barrier()
     t0 = time.perf_counter()
     for _ in range(args.steps):
-        step()
+        out, res = step()
     barrier()
     elapsed = time.perf_counter() - t0
+    if args.dump_outputs:
+        import numpy as np
+        dump_outputs(args.dump_outputs, [("decompressed", out, np.float32), ("block_results", res, np.float64)], rank, world)
     cb = torch.tensor([float(total - first)], dtype=torch.float64, device=red_dev)
     if dist is not None:
         tt = torch.tensor([elapsed], dtype=torch.float64, device=red_dev)
@@ -415,7 +449,11 @@ def main():
     ap.add_argument("--no-gather", action="store_true", help="N>1: skip the RCCL ordered gather + its verification")
     ap.add_argument("--no-extra", action="store_true", help="skip the round-trip / compress figures measured after the timed steps")
     ap.add_argument("--no-host-api", action="store_true", help="skip the PCIe-inclusive host-buffer API figures (N=1)")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="after the timed steps, write what the last one computed to DIR/<name>.npy (see the module docstring)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # `python bench.py --gpus N` on its own: start the N ranks as a CHILD process (torch.distributed.run, one rank per
@@ -546,6 +584,16 @@ def main():
     ms_per_step = elapsed * 1e3 / max(args.steps, 1)
     value = world * U / (elapsed / max(args.steps, 1)) / 1e9
     timed_ms = {k: (sum(v) / len(v) if v else None) for k, v in kern_ms.items()}
+    if args.dump_outputs:
+        # before the figures below: they run the same buffers again
+        import numpy as np
+        arrays = []
+        if phase in ("compress", "roundtrip"):
+            arrays += [("compressed", dense[:int(doff[-1].item())], np.float32), ("compressed_offsets", doff, np.float64),
+                       ("compressed_lengths", flen, np.float64)]
+        if phase in ("decompress", "roundtrip"):
+            arrays += [("decompressed", out, np.float32), ("block_results", res, np.float64)]
+        dump_outputs(args.dump_outputs, arrays, rank, world)
 
     # ---- after the timed steps: the other half of the metric's name (same data, same build) ----
     extra = None

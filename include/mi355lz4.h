@@ -84,9 +84,8 @@ int mi355lz4_device_count(void);
  * use, plus a small pool of host threads for staging pageable memory (MI355LZ4_COPY_THREADS, default 8); for the
  * duration of such a call the engine's stream is one of its own.
  *
- * Process environment: when this is the first HIP call of the process and GPU_MAX_HW_QUEUES is not set, the first
- * mi355lz4_create sets it to 8 (the pipelines above need more than HIP's default of four hardware queues to overlap);
- * MI355LZ4_KEEP_HW_QUEUES=1 turns that off.  Nothing is changed at load time. */
+ * Process environment: the library sets no environment variable; the HIP runtime's settings (GPU_MAX_HW_QUEUES
+ * among them) are the process's. */
 int mi355lz4_create(mi355lz4_ctx **out, int device);
 void mi355lz4_destroy(mi355lz4_ctx *ctx);
 /* Launch on a caller-owned hipStream_t instead (e.g. torch's current stream). */

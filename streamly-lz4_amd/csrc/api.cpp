@@ -297,17 +297,6 @@ extern "C" int mi355lz4_create(mi355lz4_ctx **out, int device)
 {
     if (!out) return fail(MI355LZ4_E_ARG, "mi355lz4_create: null out");
     *out = nullptr;
-    // The host-buffer pipelines use five streams; HIP's default of four hardware queues makes two of them share one.
-    // The variable is read when the HIP runtime initialises, so this only matters when this call is the process's
-    // first HIP call; it never overrides a value the process has set, and MI355LZ4_KEEP_HW_QUEUES=1 leaves the
-    // environment alone altogether (a process that manages its own HIP settings).  Not done at load time any more.
-    {
-        static std::once_flag once;
-        std::call_once(once, [] {
-            const char *keep = getenv("MI355LZ4_KEEP_HW_QUEUES");
-            if (!(keep && atoi(keep)) && !getenv("GPU_MAX_HW_QUEUES")) setenv("GPU_MAX_HW_QUEUES", "8", 0);
-        });
-    }
     int n = 0;
     if (hipGetDeviceCount(&n) != hipSuccess || n <= 0)
         return fail(MI355LZ4_E_NO_DEVICE, "mi355lz4: no HIP device visible (this engine has no CPU path)");
@@ -1199,8 +1188,7 @@ extern "C" int mi355lz4_event_elapsed_ms(void *start, void *stop, float *ms)
 // ---------------------------------------------------------------------------
 // The pipelined calls keep the caller's stream, two copy streams and two compute streams busy; HIP multiplexes
 // streams onto GPU_MAX_HW_QUEUES hardware queues (default 4), and streams that share a queue serialize
-// (measured: compress 33 -> 41 GB/s with 8).  mi355lz4_create asks for 8 when it is the first HIP user of the
-// process and nobody has set the variable (see there); nothing is touched at load time.
+// (measured: compress 33 -> 41 GB/s with 8).  The variable is the process's: the library does not set it.
 
 static bool pipe_trace()
 {

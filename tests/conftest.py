@@ -71,6 +71,28 @@ def linked_golden():
 
 
 @pytest.fixture(scope="session")
+def reference_vectors():
+    """The reference's results on tests/reference_cases.py's inputs (tests/golden/make_golden.py)."""
+    import json
+    with open(os.path.join(ROOT, "tests", "golden", "reference_vectors.json")) as f:
+        return json.load(f)
+
+
+@pytest.fixture(scope="session")
+def record():
+    """record(name, rec): one JSON line of a GPU test's measurements, appended to measurements/<name>.jsonl in the
+    repository (git ignores the directory)."""
+    import json
+
+    def add(name, rec):
+        d = os.path.join(ROOT, "measurements")
+        os.makedirs(d, exist_ok=True)
+        with open(os.path.join(d, name + ".jsonl"), "a") as f:
+            f.write(json.dumps(rec) + "\n")
+    return add
+
+
+@pytest.fixture(scope="session")
 def slz4():
     """The product binding.  Import fails loudly when libmi355lz4.so is missing."""
     import streamly_lz4_amd

@@ -15,7 +15,9 @@ import sys
 HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(os.path.dirname(HERE))
 sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, "tests"))
 
+import reference_cases as RC  # noqa: E402
 from oracle.oracle import Oracle, Reference  # noqa: E402
 
 O, R = Oracle(), Reference()
@@ -109,6 +111,23 @@ def main():
         json.dump(linked, f, indent=1)
     print("wrote golden.json (%d kat, %d sizes, %d malformed, %d streams) and linked_stream.json (%d bytes framed)"
           % (len(kat), len(sizes), len(mal), len(streams), len(fr)))
+
+    # (5) the reference's results on tests/reference_cases.py's inputs, for the oracle to be compared with where the
+    # reference is not built
+    vec = {"lz4_version": R.version()}
+    vec["compress"] = {key: sha(R.frame_compress(data, bl, accel, hdr, linked))
+                       for key, data, bl, accel, hdr, linked in RC.compress_cases(O)}
+    vec["decode_fuzz"] = [RC.results_record([R.decompress_block(p, cap, d) for p, cap, d in probes])
+                          for _, probes in RC.decode_fuzz_cases(O)]
+    vec["huge_length"] = {name: RC.results_record([R.decompress_block(p, cap, d) for p, cap, d in probes])
+                          for name, probes in RC.huge_length_cases()}
+    data, _ = RC.renorm_input(O)
+    fr = R.frame_compress(data, RC.RENORM_BL, 1, 8, True)
+    vec["renorm"] = {"framed_len": len(fr), "framed_sha256": sha(fr)}
+    with open(os.path.join(HERE, "reference_vectors.json"), "w") as f:
+        json.dump(vec, f, indent=1)
+    print("wrote reference_vectors.json (%d compress, %d decode fuzz, %d huge length cases, renorm)"
+          % (len(vec["compress"]), len(vec["decode_fuzz"]), len(vec["huge_length"])))
 
 
 if __name__ == "__main__":

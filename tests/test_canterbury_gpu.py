@@ -6,7 +6,6 @@ the reference's benchmark does (benchmark/Main.hs:80-84), to CANTERBURY_TEST_BYT
   * emitted size against the reference's _continue path at the same acceleration is asserted and printed,
     for independent blocks and for linked compression (previous block = dictionary).
 Skipped with an explicit message when the corpus is absent: nothing is substituted."""
-import json
 import os
 
 import numpy as np
@@ -15,12 +14,11 @@ import pytest
 import corpus
 
 pytestmark = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 BL = 65536
 
 
 @pytest.mark.parametrize("rel", corpus.FILES)
-def test_canterbury_roundtrip(engine, slz4, oracle, rel):
+def test_canterbury_roundtrip(engine, slz4, oracle, rel, record):
     path = corpus.find(rel)
     if path is None:
         pytest.skip("Canterbury file %s not found under %s (no network here; set CANTERBURY_DIR)" % (rel, corpus.corpus_dir()))
@@ -79,9 +77,7 @@ def test_canterbury_roundtrip(engine, slz4, oracle, rel):
            "gpu_ratio": round(total / ours, 4), "reference_ratio": round(total / len(ref_stream), 4),
            "size_vs_reference": round(ours / len(ref_stream), 4),
            "linked_size_vs_reference": round(ours_linked / len(ref_stream), 4)}
-    os.makedirs(os.path.join(ROOT, "gpurun_out"), exist_ok=True)
-    with open(os.path.join(ROOT, "gpurun_out", "canterbury.jsonl"), "a") as f:
-        f.write(json.dumps(rec) + "\n")
+    record("canterbury", rec)
     print(rec)
     # independent blocks give up the previous block as dictionary (6-7 % on text-like input; measured on
     # the stand-ins of the image, scripts/realtext_ratio.py and round 2: 6.0-9.5 %)

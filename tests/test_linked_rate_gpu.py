@@ -1,10 +1,7 @@
 """Linked-stream decode at a size where the rate means something: streams written by the
 reference's own linked compressor (oracle on the host), decoded by the GPU in one call, checked
-bit-exact, and the rate written to gpurun_out/linked_rate.json.  The oracle is only the data source
+bit-exact, and the rate recorded in measurements/linked_rate.jsonl.  The oracle is only the data source
 and the checker here; the timed region is the GPU call."""
-import json
-import os
-
 import numpy as np
 import pytest
 
@@ -12,11 +9,9 @@ from test_parity_gpu import _stream_layout
 
 pytestmark = pytest.mark.gpu
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-
 
 @pytest.mark.parametrize("n_streams,blocks_per_stream", [(2048, 2), (512, 8), (8, 64)])
-def test_linked_stream_rate(engine, slz4, oracle, n_streams, blocks_per_stream):
+def test_linked_stream_rate(engine, slz4, oracle, n_streams, blocks_per_stream, record):
     import torch
     dev = torch.device("cuda:0")
     bl = 65536
@@ -54,13 +49,11 @@ def test_linked_stream_rate(engine, slz4, oracle, n_streams, blocks_per_stream):
     rate = nb * bl / best / 1e6
     rec = {"streams": n_streams, "blocks_per_stream": blocks_per_stream, "block_len": bl, "data": "text, reference-linked",
            "dependent_blocks": dependent, "blocks": nb, "ms": round(best, 3), "GBps_uncompressed": round(rate, 2)}
-    os.makedirs(os.path.join(ROOT, "gpurun_out"), exist_ok=True)
-    with open(os.path.join(ROOT, "gpurun_out", "linked_rate.json"), "a") as f:
-        f.write(json.dumps(rec) + "\n")
+    record("linked_rate", rec)
     print(rec)
 
 
-def test_linked_flag_is_free_on_independent_blocks(engine, slz4):
+def test_linked_flag_is_free_on_independent_blocks(engine, slz4, record):
     """linked = 1 on a stream in which every block decodes standalone (what this engine's compressor writes,
     and what the C++ mirror / LZ4_decompress_safe_continue always pass) must cost nothing measurable: the
     call only waits for the first pass to learn that no block needs a second one."""
@@ -93,8 +86,7 @@ def test_linked_flag_is_free_on_independent_blocks(engine, slz4):
         best[linked] = min(best.get(linked, 1e9), t)
     rec = {"test": "linked flag on independent blocks", "blocks": nb, "ms_linked0": round(best[False], 4),
            "ms_linked1": round(best[True], 4)}
-    with open(os.path.join(ROOT, "gpurun_out", "linked_rate.json"), "a") as f:
-        f.write(json.dumps(rec) + "\n")
+    record("linked_rate", rec)
     print(rec)
     # one stream synchronisation (tens of microseconds), never a walk over the blocks (tens of milliseconds)
     assert best[True] <= best[False] * 1.05 + 0.05, rec
@@ -103,7 +95,7 @@ def test_linked_flag_is_free_on_independent_blocks(engine, slz4):
 @pytest.mark.parametrize("kind,n_blocks,repeat,bl", [("text", 1024, 1, 65536), ("lzsynth_shared", 512, 1, 65536),
                                                      ("text", 1024, 10, 65536), ("text", 256, 4, 262144),
                                                      ("text", 64, 4, 1 << 20)])
-def test_single_linked_stream_rate(engine, slz4, oracle, kind, n_blocks, repeat, bl):
+def test_single_linked_stream_rate(engine, slz4, oracle, kind, n_blocks, repeat, bl, record):
     """ONE long stream written by the reference's linked compressor (what a reference-written file is): the
     tolerant parallel pass + the data-parallel pointer pass (linked_ptr.hpp).  Bit-exact; the rate is recorded.
     repeat > 1: the framed stream is appended to itself (still one valid linked stream: a block written without
@@ -152,13 +144,12 @@ def test_single_linked_stream_rate(engine, slz4, oracle, kind, n_blocks, repeat,
     assert torch.equal(out, ref)
     rec = {"streams": 1, "blocks_per_stream": nb, "block_len": bl, "data": kind + ", reference-linked", "dependent_blocks": dependent,
            "ms": round(best, 3), "GBps_uncompressed": round(nb * bl / best / 1e6, 3), "ratio": round(nb * bl / len(fr), 3)}
-    with open(os.path.join(ROOT, "gpurun_out", "linked_rate.json"), "a") as f:
-        f.write(json.dumps(rec) + "\n")
+    record("linked_rate", rec)
     print(rec)
 
 
 @pytest.mark.parametrize("linked", [0, 1])
-def test_single_linked_stream_host_api_rate(engine, slz4, oracle, linked):
+def test_single_linked_stream_host_api_rate(engine, slz4, oracle, linked, record):
     """The same kind of stream through the host-buffer call (page-locked caller memory, PCIe-inclusive):
     the call is cut into groups, and the second pass of a group looks back into the groups before it.
     linked = 0 on the engine's own independent blocks of the same data is the yardstick."""
@@ -192,15 +183,14 @@ def test_single_linked_stream_host_api_rate(engine, slz4, oracle, linked):
     rec = {"api": "host-buffer C API, page-locked caller memory", "streams": 1, "blocks_per_stream": nb, "block_len": bl,
            "data": "text, " + ("reference-linked" if linked else "independent blocks (this engine's)"), "linked": linked,
            "ms": round(best * 1e3, 3), "GBps_uncompressed": round(nb * bl / best / 1e9, 3)}
-    with open(os.path.join(ROOT, "gpurun_out", "linked_rate.json"), "a") as f:
-        f.write(json.dumps(rec) + "\n")
+    record("linked_rate", rec)
     print(rec)
 
 
-def test_long_linked_stream_default_is_runin_decode(engine, slz4, oracle, monkeypatch):
+def test_long_linked_stream_default_is_runin_decode(engine, slz4, oracle, monkeypatch, record):
     """ONE reference-written linked stream long enough (9 216 blocks of 64 KiB and more) that the default path is the
     run-in decode (pieces of the stream, each decoded from 11 blocks in front of it, kernels.hip): its output must be the
-    input, and the same bytes as the pointer pass's (MI355LZ4_LINKED_RUNIN=0).  Rates go to linked_rate.json."""
+    input, and the same bytes as the pointer pass's (MI355LZ4_LINKED_RUNIN=0).  Rates go to linked_rate.jsonl."""
     import torch
     dev = torch.device("cuda:0")
     # Two copies of one stream of 6272 blocks laid end to end: still ONE valid linked stream, because the reference wrote the
@@ -246,8 +236,7 @@ def test_long_linked_stream_default_is_runin_decode(engine, slz4, oracle, monkey
         rates[label] = round(nb * bl / best / 1e6, 2)
         del out
     rec = {"streams": 1, "blocks": nb, "block_len": bl, "data": "text, reference-linked, one stream", "GBps_uncompressed": rates}
-    with open(os.path.join(ROOT, "gpurun_out", "linked_rate.json"), "a") as f:
-        f.write(json.dumps(rec) + "\n")
+    record("linked_rate", rec)
     print(rec)
     assert rates["run-in (default)"] > rates["pointer pass"]
     import ctypes as C
@@ -305,7 +294,7 @@ def _copying_stream(nb, bl=65536):
     return data, b"".join(out)
 
 
-def test_long_linked_stream_that_never_forgets(slz4, oracle):
+def test_long_linked_stream_that_never_forgets(slz4, oracle, record):
     """A long stream whose every block IS the block before it (_copying_stream, written by hand): no run-in arrives at the true
     dictionary.  The engine reads that off a sample of the stream's blocks (all of their bytes come directly from the block
     before: api.cpp, k_dict_share) and takes the pointer pass from the first call on -- without the sample the run-in decode
@@ -348,17 +337,19 @@ def test_long_linked_stream_that_never_forgets(slz4, oracle):
     assert list(st)[:3] == [0, 0, 0] and st[3] >= 600000 and st[4] == 5, list(st)
     rec = {"streams": 1, "blocks": nb, "block_len": bl, "data": "every block one match that copies the block before it, hand-written, one stream",
            "sampled_dictionary_share": st[3] / 1e6, "ms_first_call": ms[0], "ms_next_calls": ms[1:]}
-    with open(os.path.join(ROOT, "gpurun_out", "linked_rate.json"), "a") as f:
-        f.write(json.dumps(rec) + "\n")
+    record("linked_rate", rec)
     print(rec)
 
 
-def test_long_engine_written_linked_stream_takes_the_long_run_in(slz4):
+def test_long_engine_written_linked_stream_takes_the_long_run_in(slz4, monkeypatch, record):
     """The engine's own linked compressor takes half of a text block from the block before it (the reference's: a third), and
     its streams forget a missing dictionary after 9 to 15 blocks instead of 5 to 12: the default run-in would give
     a call up (round 5: the first call of an engine, 43 ms, then 22); the engine reads the stream's kind off a sample of its blocks and
     takes the long run-in from the first call on.  Bytes and results exact every time; the rates are
-    recorded.  An engine of its own."""
+    recorded.  An engine of its own.  Its scratch is reserved before the timed calls by one call that forces the same
+    run-in (MI355LZ4_LINKED_RUNIN: such a call neither samples nor touches what the engine has learnt), so that the first
+    timed call is still the engine's first choice of path but not its first allocation: a fresh 640 MiB of device memory
+    takes anywhere from 0.04 ms to a second, depending on what the device's memory went through before."""
     import torch
     dev = torch.device("cuda:0")
     eng = slz4.Engine(0)
@@ -382,6 +373,17 @@ def test_long_engine_written_linked_stream_takes_the_long_run_in(slz4):
     eng.decompress_batch_device(dense, clen, doff, nb, out, ooff, res, linked=False)
     eng.synchronize()
     assert int((res < 0).sum().item()) >= nb - 8              # (the stream really is linked)
+    import ctypes as C
+    st = (C.c_int * 5)()
+    monkeypatch.setenv("MI355LZ4_LINKED_RUNIN", "1")
+    monkeypatch.setenv("MI355LZ4_LINKED_RUNIN_BLOCKS", "17")     # (RUNIN_LONG_64K: the run-in the timed calls take)
+    eng.decompress_batch_device(dense, clen, doff, nb, out, ooff, res, linked=True)
+    eng.synchronize()
+    monkeypatch.delenv("MI355LZ4_LINKED_RUNIN")
+    monkeypatch.delenv("MI355LZ4_LINKED_RUNIN_BLOCKS")
+    assert bool((res == bl).all().item()) and torch.equal(out, src)
+    slz4.lib.mi355lz4_debug_runin_state(eng.ctx, st, None)
+    assert list(st) == [0, 0, 0, -1, 2], list(st)                 # run-in, no sample taken, nothing learnt
     e0, e1 = slz4.Event(), slz4.Event()
     ms = []
     for _ in range(3):
@@ -396,13 +398,10 @@ def test_long_engine_written_linked_stream_takes_the_long_run_in(slz4):
     rec = {"streams": 1, "blocks": nb, "block_len": bl, "data": "text, linked stream written by this engine, one stream",
            "ratio": round(nb * bl / clen, 3), "ms_first_call": ms[0], "ms_next_calls": ms[1:],
            "GBps_uncompressed_next_calls": round(nb * bl / min(ms[1:]) / 1e6, 2)}
-    with open(os.path.join(ROOT, "gpurun_out", "linked_rate.json"), "a") as f:
-        f.write(json.dumps(rec) + "\n")
+    record("linked_rate", rec)
     print(rec)
     # the long run-in is taken from the FIRST call on: how long the stream remembers a dictionary is read off a sample of its
     # blocks (api.cpp, k_dict_share), no longer learnt from a call given up (round 5: 43 ms, then 22)
-    import ctypes as C
-    st = (C.c_int * 5)()
     slz4.lib.mi355lz4_debug_runin_state(eng.ctx, st, None)
     assert list(st)[:3] == [0, 0, 0] and st[4] == 3, list(st)       # nothing was given up, nothing learnt; the long run-in
     assert ms[0] < 1.5 * min(ms[1:]), ms

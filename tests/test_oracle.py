@@ -1,9 +1,11 @@
-"""CPU: the oracle restatement against the committed golden vectors (generated from the real
-reference, tests/golden/make_golden.py) and, where oracle/_ref exists, against the reference itself."""
+"""CPU: the oracle restatement against the committed golden vectors, all of them generated from the real
+reference by tests/golden/make_golden.py: known answers, and the reference's results on tests/reference_cases.py's
+inputs."""
 import hashlib
-import random
 
 import pytest
+
+import reference_cases
 
 
 def sha(b):
@@ -81,50 +83,30 @@ def test_compress_bound(oracle):
     assert oracle.compress_bound(0) == 16 and oracle.compress_bound(0x7E000001) == 0
 
 
-# ---- against the reference itself (only where oracle/_ref was built) --------------------------
-def test_vs_reference_compress_bytes(oracle, reference):
-    for kind in ("lzsynth", "text", "random"):
-        for bl in (1, 12, 13, 100, 4096, 65536, 70000):
-            data = oracle.gen(kind, 3, bl, first_block=11).tobytes()
-            for accel in (1, 7, 400):
-                for linked in (True, False):
-                    for hdr in (8, 4):
-                        assert oracle.frame_compress(data, bl, accel, hdr, linked) == \
-                            reference.frame_compress(data, bl, accel, hdr, linked), (kind, bl, accel, linked, hdr)
+# ---- against the reference itself: its results on tests/reference_cases.py's inputs, recorded by make_golden.py ----
+def test_vs_reference_compress_bytes(oracle, reference_vectors):
+    expect = reference_vectors["compress"]
+    seen = set()
+    for key, data, bl, accel, hdr, linked in reference_cases.compress_cases(oracle):
+        assert sha(oracle.frame_compress(data, bl, accel, hdr, linked)) == expect[key], key
+        seen.add(key)
+    assert seen == set(expect)
 
 
-def test_vs_reference_decode_fuzz(oracle, reference):
-    rng = random.Random(99)
-    for it in range(400):
-        kind = rng.choice(["lzsynth", "text", "random"])
-        n = rng.choice([0, 1, 12, 13, 20, 64, 65, 100, 300, 2000])
-        data = oracle.gen(kind, 1, max(n, 1), first_block=it)[:n].tobytes()
-        comp = oracle.compress_block(data, rng.choice([1, 1, 9]))
-        probes = [(comp, n), (comp, n + 7), (comp, max(n - 1, 0)), (comp[: max(1, len(comp) // 2)], n)]
-        m = bytearray(comp)
-        m[rng.randrange(len(m))] = rng.randrange(256)
-        probes += [(bytes(m), n), (bytes(m), n + 64)]
-        d = oracle.gen("text", 1, rng.choice([3, 500, 65536, 70000]), first_block=it + 5).tobytes()
-        for payload, cap in probes:
-            for dct in (None, d):
-                a = oracle.decompress_block(payload, cap, dct)
-                b = reference.decompress_block(payload, cap, dct)
-                assert a == b, (it, len(payload), cap, dct is not None, a[0], b[0])
+def test_vs_reference_decode_fuzz(oracle, reference_vectors):
+    expect = reference_vectors["decode_fuzz"]
+    its = 0
+    for it, probes in reference_cases.decode_fuzz_cases(oracle):
+        got = reference_cases.results_record([oracle.decompress_block(p, cap, d) for p, cap, d in probes])
+        assert got == expect[it], (it, got["codes"], expect[it]["codes"])
+        its += 1
+    assert its == len(expect)
 
 
-def _huge_length_cases():
-    """Blocks whose literal / match length fields are multi-megabyte runs of 0xFF: the lengths reach
-    2^31 and beyond (cbits/lz4.c:1811-1818, 1854-1858, 2064-2065 compare them as size_t)."""
-    run = 8_600_000                                     # 255 * run > 2^31
-    lit = b"\xf0" + b"\xff" * run + b"\x07" + b"abc"    # literal length overflowing int
-    mat = b"\x1f" + b"x" + b"\x01\x00" + b"\xff" * run + b"\x03" + b"\x50hello"
-    mat_dict = b"\x1f" + b"x" + b"\x05\x00" + b"\xff" * run + b"\x03" + b"\x50hello"
-    return [("lit", lit, 4096), ("lit_bigcap", lit, 1 << 20), ("match", mat, 4096), ("match_cap64", mat, 40),
-            ("match_far", mat_dict, 1 << 16)]
-
-
-def test_huge_length_fields_vs_reference(oracle, reference):
-    for name, payload, cap in _huge_length_cases():
-        assert oracle.decompress_block(payload, cap) == reference.decompress_block(payload, cap), name
-        d = bytes(range(256)) * 16
-        assert oracle.decompress_block(payload, cap, d) == reference.decompress_block(payload, cap, d), name
+def test_huge_length_fields_vs_reference(oracle, reference_vectors):
+    expect = reference_vectors["huge_length"]
+    names = []
+    for name, probes in reference_cases.huge_length_cases():
+        assert reference_cases.results_record([oracle.decompress_block(p, cap, d) for p, cap, d in probes]) == expect[name], name
+        names.append(name)
+    assert sorted(names) == sorted(expect)

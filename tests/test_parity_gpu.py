@@ -128,10 +128,10 @@ def test_decode_fuzz_vs_oracle(engine, oracle, decoder):
 def test_decode_huge_length_fields(engine, oracle, decoder):
     """Length fields that are multi-megabyte runs of 0xFF (lengths >= 2^31): same code as the oracle, and
     nothing is written outside the block's output (cbits/lz4.c:1811-1818, 1854-1858, 2064-2065)."""
-    from test_oracle import _huge_length_cases
+    from reference_cases import huge_length_blocks
     engine.set_decoder(decoder)
     try:
-        for name, payload, cap in _huge_length_cases():
+        for name, payload, cap in huge_length_blocks():
             fr = len(payload).to_bytes(4, "little") + cap.to_bytes(4, "little") + payload
             want_code, want = oracle.decompress_block(payload, cap)
             out, blen = engine.decompress_batch(fr, raise_on_block_error=False)
