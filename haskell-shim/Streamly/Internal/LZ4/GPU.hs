@@ -31,6 +31,7 @@ module Streamly.Internal.LZ4.GPU
     , newEngine
     , freeEngine
     , setLinkedCompress
+    , setBlockChecksum
     , MultiEngine
     , newMultiEngine
     , freeMultiEngine
@@ -81,6 +82,9 @@ foreign import ccall unsafe "mi355lz4.h mi355lz4_set_linked_compress"
     c_setLinkedCompress :: Ptr C_Engine -> CInt -> IO CInt
 
 -- replaces c_compressFastContinue (Streamly/Internal/LZ4.hs:123-131), N blocks per call
+foreign import ccall unsafe "mi355lz4.h mi355lz4_set_block_checksum"
+    c_setBlockChecksum :: Ptr C_Engine -> CInt -> IO CInt
+
 foreign import ccall safe "mi355lz4.h mi355lz4_compress_batch"
     c_compressBatch
         :: Ptr C_Engine -> Ptr (Ptr Word8) -> Ptr Int32 -> CInt -> CInt -> CInt
@@ -151,6 +155,17 @@ setLinkedCompress (Engine p) on = do
     rc <- c_setLinkedCompress p (if on then 1 else 0)
     when (rc /= 0) $ error "mi355lz4_set_linked_compress failed"
 
+-- | @setBlockChecksum@ (Streamly/Internal/LZ4/Config.hs:151, @undefined@ in the reference): 'True'
+-- makes every block carry the xxh32 of its data behind it,
+-- @| compLen | uncompLen (optional) | data | checksum (4 bytes) |@.  'compressChunksGPU' writes the
+-- trailer; 'decompressChunksRawGPU' expects it behind every block and checks it on the GPU (a mismatch
+-- is an error).  The arrays fed to 'decompressChunksRawGPU' must then be sliced with the trailer
+-- (compLen + meta + 4 bytes per block), which the reference's @resizeChunksD@ does not know of.
+setBlockChecksum :: Engine -> Bool -> IO ()
+setBlockChecksum (Engine p) on = do
+    rc <- c_setBlockChecksum p (if on then 1 else 0)
+    when (rc /= 0) $ error "mi355lz4_set_block_checksum failed"
+
 batchBlocks :: Int
 batchBlocks = 4096
 
@@ -173,7 +188,8 @@ compressBatch (Engine eng) cfg speed arrs = do
     let n = length arrs
         meta = metaSizeOf cfg
         lens = map Array.byteLength arrs
-        cap = sum (map (\l -> fromIntegral (c_bound (fromIntegral l)) + meta) lens)
+        -- (+ 4: room for a block checksum, 'setBlockChecksum')
+        cap = sum (map (\l -> fromIntegral (c_bound (fromIntegral l)) + meta + 4) lens)
     (MArray.Array cont dstBegin_ dstBegin dstMax) <- MArray.newArray (max cap 1)
     allocaArray n $ \pSrc -> allocaArray n $ \pLen -> allocaArray n $ \pFlen ->
       allocaArray n $ \pStatus -> alloca $ \pOutLen -> do

@@ -58,6 +58,7 @@ extern "C" {
 #define MI355LZ4_BLK_E_COMPLEN   (-0x7F000001)  /* compLen <= 0 or > LZ4_compressBound(LZ4_MAX_INPUT_SIZE) */
 #define MI355LZ4_BLK_E_TRUNCATED (-0x7F000002)  /* header/data runs past the framed buffer */
 #define MI355LZ4_BLK_E_UNCOMPLEN (-0x7F000003)  /* negative uncompLen / exceeds output capacity */
+#define MI355LZ4_BLK_E_CHECKSUM (-0x7F000004)   /* data does not match its trailer (mi355lz4_set_block_checksum) */
 
 #define MI355LZ4_MAX_INPUT_SIZE 0x7E000000      /* = LZ4_MAX_INPUT_SIZE, cbits/lz4.h:170 */
 
@@ -341,6 +342,35 @@ int mi355lz4_generate_device(mi355lz4_ctx *ctx, int kind, uint8_t *dst, int bloc
 int mi355lz4_interleave_device(mi355lz4_ctx *ctx, const uint8_t *local, const uint64_t *localOff,
                                int nLocalBlocks, int rank, int nRanks, uint8_t *global,
                                const uint64_t *globalOff);
+
+/* ---- block checksums (Streamly.Internal.LZ4.Config setBlockChecksum, Config.hs:118-158) ----------------
+ * With the switch on, every framed block carries a 4-byte trailer behind its data:
+ *   [compLen][uncompLen (headerKind 8)][compLen bytes][xxh32 of those bytes, seed 0, little-endian]
+ * -- with headerKind 4, byte for byte an LZ4 frame block with B.Checksum set.  compLen does not count the trailer.
+ * on != 0:
+ *   compress calls (_compress_batch_device, _compress_batch; linked or not) append the trailer: framedLen[i] and
+ *   blockFramedLen[i] include it, the data bytes are those of the same call with the switch off, and the device call
+ *   needs slotStride >= LZ4_compressBound(maxBlockLen) + headerKind + 4 (mi355lz4_slot_stride_ex) or returns
+ *   MI355LZ4_E_CAPACITY;
+ *   every decode call (_decompress_batch_device, _decompress_streams_device, _decompress_linked_begin / _end / _end_last,
+ *   _decompress_batch, _decompress_streams) expects the trailer: each block's data is hashed on the device before the block
+ *   is decoded; a trailer that lies past the framed buffer gives MI355LZ4_BLK_E_TRUNCATED, a mismatch
+ *   MI355LZ4_BLK_E_CHECKSUM (the call returns MI355LZ4_E_BLOCK).  Such a block is a header-rejected block: in a linked
+ *   stream the block after it sees what it sees after any rejected block.  The host-buffer calls walk the chain with the
+ *   trailers (mi355lz4_index_host_ex).
+ * Default off.  mi355lz4_index_device and the legacy face (include/lz4.h) do not look at it. */
+int mi355lz4_set_block_checksum(mi355lz4_ctx *ctx, int on);
+/* mi355lz4_slot_stride with room for the trailer when blockChecksum != 0. */
+size_t mi355lz4_slot_stride_ex(int blockLen, int headerKind, int blockChecksum);
+/* mi355lz4_index_host over a chain whose blocks carry trailers when blockChecksum != 0 (a block spans
+ * headerKind + compLen + 4 bytes); a trailer cut short is MI355LZ4_E_STREAM. */
+int mi355lz4_index_host_ex(const uint8_t *framedIn, size_t inLen, int headerKind, int fixedUncomp, int blockChecksum,
+                           uint64_t *blockOff, int32_t *uncompLen, int maxBlocks, int *nBlocks);
+/* out[i] = xxh32(seed) of base[off[i] .. off[i] + len[i]) for i < n: any length (len[i] < 0: out[i] is not written),
+ * any alignment.  All pointers are DEVICE pointers; asynchronous on the engine's stream.  The kernel behind the block
+ * checksums. */
+int mi355lz4_xxh32_device(mi355lz4_ctx *ctx, const uint8_t *base, const uint64_t *off, const int32_t *len, int n,
+                          uint32_t seed, uint32_t *out);
 
 /* ---- timing support: HIP events on the engine's own stream ------------- */
 int mi355lz4_event_create(void **ev);

@@ -43,15 +43,23 @@ std::vector<Array> toList(ArrayStream &s);              // Stream.toList
 
 // ---- Config.hs:109-136 ------------------------------------------------------
 enum class BlockSize { BlockHasSize, BlockMax64KB, BlockMax256KB, BlockMax1MB, BlockMax4MB };
-struct BlockConfig { BlockSize blockSize = BlockSize::BlockHasSize; };
+struct BlockConfig {
+    BlockSize blockSize = BlockSize::BlockHasSize;
+    bool blockChecksum = false;     // every block carries the xxh32 of its data behind it (Config.hs:118-158)
+};
 struct FrameConfig { bool hasEndMark = false; };
 inline BlockConfig defaultBlockConfig() { return BlockConfig{}; }                       // Config.hs:159-160
 inline FrameConfig defaultFrameConfig() { return FrameConfig{}; }                       // Config.hs:100-103
 inline BlockConfig setBlockMaxSize(BlockSize bs, BlockConfig c) { c.blockSize = bs; return c; }   // Config.hs:139-140
 inline FrameConfig setFrameEndMark(bool v, FrameConfig c) { c.hasEndMark = v; return c; }         // Config.hs:78-79
+// Config.hs:151 (`undefined` there): block layout | compLen | uncompLen (optional) | data | xxh32(data), LE32 |.  The
+// combinators below write and expect the trailer; decoding checks it on the GPU and throws an Error naming the block
+// ("block checksum mismatch") after the blocks in front of it have been delivered.
+inline BlockConfig setBlockChecksum(bool v, BlockConfig c) { c.blockChecksum = v; return c; }
 
 int metaSize(const BlockConfig &c);                     // Internal/LZ4.hs:177-181
 int maxBlockSize(const BlockConfig &c);                 // Internal/LZ4.hs:275-281
+int trailerSize(const BlockConfig &c);                  // 4 with setBlockChecksum True, else 0
 
 // GPU engine handle shared by the combinators.
 class Engine {

@@ -149,6 +149,10 @@ struct mi355lz4_ctx {
     bool ownStream = false;
     int decoder = 0;
     int linkedCompress = 0;                 // compress calls treat their blocks as consecutive blocks of one stream
+    int blockChecksum = 0;                  // every block's data is followed by its xxh32 (mi355lz4_set_block_checksum)
+    DevBuf ckBuf;                           // ... the decode side's per-block verdicts (k_xxh32_verify)
+    hipEvent_t ckEvent = nullptr;           // ... end of the last decode that read them, and the stream it ran on
+    hipStream_t ckStream = nullptr;
     // workspaces of the host-buffer API (grown on demand, reused across calls)
     DevBuf in, slots, dense, out, offA, offB, lenA, lenB, res, scratch;
     DevBuf tokBuf;                          // decoder variant 3: token lists
@@ -321,9 +325,11 @@ extern "C" void mi355lz4_destroy(mi355lz4_ctx *c)
     hipSetDevice(c->device);
     if (c->stream) hipStreamSynchronize(c->stream);
     for (DevBuf *b : {&c->in, &c->slots, &c->dense, &c->out, &c->offA, &c->offB, &c->lenA, &c->lenB, &c->res, &c->scratch,
-                      &c->tolPool, &c->tolMeta, &c->linkBuf, &c->ptrBuf, &c->seg[0].b, &c->seg[1].b, &c->seg[2].b, &c->seg[3].b, &c->tokBuf})
+                      &c->tolPool, &c->tolMeta, &c->linkBuf, &c->ptrBuf, &c->seg[0].b, &c->seg[1].b, &c->seg[2].b, &c->seg[3].b, &c->tokBuf,
+                      &c->ckBuf})
         dev_release(*b);
     if (c->linkEvent) hipEventDestroy(c->linkEvent);
+    if (c->ckEvent) hipEventDestroy(c->ckEvent);
     pin_release(c->pinStat);
     pin_release(c->pinIn);
     pin_release(c->pinOut);
@@ -389,6 +395,16 @@ extern "C" int mi355lz4_set_decoder(mi355lz4_ctx *c, int variant)
     c->decoder = variant;
     return MI355LZ4_OK;
 }
+
+extern "C" int mi355lz4_set_block_checksum(mi355lz4_ctx *c, int on)
+{
+    if (!c) return fail(MI355LZ4_E_ARG, "null ctx");
+    c->blockChecksum = on ? 1 : 0;
+    return MI355LZ4_OK;
+}
+
+// the switch as the multi handle sees it (multi_device.cpp): its engines must agree
+int engine_block_checksum(const mi355lz4_ctx *c) { return c ? c->blockChecksum : 0; }
 
 extern "C" int mi355lz4_set_linked_compress(mi355lz4_ctx *c, int on)
 {
@@ -475,6 +491,12 @@ extern "C" size_t mi355lz4_slot_stride(int blockLen, int headerKind)
     return (b + 15) & ~(size_t)15;
 }
 
+extern "C" size_t mi355lz4_slot_stride_ex(int blockLen, int headerKind, int blockChecksum)
+{
+    size_t b = (size_t)mi355lz4_compress_bound(blockLen) + (size_t)headerKind + (blockChecksum ? 4u : 0u);
+    return (b + 15) & ~(size_t)15;
+}
+
 static int check_launch(const char *what)
 {
     hipError_t e = hipGetLastError();
@@ -496,7 +518,8 @@ static int encode_device(mi355lz4_ctx *c, const uint8_t *src, const uint64_t *sr
     if (nBlocks == 0) return MI355LZ4_OK;
     if (!src && maxBlockLen > 0) return fail(MI355LZ4_E_ARG, "compress_batch_device: null src");
     if (!slots || !framedLen) return fail(MI355LZ4_E_ARG, "compress_batch_device: null output");
-    if (slotStride < (size_t)mi355lz4_compress_bound(maxBlockLen) + (size_t)headerKind)
+    const size_t trailer = c->blockChecksum ? 4u : 0u;
+    if (slotStride < (size_t)mi355lz4_compress_bound(maxBlockLen) + (size_t)headerKind + trailer)
         return fail(MI355LZ4_E_CAPACITY, "compress_batch_device: slotStride %zu < bound", slotStride);
     if (accel < 1) accel = 1;                 // cbits/lz4.c:1577
     if (accel > 65537) accel = 65537;         // cbits/lz4.c:1578
@@ -507,6 +530,13 @@ static int encode_device(mi355lz4_ctx *c, const uint8_t *src, const uint64_t *sr
     a.slots = slots; a.slotStride = slotStride; a.framedLen = framedLen;
     a.stats = c->stats;
     a.linked = c->linkedCompress; a.lookBack = lookBack;
+    // block checksums: the trailers go behind the encoder's output, on the same stream, before anything reads framedLen
+    auto finish = [&]() -> int {
+        int r = check_launch("encode launch");
+        if (r || !c->blockChecksum) return r;
+        launch_xxh32_append(slots, slotStride, headerKind, framedLen, nBlocks, c->stream);
+        return check_launch("checksum launch");
+    };
     // Small batches: with fewer blocks than the chip has wave slots (256 CUs x 16), a block is cut into segments that
     // several waves compress at once (kernels.hip, "K2, small batches").  Segments of >= 4 KiB, at most 64 per block,
     // about two waves per slot in all; blocks of up to 4 MiB (24-bit positions in the records); independent blocks only.
@@ -561,13 +591,13 @@ static int encode_device(mi355lz4_ctx *c, const uint8_t *src, const uint64_t *sr
                 sa.segBytes = sa.segCount + (size_t)nBlocks * (size_t)segs;
                 sa.segPrevEnd = (int32_t *)(sa.segBytes + (size_t)nBlocks * (size_t)segs);
                 launch_encode_seg(sa, c->stream);
-                return check_launch("encode launch");
+                return finish();
             }
             (void)hipGetLastError();          // no scratch: the one-wave-per-block path needs none
         }
     }
     launch_encode(a, maxBlockLen > 65536, c->stream);
-    return check_launch("encode launch");
+    return finish();
 }
 
 extern "C" int mi355lz4_compress_batch_device(mi355lz4_ctx *c, const uint8_t *src, const uint64_t *srcOff,
@@ -662,11 +692,11 @@ static bool cu_auto(int nBlocks, uint64_t framedLen)
 #define RUNIN_BACKOFF 16       // linked calls that skip the run-in decode after the long one gave a call up as well
 #define RUNIN_SHARE_LONG 0.306  // sampled share of bytes taken directly from the block before (k_dict_share) from which the long run-in is taken ...
 #define RUNIN_SHARE_NEVER 0.60  // ... and from which the stream is taken to never forget its dictionary (pointer pass)
-static int decode_device(mi355lz4_ctx *c, const uint8_t *framed, uint64_t framedLen, const uint64_t *blockOff,
-                         int nBlocks, int headerKind, int fixedUncomp, int linked, uint8_t *out,
-                         const uint64_t *outOff, const int32_t *outCap, int32_t *result, const uint8_t *dict0,
-                         uint32_t dict0Len, const int32_t *streamFirst = nullptr, int nStreams = 0, int lookBack = 0,
-                         bool splitOk = false, bool deferEnd = false)
+static int decode_device_impl(mi355lz4_ctx *c, const uint8_t *framed, uint64_t framedLen, const uint64_t *blockOff,
+                              int nBlocks, int headerKind, int fixedUncomp, int linked, uint8_t *out,
+                              const uint64_t *outOff, const int32_t *outCap, int32_t *result, const uint8_t *dict0,
+                              uint32_t dict0Len, const int32_t *streamFirst, int nStreams, int lookBack,
+                              bool splitOk, bool deferEnd, const int32_t *ckFail)
 {
     if (!c) return fail(MI355LZ4_E_ARG, "null ctx");
     if (c->plan.active) return fail(MI355LZ4_E_ARG, "a linked decode begun with mi355lz4_decompress_linked_begin is still open");
@@ -690,6 +720,7 @@ static int decode_device(mi355lz4_ctx *c, const uint8_t *framed, uint64_t framed
     a.cuSnap = nullptr; a.cuFlags = nullptr; a.cuRes = nullptr; a.cuPass = 0;
     a.ring = nullptr; a.ringStride = 0; a.zeroPage = nullptr; a.runPiece = 0; a.runIn = 0; a.runSpin = 0; a.runRound = 0;
     a.runRes = nullptr; a.runInfo = nullptr; a.runDirty = nullptr; a.runCtl = nullptr;
+    a.ckFail = ckFail;
     const size_t nFlags = streamFirst ? (size_t)(nStreams > 0 ? nStreams : 1) : 1;
     int r;
     if (linked) {
@@ -1035,6 +1066,36 @@ static int decode_device(mi355lz4_ctx *c, const uint8_t *framed, uint64_t framed
     return check_launch("decode launch");
 }
 
+// Every decode of the engine.  With block checksums on, the blocks' data is hashed first (k_xxh32_verify, one flag per
+// block in ckBuf) and read_block_header turns a mismatch into MI355LZ4_BLK_E_CHECKSUM: to every decode path a block
+// that fails its checksum is a header-rejected block, so linked streams treat it as they treat any other.
+static int decode_device(mi355lz4_ctx *c, const uint8_t *framed, uint64_t framedLen, const uint64_t *blockOff,
+                         int nBlocks, int headerKind, int fixedUncomp, int linked, uint8_t *out,
+                         const uint64_t *outOff, const int32_t *outCap, int32_t *result, const uint8_t *dict0,
+                         uint32_t dict0Len, const int32_t *streamFirst = nullptr, int nStreams = 0, int lookBack = 0,
+                         bool splitOk = false, bool deferEnd = false)
+{
+    if (!c || !c->blockChecksum || nBlocks <= 0 || c->plan.active || !framed || !blockOff ||
+        (headerKind != 4 && headerKind != 8))
+        return decode_device_impl(c, framed, framedLen, blockOff, nBlocks, headerKind, fixedUncomp, linked, out, outOff, outCap,
+                                  result, dict0, dict0Len, streamFirst, nStreams, lookBack, splitOk, deferEnd, nullptr);
+    HIP_TRY(hipSetDevice(c->device));
+    // the flags belong to the engine: a decode on another stream first waits for the last one that read them
+    if (c->ckEvent && c->ckStream != c->stream) HIP_TRY(hipStreamWaitEvent(c->stream, c->ckEvent, 0));
+    int r;
+    if ((r = dev_reserve(c->ckBuf, (size_t)nBlocks * 4))) return r;
+    DecodeArgs v = DecodeArgs();
+    v.framed = framed; v.framedLen = framedLen; v.blockOff = blockOff; v.nBlocks = nBlocks; v.headerKind = headerKind;
+    launch_xxh32_verify(v, (int32_t *)c->ckBuf.p, c->stream);
+    if ((r = check_launch("checksum launch"))) return r;
+    r = decode_device_impl(c, framed, framedLen, blockOff, nBlocks, headerKind, fixedUncomp, linked, out, outOff, outCap,
+                           result, dict0, dict0Len, streamFirst, nStreams, lookBack, splitOk, deferEnd,
+                           (const int32_t *)c->ckBuf.p);
+    if (!c->ckEvent && hipEventCreateWithFlags(&c->ckEvent, hipEventDisableTiming) != hipSuccess) c->ckEvent = nullptr;
+    if (c->ckEvent && hipEventRecord(c->ckEvent, c->stream) == hipSuccess) c->ckStream = c->stream;
+    return r;
+}
+
 extern "C" int mi355lz4_decompress_batch_device(mi355lz4_ctx *c, const uint8_t *framed, uint64_t framedLen,
                                                 const uint64_t *blockOff, int nBlocks, int headerKind,
                                                 int fixedUncomp, int linked, uint8_t *out, const uint64_t *outOff,
@@ -1107,6 +1168,18 @@ extern "C" int mi355lz4_decompress_streams_device(mi355lz4_ctx *c, const uint8_t
                              result, nullptr, 0);
     return decode_device(c, framed, framedLen, blockOff, nBlocks, headerKind, fixedUncomp, 1, out, outOff, outCap,
                          result, nullptr, 0, streamFirst, nStreams);
+}
+
+extern "C" int mi355lz4_xxh32_device(mi355lz4_ctx *c, const uint8_t *base, const uint64_t *off, const int32_t *len, int n,
+                                     uint32_t seed, uint32_t *out)
+{
+    if (!c) return fail(MI355LZ4_E_ARG, "null ctx");
+    if (n < 0) return fail(MI355LZ4_E_ARG, "xxh32_device: bad arguments");
+    if (n == 0) return MI355LZ4_OK;
+    if (!base || !off || !len || !out) return fail(MI355LZ4_E_ARG, "xxh32_device: null pointer");
+    HIP_TRY(hipSetDevice(c->device));
+    launch_xxh32_ranges(base, off, len, n, seed, out, c->stream);
+    return check_launch("checksum launch");
 }
 
 extern "C" int mi355lz4_index_device(mi355lz4_ctx *c, const uint8_t *framed, uint64_t framedLen,
@@ -1315,7 +1388,8 @@ extern "C" int mi355lz4_compress_batch(mi355lz4_ctx *c, const uint8_t *const *sr
         total += c->linkedCompress ? (size_t)srcLen[i] : (((size_t)srcLen[i] + 15) & ~(size_t)15);
         if (srcLen[i] > maxLen) maxLen = srcLen[i];
     }
-    const size_t stride = mi355lz4_slot_stride(maxLen, headerKind);
+    const size_t stride = mi355lz4_slot_stride_ex(maxLen, headerKind, c->blockChecksum);
+    const int trailer = c->blockChecksum ? 4 : 0;
 
     // groups of consecutive blocks, about group_bytes() of input each
     std::vector<int> gFirst;
@@ -1427,7 +1501,7 @@ extern "C" int mi355lz4_compress_batch(mi355lz4_ctx *c, const uint8_t *const *sr
             for (int i = b0; i < b1; i++) {
                 const int32_t f = flenPin[i];
                 if (blockFramedLen) blockFramedLen[i] = f;
-                if (status) status[i] = (f > headerKind) ? f - headerKind : 0;
+                if (status) status[i] = (f > headerKind) ? f - headerKind - trailer : 0;
                 if (f <= headerKind) bad++;
             }
             outAt[(size_t)g] = outPos;
@@ -1454,9 +1528,18 @@ extern "C" int mi355lz4_compress_batch(mi355lz4_ctx *c, const uint8_t *const *sr
     return MI355LZ4_OK;
 }
 
+extern "C" int mi355lz4_index_host_ex(const uint8_t *framedIn, size_t inLen, int headerKind, int fixedUncomp,
+                                      int blockChecksum, uint64_t *blockOff, int32_t *uncompLen, int maxBlocks, int *nBlocks);
 extern "C" int mi355lz4_index_host(const uint8_t *framedIn, size_t inLen, int headerKind, int fixedUncomp,
                                    uint64_t *blockOff, int32_t *uncompLen, int maxBlocks, int *nBlocks)
 {
+    return mi355lz4_index_host_ex(framedIn, inLen, headerKind, fixedUncomp, 0, blockOff, uncompLen, maxBlocks, nBlocks);
+}
+
+extern "C" int mi355lz4_index_host_ex(const uint8_t *framedIn, size_t inLen, int headerKind, int fixedUncomp,
+                                      int blockChecksum, uint64_t *blockOff, int32_t *uncompLen, int maxBlocks, int *nBlocks)
+{
+    const size_t trailer = blockChecksum ? 4u : 0u;
     if (!nBlocks || (headerKind != 4 && headerKind != 8) || maxBlocks < 0 || (inLen && !framedIn))
         return fail(MI355LZ4_E_ARG, "index_host: bad arguments");
     size_t pos = 0;
@@ -1468,12 +1551,12 @@ extern "C" int mi355lz4_index_host(const uint8_t *framedIn, size_t inLen, int he
         const int32_t cl = host_le32(framedIn + pos);
         const int32_t ul = (headerKind == 8) ? host_le32(framedIn + pos + 4) : fixedUncomp;
         if (cl <= 0) return fail(MI355LZ4_E_STREAM, "index_host: block %d has compressed length %d", k, cl);
-        if (pos + (size_t)headerKind + (size_t)cl > inLen)
-            return fail(MI355LZ4_E_STREAM, "index_host: incomplete block %d (needs %d bytes)", k, cl);
+        if (pos + (size_t)headerKind + (size_t)cl + trailer > inLen)
+            return fail(MI355LZ4_E_STREAM, "index_host: incomplete block %d (needs %zu bytes)", k, (size_t)cl + trailer);
         if (k >= maxBlocks) return fail(MI355LZ4_E_CAPACITY, "index_host: more than %d blocks", maxBlocks);
         if (blockOff) blockOff[k] = pos;
         if (uncompLen) uncompLen[k] = ul;
-        pos += (size_t)headerKind + (size_t)cl;
+        pos += (size_t)headerKind + (size_t)cl + trailer;
         k++;
     }
     *nBlocks = k;
@@ -1527,7 +1610,8 @@ static int decompress_host(mi355lz4_ctx *c, const uint8_t *framedIn, size_t inLe
     std::vector<uint64_t> boff((size_t)maxBlocks + 1);
     std::vector<int32_t> ulen((size_t)maxBlocks + 1);
     int n = 0;
-    int r = mi355lz4_index_host(framedIn, inLen, headerKind, fixedUncomp, boff.data(), ulen.data(), maxBlocks, &n);
+    int r = mi355lz4_index_host_ex(framedIn, inLen, headerKind, fixedUncomp, c->blockChecksum, boff.data(), ulen.data(),
+                                   maxBlocks, &n);
     if (r) return r;
     if (n == 0) return MI355LZ4_OK;
     HIP_TRY(hipSetDevice(c->device));

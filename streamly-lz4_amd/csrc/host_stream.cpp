@@ -8,6 +8,7 @@
 // src/Streamly/Internal/LZ4.hs unless stated otherwise.
 #include "../../include/streamly_lz4.hpp"
 #include "../../include/mi355lz4.h"
+#include "block_checksum_scope.hpp"
 
 #include <cstring>
 #include <deque>
@@ -37,6 +38,8 @@ int maxBlockSize(const BlockConfig &c)                                          
     }
     return 0;
 }
+
+int trailerSize(const BlockConfig &c) { return c.blockChecksum ? 4 : 0; }
 
 static int fixedUncompSize(const BlockConfig &c)                                                 // :189-198
 {
@@ -118,16 +121,18 @@ private:
         if (batch.empty()) return;
         const int n = (int)batch.size();
         const int meta = metaSize(cfg_);
+        const int tr = trailerSize(cfg_);
         std::vector<const uint8_t *> ptrs((size_t)n);
         std::vector<int32_t> lens((size_t)n), flen((size_t)n), status((size_t)n);
         size_t cap = 0;
         for (int i = 0; i < n; i++) {
             ptrs[(size_t)i] = batch[(size_t)i].data();
             lens[(size_t)i] = (int32_t)batch[(size_t)i].size();
-            cap += (size_t)mi355lz4_compress_bound(lens[(size_t)i]) + (size_t)meta;   // :244-251
+            cap += (size_t)mi355lz4_compress_bound(lens[(size_t)i]) + (size_t)meta + (size_t)tr;   // :244-251
         }
         Array framed(cap);
         size_t outLen = 0;
+        BlockChecksumScope ck(eng_.ctx(), cfg_.blockChecksum);
         int r = mi355lz4_compress_batch(eng_.ctx(), ptrs.data(), lens.data(), n, speed_, meta, framed.data(), cap,
                                         &outLen, flen.data(), status.data());
         if (r != MI355LZ4_OK) {
@@ -189,7 +194,7 @@ public:
                 const int32_t compressedSize = le32(buf_.data());               // :471-473 (compSizeOffset = 0)
                 // a negative size would make `required` wrap; the reference would then mis-slice.
                 if (compressedSize < 0) throw Error("resizeChunksD: negative compressed length in block header");
-                const size_t required = (size_t)compressedSize + meta;          // :474
+                const size_t required = (size_t)compressedSize + meta + (size_t)trailerSize(cfg_);   // :474 (+ the trailer)
                 if (len == required) {                                          // :475-476
                     out = std::move(buf_);
                     buf_.clear();
@@ -253,7 +258,11 @@ public:
     bool next(Array &out) override
     {
         if (ready_.empty() && !done_) fill();
-        if (ready_.empty()) return false;
+        if (ready_.empty()) {
+            // a block that failed its checksum: the blocks in front of it have been delivered, now the error
+            if (!pendingErr_.empty()) { std::string e; e.swap(pendingErr_); throw Error(e); }
+            return false;
+        }
         out = std::move(ready_.front());
         ready_.pop_front();
         return true;
@@ -263,6 +272,7 @@ private:
     void fill()
     {
         const int meta = metaSize(cfg_);
+        const int tr = trailerSize(cfg_);
         std::vector<Array> batch;
         Array a;
         size_t bytes = 0, outBytes = 0;
@@ -270,8 +280,9 @@ private:
             if (!in_->next(a)) { done_ = true; break; }
             // decompressChunk's header checks, :299-318
             if (a.size() < (size_t)meta) throw Error("decompressChunk: input array is shorter than the block header");
+            if (a.size() < (size_t)(meta + tr)) throw Error("decompressChunk: input array is shorter than the block header and checksum");
             const int32_t compLen = le32(a.data());
-            const int64_t arrDataLen = (int64_t)a.size() - meta;
+            const int64_t arrDataLen = (int64_t)a.size() - meta - tr;
             const int64_t uncompLen = (meta == 8) ? (int64_t)le32(a.data() + 4) : (int64_t)fixedUncompSize(cfg_);
             if (compLen <= 0) throw Error("decompressChunk: compressed data length > 2GB");              // :309-310
             if ((int64_t)compLen < arrDataLen)                                                          // :311-315
@@ -289,7 +300,7 @@ private:
             batch.push_back(std::move(a));
         }
         if (batch.empty()) return;
-        const int n = (int)batch.size();
+        int n = (int)batch.size();
         Array framed;
         framed.reserve(bytes);
         for (auto &b : batch) framed.insert(framed.end(), b.begin(), b.end());
@@ -297,11 +308,36 @@ private:
         std::vector<int32_t> blockLen((size_t)n);
         size_t outLen = 0;
         int got = 0;
+        BlockChecksumScope ck(eng_.ctx(), cfg_.blockChecksum);
         // The reference always decodes with stream (linked) semantics; prev_ is the array its
         // DecompressDo state keeps alive (:564).
         int r = mi355lz4_decompress_batch(eng_.ctx(), framed.data(), framed.size(), meta, fixedUncompSize(cfg_), 1,
                                           prev_.empty() ? nullptr : prev_.data(), (int)prev_.size(), out.data(),
                                           out.size(), &outLen, blockLen.data(), n, &got);
+        if (r == MI355LZ4_E_BLOCK && cfg_.blockChecksum) {
+            // In stream order: the blocks in front of the first failing one are delivered (decoded again, alone: the batch
+            // call packs nothing when a block fails), then the error.  Only with block checksums, whose error is new.
+            size_t pos = 0;
+            int k = 0;
+            while (k < got && blockLen[(size_t)k] >= 0) { pos += (size_t)meta + (size_t)le32(framed.data() + pos) + (size_t)tr; k++; }
+            if (k < got) {
+                const int32_t code = blockLen[(size_t)k];
+                pendingErr_ = code == MI355LZ4_BLK_E_CHECKSUM
+                    ? "decompressChunk: block checksum mismatch in block " + std::to_string(seen_ + (uint64_t)k) +
+                      " (its data does not match its xxh32 trailer)"
+                    : "decompressChunk: c_decompressSafeContinue failed in block " + std::to_string(seen_ + (uint64_t)k) +
+                      "\ndecompLenC = " + std::to_string(code);
+                done_ = true;
+                if (k > 0) {
+                    r = mi355lz4_decompress_batch(eng_.ctx(), framed.data(), pos, meta, fixedUncompSize(cfg_), 1,
+                                                  prev_.empty() ? nullptr : prev_.data(), (int)prev_.size(), out.data(),
+                                                  out.size(), &outLen, blockLen.data(), k, &got);
+                    if (r != MI355LZ4_OK || got != k) throw Error(std::string("decompressChunks: ") + mi355lz4_last_error());
+                }
+                n = k;
+                r = MI355LZ4_OK;
+            }
+        }
         if (r == MI355LZ4_E_BLOCK) {
             size_t pos = 0;
             for (int i = 0; i < got; i++) {
@@ -311,7 +347,7 @@ private:
                                 std::to_string(compLen) + "\ncompLenC = " + std::to_string(compLen) +
                                 "\nuncompLenC = " + std::to_string(meta == 8 ? le32(framed.data() + pos + 4) : fixedUncompSize(cfg_)) +
                                 "\ndecompLenC = " + std::to_string(blockLen[(size_t)i]));
-                pos += (size_t)meta + (size_t)compLen;
+                pos += (size_t)meta + (size_t)compLen + (size_t)tr;
             }
         }
         if (r != MI355LZ4_OK) throw Error(std::string("decompressChunks: ") + mi355lz4_last_error());
@@ -322,6 +358,7 @@ private:
             if (len > 0) prev_ = ready_.back();                                 // cbits/lz4.c:2331,2353: only result > 0 moves the dictionary
             pos += len;
         }
+        seen_ += (uint64_t)n;
     }
 
     BlockConfig cfg_;
@@ -330,6 +367,8 @@ private:
     std::deque<Array> ready_;
     Array prev_;
     bool done_ = false;
+    uint64_t seen_ = 0;             // blocks of the stream in front of this batch
+    std::string pendingErr_;
 };
 } // namespace
 
@@ -398,6 +437,7 @@ ArrayBatch decompressChunksBatch(const BlockConfig &cfg, const FrameConfig &conf
     for (size_t i = 0; i < n; i++) total += (size_t)lens[i];
     ArrayBatch res;
     const int meta = metaSize(cfg);
+    const size_t tr = (size_t)trailerSize(cfg);
     if (!conf.hasEndMark && total > 0 && total < ((size_t)1 << 31)) {
         // how many whole blocks? (a header walk: compLen <= 0, or a block that runs past the end, ends the fast path)
         size_t nbk = 0, p = 0;
@@ -405,15 +445,16 @@ ArrayBatch decompressChunksBatch(const BlockConfig &cfg, const FrameConfig &conf
         while (p < total) {
             if (total - p < (size_t)meta) { whole = false; break; }
             const int32_t compLen = le32(data + p);
-            if (compLen <= 0 || (size_t)compLen > total - p - (size_t)meta) { whole = false; break; }
-            p += (size_t)meta + (size_t)compLen;
+            if (compLen <= 0 || (size_t)compLen + tr > total - p - (size_t)meta) { whole = false; break; }
+            p += (size_t)meta + (size_t)compLen + tr;
             nbk++;
         }
         if (whole && nbk > 0 && nbk < ((size_t)1 << 24)) {
             std::vector<uint64_t> boff(nbk + 1);
             std::vector<int32_t> ulen(nbk + 1), blen(nbk + 1);
             int nb = 0;
-            if (mi355lz4_index_host(data, total, meta, fixedUncompSize(cfg), boff.data(), ulen.data(), (int)nbk, &nb) ==
+            if (mi355lz4_index_host_ex(data, total, meta, fixedUncompSize(cfg), cfg.blockChecksum, boff.data(), ulen.data(),
+                                       (int)nbk, &nb) ==
                     MI355LZ4_OK && (size_t)nb == nbk) {
                 size_t cap = 0;
                 bool sane = true;
@@ -422,6 +463,7 @@ ArrayBatch decompressChunksBatch(const BlockConfig &cfg, const FrameConfig &conf
                     res.buf = buf_pool().get(cap + 16, res.cap);
                     size_t outLen = 0;
                     int got = 0;
+                    BlockChecksumScope ck(eng.ctx(), cfg.blockChecksum);
                     const int r = mi355lz4_decompress_batch(eng.ctx(), data, total, meta, fixedUncompSize(cfg), 1, nullptr, 0,
                                                             res.buf, cap + 16, &outLen, blen.data(), nb, &got);
                     if (r == MI355LZ4_OK && got == nb) {
@@ -534,10 +576,13 @@ struct slz4_engine { Engine *e; };
 
 static thread_local std::string g_slz4_err;
 
+// kind: the BlockSize (0..4), plus SLZ4_BLOCK_CHECKSUM for setBlockChecksum True
+#define SLZ4_BLOCK_CHECKSUM 0x100
 static BlockConfig cfg_from_kind(int kind)
 {
     BlockConfig c;
-    switch (kind) {
+    c.blockChecksum = (kind & SLZ4_BLOCK_CHECKSUM) != 0;
+    switch (kind & ~SLZ4_BLOCK_CHECKSUM) {
     case 0: c.blockSize = BlockSize::BlockHasSize; break;
     case 1: c.blockSize = BlockSize::BlockMax64KB; break;
     case 2: c.blockSize = BlockSize::BlockMax256KB; break;
@@ -648,6 +693,26 @@ int slz4_decompress_chunks(slz4_engine *h, int blockSizeKind, int hasEndMark, co
     } catch (const std::exception &e) {
         g_slz4_err = e.what();
         *out = nullptr;
+        return -1;
+    }
+}
+
+// decompressChunks array at a time, as a stream consumer sees it: *out always holds the arrays delivered before the
+// stream raised (all of them when it returns 0); on -1 slz4_last_error() is the error.
+int slz4_decompress_chunks_stream(slz4_engine *h, int blockSizeKind, int hasEndMark, const uint8_t *data, const uint64_t *lens,
+                                  size_t n, slz4_arrays **out)
+{
+    slz4_arrays *r = new slz4_arrays();
+    *out = r;
+    try {
+        FrameConfig fc; fc.hasEndMark = hasEndMark != 0;
+        const BlockConfig cfg = cfg_from_kind(blockSizeKind);
+        StreamPtr s = decompressChunksRaw(cfg, resizeChunks(cfg, fc, list_from_c(data, lens, n)), *h->e);
+        Array a;
+        while (s->next(a)) r->v.push_back(std::move(a));
+        return 0;
+    } catch (const std::exception &e) {
+        g_slz4_err = e.what();
         return -1;
     }
 }

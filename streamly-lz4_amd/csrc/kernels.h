@@ -9,6 +9,7 @@
 #define BLK_E_COMPLEN   (-0x7F000001)
 #define BLK_E_TRUNCATED (-0x7F000002)
 #define BLK_E_UNCOMPLEN (-0x7F000003)
+#define BLK_E_CHECKSUM  (-0x7F000004)
 // LZ4_compressBound(LZ4_MAX_INPUT_SIZE): reference lz4_MAX_OUTPUT_SIZE, Internal/LZ4.hs:145-147
 #define MAX_COMP_LEN 2122219150
 
@@ -78,6 +79,9 @@ struct DecodeArgs {
     uint32_t *cuFlags;          // [0] snapshots that changed in the last launch_cu_tails, [1] blocks the form cannot take, [2 + k] block k's snapshot changed
     int32_t *cuRes;             // [nBlocks] results of the passes (published by the caller when the snapshots have settled)
     int cuPass;
+    // block checksums (mi355lz4_set_block_checksum): every block's data is followed by a 4-byte xxh32 trailer, and
+    // ckFail[blk] != 0 says k_xxh32_verify found that they do not match; null = no trailers (read_block_header)
+    const int32_t *ckFail = nullptr;
 };
 
 struct EncodeArgs {
@@ -140,5 +144,12 @@ void launch_interleave(const uint8_t *local, const uint64_t *localOff, int nLoca
                        uint8_t *global, const uint64_t *globalOff, hipStream_t s);
 void launch_index(const uint8_t *framed, uint64_t framedLen, const uint64_t *blockOff, int nBlocks,
                   int headerKind, int fixedUncomp, int32_t *scratchSizes, uint64_t *outOff, hipStream_t s);
+// block checksums (checksum.hpp): xxh32(seed) of base + off[i], len[i] bytes -> out[i]; the compress side's trailers
+// (slot i's data hashed, the trailer written behind it, framedLen[i] += 4; failed blocks left alone); the decode side's
+// per-block flags (fail[i] = data does not match its trailer; 0 for blocks whose header or trailer is out of bounds)
+void launch_xxh32_ranges(const uint8_t *base, const uint64_t *off, const int32_t *len, int n, uint32_t seed, uint32_t *out,
+                         hipStream_t s);
+void launch_xxh32_append(uint8_t *slots, size_t slotStride, int headerKind, int32_t *framedLen, int n, hipStream_t s);
+void launch_xxh32_verify(const DecodeArgs &a, int32_t *fail, hipStream_t s);
 void launch_generate(int kind, uint8_t *dst, int blockLen, int nBlocks, uint64_t firstBlock,
                      uint64_t blockStep, uint32_t litMax, uint32_t offMax, hipStream_t s);

@@ -14,6 +14,7 @@
 // special case on the device.
 #include "../../include/mi355lz4.h"
 #include "../../include/streamly_lz4.hpp"
+#include "block_checksum_scope.hpp"
 
 #include <algorithm>
 #include <cstring>
@@ -73,6 +74,7 @@ static size_t bd_size(int code) { return (size_t)1 << (8 + 2 * code); }       //
 // ---------------------------------------------------------------------------
 Array lz4FrameCompress(const Array &data, int speed, Engine &eng, const Lz4FrameOptions &opt)
 {
+    BlockChecksumScope noTrailers(eng.ctx(), false);       // the frame's block checksums are its own (host side)
     const int code = bd_code(opt.blockMax);
     const size_t bmax = bd_size(code);
     Array out;
@@ -220,6 +222,7 @@ bool lz4FrameParse(const Array &frame, size_t &at, Lz4FrameIndex &ix)
 #endif
 Array lz4FrameDecompress(const Array &frame, Engine &eng)
 {
+    BlockChecksumScope noTrailers(eng.ctx(), false);
     Array out;
     Array scratch;                      // one group's output; grows to the budget at most, reused, never zero-filled twice
     size_t at = 0;

@@ -97,6 +97,18 @@ struct PartResult {
     int got = 0;
 };
 
+int engine_block_checksum(const mi355lz4_ctx *c);   // api.cpp
+
+// Block checksums (mi355lz4_set_block_checksum) are a property of the stream a call reads or writes: every engine of the
+// handle must have the same setting.  -1: they disagree.
+static int multi_block_checksum(const mi355lz4_multi *m)
+{
+    const int ck = engine_block_checksum(m->eng[0]);
+    for (mi355lz4_ctx *e : m->eng)
+        if (engine_block_checksum(e) != ck) return -1;
+    return ck;
+}
+
 extern "C" int mi355lz4_multi_compress_batch(mi355lz4_multi *m, const uint8_t *const *src, const int32_t *srcLen, int nBlocks,
                                              int accel, int headerKind, uint8_t *framedOut, size_t cap, size_t *outLen,
                                              int32_t *blockFramedLen, int32_t *status)
@@ -105,6 +117,8 @@ extern "C" int mi355lz4_multi_compress_batch(mi355lz4_multi *m, const uint8_t *c
     if (nBlocks < 0 || !outLen || (nBlocks > 0 && (!src || !srcLen || !framedOut)))
         return mfail(MI355LZ4_E_ARG, "mi355lz4_multi_compress_batch: bad arguments");
     *outLen = 0;
+    const int ck = multi_block_checksum(m);
+    if (ck < 0) return mfail(MI355LZ4_E_ARG, "mi355lz4_multi_compress_batch: the engines disagree on block checksums");
     if (nBlocks == 0) return MI355LZ4_OK;
     const std::vector<int> first = cut_ranges(srcLen, nBlocks, (int)m->eng.size());
     const int P = (int)first.size() - 1;
@@ -117,7 +131,7 @@ extern "C" int mi355lz4_multi_compress_batch(mi355lz4_multi *m, const uint8_t *c
         for (int i = first[(size_t)p]; i < first[(size_t)p + 1]; i++) {
             const int b = mi355lz4_compress_bound(srcLen[i]);
             if (srcLen[i] < 0 || b <= 0) return mfail(MI355LZ4_E_ARG, "mi355lz4_multi_compress_batch: a block is larger than LZ4_MAX_INPUT_SIZE");
-            bound[(size_t)p] += (size_t)b + (size_t)headerKind;
+            bound[(size_t)p] += (size_t)b + (size_t)headerKind + (ck ? 4u : 0u);
         }
         at[(size_t)p] = sum;
         sum += bound[(size_t)p];
@@ -168,13 +182,15 @@ extern "C" int mi355lz4_multi_decompress_batch(mi355lz4_multi *m, const uint8_t 
         return mfail(MI355LZ4_E_ARG, "mi355lz4_multi_decompress_batch: bad arguments");
     *outLen = 0;
     *nBlocksOut = 0;
+    const int ck = multi_block_checksum(m);
+    if (ck < 0) return mfail(MI355LZ4_E_ARG, "mi355lz4_multi_decompress_batch: the engines disagree on block checksums");
     if (inLen == 0) return MI355LZ4_OK;
     // the header chain, once, on the host (resizeChunksD's job, Internal/LZ4.hs:459-484): where every block starts and how
     // much room it asks for
     std::vector<uint64_t> boff((size_t)maxBlocks + 1);
     std::vector<int32_t> ulen((size_t)maxBlocks + 1);
     int n = 0;
-    const int ri = mi355lz4_index_host(framedIn, inLen, headerKind, fixedUncomp, boff.data(), ulen.data(), maxBlocks, &n);
+    const int ri = mi355lz4_index_host_ex(framedIn, inLen, headerKind, fixedUncomp, ck, boff.data(), ulen.data(), maxBlocks, &n);
     if (ri != MI355LZ4_OK) return mfail(ri, "mi355lz4_multi_decompress_batch", mi355lz4_last_error());
     if (n == 0) return MI355LZ4_OK;
     boff[(size_t)n] = inLen;

@@ -19,9 +19,9 @@ import numpy as np
 
 __all__ = [
     "lib", "lib_path", "Engine", "LZ4Error", "BlockSize", "BlockConfig", "FrameConfig",
-    "defaultBlockConfig", "defaultFrameConfig", "setBlockMaxSize", "setFrameEndMark",
+    "defaultBlockConfig", "defaultFrameConfig", "setBlockMaxSize", "setFrameEndMark", "setBlockChecksum",
     "compressChunks", "decompressChunks", "decompressChunksRaw", "resizeChunks",
-    "decompressChunksWith", "simpleFrameParser", "compress_bound", "slot_stride", "device_count",
+    "decompressChunksWith", "decompressChunksStream", "simpleFrameParser", "compress_bound", "slot_stride", "slot_stride_ex", "device_count",
     "xxh32", "lz4FrameCompress", "lz4FrameDecompress",
 ]
 
@@ -110,6 +110,12 @@ def _load():
     sig("mi355lz4_event_destroy", C.c_int, vp)
     sig("mi355lz4_event_record", C.c_int, vp, vp)
     sig("mi355lz4_event_elapsed_ms", C.c_int, vp, vp, C.POINTER(C.c_float))
+    # block checksums
+    sig("mi355lz4_set_block_checksum", C.c_int, vp, C.c_int)
+    sig("mi355lz4_slot_stride_ex", C.c_size_t, C.c_int, C.c_int, C.c_int)
+    sig("mi355lz4_index_host_ex", C.c_int, _u8p, C.c_size_t, C.c_int, C.c_int, C.c_int, _u64p, _i32p, C.c_int,
+        C.POINTER(C.c_int))
+    sig("mi355lz4_xxh32_device", C.c_int, vp, vp, vp, vp, C.c_int, C.c_uint32, vp)
     # legacy face (include/lz4.h)
     sig("LZ4_createStream", vp)
     sig("LZ4_freeStream", C.c_int, vp)
@@ -135,6 +141,7 @@ def _load():
     sig("slz4_resize_chunks", C.c_int, C.c_int, C.c_int, _u8p, _u64p, C.c_size_t, C.POINTER(vp))
     sig("slz4_decompress_chunks_raw", C.c_int, vp, C.c_int, _u8p, _u64p, C.c_size_t, C.POINTER(vp))
     sig("slz4_decompress_chunks", C.c_int, vp, C.c_int, C.c_int, _u8p, _u64p, C.c_size_t, C.POINTER(vp))
+    sig("slz4_decompress_chunks_stream", C.c_int, vp, C.c_int, C.c_int, _u8p, _u64p, C.c_size_t, C.POINTER(vp))
     sig("slz4_decompress_chunks_with", C.c_int, vp, _u8p, _u64p, C.c_size_t, C.POINTER(vp))
     sig("slz4_simple_frame_parser", C.c_int, _u8p, _u64p, C.c_size_t, C.POINTER(C.c_int), C.POINTER(vp))
     # standard LZ4 frames
@@ -157,6 +164,7 @@ DECLARED_SYMBOLS = [
     "mi355lz4_event_destroy", "mi355lz4_event_record", "mi355lz4_event_elapsed_ms",
     "mi355lz4_create_multi", "mi355lz4_destroy_multi", "mi355lz4_multi_device_count", "mi355lz4_multi_engine", "mi355lz4_multi_last_error",
     "mi355lz4_multi_compress_batch", "mi355lz4_multi_decompress_batch",
+    "mi355lz4_set_block_checksum", "mi355lz4_slot_stride_ex", "mi355lz4_index_host_ex", "mi355lz4_xxh32_device",
     "LZ4_createStream", "LZ4_freeStream", "LZ4_createStreamDecode", "LZ4_freeStreamDecode", "LZ4_compressBound",
     "LZ4_compress_fast_continue", "LZ4_decompress_safe_continue",
 ]
@@ -179,6 +187,25 @@ def slot_stride(block_len, header_kind=8):
     return lib.mi355lz4_slot_stride(int(block_len), int(header_kind))
 
 
+def slot_stride_ex(block_len, header_kind=8, block_checksum=False):
+    return lib.mi355lz4_slot_stride_ex(int(block_len), int(header_kind), int(bool(block_checksum)))
+
+
+def index_host(framed, header_kind=8, fixed_uncomp=0, block_checksum=False, max_blocks=None):
+    """Walk a dense framed stream's header chain on the host (mi355lz4_index_host_ex).  Returns (block offsets, uncompressed
+    sizes); raises LZ4Error on a malformed chain."""
+    src = np.frombuffer(bytes(framed), dtype=np.uint8)
+    if max_blocks is None:
+        max_blocks = src.size // (header_kind + 1) + 1
+    boff = np.zeros(max_blocks + 1, dtype=np.uint64)
+    ulen = np.zeros(max_blocks + 1, dtype=np.int32)
+    nb = C.c_int()
+    _check(lib.mi355lz4_index_host_ex(src.ctypes.data_as(_u8p), src.size, int(header_kind), int(fixed_uncomp),
+                                      int(bool(block_checksum)), boff.ctypes.data_as(_u64p), ulen.ctypes.data_as(_i32p),
+                                      int(max_blocks), C.byref(nb)), "index_host_ex")
+    return boff[: nb.value].tolist(), ulen[: nb.value].tolist()
+
+
 def device_count():
     return lib.mi355lz4_device_count()
 
@@ -195,8 +222,13 @@ class BlockSize:
 
 
 class BlockConfig:
-    def __init__(self, blockSize=BlockSize.BlockHasSize):
+    def __init__(self, blockSize=BlockSize.BlockHasSize, blockChecksum=False):
         self.blockSize = blockSize
+        self.blockChecksum = bool(blockChecksum)   # Config.hs:151: xxh32 of every block's data behind it
+
+    @property
+    def _kind(self):  # the C surface's kind: BlockSize, plus SLZ4_BLOCK_CHECKSUM (0x100)
+        return int(self.blockSize) | (0x100 if self.blockChecksum else 0)
 
     @property
     def metaSize(self):  # Internal/LZ4.hs:177-181
@@ -217,7 +249,12 @@ defaultFrameConfig = FrameConfig()
 
 
 def setBlockMaxSize(bs, cfg):
-    return BlockConfig(bs)
+    return BlockConfig(bs, cfg.blockChecksum)
+
+
+def setBlockChecksum(v, cfg):
+    """Config.hs:151 (undefined in the reference): every block carries the xxh32 of its data behind it."""
+    return BlockConfig(cfg.blockSize, v)
 
 
 def setFrameEndMark(v, cfg):
@@ -279,6 +316,14 @@ class MultiEngine:
             lib.mi355lz4_multi_last_error.restype = C.c_char_p
             raise LZ4Error("%s failed (%d): %s" % (what, rc, (lib.mi355lz4_multi_last_error() or b"").decode()))
 
+    def set_block_checksum(self, on):
+        """Block checksums on every engine of the handle (include/mi355lz4.h, mi355lz4_set_block_checksum)."""
+        lib.mi355lz4_multi_engine.restype = C.c_void_p
+        for i in range(self.n):
+            _check(lib.mi355lz4_set_block_checksum(C.c_void_p(lib.mi355lz4_multi_engine(self._h, i)), int(bool(on))),
+                   "set_block_checksum")
+        self._block_checksum = bool(on)
+
     def set_decoder(self, variant):
         lib.mi355lz4_multi_engine.restype = C.c_void_p
         for i in range(self.n):
@@ -290,7 +335,7 @@ class MultiEngine:
         arrs = [np.frombuffer(bytes(b), dtype=np.uint8) if not isinstance(b, np.ndarray) else b for b in blocks]
         ptrs = (_u8p * max(n, 1))(*[a.ctypes.data_as(_u8p) for a in arrs])
         lens = np.array([a.size for a in arrs], dtype=np.int32)
-        cap = int(sum(compress_bound(int(x)) + header_kind for x in lens)) + 16
+        cap = int(sum(compress_bound(int(x)) + header_kind + 4 for x in lens)) + 16
         out = np.empty(cap, dtype=np.uint8)
         out_len = C.c_size_t()
         flen = np.zeros(max(n, 1), dtype=np.int32)
@@ -308,8 +353,9 @@ class MultiEngine:
         boff = np.zeros(max_blocks + 1, dtype=np.uint64)
         ulen = np.zeros(max_blocks + 1, dtype=np.int32)
         nb = C.c_int()
-        _check(lib.mi355lz4_index_host(src.ctypes.data_as(_u8p), src.size, header_kind, fixed_uncomp,
-                                       boff.ctypes.data_as(_u64p), ulen.ctypes.data_as(_i32p), max_blocks, C.byref(nb)), "index_host")
+        _check(lib.mi355lz4_index_host_ex(src.ctypes.data_as(_u8p), src.size, header_kind, fixed_uncomp,
+                                          int(getattr(self, "_block_checksum", False)), boff.ctypes.data_as(_u64p),
+                                          ulen.ctypes.data_as(_i32p), max_blocks, C.byref(nb)), "index_host")
         cap = int(ulen[: nb.value].astype(np.int64).clip(min=0).sum()) + 16
         out = np.empty(cap, dtype=np.uint8)
         out_len = C.c_size_t()
@@ -338,6 +384,7 @@ class Engine:
         # engine to one stream instead.
         self._pinned = False
         self._cur_stream = None
+        self._block_checksum = False
         self._follow_torch()
 
     def _follow_torch(self):
@@ -381,6 +428,19 @@ class Engine:
     def set_linked_compress(self, on):
         """Compress calls write ONE linked stream (previous block = dictionary), like the reference's compressor."""
         lib.slz4_engine_set_linked_compress(self._h, int(bool(on)))
+
+    def set_block_checksum(self, on):
+        """Every block carries its xxh32 behind its data: written by the compress calls, verified on the device by every
+        decode call (include/mi355lz4.h, mi355lz4_set_block_checksum; Config.hs setBlockChecksum)."""
+        _check(lib.mi355lz4_set_block_checksum(self.ctx, int(bool(on))), "set_block_checksum")
+        self._block_checksum = bool(on)
+
+    def xxh32_device(self, base, off, length, n, seed, out):
+        """out[i] = xxh32(seed) of base[off[i] : off[i] + length[i]] for i < n (uint8 / int64 / int32 / int32 device
+        tensors); asynchronous on the engine's stream."""
+        self._follow_torch()
+        _check(lib.mi355lz4_xxh32_device(self.ctx, _dptr(base), _dptr(off), _dptr(length), int(n), int(seed) & 0xFFFFFFFF,
+                                         _dptr(out)), "xxh32_device")
 
     def set_linked_async(self, max_decoded_block_size):
         """Linked device decodes enqueue only, no host wait (include/mi355lz4.h); 0 = default (wait)."""
@@ -491,7 +551,7 @@ class Engine:
         arrs = [np.frombuffer(bytes(b), dtype=np.uint8) if not isinstance(b, np.ndarray) else b for b in blocks]
         ptrs = (_u8p * max(n, 1))(*[a.ctypes.data_as(_u8p) for a in arrs])
         lens = np.array([a.size for a in arrs], dtype=np.int32)
-        cap = int(sum(compress_bound(int(x)) + header_kind for x in lens)) + 16
+        cap = int(sum(compress_bound(int(x)) + header_kind + 4 for x in lens)) + 16
         out = np.empty(cap, dtype=np.uint8)
         out_len = C.c_size_t()
         flen = np.zeros(max(n, 1), dtype=np.int32)
@@ -510,9 +570,9 @@ class Engine:
         boff = np.zeros(max_blocks + 1, dtype=np.uint64)
         ulen = np.zeros(max_blocks + 1, dtype=np.int32)
         nb = C.c_int()
-        _check(lib.mi355lz4_index_host(src.ctypes.data_as(_u8p), src.size, header_kind, fixed_uncomp,
-                                       boff.ctypes.data_as(_u64p), ulen.ctypes.data_as(_i32p), max_blocks, C.byref(nb)),
-               "index_host")
+        _check(lib.mi355lz4_index_host_ex(src.ctypes.data_as(_u8p), src.size, header_kind, fixed_uncomp,
+                                          int(self._block_checksum), boff.ctypes.data_as(_u64p),
+                                          ulen.ctypes.data_as(_i32p), max_blocks, C.byref(nb)), "index_host")
         cap = int(ulen[: nb.value].astype(np.int64).clip(min=0).sum()) + 16
         out = np.empty(cap, dtype=np.uint8)
         out_len = C.c_size_t()
@@ -535,9 +595,9 @@ class Engine:
         boff = np.zeros(max_blocks + 1, dtype=np.uint64)
         ulen = np.zeros(max_blocks + 1, dtype=np.int32)
         nb = C.c_int()
-        _check(lib.mi355lz4_index_host(src.ctypes.data_as(_u8p), src.size, header_kind, fixed_uncomp,
-                                       boff.ctypes.data_as(_u64p), ulen.ctypes.data_as(_i32p), max_blocks, C.byref(nb)),
-               "index_host")
+        _check(lib.mi355lz4_index_host_ex(src.ctypes.data_as(_u8p), src.size, header_kind, fixed_uncomp,
+                                          int(self._block_checksum), boff.ctypes.data_as(_u64p),
+                                          ulen.ctypes.data_as(_i32p), max_blocks, C.byref(nb)), "index_host")
         cap = int(ulen[: nb.value].astype(np.int64).clip(min=0).sum()) + 16
         out = np.empty(cap, dtype=np.uint8)
         out_len = C.c_size_t()
@@ -626,21 +686,21 @@ def _run(fn, *args, views=False):
 def compressChunks(cfg, speed, arrays, engine):
     """Streamly.LZ4.compressChunks (reference src/Streamly/LZ4.hs:94-100)."""
     data, lens, n = _pack(arrays)
-    return _run(lib.slz4_compress_chunks, engine._h, cfg.blockSize, int(speed), data.ctypes.data_as(_u8p),
+    return _run(lib.slz4_compress_chunks, engine._h, cfg._kind, int(speed), data.ctypes.data_as(_u8p),
                 lens.ctypes.data_as(_u64p), n)
 
 
 def resizeChunks(cfg, conf, arrays):
     """Streamly.Internal.LZ4.resizeChunksD (reference src/Streamly/Internal/LZ4.hs:432-523).  Host only."""
     data, lens, n = _pack(arrays)
-    return _run(lib.slz4_resize_chunks, cfg.blockSize, int(conf.hasEndMark), data.ctypes.data_as(_u8p),
+    return _run(lib.slz4_resize_chunks, cfg._kind, int(conf.hasEndMark), data.ctypes.data_as(_u8p),
                 lens.ctypes.data_as(_u64p), n)
 
 
 def decompressChunksRaw(cfg, arrays, engine):
     """Streamly.Internal.LZ4.decompressChunksRawD (reference src/Streamly/Internal/LZ4.hs:539-567)."""
     data, lens, n = _pack(arrays)
-    return _run(lib.slz4_decompress_chunks_raw, engine._h, cfg.blockSize, data.ctypes.data_as(_u8p),
+    return _run(lib.slz4_decompress_chunks_raw, engine._h, cfg._kind, data.ctypes.data_as(_u8p),
                 lens.ctypes.data_as(_u64p), n)
 
 
@@ -649,8 +709,19 @@ def decompressChunks(cfg, arrays, engine, conf=defaultFrameConfig, views=False):
     views=True returns the arrays as memoryviews into one result buffer (the reference's arrays are such slices) instead
     of one bytes object -- one copy -- per array."""
     data, lens, n = _pack(arrays)
-    return _run(lib.slz4_decompress_chunks, engine._h, cfg.blockSize, int(conf.hasEndMark), data.ctypes.data_as(_u8p),
+    return _run(lib.slz4_decompress_chunks, engine._h, cfg._kind, int(conf.hasEndMark), data.ctypes.data_as(_u8p),
                 lens.ctypes.data_as(_u64p), n, views=views)
+
+
+def decompressChunksStream(cfg, arrays, engine, conf=defaultFrameConfig):
+    """decompressChunks array at a time, as a consumer of the stream sees it: returns (the arrays delivered, None), or
+    (the arrays delivered before the stream raised, the LZ4Error it raised)."""
+    data, lens, n = _pack(arrays)
+    h = C.c_void_p()
+    rc = lib.slz4_decompress_chunks_stream(engine._h, cfg._kind, int(conf.hasEndMark), data.ctypes.data_as(_u8p),
+                                           lens.ctypes.data_as(_u64p), n, C.byref(h))
+    err = LZ4Error((lib.slz4_last_error() or b"").decode("utf-8", "replace")) if rc != 0 else None
+    return _unpack(h), err
 
 
 def decompressChunksWith(arrays, engine):
