@@ -7,6 +7,7 @@
 #include "../../include/lz4.h"
 
 #include "kernels.h"
+#include "linked_plan.hpp"
 
 #include <hip/hip_runtime.h>
 
@@ -174,11 +175,8 @@ struct mi355lz4_ctx {
     int nSeg = 0;
     unsigned long long segTick = 0;
     int linkedAsyncCap = 0;                // > 0: linked device decodes do not wait on the host (mi355lz4_set_linked_async)
-    // the run-in decode adapts to what the engine's streams are like (the calls that follow one are, as a rule, more of the same):
-    bool runinLong = false;                // a call was given up with the default run-in (chains of pieces to redo): the long one from here on
-    int runinLongOk = 0;                   // ... calls in a row that finished with it (after RUNIN_LONG_PROBE the default is tried again)
-    int runinSkip = 0;                     // ... and given up with the long one too: this many linked decodes go straight to the pointer pass
-    int linkedPath = -1;                   // diagnostics: how the last linked call was finished (mi355lz4_debug_runin_state)
+    RuninState runin;                      // the run-in decode's adaptive state (linked_plan.hpp)
+    int linkedPath = -1;                   // diagnostics: how the last linked call was finished (LinkedPath; mi355lz4_debug_runin_state)
     int runinShareE6 = -1;                 // diagnostics: the dictionary share the last linked call sampled, in millionths (-1: none)
     int segMode = -1;                      // small-batch segments per block: -1 auto, 0 off, k forced (mi355lz4_set_segments)
     hipEvent_t linkEvent = nullptr;        // end of the last linked decode's use of linkBuf / tolPool / tolMeta / ptrBuf
@@ -428,16 +426,15 @@ extern "C" int mi355lz4_debug_stats(mi355lz4_ctx *c, int enable, unsigned long l
     return MI355LZ4_OK;
 }
 
-// Diagnostic hook (not part of the public header): the run-in decode's adaptive state {runinLong, runinLongOk, runinSkip} and, in
+// Diagnostic hook (not part of the public header): the run-in decode's adaptive state {longRun, longOk, skip} (RuninState) and, in
 // get[3], the dictionary share the last linked call sampled (millionths; -1: none) and, in get[4], how the last linked call was
-// finished: 0 no block needed its dictionary, 1 short runs walked, 2 run-in decode, 3 long run-in decode, 4 run-in decode given up
-// and the lists/pointer passes, 5 the lists/pointer passes (or the walk) at once, 6 big blocks by the workgroup form against guessed dictionaries.  get (may be null, 5 ints) receives it; set (may
-// be null, 3 ints) replaces the state.  Lets a test drive default -> long -> skip -> probe.
+// finished (LinkedPath): 0 None, 1 Runs, 2 RunIn, 3 RunInLong, 4 RunInGivenUp, 5 Pointer, 6 Big.  get (may be null, 5 ints) receives
+// it; set (may be null, 3 ints) replaces the state.  Lets a test drive default -> long -> skip -> probe.
 extern "C" int mi355lz4_debug_runin_state(mi355lz4_ctx *c, int *get, const int *set)
 {
     if (!c) return fail(MI355LZ4_E_ARG, "null ctx");
-    if (get) { get[0] = c->runinLong ? 1 : 0; get[1] = c->runinLongOk; get[2] = c->runinSkip; get[3] = c->runinShareE6; get[4] = c->linkedPath; }
-    if (set) { c->runinLong = set[0] != 0; c->runinLongOk = set[1]; c->runinSkip = set[2]; }
+    if (get) { get[0] = c->runin.longRun ? 1 : 0; get[1] = c->runin.longOk; get[2] = c->runin.skip; get[3] = c->runinShareE6; get[4] = c->linkedPath; }
+    if (set) { c->runin.longRun = set[0] != 0; c->runin.longOk = set[1]; c->runin.skip = set[2]; }
     return MI355LZ4_OK;
 }
 
@@ -662,435 +659,263 @@ static int linked_finish(mi355lz4_ctx *c)
     return check_launch("decode launch");
 }
 
-// Whether a call of decoder variant 0 takes the workgroup-per-block decoder (decode_cu.hpp): a CU decodes a 64 KiB block in 0.09-0.11 ms
-// where a wavefront takes 0.2-0.3, but 19 wavefronts share a CU.  Measured (device-resident, ms, workgroup / wavefront form; lzsynth):
-// 64 KiB blocks: 256: 0.10 / 0.20, 512: 0.20 / 0.21, 768: 0.29 / 0.21; 16 KiB: 256: 0.045 / 0.074, 512: 0.083 / 0.075; 4 KiB: 160: 0.042 /
-// 0.037 (a workgroup's fixed costs are 28 us a block).  So: up to one block per CU when blocks are not tiny, up to two when they are big --
-// judged by the compressed bytes per block, which is all the host knows.  MI355LZ4_CU_BLOCKS = n: up to n blocks whatever their size, 0 = never.
-static bool cu_auto(int nBlocks, uint64_t framedLen)
+// The steps of a linked decode return STEP_NEXT or what the call returns; ending, they order the link scratch behind what they queued.
+// pinStat words: 0-7 the summary, 8-9 the share sample, 10-11 big-pass flags, 12-13 runCtl; _linked_end_last: 8-11 its own (below).
+constexpr int STEP_NEXT = 1;
+static int link_done(mi355lz4_ctx *c) { link_scratch_release(c); return check_launch("decode launch"); }
+static int link_fail(mi355lz4_ctx *c, int rc) { link_scratch_release(c); return rc; }
+#define LINK_TRY(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) return link_fail(c, fail(MI355LZ4_E_HIP, "%s: %s", #x, hipGetErrorString(e_))); } while (0)
+static int link_summary(mi355lz4_ctx *c, const LinkStat &st, int nBlocks)
 {
-    static const int forced = [] {
-        const char *e = getenv("MI355LZ4_CU_BLOCKS");
-        return e ? atoi(e) : -1;
-    }();
-    if (forced >= 0) return nBlocks <= forced;
-    const uint64_t avg = framedLen / (uint64_t)(nBlocks > 0 ? nBlocks : 1);
-    if (avg < 3072) return false;
-    return nBlocks <= 256 || (nBlocks <= 512 && avg >= 16384);
+    if (st.count == 0) return link_done(c);
+    const int first = (int)st.first, last = (int)st.last;
+    if (first < 0 || last >= nBlocks || first > last)
+        return link_fail(c, fail(MI355LZ4_E_HIP, "decompress: bad failure range %d..%d", first, last));
+    return STEP_NEXT;
 }
-
-// run-in decode of long linked streams: blocks of 64 KiB of run-in, and the span (in 64 KiB) from which it is the default
-#ifndef RUNIN_DEFAULT_64K
-#define RUNIN_DEFAULT_64K 11
-#endif
-#ifndef RUNIN_MIN_SPAN
-#define RUNIN_MIN_SPAN 9216
-#endif
-#define RUNIN_ROUNDS 8          // launches of pieces to be redone before the call is left to the pointer pass
-#define RUNIN_LONG_64K 17      // the long run-in (blocks of 64 KiB): taken after the default one gave a call up for what the data is like
-#define RUNIN_LONG_PROBE 32    // calls in a row finished with the long run-in before the default is tried again
-#define RUNIN_BACKOFF 16       // linked calls that skip the run-in decode after the long one gave a call up as well
-#define RUNIN_SHARE_LONG 0.306  // sampled share of bytes taken directly from the block before (k_dict_share) from which the long run-in is taken ...
-#define RUNIN_SHARE_NEVER 0.60  // ... and from which the stream is taken to never forget its dictionary (pointer pass)
-static int decode_device_impl(mi355lz4_ctx *c, const uint8_t *framed, uint64_t framedLen, const uint64_t *blockOff,
-                              int nBlocks, int headerKind, int fixedUncomp, int linked, uint8_t *out,
-                              const uint64_t *outOff, const int32_t *outCap, int32_t *result, const uint8_t *dict0,
-                              uint32_t dict0Len, const int32_t *streamFirst, int nStreams, int lookBack,
-                              bool splitOk, bool deferEnd, const int32_t *ckFail)
+// The big-block path's scratch: a 64 KiB snapshot per block (ptrBuf) and, in tolMeta, 64 KiB of zeros, the flags and the results;
+// pass 1: the first launch makes the path's first pass.  Scratch that cannot be had is no error: the call takes the other paths.
+static bool big_scratch(mi355lz4_ctx *c, DecodeArgs &a, int pass)
 {
-    if (!c) return fail(MI355LZ4_E_ARG, "null ctx");
-    if (c->plan.active) return fail(MI355LZ4_E_ARG, "a linked decode begun with mi355lz4_decompress_linked_begin is still open");
-    if (nBlocks < 0 || (headerKind != 4 && headerKind != 8) || fixedUncomp < 0)
-        return fail(MI355LZ4_E_ARG, "decompress_batch_device: bad arguments");
-    if (nBlocks == 0) return MI355LZ4_OK;
-    if (!framed || !blockOff || !outOff || !result) return fail(MI355LZ4_E_ARG, "decompress_batch_device: null pointer");
-    HIP_TRY(hipSetDevice(c->device));
-    DecodeArgs a;
-    a.framed = framed; a.framedLen = framedLen; a.blockOff = blockOff; a.nBlocks = nBlocks;
-    a.headerKind = headerKind; a.fixedUncomp = fixedUncomp; a.linked = linked ? 1 : 0;
-    a.out = out; a.outOff = outOff; a.outCap = outCap; a.result = result;
-    a.dict0 = dict0; a.dict0Len = dict0Len;
-    a.streamFirst = streamFirst; a.nStreams = nStreams; a.lookBack = lookBack;
-    a.tolPool = nullptr; a.tolRegions = 0; a.tolPer = 0; a.tolCounter = nullptr; a.tolRegion = a.tolCount = a.tolSize = nullptr;
-    a.linkStat = nullptr; a.segFirst = 0; a.segEnd = nBlocks; a.ptr = nullptr; a.ptrCap = 0; a.ptrCtl = nullptr;
-    a.ptrBad = nullptr;
-    a.asyncGate = 0;
-    a.onlyBlk = -1;
-    a.tokList = nullptr; a.tokCnt = nullptr; a.runList = nullptr; a.runCap = 0; a.cuDbg = c->cuDbg; a.cuBail = c->decoder == 0;
-    a.cuSnap = nullptr; a.cuFlags = nullptr; a.cuRes = nullptr; a.cuPass = 0;
-    a.ring = nullptr; a.ringStride = 0; a.zeroPage = nullptr; a.runPiece = 0; a.runIn = 0; a.runSpin = 0; a.runRound = 0;
-    a.runRes = nullptr; a.runInfo = nullptr; a.runDirty = nullptr; a.runCtl = nullptr;
-    a.ckFail = ckFail;
-    const size_t nFlags = streamFirst ? (size_t)(nStreams > 0 ? nStreams : 1) : 1;
-    int r;
-    if (linked) {
-        link_scratch_acquire(c);
-        // the standalone pass counts the blocks that need their dictionary: {count, first, last, -, largest capacity}
-        if ((r = dev_reserve(c->linkBuf, 64 + ptr_ctl_bytes() + 4 * nFlags)) || (r = pin_reserve(c->pinStat, 64))) return r;
-        a.linkStat = (uint32_t *)c->linkBuf.p;
-        HIP_TRY(hipMemsetAsync(a.linkStat, 0, 32, c->stream));
-        HIP_TRY(hipMemsetAsync(a.linkStat + 1, 0xff, 4, c->stream));
+    const size_t metaBytes = 65536 + ((size_t)a.nBlocks * 2 + 4) * sizeof(uint32_t);
+    const bool ok = dev_reserve(c->ptrBuf, (size_t)a.nBlocks * 65536u) == 0 && dev_reserve(c->tolMeta, metaBytes) == 0 &&
+                    hipMemsetAsync(c->tolMeta.p, 0, metaBytes, c->stream) == hipSuccess;
+    (void)hipGetLastError();
+    if (!ok) return false;
+    uint8_t *meta = (uint8_t *)c->tolMeta.p;
+    a.zeroPage = meta; a.cuSnap = (uint8_t *)c->ptrBuf.p; a.cuPass = pass;
+    a.cuFlags = (uint32_t *)(meta + 65536); a.cuRes = (int32_t *)(meta + 65536 + ((size_t)a.nBlocks + 4) * sizeof(uint32_t));
+    return true;
+}
+// Big blocks (big_arm): every dependent block by the workgroup form against a GUESS of its dictionary -- zeros, then its predecessor's
+// last 64 KiB a pass ago -- until a pass changes none (k_decode_cu_linked).  A block of 1 MiB forgets a wrong dictionary long before its
+// end: two passes do as a rule, the first maybe made by the first launch (pre).  Anything the form cannot take (a failing block,
+// CU_REDO, snapshots that do not settle in BIG_PASSES) leaves the call to the next steps: the results so far live in scratch.
+static int linked_big(mi355lz4_ctx *c, DecodeArgs &a, const DecodeKnobs &k, const LinkStat &st, BigArm arm, bool pre)
+{
+    bool late = false;
+    if (arm != BigArm::No && !pre) {           // (also when the scratch could not be had before the first launch)
+        late = big_takes(k, st) && big_scratch(c, a, 0);
+        (void)hipGetLastError();
     }
-    // Big linked blocks (the path behind the first pass, below): armed here, so that the first launch goes straight on with that
-    // path's pass 1 for the blocks that do not decode on their own.  What the host knows beforehand is the compressed size: from half
-    // the path's block size on (a stream of blocks of half that size at a ratio of 2 would otherwise pay a pass it has no use for:
-    // +0.85 ms for 512 blocks of 256 KiB); big blocks that compress better than that are armed behind the first pass (bigLate).
-    bool bigPre = false, bigEligible = false;
-    {
-        const char *envBig = getenv("MI355LZ4_LINKED_BIG");
-        const long bigKiB = envBig ? atol(envBig) : 512;
-        const bool plainBig = !getenv("MI355LZ4_LINKED_PTR") && !getenv("MI355LZ4_LINKED_POOL_BLOCKS") && !getenv("MI355LZ4_LINKED_RUNS") &&
-                              !getenv("MI355LZ4_LINKED_RUNIN") && !getenv("MI355LZ4_LINKED_ASYNC");
-        bigEligible = linked && bigKiB > 0 && plainBig && !streamFirst && !splitOk && !deferEnd && lookBack >= 0 && !dict0 && c->decoder == 0 &&
-                      !c->stats && c->linkedAsyncCap <= 0 && nBlocks >= 2 && nBlocks <= 512 && cu_auto(nBlocks, framedLen);
-        if (bigEligible && framedLen / (uint64_t)nBlocks >= (uint64_t)bigKiB * 1024u / 2u) {
-            const size_t metaBytes = 65536 + ((size_t)nBlocks * 2 + 4) * sizeof(uint32_t);
-            if (dev_reserve(c->ptrBuf, (size_t)nBlocks * 65536u) == 0 && dev_reserve(c->tolMeta, metaBytes) == 0 &&
-                hipMemsetAsync(c->tolMeta.p, 0, metaBytes, c->stream) == hipSuccess) {
-                uint8_t *meta = (uint8_t *)c->tolMeta.p;
-                a.zeroPage = meta; a.cuSnap = (uint8_t *)c->ptrBuf.p;
-                a.cuFlags = (uint32_t *)(meta + 65536); a.cuRes = (int32_t *)(meta + 65536 + ((size_t)nBlocks + 4) * sizeof(uint32_t));
-                a.cuPass = 1;
-                bigPre = true;
-            }
-            (void)hipGetLastError();
+    if (!pre && !late) return STEP_NEXT;
+    if (big_takes(k, st)) {
+        uint32_t *flags = (uint32_t *)c->pinStat.p + 10;
+        bool settled = false; int passes = 0;
+        for (int pass = 1; pass <= BIG_PASSES && !settled; pass++) {
+            a.cuPass = pass; passes = pass;
+            launch_cu_linked(a, pass > 1 || late, c->stream);
+            if (hipGetLastError() != hipSuccess) break;
+            if (pass == 1) continue;                                  // (every snapshot is new after the first pass)
+            LINK_TRY(hipMemcpyAsync(flags, a.cuFlags, 8, hipMemcpyDeviceToHost, c->stream));
+            LINK_TRY(hipStreamSynchronize(c->stream));
+            if (flags[1] != 0) break;                                 // a block this form cannot take
+            settled = flags[0] == 0;
         }
-    }
-    if (c->decoder == 1)
-        launch_decode_seq(a, c->stream);
-#ifdef MI355LZ4_EXPERIMENTS
-    else if (c->decoder == 3 && dev_reserve(c->tokBuf, (size_t)(framedLen >> 1) + 192 + ((size_t)nBlocks + 1) * sizeof(int32_t)) == 0) {
-        // experiment: the parse as a pass of its own (token lists), then the list-driven decoder
-        a.tokCnt = (int32_t *)c->tokBuf.p;
-        a.tokList = (uint8_t *)c->tokBuf.p + ((((size_t)nBlocks + 1) * sizeof(int32_t) + 63) & ~(size_t)63);
-        launch_decode_tok(a, c->stream);
-    }
-#endif
-    else if (!c->stats && (c->decoder == 4 || (c->decoder == 0 && cu_auto(nBlocks, framedLen))))
-        // Calls that do not fill the GPU -- one workgroup per block instead of one wavefront (decode_cu.hpp; cu_auto above says
-        // which calls those are).  (Variant 4 forces it for any number of blocks: the tests.)  A linked call's first pass is this
-        // same standalone decode (decompressChunks always asks for linked = 1, and what this engine's compressor writes are
-        // independent blocks): a block that needs its dictionary fails here as it does there -- 50 us later -- and is counted.
-        launch_decode_cu(a, c->stream);
-    else
-        launch_decode_par(a, c->stats, c->stream);
-    if (!linked) return check_launch("decode launch");
-    // Linked streams.  Whether there is a second pass at all, and over which blocks, is decided here: the
-    // call waits for the standalone pass (a stream of independent blocks pays this wait and nothing else).
-    uint32_t *stat = (uint32_t *)c->pinStat.p;
-    // Asynchronous form (mi355lz4_set_linked_async; MI355LZ4_LINKED_ASYNC=<largest decoded block size> for the tests):
-    // no wait on the host.  The second pass is enqueued over ALL blocks, its kernels return at once when the first
-    // pass counted no dependent block; what the wait would have told -- the range of dependent blocks and the largest
-    // block -- is replaced by the whole call and the caller's bound.  One stream only (the streams call keeps the wait:
-    // its choice between walk and pointer pass needs the counts).
-    int asyncCap = c->linkedAsyncCap;
-    if (const char *e = getenv("MI355LZ4_LINKED_ASYNC")) asyncCap = atoi(e);
-    if (asyncCap > 0 && !streamFirst) {
-        a.asyncGate = 1;
-        stat[0] = (uint32_t)nBlocks; stat[1] = 0; stat[2] = (uint32_t)(nBlocks - 1); stat[3] = (uint32_t)nBlocks;
-        stat[4] = (uint32_t)asyncCap;
-    } else {
-        launch_longest_stream(a, c->stream);
-        HIP_TRY(hipMemcpyAsync(stat, a.linkStat, 32, hipMemcpyDeviceToHost, c->stream));
-        HIP_TRY(hipStreamSynchronize(c->stream));
-    }
-    c->runinShareE6 = -1; c->linkedPath = 0;
-    if (stat[0] == 0) { link_scratch_release(c); return check_launch("decode launch"); }
-    int first = (int)stat[1], last = (int)stat[2];
-    if (first < 0 || last >= nBlocks || first > last) {
-        link_scratch_release(c);          // the first pass is in flight on linkBuf: the next linked call must be ordered behind it
-        return fail(MI355LZ4_E_HIP, "decompress: bad failure range %d..%d", first, last);
-    }
-    // Big blocks (BlockMax1MB / BlockMax4MB streams, Config.hs:109-116), few enough for a CU each: every dependent block by the
-    // workgroup-per-block decoder against a GUESS of its dictionary -- zeros, then what its predecessor's last 64 KiB were a pass ago --
-    // until a pass changes none of those (kernels.hip, k_decode_cu_linked).  A block of 1 MiB forgets a wrong dictionary long before
-    // its end, so two passes do as a rule, and the first of them has been made by the first launch (bigPre, above).
-    // MI355LZ4_LINKED_BIG = 0: never; = n: blocks from n KiB on (default 512: smaller blocks' ends still carry the wrong dictionary,
-    // pass after pass).  Anything the form cannot take (a failing block, CU_REDO, snapshots that do not settle in BIG_PASSES)
-    // leaves the call to the passes below: the results so far live in scratch.
-    bool bigLate = false;
-    if (bigEligible && !bigPre && !a.asyncGate) {
-        const char *envBig = getenv("MI355LZ4_LINKED_BIG");
-        const long bigKiB = envBig ? atol(envBig) : 512;
-        const size_t metaBytes = 65536 + ((size_t)nBlocks * 2 + 4) * sizeof(uint32_t);
-        if ((uint64_t)stat[4] >= (uint64_t)bigKiB * 1024u && dev_reserve(c->ptrBuf, (size_t)nBlocks * 65536u) == 0 &&
-            dev_reserve(c->tolMeta, metaBytes) == 0 && hipMemsetAsync(c->tolMeta.p, 0, metaBytes, c->stream) == hipSuccess) {
-            uint8_t *meta = (uint8_t *)c->tolMeta.p;
-            a.zeroPage = meta; a.cuSnap = (uint8_t *)c->ptrBuf.p;
-            a.cuFlags = (uint32_t *)(meta + 65536); a.cuRes = (int32_t *)(meta + 65536 + ((size_t)nBlocks + 4) * sizeof(uint32_t));
-            bigLate = true;
+        if (settled) {
+            launch_cu_publish(a, c->stream);
+            c->linkedPath = (int)LinkedPath::Big; c->runinShareE6 = passes;   // (diagnostics: Big reports its passes where the others report the sampled share)
+            return link_done(c);
         }
         (void)hipGetLastError();
     }
-    if (bigPre || bigLate) {
-        const char *envBig = getenv("MI355LZ4_LINKED_BIG");
-        const long bigKiB = envBig ? atol(envBig) : 512;
-        if (!a.asyncGate && (uint64_t)stat[4] >= (uint64_t)bigKiB * 1024u) {
-#define BIG_PASSES 6
-#define BIG_TRY(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { link_scratch_release(c); return fail(MI355LZ4_E_HIP, "%s: %s", #x, hipGetErrorString(e_)); } } while (0)
-            bool settled = false;
-            int passes = 0;
-            for (int pass = 1; pass <= BIG_PASSES && !settled; pass++) {
-                a.cuPass = pass; passes = pass;
-                launch_cu_linked(a, pass > 1 || bigLate, c->stream);
-                if (hipGetLastError() != hipSuccess) break;
-                if (pass == 1) continue;                                  // (every snapshot is new after the first pass)
-                BIG_TRY(hipMemcpyAsync(stat + 10, a.cuFlags, 8, hipMemcpyDeviceToHost, c->stream));
-                BIG_TRY(hipStreamSynchronize(c->stream));
-                if (stat[11] != 0) break;                                 // a block this form cannot take
-                settled = stat[10] == 0;
-            }
-            if (settled) {
-                launch_cu_publish(a, c->stream);
-                c->linkedPath = 6; c->runinShareE6 = passes;              // (diagnostics: path 6 reports its passes where the others report the sampled share)
-                link_scratch_release(c);
-                return check_launch("decode launch");
-            }
-#undef BIG_TRY
-            (void)hipGetLastError();
-        }
-        a.zeroPage = nullptr; a.cuSnap = nullptr; a.cuFlags = nullptr; a.cuRes = nullptr; a.cuPass = 0;
+    a.zeroPage = nullptr; a.cuSnap = nullptr; a.cuFlags = nullptr; a.cuRes = nullptr; a.cuPass = 0;
+    return STEP_NEXT;
+}
+// Short runs (runs_take): every run walked by a wave of its own with the exact decoder and its dictionary, from a list of their starts
+static int linked_runs(mi355lz4_ctx *c, DecodeArgs &a, const DecodeCall &d, const EngineMode &m, const DecodeKnobs &k, const LinkStat &st)
+{
+    if (!runs_take(d, m, k, st)) return STEP_NEXT;
+    const int runs = (int)st.runs > 0 ? (int)st.runs : 1;
+    if (int r = dev_reserve(c->tolMeta, ((size_t)runs + 1) * sizeof(int32_t))) return link_fail(c, r);
+    a.runList = (int32_t *)c->tolMeta.p; a.runCap = runs;
+    if (hipMemsetAsync(a.runList, 0, sizeof(int32_t), c->stream) != hipSuccess)
+        return link_fail(c, fail(MI355LZ4_E_HIP, "decompress: the run list could not be cleared"));
+    a.segFirst = (int)st.first; a.segEnd = (int)st.last + 1;
+    launch_linked_runs(a, c->stream);
+    c->linkedPath = (int)LinkedPath::Runs;
+    return link_done(c);
+}
+// Long runs of dependent blocks (a reference-written stream is ONE) in pieces, every piece decoded from a few blocks in front of it
+// ("run-in": by then the dictionary is the true one; checked against what the piece in front wrote, redone where not: kernels.hip,
+// "RUN-IN DECODE").  Serial chain: run-in + piece blocks (0.53 ms per 64 KiB of text); one wave and a ring of two blocks per piece.
+// Not finished (a broken block, rounds that run out, no scratch): finished segments are final, st is taken again for the rest.
+static int linked_runin(mi355lz4_ctx *c, DecodeArgs &a, const DecodeCall &d, const EngineMode &m, const DecodeKnobs &k, LinkStat &st)
+{
+    const int first = (int)st.first, last = (int)st.last, span0 = last - first + 1;
+    uint32_t *pin = (uint32_t *)c->pinStat.p;
+    RuninPlan p = runin_plan(c->runin, d, m, k, span0, st.maxCap);
+    double share = -1;
+    if (p.sample) {
+        const int nS = span0 < 32 ? span0 : 32, step = span0 / nS;
+        a.segFirst = first;
+        bool sampled = hipMemsetAsync(a.linkStat + 8, 0, 8, c->stream) == hipSuccess;
+        if (sampled) launch_dict_share(a, step, nS, c->stream);
+        sampled = sampled && hipMemcpyAsync(pin + 8, a.linkStat + 8, 8, hipMemcpyDeviceToHost, c->stream) == hipSuccess &&
+                  hipStreamSynchronize(c->stream) == hipSuccess;
+        (void)hipGetLastError();
+        if (sampled && pin[9] > 0) { share = (double)pin[8] / (double)pin[9]; c->runinShareE6 = (int)(share * 1e6); }
     }
-    // Few dependent blocks, in short runs (stat[5] = longest run of blocks without output): every run is walked by a
-    // wave of its own with the exact decoder and its dictionary; no lists, no pointers.  MI355LZ4_LINKED_RUNS = longest run
-    // taken this way (default 4; 0 = never; the tests force it for whole streams).
-    {
-        const char *envRuns = getenv("MI355LZ4_LINKED_RUNS");
-        const unsigned runMax = envRuns ? (unsigned)atoi(envRuns) : 4u;
-        const bool plain = !getenv("MI355LZ4_LINKED_PTR") && !getenv("MI355LZ4_LINKED_POOL_BLOCKS");
-        if (!streamFirst && !a.asyncGate && !splitOk && !deferEnd && runMax > 0 && stat[5] >= 1 && stat[5] <= runMax &&
-            (envRuns || plain)) {
-            // the runs' first blocks as a list taken from the first pass's results (stat[6] = how many there are in the call)
-            const int runs = (int)stat[6] > 0 ? (int)stat[6] : 1;
-            if ((r = dev_reserve(c->tolMeta, ((size_t)runs + 1) * sizeof(int32_t)))) { link_scratch_release(c); return r; }
-            a.runList = (int32_t *)c->tolMeta.p; a.runCap = runs;
-            if (hipMemsetAsync(a.runList, 0, sizeof(int32_t), c->stream) != hipSuccess) {
-                link_scratch_release(c);
-                return fail(MI355LZ4_E_HIP, "decompress: the run list could not be cleared");
+    if (p.use) runin_after_sample(p, k, span0, share);
+    if (!p.use) return STEP_NEXT;
+    a.runSpin = k.runinSpin;
+    const size_t nPiecesMax = ((size_t)p.segBlocks + p.piece - 1) / p.piece, metaBytes = 65536 + (size_t)p.segBlocks * 4 + nPiecesMax * 20 + 64;
+    bool done = false;
+    if (dev_reserve(c->ptrBuf, nPiecesMax * 2u * p.stride) == 0 && dev_reserve(c->tolMeta, metaBytes) == 0) {
+        uint8_t *meta = (uint8_t *)c->tolMeta.p, *tail = meta + 65536 + (size_t)p.segBlocks * 4;
+        a.zeroPage = meta; a.ring = (uint8_t *)c->ptrBuf.p; a.ringStride = p.stride; a.runPiece = p.piece; a.runIn = p.runIn;
+        a.runRes = (int32_t *)(meta + 65536); a.runInfo = (int32_t *)tail;
+        a.runDirty = (uint32_t *)(tail + nPiecesMax * 16); a.runCtl = (uint32_t *)(tail + nPiecesMax * 20);
+        // (a kernel that did not launch must not read as "nothing left to do": runCtl was zeroed by the host)
+        uint32_t *ctl = pin + 12;
+        LINK_TRY(hipMemsetAsync(meta, 0x00, 65536, c->stream));
+        done = true;
+        for (int s0 = first; s0 <= last && done; s0 += p.segBlocks) {
+            a.segFirst = s0; a.segEnd = (s0 + p.segBlocks < last + 1) ? s0 + p.segBlocks : last + 1;
+            LINK_TRY(hipMemsetAsync(a.runCtl, 0, 8, c->stream));
+            launch_runin_decode(a, c->stream);
+            bool segDone = false, launched = hipGetLastError() == hipSuccess;
+            for (int round = 0; round < RUNIN_ROUNDS && !segDone && launched; round++) {
+                a.runRound = round;
+                if (round) LINK_TRY(hipMemsetAsync(a.runCtl, 0, 4, c->stream));
+                launch_runin_fix(a, c->stream);
+                if (hipGetLastError() != hipSuccess) { launched = false; break; }
+                LINK_TRY(hipMemcpyAsync(ctl, a.runCtl, 8, hipMemcpyDeviceToHost, c->stream));
+                LINK_TRY(hipStreamSynchronize(c->stream));
+                if (ctl[1] != 0) break;                 // a block failed with the dictionary it got, or a chain of dirty pieces
+                segDone = ctl[0] == 0;
             }
-            a.segFirst = first; a.segEnd = last + 1;
-            launch_linked_runs(a, c->stream);
-            c->linkedPath = 1;
-            link_scratch_release(c);
-            return check_launch("decode launch");
-        }
-    }
-    // Long runs of dependent blocks -- a stream written by the reference's compressor is ONE such run -- in pieces of
-    // consecutive blocks, every piece decoded from a few blocks in front of it ("run-in": by the time the wave reaches
-    // the piece the dictionary it carries is the true one; checked against what the piece in front wrote, redone where it
-    // is not: kernels.hip, "RUN-IN DECODE").  A call's serial chain is run-in + piece blocks (0.53 ms per 64 KiB of text), one
-    // wave per piece, a ring of two blocks of scratch per piece.
-    // MI355LZ4_LINKED_RUNIN: 0 = never, 1 = whenever it applies (the tests); MI355LZ4_LINKED_RUNIN_BLOCKS: blocks of
-    // run-in; MI355LZ4_LINKED_RUNIN_PIECE: blocks per piece (default: as many as give every piece a wave slot of its own).
-    {
-        const char *envRun = getenv("MI355LZ4_LINKED_RUNIN"), *envPiece = getenv("MI355LZ4_LINKED_RUNIN_PIECE"),
-                   *envBlocks = getenv("MI355LZ4_LINKED_RUNIN_BLOCKS");
-        const bool plain = !getenv("MI355LZ4_LINKED_PTR") && !getenv("MI355LZ4_LINKED_POOL_BLOCKS") && !getenv("MI355LZ4_LINKED_RUNS");
-        const int span0 = last - first + 1;
-        const uint64_t per64 = ((uint64_t)stat[4] + 65535u) / 65536u > 0 ? ((uint64_t)stat[4] + 65535u) / 65536u : 1u;
-        const uint64_t stride = per64 * 65536u;
-        // (the engine's own linked compressor probes every position and takes half of a text block from the block before it, the
-        // reference's a third: its streams forget a dictionary after 9 to 15 blocks instead of 5 to 12 and take the long run-in,
-        // which pays from twice the span)
-        // (the state decays with EVERY linked call that gets here, whatever path it then takes: an engine whose later streams are
-        // shorter than the long run-in's threshold would otherwise never try the default again)
-        if (!envRun && c->runinLong && ++c->runinLongOk >= RUNIN_LONG_PROBE) { c->runinLong = false; c->runinLongOk = 0; }
-        bool longRun = c->runinLong && !envRun;
-        // (a range begun with mi355lz4_decompress_linked_begin that has no seam to wait for -- the stream's first range --
-        // is finished here like a plain call: _end and _end_last then find nothing left to do)
-        // (a handful of huge blocks has the bytes but not the pieces: at least 64 dependent blocks; and a piece's ring is two
-        // strides, so strides beyond 1 GiB -- one piece would pass the 2 GiB the rings may take -- stay with the pointer pass)
-        bool useRunIn = !streamFirst && !a.asyncGate && (!(splitOk || deferEnd) || lookBack == 0) &&
-                        (envRun ? atoi(envRun) != 0
-                                : (plain && span0 >= 64 && 2u * stride <= ((uint64_t)1 << 31) &&
-                                   (uint64_t)span0 * per64 >= (longRun ? 2 * RUNIN_MIN_SPAN : RUNIN_MIN_SPAN)));
-        if (useRunIn && !envRun && c->runinSkip > 0) { c->runinSkip--; useRunIn = false; }
-        // How long the stream remembers a missing dictionary is read off the DATA before the first try (what the engine has learnt
-        // from calls given up -- above -- stays as the second opinion): over 32 blocks spread over the span, the share of the bytes of
-        // a block's first 1024 sequences that matches take directly from the block before it (k_dict_share: tokens only, 0.1 ms; a
-        // block's head leans on the block before it more than its body: whole blocks give 0.065 / 0.077 where the heads give 0.29 /
-        // 0.32).  Measured (scripts/runin_share.py): the reference's linked text 0.291-0.292 (forgotten after 5 to 12 blocks: the
-        // default run-in), the engine's own linked text 0.321-0.325 (9 to 15 blocks: the long one), Python sources written by the
-        // reference 0.19, noise with a period just under 64 KiB 0.9 (never: pointer pass).  The two text writers are 10 % apart --
-        // a threshold between them is a calibration on two generators, not a law; a stream on the wrong side of it costs what it
-        // cost before this rule (the default run-in given up once, or the long one where the default would have done).
-        if (useRunIn && !envRun) {
-            const int nS = span0 < 32 ? span0 : 32, step = span0 / nS;
-            a.segFirst = first;
-            bool sampled = hipMemsetAsync(a.linkStat + 8, 0, 8, c->stream) == hipSuccess;
-            if (sampled) launch_dict_share(a, step, nS, c->stream);
-            sampled = sampled && hipMemcpyAsync(stat + 8, a.linkStat + 8, 8, hipMemcpyDeviceToHost, c->stream) == hipSuccess &&
-                      hipStreamSynchronize(c->stream) == hipSuccess;
-            (void)hipGetLastError();
-            if (sampled && stat[9] > 0) {
-                const double share = (double)stat[8] / (double)stat[9];
-                c->runinShareE6 = (int)(share * 1e6);
-                if (share >= RUNIN_SHARE_NEVER) useRunIn = false;
-                else if (share >= RUNIN_SHARE_LONG) longRun = true;
-                if (longRun && (uint64_t)span0 * per64 < 2 * RUNIN_MIN_SPAN) useRunIn = false;
-            }
-        }
-        if (useRunIn) {
-            // run-in length: on text the 5th to 12th block of 64 KiB is the first without a byte of the missing dictionary
-            // (scripts/runin_sim.py); bigger blocks carry it further in bytes -- 256 KiB: 4 blocks, 1 MiB: 2, measured
-            const uint64_t run64 = longRun ? RUNIN_LONG_64K : RUNIN_DEFAULT_64K;
-            int runIn = (envBlocks && atoi(envBlocks) > 0) ? atoi(envBlocks)
-                        : (per64 == 1 ? (int)run64 : (int)((run64 + per64) / per64) + 1);
-            if (runIn > 64) runIn = 64;
-            // pieces: one wave slot each (256 CUs x 16 waves), and at most 2 GiB of rings
-            uint64_t maxPieces = ((uint64_t)1 << 31) / (2u * stride);
-            if (maxPieces < 1) maxPieces = 1;
-            if (maxPieces > 4096) maxPieces = 4096;
-            int piece = (int)(((uint64_t)span0 + maxPieces - 1) / maxPieces);
-            if (envPiece && atoi(envPiece) > 0) piece = atoi(envPiece);
-            if (piece < 1) piece = 1;
-            const char *envSpin = getenv("MI355LZ4_LINKED_RUNIN_SPIN");
-            a.runSpin = envSpin ? atoi(envSpin) : 10000;
-            int segBlocks = (int)((maxPieces * (uint64_t)piece < (uint64_t)span0) ? maxPieces * (uint64_t)piece : (uint64_t)span0);
-            const size_t nPiecesMax = ((size_t)segBlocks + piece - 1) / piece;
-            const size_t metaBytes = 65536 + (size_t)segBlocks * 4 + nPiecesMax * 20 + 64;
-            bool done = false;
-            if (dev_reserve(c->ptrBuf, nPiecesMax * 2u * stride) == 0 && dev_reserve(c->tolMeta, metaBytes) == 0) {
-                uint8_t *meta = (uint8_t *)c->tolMeta.p;
-                a.zeroPage = meta; a.ring = (uint8_t *)c->ptrBuf.p; a.ringStride = stride; a.runPiece = piece; a.runIn = runIn;
-                a.runRes = (int32_t *)(meta + 65536);
-                a.runInfo = (int32_t *)(meta + 65536 + (size_t)segBlocks * 4);
-                a.runDirty = (uint32_t *)(meta + 65536 + (size_t)segBlocks * 4 + nPiecesMax * 16);
-                a.runCtl = (uint32_t *)(meta + 65536 + (size_t)segBlocks * 4 + nPiecesMax * 20);
-                // (a failure in here leaves the linked scratch to the next call like every other error path: RUNIN_TRY; and a kernel
-                // that did not launch must not read as "nothing left to do": runCtl was zeroed by the host)
-#define RUNIN_TRY(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { link_scratch_release(c); return fail(MI355LZ4_E_HIP, "%s: %s", #x, hipGetErrorString(e_)); } } while (0)
-                RUNIN_TRY(hipMemsetAsync(meta, 0x00, 65536, c->stream));
-                done = true;
-                for (int s0 = first; s0 <= last && done; s0 += segBlocks) {
-                    a.segFirst = s0; a.segEnd = (s0 + segBlocks < last + 1) ? s0 + segBlocks : last + 1;
-                    RUNIN_TRY(hipMemsetAsync(a.runCtl, 0, 8, c->stream));
-                    launch_runin_decode(a, c->stream);
-                    bool segDone = false, launched = hipGetLastError() == hipSuccess;
-                    for (int round = 0; round < RUNIN_ROUNDS && !segDone && launched; round++) {
-                        a.runRound = round;
-                        if (round) RUNIN_TRY(hipMemsetAsync(a.runCtl, 0, 4, c->stream));
-                        launch_runin_fix(a, c->stream);
-                        if (hipGetLastError() != hipSuccess) { launched = false; break; }
-                        RUNIN_TRY(hipMemcpyAsync(stat, a.runCtl, 8, hipMemcpyDeviceToHost, c->stream));
-                        RUNIN_TRY(hipStreamSynchronize(c->stream));
-                        if (stat[1] != 0) break;                 // a block failed with the dictionary it got, or a chain of dirty pieces
-                        segDone = stat[0] == 0;
-                    }
-                    if (!launched) { stat[1] = 1u; segDone = false; }   // (left to the passes below, like a broken block)
-                    done = segDone;
-                    // given up for what the DATA is like (chains of pieces to redo, rounds that do not end), not for a broken block:
-                    // the engine's next calls take the long run-in, or -- that was the long one -- RUNIN_BACKOFF of them do not try
-                    if (!segDone && !(stat[1] & 1u) && !envRun) {
-                        if (!longRun) c->runinLong = true;
-                        else c->runinSkip = RUNIN_BACKOFF;
-                        c->runinLongOk = 0;
-                    }
-                    if (segDone) launch_runin_publish(a, c->stream);
-                }
-            }
-            (void)hipGetLastError();                             // (only a failed reservation is left to swallow here)
-            a.ring = nullptr; a.zeroPage = nullptr; a.runRes = nullptr; a.runCtl = nullptr; a.runInfo = nullptr; a.runDirty = nullptr;
-            a.runPiece = 0; a.runIn = 0;
-            c->linkedPath = done ? (longRun ? 3 : 2) : 4;
-            if (done) { link_scratch_release(c); return check_launch("decode launch"); }
-            // Not finished this way (a broken block, rounds that run out, no scratch): the segments that did finish are final,
-            // the one that did not has the first pass's results still; its blocks go through the passes below
-            a.segFirst = 0; a.segEnd = nBlocks;
-            RUNIN_TRY(hipMemsetAsync(a.linkStat, 0, 32, c->stream));
-            RUNIN_TRY(hipMemsetAsync(a.linkStat + 1, 0xff, 4, c->stream));
-            launch_link_stat(a, c->stream);
-            RUNIN_TRY(hipMemcpyAsync(stat, a.linkStat, 32, hipMemcpyDeviceToHost, c->stream));
-            RUNIN_TRY(hipStreamSynchronize(c->stream));
-#undef RUNIN_TRY
-            if (stat[0] == 0) { link_scratch_release(c); return check_launch("decode launch"); }
-            first = (int)stat[1]; last = (int)stat[2];
-            if (first < 0 || last >= nBlocks || first > last) {
-                link_scratch_release(c);
-                return fail(MI355LZ4_E_HIP, "decompress: bad failure range %d..%d", first, last);
-            }
+            done = segDone;
+            if (segDone) launch_runin_publish(a, c->stream);
+            else runin_given_up(c->runin, p, k, launched ? ctl[1] : 1u);
         }
     }
-    // Lists of deferred matches for up to POOL_BLOCKS dependent blocks at a time (64 KiB each: one byte per output
-    // byte) and source pointers for up to PTR_BLOCKS of them (four bytes per output byte); without the lists the
-    // blocks are walked one after the other.  (Read per call: the tests shrink both to reach every seam.)
-    const char *envPool = getenv("MI355LZ4_LINKED_POOL_BLOCKS"), *envPtr = getenv("MI355LZ4_LINKED_PTR"),
-               *envSeg = getenv("MI355LZ4_LINKED_PTR_BLOCKS");
-    if (c->linkedPath != 4) c->linkedPath = 5;
-    const int poolMax = envPool ? atoi(envPool) : 16384;
-    const int ptrMax = (envSeg && atoi(envSeg) > 0) ? atoi(envSeg) : 4096;
-    const bool usePtr = !envPtr || atoi(envPtr) != 0;
-    // Many short streams are walked side by side, one wavefront per stream, faster than their bytes are resolved
-    // through pointers: a walk costs ~0.42 ms per dependent block of the longest stream (up to ~5000 streams at a
-    // time), the pointer passes ~0.55 ms + 1.15 us per dependent block of the call (MI355X, text-like data).
-    const bool walkStreams = streamFirst && !getenv("MI355LZ4_LINKED_PTR") &&
-                             0.42 * (double)(stat[3] > 0 ? stat[3] - 1 : 0) * (double)(1 + nStreams / 5000) <
-                                 0.55 + 1.15e-3 * (double)stat[0];
-    // The defaults are sized for 64 KiB blocks; a bigger block takes as many list regions and pointers as it has
-    // 64 KiB pieces (blocks beyond 4 MiB have no list and are walked), so fewer blocks make a segment.
-    const int span = last - first + 1;
-    const int per = (int)((stat[4] + 65535u) / 65536u) > 0 ? (int)((stat[4] + 65535u) / 65536u) : 1;
-    const int poolBlocks = envPool ? poolMax : (poolMax / per > 0 ? poolMax / per : 1);
-    const int ptrBlocks = (envSeg && atoi(envSeg) > 0) ? ptrMax : (ptrMax / per > 0 ? ptrMax / per : 1);
-    const int pool = (poolMax > 0 && !walkStreams) ? ((span < poolBlocks) ? span : poolBlocks) : span;
-    int seg = pool;
-    if (poolMax > 0 && !walkStreams && dev_reserve(c->tolPool, (size_t)pool * per * tol_region_bytes()) == 0 &&
-        dev_reserve(c->tolMeta, ((size_t)nBlocks * 3 + 4) * sizeof(int32_t)) == 0) {
-        a.tolPool = c->tolPool.p; a.tolRegions = pool * per; a.tolPer = per;
-        a.tolCounter = (uint32_t *)c->tolMeta.p;
-        a.tolRegion = (int32_t *)c->tolMeta.p + 4;
-        a.tolCount = a.tolRegion + nBlocks;
-        a.tolSize = a.tolCount + nBlocks;
-        const int pseg = (pool < ptrBlocks) ? pool : ptrBlocks;
-        const size_t ptrs = ((size_t)pseg + 1) * per * 65536 + 65536;
-        if (usePtr && ptrs < ((size_t)1 << 31) && dev_reserve(c->ptrBuf, ptrs * sizeof(uint32_t)) == 0) {
-            a.ptr = (uint32_t *)c->ptrBuf.p; a.ptrCap = ptrs;
+    (void)hipGetLastError();                             // (only a failed reservation is left to swallow here)
+    a.ring = nullptr; a.zeroPage = nullptr; a.runRes = nullptr; a.runCtl = nullptr; a.runInfo = nullptr; a.runDirty = nullptr;
+    a.runPiece = 0; a.runIn = 0;
+    c->linkedPath = (int)(done ? (p.longRun ? LinkedPath::RunInLong : LinkedPath::RunIn) : LinkedPath::RunInGivenUp);
+    if (done) return link_done(c);
+    a.segFirst = 0; a.segEnd = a.nBlocks;
+    LINK_TRY(hipMemsetAsync(a.linkStat, 0, 32, c->stream));
+    LINK_TRY(hipMemsetAsync(a.linkStat + 1, 0xff, 4, c->stream));
+    launch_link_stat(a, c->stream);
+    LINK_TRY(hipMemcpyAsync(pin, a.linkStat, 32, hipMemcpyDeviceToHost, c->stream));
+    LINK_TRY(hipStreamSynchronize(c->stream));
+    st = LinkStat::from(pin);
+    return link_summary(c, st, a.nBlocks);
+}
+// The lists / pointer passes (ptr_plan), or the serial walk without their scratch; the data half in linked_finish (now, or at _end)
+static int linked_pointer(mi355lz4_ctx *c, DecodeArgs &a, const DecodeCall &d, const DecodeKnobs &k, const LinkStat &st)
+{
+    const int first = (int)st.first, last = (int)st.last, span = last - first + 1;
+    if (c->linkedPath != (int)LinkedPath::RunInGivenUp) c->linkedPath = (int)LinkedPath::Pointer;
+    const PtrPlan p = ptr_plan(d, k, st, span);
+    int seg = p.pool;
+    if (p.lists && dev_reserve(c->tolPool, (size_t)p.pool * p.per * tol_region_bytes()) == 0 &&
+        dev_reserve(c->tolMeta, ((size_t)a.nBlocks * 3 + 4) * sizeof(int32_t)) == 0) {
+        a.tolPool = c->tolPool.p; a.tolRegions = p.pool * p.per; a.tolPer = p.per;
+        a.tolCounter = (uint32_t *)c->tolMeta.p; a.tolRegion = (int32_t *)c->tolMeta.p + 4;
+        a.tolCount = a.tolRegion + a.nBlocks; a.tolSize = a.tolCount + a.nBlocks;
+        if (p.usePtr && dev_reserve(c->ptrBuf, p.ptrs * sizeof(uint32_t)) == 0) {
+            a.ptr = (uint32_t *)c->ptrBuf.p; a.ptrCap = p.ptrs;
             a.ptrCtl = (uint8_t *)c->linkBuf.p + 64;
             a.ptrBad = (uint32_t *)((uint8_t *)c->linkBuf.p + 64 + ptr_ctl_bytes());
-            seg = pseg;
+            seg = p.seg;
         }
     }
     (void)hipGetLastError();          // scratch that could not be had is not an error: the serial walk needs none
     c->plan.active = true;
-    c->plan.a = a; c->plan.first = first; c->plan.last = last; c->plan.pool = pool; c->plan.seg = seg;
-    // When one segment covers every dependent block, the half of the second pass that reads no output byte can be
-    // issued now: lists, pointers and the first jump pass depend on the tokens only.
-    c->plan.split = splitOk && a.ptr && span <= seg && span <= pool;
+    c->plan.a = a; c->plan.first = first; c->plan.last = last; c->plan.pool = p.pool; c->plan.seg = seg;
+    c->plan.split = linked_split(d.splitOk, a.ptr != nullptr, span, seg, p.pool);
     if (c->plan.split) {
         a.segFirst = first; a.segEnd = last + 1;
         launch_linked_tolerant(a, c->stream);
         launch_linked_resolve_a(a, c->stream);
         c->plan.a = a;
     }
-    if (!deferEnd) return linked_finish(c);
-    return check_launch("decode launch");
+    return d.deferEnd ? check_launch("decode launch") : linked_finish(c);
 }
+
+static int decode_device_impl(mi355lz4_ctx *c, const DecodeCall &d, const int32_t *ckFail)
+{
+    if (!c) return fail(MI355LZ4_E_ARG, "null ctx");
+    if (c->plan.active) return fail(MI355LZ4_E_ARG, "a linked decode begun with mi355lz4_decompress_linked_begin is still open");
+    if (d.nBlocks < 0 || (d.headerKind != 4 && d.headerKind != 8) || d.fixedUncomp < 0)
+        return fail(MI355LZ4_E_ARG, "decompress_batch_device: bad arguments");
+    if (d.nBlocks == 0) return MI355LZ4_OK;
+    if (!d.framed || !d.blockOff || !d.outOff || !d.result) return fail(MI355LZ4_E_ARG, "decompress_batch_device: null pointer");
+    HIP_TRY(hipSetDevice(c->device));
+    const DecodeKnobs k = read_decode_knobs();
+    const EngineMode m{c->decoder, c->stats != nullptr, k.asyncSet ? k.asyncCap : c->linkedAsyncCap};
+    DecodeArgs a{};
+    a.framed = d.framed; a.framedLen = d.framedLen; a.blockOff = d.blockOff; a.nBlocks = d.nBlocks; a.segEnd = d.nBlocks;
+    a.headerKind = d.headerKind; a.fixedUncomp = d.fixedUncomp; a.linked = d.linked ? 1 : 0;
+    a.out = d.out; a.outOff = d.outOff; a.outCap = d.outCap; a.result = d.result; a.dict0 = d.dict0; a.dict0Len = d.dict0Len;
+    a.streamFirst = d.streamFirst; a.nStreams = d.nStreams; a.lookBack = d.lookBack;
+    a.onlyBlk = -1; a.cuDbg = c->cuDbg; a.cuBail = c->decoder == 0; a.ckFail = ckFail;
+    int r;
+    if (d.linked) {
+        link_scratch_acquire(c);
+        const size_t nFlags = d.streamFirst ? (size_t)(d.nStreams > 0 ? d.nStreams : 1) : 1;
+        if ((r = dev_reserve(c->linkBuf, 64 + ptr_ctl_bytes() + 4 * nFlags)) || (r = pin_reserve(c->pinStat, 64))) return r;
+        a.linkStat = (uint32_t *)c->linkBuf.p;
+        HIP_TRY(hipMemsetAsync(a.linkStat, 0, 32, c->stream));
+        HIP_TRY(hipMemsetAsync(a.linkStat + 1, 0xff, 4, c->stream));
+    }
+    const BigArm big = big_arm(d, m, k);
+    const bool bigPre = big == BigArm::BeforeFirstPass && big_scratch(c, a, 1);
+    switch (first_pass(d, m, k)) {
+    case FirstPass::Seq: launch_decode_seq(a, c->stream); break;
+    case FirstPass::Cu: launch_decode_cu(a, c->stream); break;
+#ifdef MI355LZ4_EXPERIMENTS
+    case FirstPass::Tok:   // experiment: the parse as a pass of its own (token lists), then the list-driven decoder
+        if (dev_reserve(c->tokBuf, (size_t)(d.framedLen >> 1) + 192 + ((size_t)d.nBlocks + 1) * sizeof(int32_t)) == 0) {
+            a.tokCnt = (int32_t *)c->tokBuf.p;
+            a.tokList = (uint8_t *)c->tokBuf.p + ((((size_t)d.nBlocks + 1) * sizeof(int32_t) + 63) & ~(size_t)63);
+            launch_decode_tok(a, c->stream);
+            break;
+        }
+        [[fallthrough]];
+#endif
+    default: launch_decode_par(a, c->stats, c->stream);
+    }
+    if (!d.linked) return check_launch("decode launch");
+    // Linked: the call waits for the standalone pass (independent blocks pay this wait and nothing else).  Asynchronous form: no wait;
+    // the second pass is enqueued over ALL blocks, its kernels return at once when the first pass counted no dependent block.
+    LinkStat st;
+    if (async_gate(d, m)) { a.asyncGate = 1; st = LinkStat::whole_call(d.nBlocks, m.asyncCap); } else {
+        launch_longest_stream(a, c->stream);
+        HIP_TRY(hipMemcpyAsync(c->pinStat.p, a.linkStat, 32, hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(hipStreamSynchronize(c->stream));
+        st = LinkStat::from((const uint32_t *)c->pinStat.p);
+    }
+    c->runinShareE6 = -1; c->linkedPath = (int)LinkedPath::None;
+    if ((r = link_summary(c, st, d.nBlocks)) != STEP_NEXT) return r;
+    if ((r = linked_big(c, a, k, st, big, bigPre)) != STEP_NEXT) return r;
+    if ((r = linked_runs(c, a, d, m, k, st)) != STEP_NEXT) return r;
+    if ((r = linked_runin(c, a, d, m, k, st)) != STEP_NEXT) return r;
+    return linked_pointer(c, a, d, k, st);
+}
+#undef LINK_TRY
 
 // Every decode of the engine.  With block checksums on, the blocks' data is hashed first (k_xxh32_verify, one flag per
 // block in ckBuf) and read_block_header turns a mismatch into MI355LZ4_BLK_E_CHECKSUM: to every decode path a block
 // that fails its checksum is a header-rejected block, so linked streams treat it as they treat any other.
-static int decode_device(mi355lz4_ctx *c, const uint8_t *framed, uint64_t framedLen, const uint64_t *blockOff,
-                         int nBlocks, int headerKind, int fixedUncomp, int linked, uint8_t *out,
-                         const uint64_t *outOff, const int32_t *outCap, int32_t *result, const uint8_t *dict0,
-                         uint32_t dict0Len, const int32_t *streamFirst = nullptr, int nStreams = 0, int lookBack = 0,
-                         bool splitOk = false, bool deferEnd = false)
+static int decode_device(mi355lz4_ctx *c, const DecodeCall &d)
 {
-    if (!c || !c->blockChecksum || nBlocks <= 0 || c->plan.active || !framed || !blockOff ||
-        (headerKind != 4 && headerKind != 8))
-        return decode_device_impl(c, framed, framedLen, blockOff, nBlocks, headerKind, fixedUncomp, linked, out, outOff, outCap,
-                                  result, dict0, dict0Len, streamFirst, nStreams, lookBack, splitOk, deferEnd, nullptr);
+    if (!c || !c->blockChecksum || d.nBlocks <= 0 || c->plan.active || !d.framed || !d.blockOff ||
+        (d.headerKind != 4 && d.headerKind != 8))
+        return decode_device_impl(c, d, nullptr);
     HIP_TRY(hipSetDevice(c->device));
     // the flags belong to the engine: a decode on another stream first waits for the last one that read them
     if (c->ckEvent && c->ckStream != c->stream) HIP_TRY(hipStreamWaitEvent(c->stream, c->ckEvent, 0));
     int r;
-    if ((r = dev_reserve(c->ckBuf, (size_t)nBlocks * 4))) return r;
+    if ((r = dev_reserve(c->ckBuf, (size_t)d.nBlocks * 4))) return r;
     DecodeArgs v = DecodeArgs();
-    v.framed = framed; v.framedLen = framedLen; v.blockOff = blockOff; v.nBlocks = nBlocks; v.headerKind = headerKind;
+    v.framed = d.framed; v.framedLen = d.framedLen; v.blockOff = d.blockOff; v.nBlocks = d.nBlocks; v.headerKind = d.headerKind;
     launch_xxh32_verify(v, (int32_t *)c->ckBuf.p, c->stream);
     if ((r = check_launch("checksum launch"))) return r;
-    r = decode_device_impl(c, framed, framedLen, blockOff, nBlocks, headerKind, fixedUncomp, linked, out, outOff, outCap,
-                           result, dict0, dict0Len, streamFirst, nStreams, lookBack, splitOk, deferEnd,
-                           (const int32_t *)c->ckBuf.p);
+    r = decode_device_impl(c, d, (const int32_t *)c->ckBuf.p);
     if (!c->ckEvent && hipEventCreateWithFlags(&c->ckEvent, hipEventDisableTiming) != hipSuccess) c->ckEvent = nullptr;
     if (c->ckEvent && hipEventRecord(c->ckEvent, c->stream) == hipSuccess) c->ckStream = c->stream;
     return r;
@@ -1101,8 +926,7 @@ extern "C" int mi355lz4_decompress_batch_device(mi355lz4_ctx *c, const uint8_t *
                                                 int fixedUncomp, int linked, uint8_t *out, const uint64_t *outOff,
                                                 const int32_t *outCap, int32_t *result)
 {
-    return decode_device(c, framed, framedLen, blockOff, nBlocks, headerKind, fixedUncomp, linked, out, outOff,
-                         outCap, result, nullptr, 0);
+    return decode_device(c, {framed, framedLen, blockOff, nBlocks, headerKind, fixedUncomp, linked, out, outOff, outCap, result});
 }
 
 extern "C" int mi355lz4_decompress_linked_begin(mi355lz4_ctx *c, const uint8_t *framed, uint64_t framedLen,
@@ -1111,8 +935,9 @@ extern "C" int mi355lz4_decompress_linked_begin(mi355lz4_ctx *c, const uint8_t *
                                                int32_t *result, int lookBack)
 {
     if (lookBack < 0 || lookBack > 1) return fail(MI355LZ4_E_ARG, "decompress_linked_begin: lookBack must be 0 or 1");
-    return decode_device(c, framed, framedLen, blockOff, nBlocks, headerKind, fixedUncomp, 1, out, outOff, outCap, result,
-                         nullptr, 0, nullptr, 0, lookBack, true, true);
+    DecodeCall d{framed, framedLen, blockOff, nBlocks, headerKind, fixedUncomp, 1, out, outOff, outCap, result};
+    d.lookBack = lookBack; d.splitOk = d.deferEnd = true;
+    return decode_device(c, d);
 }
 
 extern "C" int mi355lz4_decompress_linked_end(mi355lz4_ctx *c)
@@ -1163,11 +988,9 @@ extern "C" int mi355lz4_decompress_streams_device(mi355lz4_ctx *c, const uint8_t
 {
     if (nStreams < 0 || (nStreams > 0 && !streamFirst))
         return fail(MI355LZ4_E_ARG, "decompress_streams_device: bad stream table");
-    if (nStreams == 0)                        // no streams: every block is decoded on its own
-        return decode_device(c, framed, framedLen, blockOff, nBlocks, headerKind, fixedUncomp, 0, out, outOff, outCap,
-                             result, nullptr, 0);
-    return decode_device(c, framed, framedLen, blockOff, nBlocks, headerKind, fixedUncomp, 1, out, outOff, outCap,
-                         result, nullptr, 0, streamFirst, nStreams);
+    DecodeCall d{framed, framedLen, blockOff, nBlocks, headerKind, fixedUncomp, nStreams > 0, out, outOff, outCap, result};
+    if (nStreams > 0) { d.streamFirst = streamFirst; d.nStreams = nStreams; }   // (no streams: every block is decoded on its own)
+    return decode_device(c, d);
 }
 
 extern "C" int mi355lz4_xxh32_device(mi355lz4_ctx *c, const uint8_t *base, const uint64_t *off, const int32_t *len, int n,
@@ -1656,9 +1479,10 @@ static int decompress_host(mi355lz4_ctx *c, const uint8_t *framedIn, size_t inLe
         HIP_TRY(hipStreamSynchronize(c->stream));
         sfDev = (const int32_t *)c->lenA.p;
     }
-    r = decode_device(c, (const uint8_t *)c->in.p, inLen, (const uint64_t *)c->offA.p, n, headerKind, fixedUncomp,
-                      linked, (uint8_t *)c->out.p, (const uint64_t *)c->offB.p, nullptr, (int32_t *)c->res.p,
-                      dlen ? (const uint8_t *)c->scratch.p : nullptr, dlen, sfDev, nStreams);
+    DecodeCall d{(const uint8_t *)c->in.p, inLen, (const uint64_t *)c->offA.p, n, headerKind, fixedUncomp, linked,
+                 (uint8_t *)c->out.p, (const uint64_t *)c->offB.p, nullptr, (int32_t *)c->res.p};
+    d.dict0 = dlen ? (const uint8_t *)c->scratch.p : nullptr; d.dict0Len = dlen; d.streamFirst = sfDev; d.nStreams = nStreams;
+    r = decode_device(c, d);
     if (r) return r;
     std::vector<int32_t> res((size_t)n);
     HIP_TRY(hipMemcpyAsync(res.data(), c->res.p, (size_t)n * 4, hipMemcpyDeviceToHost, c->stream));
@@ -1776,9 +1600,10 @@ static int decompress_host_pipelined(mi355lz4_ctx *c, const uint8_t *framedIn, s
             if (linked && g + 1 < G && (r = stage_in(g + 1))) return r;
             HIP_TRY(hipStreamWaitEvent(c->stream, evIn[(size_t)g], 0));
             // the group's blocks, with the whole framed buffer as bounds and the blocks before it as look-back
-            r = decode_device(c, (const uint8_t *)c->in.p, inLen, (const uint64_t *)c->offA.p + b0, b1 - b0, headerKind,
-                              fixedUncomp, linked, (uint8_t *)c->out.p, (const uint64_t *)c->offB.p + b0, nullptr,
-                              (int32_t *)c->res.p + b0, dlen ? (const uint8_t *)c->scratch.p : nullptr, dlen, nullptr, 0, b0);
+            DecodeCall d{(const uint8_t *)c->in.p, inLen, (const uint64_t *)c->offA.p + b0, b1 - b0, headerKind, fixedUncomp, linked,
+                         (uint8_t *)c->out.p, (const uint64_t *)c->offB.p + b0, nullptr, (int32_t *)c->res.p + b0};
+            d.dict0 = dlen ? (const uint8_t *)c->scratch.p : nullptr; d.dict0Len = dlen; d.lookBack = b0;
+            r = decode_device(c, d);
             if (r) return r;
             HIP_TRY(hipMemcpyAsync(resPin + b0, (const int32_t *)c->res.p + b0, (size_t)(b1 - b0) * 4, hipMemcpyDeviceToHost, c->stream));
             HIP_TRY(hipEventRecord(evK[(size_t)g], c->stream));

@@ -5,10 +5,12 @@
 //   * the staging copy pool (api.cpp) hammered from several caller threads at once;
 //   * the stream state machines that need no codec: resizeChunks at every split size the reference tests
 //     (test/Main.hs:217-224), end mark, the frame-header parser, and their error paths;
-//   * the legacy LZ4_* entry points' no-device behaviour (create/free, compressBound, 0 / -1 returns).
+//   * the legacy LZ4_* entry points' no-device behaviour (create/free, compressBound, 0 / -1 returns);
+//   * the decode planner (linked_plan.hpp): a table of call shape -> path.
 #include "../../include/lz4.h"
 #include "../../include/mi355lz4.h"
 #include "../../include/streamly_lz4.hpp"
+#include "../../streamly-lz4_amd/csrc/linked_plan.hpp"
 
 #include <cstdio>
 #include <cstdlib>
@@ -204,8 +206,347 @@ static void frame_parser_fuzz()
     CHECK(xxh32(nullptr, 0, 0) == 0x02CC5D05u);
 }
 
+// ---------------------------------------------------------------------------------------------------------------------------------
+// Call shape -> path (linked_plan.hpp).  Every row records what decode_device_impl did at 55f3f47, before the decisions moved into
+// the planner: the comments quote that code's conditions, and the expected values were read off it, not off the planner.
+// ---------------------------------------------------------------------------------------------------------------------------------
+static const int32_t kStreamTable[3] = {0, 1, 2};   // (the planner only asks whether there is a stream table / a dictionary)
+static const uint8_t kDict[1] = {0};
+
+static DecodeCall linked_call(int nBlocks, uint64_t framedLen)
+{
+    DecodeCall s{};
+    s.linked = 1; s.nBlocks = nBlocks; s.framedLen = framedLen;
+    return s;
+}
+
+static void plan_first_pass()
+{
+    // decoder == 1: seq; decoder == 3 (experiments): tok; !stats && (decoder == 4 || (decoder == 0 && cu_auto(nBlocks, framedLen))):
+    // cu; else par.  cu_auto: CU_BLOCKS >= 0: nBlocks <= it; avg = framedLen / nBlocks < 3072: no; nBlocks <= 256 || (nBlocks <= 512
+    // && avg >= 16384)
+    struct Row { int decoder; bool stats; int nBlocks; uint64_t framedLen; int cuBlocks; FirstPass want; } rows[] = {
+        {0, false, 256, 256 * 3072ull, -1, FirstPass::Cu},       // avg 3072: not below 3072
+        {0, false, 256, 256 * 3072ull - 1, -1, FirstPass::Par},  // avg 3071
+        {0, false, 257, 257 * 16384ull, -1, FirstPass::Cu},      // 257..512 blocks from 16384 bytes a block
+        {0, false, 257, 257 * 16384ull - 1, -1, FirstPass::Par},
+        {0, false, 512, 512 * 16384ull, -1, FirstPass::Cu},
+        {0, false, 513, 513 * 65536ull, -1, FirstPass::Par},
+        {0, true, 16, 16 * 65536ull, -1, FirstPass::Par},        // stats: never the workgroup form
+        {1, false, 16, 16 * 65536ull, -1, FirstPass::Seq},
+        {1, true, 16, 16 * 65536ull, -1, FirstPass::Seq},
+        {2, false, 16, 16 * 65536ull, -1, FirstPass::Par},
+        {3, false, 16, 16 * 65536ull, -1, FirstPass::Tok},
+        {4, false, 100000, 100000ull, -1, FirstPass::Cu},        // variant 4: any number of blocks, any size
+        {4, true, 16, 16 * 65536ull, -1, FirstPass::Par},
+        {0, false, 1000, 1000ull, 1000, FirstPass::Cu},          // CU_BLOCKS = 1000: up to 1000 blocks whatever their size
+        {0, false, 1001, 1001 * 65536ull, 1000, FirstPass::Par},
+        {0, false, 1, 65536ull, 0, FirstPass::Par},              // CU_BLOCKS = 0: never
+    };
+    for (const Row &r : rows) {
+        DecodeKnobs k;
+        k.cuBlocks = r.cuBlocks;
+        EngineMode m;
+        m.decoder = r.decoder; m.stats = r.stats;
+        CHECK(first_pass(linked_call(r.nBlocks, r.framedLen), m, k) == r.want);
+    }
+}
+
+static void plan_big()
+{
+    // bigEligible = linked && bigKiB > 0 && plainBig (none of PTR, POOL_BLOCKS, RUNS, RUNIN, ASYNC set) && !streamFirst && !splitOk &&
+    // !deferEnd && lookBack >= 0 && !dict0 && decoder == 0 && !stats && linkedAsyncCap <= 0 && 2 <= nBlocks <= 512 && cu_auto;
+    // bigPre = bigEligible && framedLen / nBlocks >= bigKiB * 1024 / 2; the passes (and bigLate) need stat[4] >= bigKiB * 1024
+    const DecodeCall base = linked_call(64, 64 * 262144ull);
+    const DecodeKnobs k0;
+    const EngineMode m0;
+    CHECK(big_arm(base, m0, k0) == BigArm::BeforeFirstPass);                          // exactly bigKiB * 512 bytes a block
+    CHECK(big_arm(linked_call(64, 64 * 262144ull - 1), m0, k0) == BigArm::AfterWait);  // one byte below
+    CHECK(big_arm(linked_call(2, 2 * 262144ull), m0, k0) == BigArm::BeforeFirstPass);
+    CHECK(big_arm(linked_call(512, 512 * 262144ull), m0, k0) == BigArm::BeforeFirstPass);
+    auto no = [&](DecodeCall s, EngineMode m, DecodeKnobs k) { CHECK(big_arm(s, m, k) == BigArm::No); };
+    { DecodeCall s = base; s.linked = 0; no(s, m0, k0); }
+    { DecodeKnobs k; k.bigKiB = 0; no(base, m0, k); }                                   // LINKED_BIG=0
+    { DecodeKnobs k; k.ptrSet = true; no(base, m0, k); }
+    { DecodeKnobs k; k.poolSet = true; no(base, m0, k); }
+    { DecodeKnobs k; k.runsSet = true; no(base, m0, k); }
+    { DecodeKnobs k; k.runinSet = true; no(base, m0, k); }
+    { DecodeKnobs k; k.asyncSet = true; no(base, m0, k); }                              // (even LINKED_ASYNC=0)
+    { DecodeCall s = base; s.streamFirst = kStreamTable; s.nStreams = 2; no(s, m0, k0); }
+    { DecodeCall s = base; s.splitOk = true; no(s, m0, k0); }
+    { DecodeCall s = base; s.deferEnd = true; no(s, m0, k0); }
+    { DecodeCall s = base; s.lookBack = -1; no(s, m0, k0); }
+    { DecodeCall s = base; s.dict0 = kDict; no(s, m0, k0); }
+    { EngineMode m; m.decoder = 4; no(base, m, k0); }
+    { EngineMode m; m.decoder = 1; no(base, m, k0); }
+    { EngineMode m; m.stats = true; no(base, m, k0); }
+    { EngineMode m; m.asyncCap = 1; no(base, m, k0); }                                  // mi355lz4_set_linked_async
+    no(linked_call(1, 262144ull), m0, k0);
+    no(linked_call(513, 513 * 262144ull), m0, k0);
+    { DecodeKnobs k; k.cuBlocks = 63; no(base, m0, k); }                                // cu_auto says no
+    { DecodeKnobs k; k.bigKiB = 1024; CHECK(big_arm(base, m0, k) == BigArm::AfterWait); }
+    LinkStat st;
+    st.maxCap = 512 * 1024;
+    CHECK(big_takes(k0, st));                                                           // exactly bigKiB * 1024
+    st.maxCap = 512 * 1024 - 1;
+    CHECK(!big_takes(k0, st));
+}
+
+static void plan_runs()
+{
+    // !streamFirst && !asyncGate && !splitOk && !deferEnd && runMax > 0 && stat[5] >= 1 && stat[5] <= runMax && (RUNS set || plain);
+    // runMax = RUNS or 4; plain = neither PTR nor POOL_BLOCKS set
+    const DecodeCall s0 = linked_call(100, 100 * 20000ull);
+    const EngineMode m0;
+    auto take = [&](uint32_t longest, const DecodeKnobs &k, DecodeCall s, EngineMode m) {
+        LinkStat st;
+        st.count = 3; st.longestRun = longest; st.runs = 3;
+        return runs_take(s, m, k, st);
+    };
+    const DecodeKnobs k0;
+    CHECK(!take(0, k0, s0, m0));
+    CHECK(take(1, k0, s0, m0));
+    CHECK(take(4, k0, s0, m0));
+    CHECK(!take(5, k0, s0, m0));
+    { DecodeKnobs k; k.runsSet = true; k.runMax = 8; CHECK(take(5, k, s0, m0)); }
+    { DecodeKnobs k; k.runsSet = true; k.runMax = 0; CHECK(!take(1, k, s0, m0)); }
+    { DecodeKnobs k; k.ptrSet = true; CHECK(!take(1, k, s0, m0)); }
+    { DecodeKnobs k; k.poolSet = true; CHECK(!take(1, k, s0, m0)); }
+    { DecodeKnobs k; k.ptrSet = true; k.runsSet = true; CHECK(take(1, k, s0, m0)); }    // RUNS set wins over plain
+    { DecodeCall s = s0; s.streamFirst = kStreamTable; s.nStreams = 4; CHECK(!take(1, k0, s, m0)); }
+    { DecodeCall s = s0; s.splitOk = true; CHECK(!take(1, k0, s, m0)); }
+    { DecodeCall s = s0; s.deferEnd = true; CHECK(!take(1, k0, s, m0)); }
+    { EngineMode m; m.asyncCap = 65536; CHECK(!take(1, k0, s0, m)); }                   // asyncGate
+}
+
+static void plan_runin()
+{
+    // decay: if (!RUNIN set && runinLong && ++runinLongOk >= 32) { runinLong = false; runinLongOk = 0; }; longRun = runinLong && !RUNIN set
+    // use = !streamFirst && !asyncGate && (!(splitOk || deferEnd) || lookBack == 0) && (RUNIN set ? atoi != 0 : (plain && span0 >= 64
+    //       && 2 * stride <= 2^31 && span0 * per64 >= (longRun ? 2 * 9216 : 9216))); plain = none of PTR, POOL_BLOCKS, RUNS set;
+    //       per64 = max(1, ceil(stat[4] / 64 KiB)), stride = per64 * 64 KiB
+    // if (use && !RUNIN set && runinSkip > 0) { runinSkip--; use = false; }; the share is sampled when use && !RUNIN set
+    auto plan = [](int span0, uint32_t maxCap, const DecodeKnobs &k = DecodeKnobs(), DecodeCall s = linked_call(100000, 1),
+                   RuninState st = RuninState(), EngineMode m = EngineMode()) { return runin_plan(st, s, m, k, span0, maxCap); };
+    const uint32_t b64 = 65536;
+    CHECK(plan(RUNIN_MIN_SPAN, b64).use && plan(RUNIN_MIN_SPAN, b64).sample);
+    CHECK(!plan(RUNIN_MIN_SPAN - 1, b64).use);
+    CHECK(plan(RUNIN_MIN_SPAN / 4, 4 * b64).use && plan(RUNIN_MIN_SPAN / 4, 4 * b64).per64 == 4);
+    CHECK(!plan(RUNIN_MIN_SPAN / 4 - 1, 4 * b64).use);
+    CHECK(plan(RUNIN_MIN_SPAN / 4, 4 * b64 - 1).use);                                  // per64 rounds up
+    CHECK(plan(1, 0).per64 == 1);
+    CHECK(!plan(63, 200 * b64).use);                                                   // the span from 64 blocks on
+    CHECK(plan(64, 144 * b64).use);                                                    // 64 x 144 = 9216
+    CHECK(!plan(64, 143 * b64).use);
+    CHECK(plan(64, 1u << 30).use);                                                     // strides of 1 GiB: two of them are 2 GiB
+    CHECK(!plan(64, (1u << 30) + 1).use);
+    {
+        RuninState st;
+        st.longRun = true;
+        DecodeCall s = linked_call(100000, 1);
+        for (int span : {2 * RUNIN_MIN_SPAN, 2 * RUNIN_MIN_SPAN - 1}) {
+            RuninState t = st;
+            const RuninPlan p = runin_plan(t, s, EngineMode(), DecodeKnobs(), span, b64);
+            CHECK(p.longRun && p.use == (span == 2 * RUNIN_MIN_SPAN) && t.longOk == 1);
+        }
+        for (int span : {2 * RUNIN_MIN_SPAN / 4, 2 * RUNIN_MIN_SPAN / 4 - 1}) {
+            RuninState t = st;
+            CHECK(runin_plan(t, s, EngineMode(), DecodeKnobs(), span, 4 * b64).use == (span == 2 * RUNIN_MIN_SPAN / 4));
+        }
+    }
+    for (int lookBack : {0, 1}) {
+        DecodeCall s = linked_call(100000, 1);
+        s.lookBack = lookBack; s.splitOk = s.deferEnd = true;
+        CHECK(plan(RUNIN_MIN_SPAN, b64, DecodeKnobs(), s).use == (lookBack == 0));
+        s.splitOk = false;
+        CHECK(plan(RUNIN_MIN_SPAN, b64, DecodeKnobs(), s).use == (lookBack == 0));
+        s.lookBack = lookBack; s.splitOk = s.deferEnd = false;
+        CHECK(plan(RUNIN_MIN_SPAN, b64, DecodeKnobs(), s).use);                        // a plain call: any lookBack
+    }
+    { DecodeCall s = linked_call(100000, 1); s.streamFirst = kStreamTable; s.nStreams = 3; CHECK(!plan(RUNIN_MIN_SPAN, b64, DecodeKnobs(), s).use); }
+    { EngineMode m; m.asyncCap = 65536; CHECK(!plan(RUNIN_MIN_SPAN, b64, DecodeKnobs(), linked_call(100000, 1), RuninState(), m).use); }
+    { DecodeKnobs k; k.runsSet = true; CHECK(!plan(RUNIN_MIN_SPAN, b64, k).use); }
+    { DecodeKnobs k; k.ptrSet = true; CHECK(!plan(RUNIN_MIN_SPAN, b64, k).use); }
+    { DecodeKnobs k; k.poolSet = true; CHECK(!plan(RUNIN_MIN_SPAN, b64, k).use); }
+    { DecodeKnobs k; k.runinSet = true; k.runin = 1; const RuninPlan p = plan(1, b64, k); CHECK(p.use && !p.sample); }
+    { DecodeKnobs k; k.runinSet = true; k.runin = 0; CHECK(!plan(RUNIN_MIN_SPAN, b64, k).use); }
+    // the skip counter: only when the run-in would be taken, and not when it is forced
+    {
+        RuninState st;
+        st.skip = 3;
+        DecodeCall s = linked_call(100000, 1);
+        CHECK(!runin_plan(st, s, EngineMode(), DecodeKnobs(), RUNIN_MIN_SPAN, b64).use && st.skip == 2);
+        CHECK(!runin_plan(st, s, EngineMode(), DecodeKnobs(), 10, b64).use && st.skip == 2);
+        DecodeKnobs k;
+        k.runinSet = true; k.runin = 1;
+        CHECK(runin_plan(st, s, EngineMode(), k, RUNIN_MIN_SPAN, b64).use && st.skip == 2);
+    }
+    // the probe: the long run-in for 31 more calls that get here, whatever their size, then the default again; a forced run-in does
+    // not count
+    {
+        RuninState st;
+        st.longRun = true;
+        DecodeCall s = linked_call(100000, 1);
+        s.streamFirst = kStreamTable; s.nStreams = 2;
+        for (int call = 1; call <= RUNIN_LONG_PROBE; call++) {
+            const RuninPlan p = runin_plan(st, s, EngineMode(), DecodeKnobs(), 10, b64);
+            CHECK(!p.use && p.longRun == (call < RUNIN_LONG_PROBE) && st.longRun == (call < RUNIN_LONG_PROBE));
+            CHECK(st.longOk == (call < RUNIN_LONG_PROBE ? call : 0));
+        }
+        st.longRun = true; st.longOk = 5;
+        DecodeKnobs k;
+        k.runinSet = true; k.runin = 1;
+        CHECK(!runin_plan(st, linked_call(100000, 1), EngineMode(), k, 10, b64).longRun && st.longOk == 5 && st.longRun);
+    }
+    // after the sample: share >= 0.60: no run-in; >= 0.306: the long one, which needs span0 * per64 >= 2 * RUNIN_MIN_SPAN
+    auto after = [&](int span0, double share) {
+        RuninPlan p = plan(span0, b64);
+        runin_after_sample(p, DecodeKnobs(), span0, share);
+        return p;
+    };
+    const int big = 2 * RUNIN_MIN_SPAN;
+    CHECK(after(big, 0.3059).use && !after(big, 0.3059).longRun);
+    CHECK(after(big, 0.306).use && after(big, 0.306).longRun);
+    CHECK(!after(RUNIN_MIN_SPAN, 0.306).use);
+    CHECK(after(RUNIN_MIN_SPAN, -1).use && !after(RUNIN_MIN_SPAN, -1).longRun);      // no sample
+    CHECK(after(big, 0.5999).use && after(big, 0.5999).longRun);
+    CHECK(!after(big, 0.60).use);
+    // sizes: runIn = RUNIN_BLOCKS > 0 ? it : (per64 == 1 ? run64 : (run64 + per64) / per64 + 1), run64 = longRun ? 17 : 11, at most
+    // 64; maxPieces = 2^31 / (2 * stride) within [1, 4096]; piece = ceil(span0 / maxPieces), or RUNIN_PIECE > 0, at least 1;
+    // segBlocks = min(maxPieces * piece, span0)
+    struct Size { int span0; uint32_t maxCap; bool longRun; int blocks, pieceKnob; int runIn, piece, segBlocks; uint64_t maxPieces; } sizes[] = {
+        {9216, 65536, false, 0, 0, 11, 3, 9216, 4096},
+        {18432, 65536, true, 0, 0, 17, 5, 18432, 4096},
+        {2304, 4 * 65536, false, 0, 0, 4, 1, 2304, 4096},
+        {576, 16 * 65536, false, 0, 0, 2, 1, 576, 1024},
+        {1152, 16 * 65536, true, 0, 0, 3, 2, 1152, 1024},
+        {64, 1u << 30, false, 0, 0, 2, 64, 64, 1},
+        {9216, 65536, false, 5, 7, 5, 7, 9216, 4096},
+        {9216, 65536, false, 100, 0, 64, 3, 9216, 4096},                                // runIn capped at 64
+        {20000, 65536, false, 0, 2, 11, 2, 8192, 4096},                                  // forced pieces: segments of 4096 x 2 blocks
+        {3, 0x7fffffffu, false, 0, 0, 2, 3, 3, 1},                                       // (forced run-in) 2 GiB strides: one piece
+    };
+    for (const Size &z : sizes) {
+        DecodeKnobs k;
+        k.runinBlocks = z.blocks; k.runinPiece = z.pieceKnob;
+        k.runinSet = true; k.runin = 1;
+        RuninState st;
+        RuninPlan p = runin_plan(st, linked_call(100000, 1), EngineMode(), k, z.span0, z.maxCap);
+        p.longRun = z.longRun;
+        runin_after_sample(p, k, z.span0, -1);
+        CHECK(p.use && p.runIn == z.runIn && p.piece == z.piece && p.segBlocks == z.segBlocks && p.maxPieces == z.maxPieces);
+    }
+    // given up: if (!segDone && !(stat[1] & 1u) && !RUNIN set) { if (!longRun) runinLong = true; else runinSkip = 16; runinLongOk = 0; }
+    {
+        RuninState st;
+        st.longOk = 7;
+        RuninPlan p;
+        runin_given_up(st, p, DecodeKnobs(), 0);                                         // rounds that ran out: default -> long
+        CHECK(st.longRun && st.longOk == 0 && st.skip == 0);
+        p.longRun = true;
+        st.longOk = 3;
+        runin_given_up(st, p, DecodeKnobs(), 2);                                         // a chain of dirty pieces: long -> skip 16
+        CHECK(st.longRun && st.longOk == 0 && st.skip == RUNIN_BACKOFF && RUNIN_BACKOFF == 16);
+        RuninState t;
+        runin_given_up(t, RuninPlan(), DecodeKnobs(), 1);                                // a broken block teaches nothing
+        DecodeKnobs k;
+        k.runinSet = true; k.runin = 1;
+        runin_given_up(t, RuninPlan(), k, 0);                                            // nor does a forced run-in
+        CHECK(!t.longRun && t.skip == 0);
+    }
+}
+
+static void plan_pointer()
+{
+    // poolMax = POOL_BLOCKS or 16384; ptrMax = PTR_BLOCKS > 0 ? it : 4096; usePtr = !PTR || atoi(PTR) != 0; per = max(1, ceil(stat[4] /
+    // 64 KiB)); walkStreams = streamFirst && !PTR set && 0.42 * (stat[3] > 0 ? stat[3] - 1 : 0) * (1 + nStreams / 5000) < 0.55 +
+    // 1.15e-3 * stat[0]; poolBlocks = POOL_BLOCKS set ? poolMax : max(1, poolMax / per); ptrBlocks = PTR_BLOCKS > 0 ? ptrMax :
+    // max(1, ptrMax / per); pool = (poolMax > 0 && !walkStreams) ? min(span, poolBlocks) : span; pointers when usePtr and
+    // (min(pool, ptrBlocks) + 1) * per * 64 KiB + 64 KiB < 2^31; split = splitOk && a.ptr && span <= seg && span <= pool
+    auto plan = [](int span, uint32_t maxCap, const DecodeKnobs &k = DecodeKnobs(), DecodeCall s = linked_call(100000, 1),
+                   uint32_t count = 100, uint32_t longestStream = 0) {
+        LinkStat st;
+        st.count = count; st.maxCap = maxCap; st.longestStream = longestStream;
+        return ptr_plan(s, k, st, span);
+    };
+    {
+        const PtrPlan p = plan(10000, 65536);
+        CHECK(p.per == 1 && p.poolBlocks == 16384 && p.ptrBlocks == 4096 && p.lists && p.pool == 10000 && p.seg == 4096 && p.usePtr);
+        CHECK(p.ptrs == 4098ull * 65536 && !p.walkStreams);
+    }
+    {
+        const PtrPlan p = plan(10000, 16 * 65536);
+        CHECK(p.per == 16 && p.poolBlocks == 1024 && p.ptrBlocks == 256 && p.pool == 1024 && p.seg == 256 && p.usePtr);
+    }
+    CHECK(plan(10, 0).per == 1);
+    { DecodeKnobs k; k.poolSet = true; k.poolMax = 0; const PtrPlan p = plan(10000, 65536, k); CHECK(!p.lists && p.pool == 10000); }
+    { DecodeKnobs k; k.poolSet = true; k.poolMax = 3; const PtrPlan p = plan(10000, 16 * 65536, k); CHECK(p.poolBlocks == 3 && p.pool == 3); }
+    { DecodeKnobs k; k.ptrSet = true; k.ptr = 0; const PtrPlan p = plan(10000, 65536, k); CHECK(p.lists && !p.usePtr); }
+    { DecodeKnobs k; k.ptrSet = true; k.ptr = 1; CHECK(plan(10000, 65536, k).usePtr); }
+    { DecodeKnobs k; k.ptrBlocks = 2; const PtrPlan p = plan(10000, 16 * 65536, k); CHECK(p.ptrBlocks == 2 && p.seg == 2); }
+    {
+        DecodeKnobs k;
+        k.poolSet = true; k.poolMax = 10000; k.ptrBlocks = 1000;
+        const PtrPlan p = plan(10000, 64 * 65536, k);                                    // 2^31 pointers or more: none
+        CHECK(p.pool == 10000 && p.seg == 1000 && !p.usePtr);
+    }
+    // walk: a longest stream of 3 costs 0.42 * 2 = 0.84 against the pointer passes' 0.55 + 1.15e-3 * count: walked from count 253 on
+    DecodeCall s = linked_call(100000, 1);
+    s.streamFirst = kStreamTable; s.nStreams = 10;
+    CHECK(plan(100, 65536, DecodeKnobs(), s, 1, 2).walkStreams);
+    CHECK(plan(100, 65536, DecodeKnobs(), s, 253, 3).walkStreams);
+    CHECK(!plan(100, 65536, DecodeKnobs(), s, 252, 3).walkStreams && plan(100, 65536, DecodeKnobs(), s, 252, 3).lists);
+    { const PtrPlan p = plan(100, 65536, DecodeKnobs(), s, 1, 2); CHECK(!p.lists && p.pool == 100); }
+    { DecodeKnobs k; k.ptrSet = true; CHECK(!plan(100, 65536, k, s, 1, 2).walkStreams); }
+    CHECK(!plan(100, 65536, DecodeKnobs(), linked_call(100000, 1), 1, 2).walkStreams);  // one stream: never
+    s.nStreams = 5000;
+    CHECK(!plan(100, 65536, DecodeKnobs(), s, 1, 2).walkStreams);                        // 0.84 > 0.55115
+    CHECK(linked_split(true, true, 10, 10, 10));
+    CHECK(!linked_split(false, true, 10, 10, 10));
+    CHECK(!linked_split(true, false, 10, 10, 10));
+    CHECK(!linked_split(true, true, 11, 10, 20));
+    CHECK(!linked_split(true, true, 11, 20, 10));
+}
+
+static void plan_knobs()
+{
+    // the asynchronous form's stand-in summary: stat = {nBlocks, 0, nBlocks - 1, nBlocks, asyncCap}
+    const LinkStat a = LinkStat::whole_call(40, 1 << 20);
+    CHECK(a.count == 40 && a.first == 0 && a.last == 39 && a.longestStream == 40 && a.maxCap == (1u << 20));
+    CHECK(async_gate(linked_call(4, 4), EngineMode{0, false, 1}) && !async_gate(linked_call(4, 4), EngineMode{0, false, 0}));
+    const char *names[] = {"MI355LZ4_LINKED_BIG", "MI355LZ4_LINKED_ASYNC", "MI355LZ4_LINKED_RUNS", "MI355LZ4_LINKED_RUNIN",
+                           "MI355LZ4_LINKED_RUNIN_BLOCKS", "MI355LZ4_LINKED_RUNIN_PIECE", "MI355LZ4_LINKED_RUNIN_SPIN",
+                           "MI355LZ4_LINKED_PTR", "MI355LZ4_LINKED_POOL_BLOCKS", "MI355LZ4_LINKED_PTR_BLOCKS"};
+    for (const char *n : names) unsetenv(n);
+    DecodeKnobs k = read_decode_knobs();
+    CHECK(k.bigKiB == 512 && !k.asyncSet && k.runMax == 4 && !k.runinSet && k.runinSpin == 10000 && k.ptr == 1 && k.poolMax == 16384);
+    CHECK(k.runsAuto() && k.runinAuto() && k.bigAuto());
+    setenv("MI355LZ4_LINKED_RUNS", "0", 1);
+    k = read_decode_knobs();                                 // read per call
+    CHECK(k.runsSet && k.runMax == 0 && k.runsAuto() && !k.runinAuto() && !k.bigAuto());
+    setenv("MI355LZ4_LINKED_PTR", "0", 1);
+    k = read_decode_knobs();
+    CHECK(k.ptrSet && k.ptr == 0 && !k.runsAuto());
+    for (const char *n : names) unsetenv(n);
+    setenv("MI355LZ4_LINKED_ASYNC", "0", 1);                 // set at all: no big blocks
+    k = read_decode_knobs();
+    CHECK(k.asyncSet && k.asyncCap == 0 && k.runinAuto() && !k.bigAuto());
+    unsetenv("MI355LZ4_LINKED_ASYNC");
+}
+
+static void linked_plan_table()
+{
+    plan_first_pass();
+    plan_big();
+    plan_runs();
+    plan_runin();
+    plan_pointer();
+    plan_knobs();
+}
+
 int main()
 {
+    linked_plan_table();
     frame_parser_fuzz();
     pool_stress();
     resize_checks();

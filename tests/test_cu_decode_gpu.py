@@ -138,7 +138,7 @@ def test_cu_decoder_is_the_default_for_small_calls_only(engine, oracle):
 
 
 def test_runin_state_decays_with_every_linked_call(engine, oracle):
-    """The run-in decode's adaptive state (api.cpp: runinLong, runinLongOk, runinSkip): an engine that was sent to the long run-in
+    """The run-in decode's adaptive state (linked_plan.hpp: RuninState, runin_plan): an engine that was sent to the long run-in
     tries the default again after RUNIN_LONG_PROBE (32) linked calls of ANY size, not only after that many long run-ins."""
     import ctypes as C
     S = pytest.importorskip("streamly_lz4_amd")
