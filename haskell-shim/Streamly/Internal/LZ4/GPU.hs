@@ -32,6 +32,7 @@ module Streamly.Internal.LZ4.GPU
     , freeEngine
     , setLinkedCompress
     , setBlockChecksum
+    , setCompressionLevel
     , MultiEngine
     , newMultiEngine
     , freeMultiEngine
@@ -84,6 +85,9 @@ foreign import ccall unsafe "mi355lz4.h mi355lz4_set_linked_compress"
 -- replaces c_compressFastContinue (Streamly/Internal/LZ4.hs:123-131), N blocks per call
 foreign import ccall unsafe "mi355lz4.h mi355lz4_set_block_checksum"
     c_setBlockChecksum :: Ptr C_Engine -> CInt -> IO CInt
+
+foreign import ccall unsafe "mi355lz4.h mi355lz4_set_compression_level"
+    c_setCompressionLevel :: Ptr C_Engine -> CInt -> IO CInt
 
 foreign import ccall safe "mi355lz4.h mi355lz4_compress_batch"
     c_compressBatch
@@ -165,6 +169,15 @@ setBlockChecksum :: Engine -> Bool -> IO ()
 setBlockChecksum (Engine p) on = do
     rc <- c_setBlockChecksum p (if on then 1 else 0)
     when (rc /= 0) $ error "mi355lz4_set_block_checksum failed"
+
+-- | The compression level of 'compressChunksGPU' (the @lz4 -1@ .. @-12@ choice, which the reference
+-- does not offer): 0, the default, is the fast encoder and the @speed@ argument applies; 1..9 select
+-- the GPU hash-chain encoder (LZ4HC's levels, smaller output, @speed@ ignored); 10..12 behave as 9.
+-- The blocks are ordinary LZ4 blocks: 'decompressChunksRawGPU' and the reference read them unchanged.
+setCompressionLevel :: Engine -> Int -> IO ()
+setCompressionLevel (Engine p) level = do
+    rc <- c_setCompressionLevel p (fromIntegral level)
+    when (rc /= 0) $ error "mi355lz4_set_compression_level: a level is 0..12"
 
 batchBlocks :: Int
 batchBlocks = 4096

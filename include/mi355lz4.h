@@ -360,6 +360,17 @@ int mi355lz4_interleave_device(mi355lz4_ctx *ctx, const uint8_t *local, const ui
  *   trailers (mi355lz4_index_host_ex).
  * Default off.  mi355lz4_index_device and the legacy face (include/lz4.h) do not look at it. */
 int mi355lz4_set_block_checksum(mi355lz4_ctx *ctx, int on);
+/* Compression level of the engine's compress calls (_compress_batch_device, _compress_batch, the frame and legacy faces
+ * that go through them; linked or not, block checksums or not):
+ *   0      the default: the fast encoder, `accel` as in LZ4_compress_fast; its output is unchanged by this call;
+ *   1..9   the hash-chain encoder (LZ4HC's levels): every position's longest match within 2^(level-1) chain steps, a
+ *          one-step lazy parse; smaller output, slower; `accel` is ignored.  Deterministic, plain LZ4 blocks that
+ *          every decoder reads; linked compression uses the same dictionary as level 0;
+ *   10..12 accepted, searched as 9 (mi355lz4_get_compression_level then returns 9).
+ * Anything else, or a null ctx: MI355LZ4_E_ARG.  The multi handle's compress call needs its engines to agree. */
+int mi355lz4_set_compression_level(mi355lz4_ctx *ctx, int level);
+/* The effective level (0..9), or MI355LZ4_E_ARG for a null ctx. */
+int mi355lz4_get_compression_level(const mi355lz4_ctx *ctx);
 /* mi355lz4_slot_stride with room for the trailer when blockChecksum != 0. */
 size_t mi355lz4_slot_stride_ex(int blockLen, int headerKind, int blockChecksum);
 /* mi355lz4_index_host over a chain whose blocks carry trailers when blockChecksum != 0 (a block spans

@@ -76,6 +76,11 @@ public:
     // reads either kind.  Default off: independent blocks.
     void setLinkedCompress(bool on);
     bool linkedCompress() const { return linked_; }
+    // Compression level of compressChunks and lz4FrameCompress (mi355lz4_set_compression_level): 0 (default) the fast
+    // encoder, 1..9 the hash-chain encoder (LZ4HC's levels; `speed` is then ignored), 10..12 as 9.  Throws Error otherwise.
+    // The streams and frames it writes are ordinary ones: nothing on the decode side changes.
+    void setCompressionLevel(int level);
+    int compressionLevel() const;
 private:
     mi355lz4_ctx *ctx_ = nullptr;
     size_t batch_;

@@ -151,6 +151,7 @@ struct mi355lz4_ctx {
     int decoder = 0;
     int linkedCompress = 0;                 // compress calls treat their blocks as consecutive blocks of one stream
     int blockChecksum = 0;                  // every block's data is followed by its xxh32 (mi355lz4_set_block_checksum)
+    int compLevel = 0;                      // 0: k_encode (fast); 1..9: k_encode_hc (mi355lz4_set_compression_level)
     DevBuf ckBuf;                           // ... the decode side's per-block verdicts (k_xxh32_verify)
     hipEvent_t ckEvent = nullptr;           // ... end of the last decode that read them, and the stream it ran on
     hipStream_t ckStream = nullptr;
@@ -404,6 +405,22 @@ extern "C" int mi355lz4_set_block_checksum(mi355lz4_ctx *c, int on)
 // the switch as the multi handle sees it (multi_device.cpp): its engines must agree
 int engine_block_checksum(const mi355lz4_ctx *c) { return c ? c->blockChecksum : 0; }
 
+extern "C" int mi355lz4_set_compression_level(mi355lz4_ctx *c, int level)
+{
+    if (!c) return fail(MI355LZ4_E_ARG, "null ctx");
+    if (level < 0 || level > 12) return fail(MI355LZ4_E_ARG, "compression level %d: 0..12", level);
+    c->compLevel = level > 9 ? 9 : level;      // 10..12 (LZ4HC's optimal parser) search as 9
+    return MI355LZ4_OK;
+}
+
+extern "C" int mi355lz4_get_compression_level(const mi355lz4_ctx *c)
+{
+    if (!c) return fail(MI355LZ4_E_ARG, "null ctx");
+    return c->compLevel;
+}
+
+int engine_compression_level(const mi355lz4_ctx *c) { return c ? c->compLevel : 0; }
+
 extern "C" int mi355lz4_set_linked_compress(mi355lz4_ctx *c, int on)
 {
     if (!c) return fail(MI355LZ4_E_ARG, "null ctx");
@@ -534,6 +551,11 @@ static int encode_device(mi355lz4_ctx *c, const uint8_t *src, const uint64_t *sr
         launch_xxh32_append(slots, slotStride, headerKind, framedLen, nBlocks, c->stream);
         return check_launch("checksum launch");
     };
+    // compression levels 1..12: the hash-chain encoder, every block size, linked or not; accel does not apply (as in LZ4HC)
+    if (c->compLevel > 0) {
+        launch_encode_hc(a, c->compLevel, c->stream);
+        return finish();
+    }
     // Small batches: with fewer blocks than the chip has wave slots (256 CUs x 16), a block is cut into segments that
     // several waves compress at once (kernels.hip, "K2, small batches").  Segments of >= 4 KiB, at most 64 per block,
     // about two waves per slot in all; blocks of up to 4 MiB (24-bit positions in the records); independent blocks only.

@@ -81,6 +81,12 @@ Engine::Engine(int device, size_t batchBlocks) : batch_(batchBlocks ? batchBlock
         throw Error(std::string("streamly_lz4::Engine: ") + mi355lz4_last_error());
 }
 void Engine::setLinkedCompress(bool on) { mi355lz4_set_linked_compress(ctx_, on ? 1 : 0); linked_ = on; }
+void Engine::setCompressionLevel(int level)
+{
+    if (mi355lz4_set_compression_level(ctx_, level) != MI355LZ4_OK)
+        throw Error(std::string("streamly_lz4::Engine::setCompressionLevel: ") + mi355lz4_last_error());
+}
+int Engine::compressionLevel() const { return mi355lz4_get_compression_level(ctx_); }
 
 Engine::~Engine() { mi355lz4_destroy(ctx_); }
 

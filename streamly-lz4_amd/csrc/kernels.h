@@ -138,6 +138,7 @@ void launch_linked_runs(const DecodeArgs &a, hipStream_t s);      // one stream,
 size_t ptr_ctl_bytes();
 size_t tol_region_bytes();
 void launch_encode(const EncodeArgs &a, bool bigBlocks, hipStream_t s);   // bigBlocks: some block is above 64 KiB
+void launch_encode_hc(const EncodeArgs &a, int level, hipStream_t s);      // compression levels 1..12 (encode_hc.hpp)
 void launch_compact(const uint8_t *slots, size_t slotStride, const int32_t *framedLen, int nBlocks,
                     uint8_t *dense, size_t denseCap, uint64_t *denseOff, hipStream_t s);
 void launch_interleave(const uint8_t *local, const uint64_t *localOff, int nLocal, int rank, int nRanks,

@@ -4,6 +4,7 @@
 //       k_decode_tolerant, k_ptr_*       linked streams, second pass (linked_ptr.hpp)
 //       k_decode_fixup_regions / _linked ... its in-order fallbacks (linked_replay.hpp)
 //   K2  k_encode<TabT, DICT>             block encode, independent or linked (encode_wave.hpp)
+//       k_encode_hc                      high-compression levels: hash chains + lazy parse (encode_hc.hpp)
 //   K3  k_scan_u64 + k_copy_slots        size scan + compaction into the framed stream
 //       k_header_sizes                   uncompressed-size scan from block headers
 //       k_generate                       synthetic inputs (bench/test support)
@@ -20,6 +21,7 @@
 #include "linked_replay.hpp"
 #include "linked_ptr.hpp"
 #include "encode_wave.hpp"
+#include "encode_hc.hpp"
 #include "checksum.hpp"
 
 using namespace lz4dev;
@@ -188,6 +190,46 @@ void launch_encode(const EncodeArgs &a, bool bigBlocks, hipStream_t s)
 #else
     else hipLaunchKernelGGL((k_encode<false, true>), grid, wg, 0, s, a);
 #endif
+}
+
+// ---------------------------------------------------------------------------
+// K2, high-compression levels (encode_hc.hpp): one workgroup of HC_THREADS per block, all of a CU's LDS, a persistent grid
+// of one workgroup per CU striding over the blocks.  Same slots, headers, framedLen and dictionary as k_encode.
+// ---------------------------------------------------------------------------
+__global__ __launch_bounds__(HC_THREADS) void k_encode_hc(EncodeArgs a, int depth)
+{
+    __shared__ HcLds L;
+    for (int blk = (int)blockIdx.x; blk < a.nBlocks; blk += (int)gridDim.x) {
+        const uint64_t off = a.srcOff ? a.srcOff[blk] : (uint64_t)blk * a.blockStride;
+        const int n = a.srcLen ? a.srcLen[blk] : a.uniformLen;
+        uint8_t *slot = a.slots + (size_t)blk * a.slotStride;
+        int dictLen = 0;
+        if (a.linked && (blk > 0 || a.lookBack > 0)) {           // k_encode's dictionary: the block directly in front
+            const uint64_t poff = a.srcOff ? a.srcOff[blk - 1] : (uint64_t)(blk - 1) * a.blockStride;
+            const int pn = a.srcLen ? a.srcLen[blk - 1] : a.uniformLen;
+            if (pn > 0 && poff + (uint64_t)pn == off) dictLen = min(pn, 65536);
+        }
+        int c = 0;
+        if (n >= 0) c = encode_block_hc(L, a.src + off, n, dictLen, slot + a.headerKind, depth);
+        if (threadIdx.x == 0) {
+            store_le32(slot, c);
+            if (a.headerKind == 8) store_le32(slot + 4, n);
+            a.framedLen[blk] = (c > 0) ? a.headerKind + c : 0;
+        }
+    }
+}
+
+void launch_encode_hc(const EncodeArgs &a, int level, hipStream_t s)
+{
+    if (a.nBlocks <= 0) return;
+    static int cus[64];
+    int dev = 0;
+    (void)hipGetDevice(&dev);
+    int &nc = cus[dev & 63];
+    if (nc <= 0 && hipDeviceGetAttribute(&nc, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) nc = 256;
+    const int depth = 1 << (min(level, 9) - 1);
+    const unsigned grid = (unsigned)min(a.nBlocks, max(nc, 1));
+    hipLaunchKernelGGL(k_encode_hc, dim3(grid), dim3(HC_THREADS), 0, s, a, depth);
 }
 
 // ---------------------------------------------------------------------------

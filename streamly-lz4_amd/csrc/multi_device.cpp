@@ -98,6 +98,7 @@ struct PartResult {
 };
 
 int engine_block_checksum(const mi355lz4_ctx *c);   // api.cpp
+int engine_compression_level(const mi355lz4_ctx *c);   // api.cpp
 
 // Block checksums (mi355lz4_set_block_checksum) are a property of the stream a call reads or writes: every engine of the
 // handle must have the same setting.  -1: they disagree.
@@ -107,6 +108,15 @@ static int multi_block_checksum(const mi355lz4_multi *m)
     for (mi355lz4_ctx *e : m->eng)
         if (engine_block_checksum(e) != ck) return -1;
     return ck;
+}
+
+// The compression level (mi355lz4_set_compression_level) decides the bytes a compress call writes: the engines must agree,
+// or the output would depend on how the blocks were spread over the devices.
+static bool multi_same_level(const mi355lz4_multi *m)
+{
+    for (mi355lz4_ctx *e : m->eng)
+        if (engine_compression_level(e) != engine_compression_level(m->eng[0])) return false;
+    return true;
 }
 
 extern "C" int mi355lz4_multi_compress_batch(mi355lz4_multi *m, const uint8_t *const *src, const int32_t *srcLen, int nBlocks,
@@ -119,6 +129,8 @@ extern "C" int mi355lz4_multi_compress_batch(mi355lz4_multi *m, const uint8_t *c
     *outLen = 0;
     const int ck = multi_block_checksum(m);
     if (ck < 0) return mfail(MI355LZ4_E_ARG, "mi355lz4_multi_compress_batch: the engines disagree on block checksums");
+    if (!multi_same_level(m))
+        return mfail(MI355LZ4_E_ARG, "mi355lz4_multi_compress_batch: the engines disagree on the compression level");
     if (nBlocks == 0) return MI355LZ4_OK;
     const std::vector<int> first = cut_ranges(srcLen, nBlocks, (int)m->eng.size());
     const int P = (int)first.size() - 1;

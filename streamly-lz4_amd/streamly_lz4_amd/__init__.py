@@ -116,6 +116,9 @@ def _load():
     sig("mi355lz4_index_host_ex", C.c_int, _u8p, C.c_size_t, C.c_int, C.c_int, C.c_int, _u64p, _i32p, C.c_int,
         C.POINTER(C.c_int))
     sig("mi355lz4_xxh32_device", C.c_int, vp, vp, vp, vp, C.c_int, C.c_uint32, vp)
+    # compression levels
+    sig("mi355lz4_set_compression_level", C.c_int, vp, C.c_int)
+    sig("mi355lz4_get_compression_level", C.c_int, vp)
     # legacy face (include/lz4.h)
     sig("LZ4_createStream", vp)
     sig("LZ4_freeStream", C.c_int, vp)
@@ -165,6 +168,7 @@ DECLARED_SYMBOLS = [
     "mi355lz4_create_multi", "mi355lz4_destroy_multi", "mi355lz4_multi_device_count", "mi355lz4_multi_engine", "mi355lz4_multi_last_error",
     "mi355lz4_multi_compress_batch", "mi355lz4_multi_decompress_batch",
     "mi355lz4_set_block_checksum", "mi355lz4_slot_stride_ex", "mi355lz4_index_host_ex", "mi355lz4_xxh32_device",
+    "mi355lz4_set_compression_level", "mi355lz4_get_compression_level",
     "LZ4_createStream", "LZ4_freeStream", "LZ4_createStreamDecode", "LZ4_freeStreamDecode", "LZ4_compressBound",
     "LZ4_compress_fast_continue", "LZ4_decompress_safe_continue",
 ]
@@ -324,6 +328,13 @@ class MultiEngine:
                    "set_block_checksum")
         self._block_checksum = bool(on)
 
+    def set_compression_level(self, level):
+        """Compression level on every engine of the handle (include/mi355lz4.h, mi355lz4_set_compression_level)."""
+        lib.mi355lz4_multi_engine.restype = C.c_void_p
+        for i in range(self.n):
+            _check(lib.mi355lz4_set_compression_level(C.c_void_p(lib.mi355lz4_multi_engine(self._h, i)), int(level)),
+                   "set_compression_level")
+
     def set_decoder(self, variant):
         lib.mi355lz4_multi_engine.restype = C.c_void_p
         for i in range(self.n):
@@ -434,6 +445,17 @@ class Engine:
         decode call (include/mi355lz4.h, mi355lz4_set_block_checksum; Config.hs setBlockChecksum)."""
         _check(lib.mi355lz4_set_block_checksum(self.ctx, int(bool(on))), "set_block_checksum")
         self._block_checksum = bool(on)
+
+    def set_compression_level(self, level):
+        """0 (default): the fast encoder.  1..9: the hash-chain encoder (LZ4HC's levels: chain depth 2^(level-1), lazy
+        parse; smaller output, `accel` ignored); 10..12 behave as 9.  Every compress call of the engine -- device and host
+        calls, compressChunks, frames -- uses it (include/mi355lz4.h, mi355lz4_set_compression_level)."""
+        _check(lib.mi355lz4_set_compression_level(self.ctx, int(level)), "set_compression_level")
+
+    @property
+    def compression_level(self):
+        """The effective compression level (0..9)."""
+        return int(lib.mi355lz4_get_compression_level(self.ctx))
 
     def xxh32_device(self, base, off, length, n, seed, out):
         """out[i] = xxh32(seed) of base[off[i] : off[i] + length[i]] for i < n (uint8 / int64 / int32 / int32 device
