@@ -33,6 +33,8 @@ module Streamly.Internal.LZ4.GPU
     , setLinkedCompress
     , setBlockChecksum
     , setCompressionLevel
+    , setCompressExact
+    , resetCompressStream
     , MultiEngine
     , newMultiEngine
     , freeMultiEngine
@@ -88,6 +90,15 @@ foreign import ccall unsafe "mi355lz4.h mi355lz4_set_block_checksum"
 
 foreign import ccall unsafe "mi355lz4.h mi355lz4_set_compression_level"
     c_setCompressionLevel :: Ptr C_Engine -> CInt -> IO CInt
+
+foreign import ccall unsafe "mi355lz4.h mi355lz4_set_compress_exact"
+    c_setCompressExact :: Ptr C_Engine -> CInt -> IO CInt
+
+foreign import ccall unsafe "mi355lz4.h mi355lz4_compress_exact_reset"
+    c_compressExactReset :: Ptr C_Engine -> IO CInt
+
+foreign import ccall unsafe "mi355lz4.h mi355lz4_get_compress_exact"
+    c_getCompressExact :: Ptr C_Engine -> IO CInt
 
 foreign import ccall safe "mi355lz4.h mi355lz4_compress_batch"
     c_compressBatch
@@ -179,6 +190,21 @@ setCompressionLevel (Engine p) level = do
     rc <- c_setCompressionLevel p (fromIntegral level)
     when (rc /= 0) $ error "mi355lz4_set_compression_level: a level is 0..12"
 
+-- | Reference-exact compression: while on, 'compressChunksGPU' writes the bytes the reference's 'compressChunks' writes
+-- (one linked stream, @LZ4_compress_fast_continue@'s), for compression level 0.  Like @compressChunksD@, which creates
+-- one @LZ4_stream_t@ per stream, 'compressChunksGPU' starts a new stream when its output is first pulled, and its
+-- batches continue it.  Switching the mode on starts a new stream too.
+setCompressExact :: Engine -> Bool -> IO ()
+setCompressExact (Engine p) on = do
+    rc <- c_setCompressExact p (if on then 1 else 0)
+    when (rc /= 0) $ error "mi355lz4_set_compress_exact failed"
+
+-- | Start a new exact compress stream (@LZ4_createStream@).
+resetCompressStream :: Engine -> IO ()
+resetCompressStream (Engine p) = do
+    rc <- c_compressExactReset p
+    when (rc /= 0) $ error "mi355lz4_compress_exact_reset failed"
+
 batchBlocks :: Int
 batchBlocks = 4096
 
@@ -245,6 +271,26 @@ compressChunksGPU eng cfg speed0 =
       Stream.concatMap Stream.fromList
     . Stream.mapM (liftIO . compressBatch eng cfg (max speed0 0))
     . Stream.groupsOf batchBlocks Fold.toList
+    . startExactStream eng
+
+-- | Before the first array is pulled: a new exact stream when the engine is in the reference-exact mode (one
+-- @LZ4_stream_t@ per @compressChunksD@, Streamly/Internal/LZ4.hs:353-394); otherwise nothing.
+startExactStream :: MonadIO m => Engine -> Stream.Stream m a -> Stream.Stream m a
+startExactStream (Engine p) (Stream.Stream step0 st0) = Stream.Stream step (Left st0)
+  where
+    step _ (Left st) = do
+        liftIO $ do
+            on <- c_getCompressExact p
+            when (on == 1) $ do
+                rc <- c_compressExactReset p
+                when (rc /= 0) $ error "mi355lz4_compress_exact_reset failed"
+        return $ Stream.Skip (Right st)
+    step gst (Right st) = do
+        r <- step0 gst st
+        return $ case r of
+            Stream.Yield a st' -> Stream.Yield a (Right st')
+            Stream.Skip st' -> Stream.Skip (Right st')
+            Stream.Stop -> Stream.Stop
 
 -- | Drop-in for @decompressChunksRawD@ (Streamly/Internal/LZ4.hs:539-567): the incoming
 -- arrays are resized blocks; the previous output array is threaded through as the

@@ -371,6 +371,24 @@ int mi355lz4_set_block_checksum(mi355lz4_ctx *ctx, int on);
 int mi355lz4_set_compression_level(mi355lz4_ctx *ctx, int level);
 /* The effective level (0..9), or MI355LZ4_E_ARG for a null ctx. */
 int mi355lz4_get_compression_level(const mi355lz4_ctx *ctx);
+/* Reference-exact compression.  While on, the ctx holds ONE compress stream -- the device counterpart of LZ4_stream_t --
+ * and every _compress_batch / _compress_batch_device call appends its blocks to it, in order: block i's bytes are those of
+ * LZ4_compress_fast_continue on one stream over separately allocated arrays (the external-dictionary path, as
+ * Streamly.Internal.LZ4's compressChunksD drives it), whatever `accel` (clamped to 1..65537), lengths (0 up to
+ * LZ4_MAX_INPUT_SIZE) or placement in memory; across calls, through the 2 GiB renormalisation.  The engine keeps its own
+ * copy of the table, the offsets and the previous array's last 64 KiB: the caller may free a call's buffers.
+ * Header kinds 4 / 8, block checksums, compaction and the pipelined host call work unchanged; the linked switch
+ * (mi355lz4_set_linked_compress) is ignored; frames (lz4FrameCompress) and the legacy face do not use the stream.
+ * The device call waits on the engine's stream (it reads the lengths, and its verify step decides which speculated
+ * pieces are redone).  Refused with MI355LZ4_E_ARG at the compress call: a compression level other than 0, forced
+ * segments (mi355lz4_set_segments k > 0); the multi handle refuses engines in this mode.
+ * Switching it on starts a new stream; default off, and off nothing changes.  MI355LZ4_EXACT_RUNIN=R (default 12; 0: one
+ * serial chain) and MI355LZ4_EXACT_PIECE=P (default max(4, blocks / 2048)) set the speculation, read per call. */
+int mi355lz4_set_compress_exact(mi355lz4_ctx *ctx, int on);
+/* 1 while the mode is on, 0 off, MI355LZ4_E_ARG for a null ctx. */
+int mi355lz4_get_compress_exact(const mi355lz4_ctx *ctx);
+/* Start a new exact stream (LZ4_createStream): the next call's first block has no dictionary and a zeroed table. */
+int mi355lz4_compress_exact_reset(mi355lz4_ctx *ctx);
 /* mi355lz4_slot_stride with room for the trailer when blockChecksum != 0. */
 size_t mi355lz4_slot_stride_ex(int blockLen, int headerKind, int blockChecksum);
 /* mi355lz4_index_host over a chain whose blocks carry trailers when blockChecksum != 0 (a block spans

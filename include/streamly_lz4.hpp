@@ -81,6 +81,12 @@ public:
     // The streams and frames it writes are ordinary ones: nothing on the decode side changes.
     void setCompressionLevel(int level);
     int compressionLevel() const;
+    // Reference-exact compression (mi355lz4_set_compress_exact): compressChunks writes the bytes the reference's
+    // compressChunksD writes -- one linked stream, LZ4_compress_fast_continue's -- for level 0.  compressChunks starts a
+    // new stream when it starts and continues it across its batches.  Switching it on starts a new stream.
+    void setCompressExact(bool on);
+    bool compressExact() const;
+    void resetCompressStream();
 private:
     mi355lz4_ctx *ctx_ = nullptr;
     size_t batch_;

@@ -152,6 +152,11 @@ struct mi355lz4_ctx {
     int linkedCompress = 0;                 // compress calls treat their blocks as consecutive blocks of one stream
     int blockChecksum = 0;                  // every block's data is followed by its xxh32 (mi355lz4_set_block_checksum)
     int compLevel = 0;                      // 0: k_encode (fast); 1..9: k_encode_hc (mi355lz4_set_compression_level)
+    int compExact = 0;                      // compress calls continue ONE reference-exact stream (mi355lz4_set_compress_exact)
+    // ... that stream's state (the device counterpart of LZ4_stream_t): currentOffset and dictSize here, the table and
+    // the previous array's last bytes in exState; fresh = the table is still to be zeroed (a new stream)
+    struct ExactStream { uint32_t cur = 0, dictSize = 0; int dictBytes = 0; bool fresh = true; int last[4] = {0, 0, 0, 0}; } ex;
+    DevBuf exState, exMeta, exTabs, exFlags;
     DevBuf ckBuf;                           // ... the decode side's per-block verdicts (k_xxh32_verify)
     hipEvent_t ckEvent = nullptr;           // ... end of the last decode that read them, and the stream it ran on
     hipStream_t ckStream = nullptr;
@@ -325,7 +330,7 @@ extern "C" void mi355lz4_destroy(mi355lz4_ctx *c)
     if (c->stream) hipStreamSynchronize(c->stream);
     for (DevBuf *b : {&c->in, &c->slots, &c->dense, &c->out, &c->offA, &c->offB, &c->lenA, &c->lenB, &c->res, &c->scratch,
                       &c->tolPool, &c->tolMeta, &c->linkBuf, &c->ptrBuf, &c->seg[0].b, &c->seg[1].b, &c->seg[2].b, &c->seg[3].b, &c->tokBuf,
-                      &c->ckBuf})
+                      &c->ckBuf, &c->exState, &c->exMeta, &c->exTabs, &c->exFlags})
         dev_release(*b);
     if (c->linkEvent) hipEventDestroy(c->linkEvent);
     if (c->ckEvent) hipEventDestroy(c->ckEvent);
@@ -420,6 +425,45 @@ extern "C" int mi355lz4_get_compression_level(const mi355lz4_ctx *c)
 }
 
 int engine_compression_level(const mi355lz4_ctx *c) { return c ? c->compLevel : 0; }
+
+extern "C" int mi355lz4_set_compress_exact(mi355lz4_ctx *c, int on)
+{
+    if (!c) return fail(MI355LZ4_E_ARG, "null ctx");
+    c->compExact = on ? 1 : 0;
+    if (on) c->ex = mi355lz4_ctx::ExactStream();     // switching it on starts a new stream
+    return MI355LZ4_OK;
+}
+
+extern "C" int mi355lz4_get_compress_exact(const mi355lz4_ctx *c)
+{
+    if (!c) return fail(MI355LZ4_E_ARG, "null ctx");
+    return c->compExact;
+}
+
+extern "C" int mi355lz4_compress_exact_reset(mi355lz4_ctx *c)
+{
+    if (!c) return fail(MI355LZ4_E_ARG, "null ctx");
+    c->ex = mi355lz4_ctx::ExactStream();              // LZ4_createStream: the table is zeroed by the next call
+    return MI355LZ4_OK;
+}
+
+int engine_compress_exact(const mi355lz4_ctx *c) { return c ? c->compExact : 0; }
+int engine_swap_compress_exact(mi355lz4_ctx *c, int on)
+{
+    if (!c) return 0;
+    const int was = c->compExact;
+    c->compExact = on;
+    return was;
+}
+
+// Diagnostic hook (not part of the public header): the last exact compress call's pieces.  get (4 ints): pieces in all,
+// pieces speculated (started from a zeroed table), speculated pieces whose assumption held, pieces redone.
+extern "C" int mi355lz4_debug_exact_state(mi355lz4_ctx *c, int *get)
+{
+    if (!c || !get) return fail(MI355LZ4_E_ARG, "debug_exact_state: null argument");
+    for (int i = 0; i < 4; i++) get[i] = c->ex.last[i];
+    return MI355LZ4_OK;
+}
 
 extern "C" int mi355lz4_set_linked_compress(mi355lz4_ctx *c, int on)
 {
@@ -521,9 +565,127 @@ static int check_launch(const char *what)
 // ---------------------------------------------------------------------------
 // device-resident batched API
 // ---------------------------------------------------------------------------
+// ---------------------------------------------------------------------------
+// Reference-exact compression (mi355lz4_set_compress_exact; encode_exact.hpp).  The host follows the
+// stream's scalar state (currentOffset, dictSize, renorms) from the lengths alone; the device holds the table and the
+// dictionary bytes.  Pieces of P blocks are speculated from a zeroed table R blocks early and verified in parallel; the
+// ones whose assumption failed are redone from their predecessor's true table, serially and in order.
+// ---------------------------------------------------------------------------
+static int env_int(const char *name, int dflt)
+{
+    const char *e = getenv(name);
+    return (e && *e) ? atoi(e) : dflt;
+}
+
+static int exact_encode(mi355lz4_ctx *c, EncodeArgs a, const int32_t *hostLen)
+{
+    const int n = a.nBlocks;
+    std::vector<int32_t> lens((size_t)n, a.uniformLen);
+    if (hostLen) {
+        std::copy(hostLen, hostLen + n, lens.begin());
+    } else if (a.srcLen) {                      // the device call: the plan needs the lengths (a wait on the engine's stream)
+        HIP_TRY(hipMemcpyAsync(lens.data(), a.srcLen, (size_t)n * 4, hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(hipStreamSynchronize(c->stream));
+    }
+    for (int j = 0; j < n; j++)
+        if (lens[(size_t)j] < 0 || lens[(size_t)j] > a.uniformLen)
+            return fail(MI355LZ4_E_ARG, "compress_exact: block %d length %d outside 0..maxBlockLen", j, lens[(size_t)j]);
+    // cbits/lz4.c:1565-1637 with the lengths alone: renorm (:1545-1562), dictionaries under 4 bytes (:1581-1587), dictSmall
+    std::vector<ExactBlock> meta((size_t)n + 1);
+    uint32_t cur = c->ex.cur, dictSize = c->ex.dictSize;
+    for (int j = 0; j < n; j++) {
+        const uint32_t len = (uint32_t)lens[(size_t)j];
+        ExactBlock &m = meta[(size_t)j];
+        m.delta = 0;
+        if (cur + len > 0x80000000u) {
+            m.delta = cur - 65536u;
+            cur = 65536u;
+            if (dictSize > 65536u) dictSize = 65536u;
+        }
+        if (dictSize - 1u < 4u - 1u) dictSize = 0;
+        m.start = cur; m.dictSize = dictSize; m.n = (int32_t)len; m.pad = 0;
+        m.dictSmall = (dictSize < 65536u && dictSize < cur) ? 1 : 0;
+        cur += len;
+        dictSize = len;
+    }
+    meta[(size_t)n] = ExactBlock{cur, dictSize, 0u, 0, 0, 0};
+
+    // R = 0: no speculation, one serial chain
+    const int R = std::max(0, env_int("MI355LZ4_EXACT_RUNIN", 12));
+    int P = env_int("MI355LZ4_EXACT_PIECE", 0);
+    if (P <= 0) P = std::max(4, (n + 2047) / 2048);
+    if (R == 0) P = n;
+    const int np = (n + P - 1) / P;
+    const size_t tabBytes = (size_t)EXACT_TABLE * 4;
+    int r;
+    if (!c->exState.p) {                         // never grown: it holds the stream
+        HIP_TRY(hipMalloc(&c->exState.p, tabBytes + 65536));
+        c->exState.cap = tabBytes + 65536;
+    }
+    if ((r = dev_reserve(c->exMeta, ((size_t)n + 1) * sizeof(ExactBlock)))) return r;
+    if ((r = dev_reserve(c->exTabs, 2 * (size_t)np * tabBytes))) return r;
+    if ((r = dev_reserve(c->exFlags, (size_t)np * 4 + 64))) return r;     // eq[np]
+    if (c->ex.fresh) {
+        HIP_TRY(hipMemsetAsync(c->exState.p, 0, tabBytes, c->stream));
+        c->ex.fresh = false;
+    }
+    ExactArgs x;
+    x.e = a;
+    x.meta = (const ExactBlock *)c->exMeta.p;
+    x.dict0 = (const uint8_t *)c->exState.p + tabBytes;
+    x.dict0Len = c->ex.dictBytes;
+    x.state = (uint32_t *)c->exState.p;
+    x.dictSave = (uint8_t *)c->exState.p + tabBytes;
+    x.assumed = (uint32_t *)c->exTabs.p;
+    x.finalT = (uint32_t *)c->exTabs.p + (size_t)np * EXACT_TABLE;
+    x.eq = (int32_t *)c->exFlags.p;
+    x.piece = P; x.runin = R; x.nPieces = np;
+    HIP_TRY(hipMemcpyAsync(c->exMeta.p, meta.data(), meta.size() * sizeof(ExactBlock), hipMemcpyHostToDevice, c->stream));
+    launch_exact_chain(x, 0, np, 0, c->stream);
+    if ((r = check_launch("exact chain launch"))) return r;
+
+    // which pieces started from the stream's true state (exact by construction), which were speculated
+    std::vector<char> exactStart((size_t)np);
+    int speculated = 0, redone = 0;
+    for (int p = 0; p < np; p++) {
+        exactStart[(size_t)p] = (p == 0 || p * P - R <= 0) ? 1 : 0;
+        if (!exactStart[(size_t)p]) speculated++;
+    }
+    std::vector<int32_t> eq((size_t)np, 0);
+    if (speculated) {
+        launch_exact_verify(x, 1, np - 1, c->stream);
+        if ((r = check_launch("exact verify launch"))) return r;
+        HIP_TRY(hipMemcpyAsync(eq.data(), x.eq, (size_t)np * 4, hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(hipStreamSynchronize(c->stream));
+    }
+    // In order: piece p is exact when it started from the true state, or piece p-1 is exact and p's assumed table is
+    // p-1's final one (eq[p]).  The first piece that is neither is redone from p-1's final table, which makes it exact,
+    // and the comparison of its successor is repeated against the new final table.  One piece per round, one wait.
+    for (int p = 1; p < np; p++) {
+        if (exactStart[(size_t)p] || eq[(size_t)p]) continue;
+        launch_exact_chain(x, p, 1, 1, c->stream);
+        const bool check = p + 1 < np && !exactStart[(size_t)p + 1];
+        if (check) launch_exact_verify(x, p + 1, 1, c->stream);
+        if ((r = check_launch("exact redo launch"))) return r;
+        if (check) {
+            HIP_TRY(hipMemcpyAsync(&eq[(size_t)p + 1], x.eq + p + 1, 4, hipMemcpyDeviceToHost, c->stream));
+            HIP_TRY(hipStreamSynchronize(c->stream));
+        }
+        redone++;
+    }
+    launch_exact_finish(x, c->stream);
+    if ((r = check_launch("exact finish launch"))) return r;
+    HIP_TRY(hipStreamSynchronize(c->stream));     // meta is a host vector of this frame
+    c->ex.cur = cur;
+    c->ex.dictSize = dictSize;
+    c->ex.dictBytes = (int)std::min<uint32_t>((uint32_t)lens[(size_t)n - 1], 65536u);
+    c->ex.last[0] = np; c->ex.last[1] = speculated; c->ex.last[2] = speculated - redone; c->ex.last[3] = redone;
+    return MI355LZ4_OK;
+}
+
 static int encode_device(mi355lz4_ctx *c, const uint8_t *src, const uint64_t *srcOff, const int32_t *srcLen,
                          uint64_t blockStride, int maxBlockLen, int nBlocks, int accel, int headerKind, uint8_t *slots,
-                         size_t slotStride, int32_t *framedLen, int lookBack)
+                         size_t slotStride, int32_t *framedLen, int lookBack, const int32_t *hostLen = nullptr)
 {
     if (!c) return fail(MI355LZ4_E_ARG, "null ctx");
     if (nBlocks < 0 || (headerKind != 4 && headerKind != 8) || maxBlockLen < 0 ||
@@ -551,6 +713,15 @@ static int encode_device(mi355lz4_ctx *c, const uint8_t *src, const uint64_t *sr
         launch_xxh32_append(slots, slotStride, headerKind, framedLen, nBlocks, c->stream);
         return check_launch("checksum launch");
     };
+    // the reference-exact stream: its own chain of kernels, whatever the linked switch says
+    if (c->compExact) {
+        if (c->compLevel != 0)
+            return fail(MI355LZ4_E_ARG, "compress_exact: compression level %d; the exact mode is level 0's encoder", c->compLevel);
+        if (c->segMode > 0)
+            return fail(MI355LZ4_E_ARG, "compress_exact: forced segments (mi355lz4_set_segments %d) cannot give the reference's bytes", c->segMode);
+        const int r = exact_encode(c, a, hostLen);
+        return r ? r : finish();
+    }
     // compression levels 1..12: the hash-chain encoder, every block size, linked or not; accel does not apply (as in LZ4HC)
     if (c->compLevel > 0) {
         launch_encode_hc(a, c->compLevel, c->stream);
@@ -1310,13 +1481,13 @@ extern "C" int mi355lz4_compress_batch(mi355lz4_ctx *c, const uint8_t *const *sr
             }
         }
         HIP_TRY(hipEventRecord(evIn[(size_t)g], c->sIn));
-        StreamSwap on(c, c->sK[g & 1]);
+        StreamSwap on(c, c->sK[c->compExact ? 0 : (g & 1)]);   // an exact stream's groups follow each other
         HIP_TRY(hipStreamWaitEvent(c->stream, evIn[(size_t)g], 0));
         PTRACE("compress: group %d H2D enqueued (%zu bytes, direct %d)", g, hi - lo, (int)directIn);
         // (a linked stream: the last block of the group before is this group's first dictionary)
         r = encode_device(c, (const uint8_t *)c->in.p, (const uint64_t *)c->offA.p + b0,
                           (const int32_t *)c->lenA.p + b0, 0, maxLen, b1 - b0, accel, headerKind,
-                          (uint8_t *)c->slots.p + (size_t)b0 * stride, stride, (int32_t *)c->lenB.p + b0, b0);
+                          (uint8_t *)c->slots.p + (size_t)b0 * stride, stride, (int32_t *)c->lenB.p + b0, b0, srcLen + b0);
         if (r) return r;
         uint64_t *goff = (uint64_t *)c->offB.p + b0 + g;                       // b1 - b0 + 1 offsets of this group
         r = mi355lz4_compact_device(c, (const uint8_t *)c->slots.p + (size_t)b0 * stride, stride,

@@ -87,6 +87,17 @@ void Engine::setCompressionLevel(int level)
         throw Error(std::string("streamly_lz4::Engine::setCompressionLevel: ") + mi355lz4_last_error());
 }
 int Engine::compressionLevel() const { return mi355lz4_get_compression_level(ctx_); }
+void Engine::setCompressExact(bool on)
+{
+    if (mi355lz4_set_compress_exact(ctx_, on ? 1 : 0) != MI355LZ4_OK)
+        throw Error(std::string("streamly_lz4::Engine::setCompressExact: ") + mi355lz4_last_error());
+}
+bool Engine::compressExact() const { return mi355lz4_get_compress_exact(ctx_) == 1; }
+void Engine::resetCompressStream()
+{
+    if (mi355lz4_compress_exact_reset(ctx_) != MI355LZ4_OK)
+        throw Error(std::string("streamly_lz4::Engine::resetCompressStream: ") + mi355lz4_last_error());
+}
 
 Engine::~Engine() { mi355lz4_destroy(ctx_); }
 
@@ -97,7 +108,10 @@ namespace {
 class CompressStream : public ArrayStream {
 public:
     CompressStream(BlockConfig cfg, int speed, StreamPtr in, Engine &eng)
-        : cfg_(cfg), speed_(speed < 0 ? 0 : speed) /* speed = max speed0 0, :364 */, in_(std::move(in)), eng_(eng) {}
+        : cfg_(cfg), speed_(speed < 0 ? 0 : speed) /* speed = max speed0 0, :364 */, in_(std::move(in)), eng_(eng)
+    {
+        if (eng_.compressExact()) eng_.resetCompressStream();   // one stream per compressChunksD (:357), across the batches
+    }
 
     bool next(Array &out) override
     {

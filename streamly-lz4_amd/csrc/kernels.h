@@ -101,6 +101,34 @@ struct EncodeArgs {
     int lookBack;                // linked: blocks of the same stream that precede block 0 in srcOff[] / srcLen[]
 };
 
+// reference-exact compression (encode_exact.hpp, mi355lz4_set_compress_exact): one block of the stream as the host
+// computed it from the lengths -- the state LZ4_compress_fast_continue reaches before it calls the encoder
+// (cbits/lz4.c:1565-1627)
+struct ExactBlock {
+    uint32_t start;      // currentOffset after the renorm (startIndex)
+    uint32_t dictSize;   // after the renorm clamp and the reset of dictionaries under 4 bytes
+    uint32_t delta;      // LZ4_renormDictT before this block: entries < delta -> 0, the others -= delta (0: none)
+    int32_t n;           // the array's length
+    int32_t dictSmall;   // cbits/lz4.c:1627
+    int32_t pad;
+};
+#define EXACT_TABLE 4096     // LZ4_HASHLOG 12, byU32
+
+struct ExactArgs {
+    EncodeArgs e;                // blocks, slots, headers, framedLen, accel (clamped); e.linked is not used
+    const ExactBlock *meta;      // nBlocks + 1 entries (the last: the state after the call)
+    const uint8_t *dict0;        // the dictionary in force before block 0: dict0Len bytes (the previous array's last ones)
+    int dict0Len;
+    uint32_t *state;             // the stream's table before the call (k_exact_chain reads), after it (k_exact_finish writes)
+    uint8_t *dictSave;           // k_exact_finish: the last array's last min(n, 65536) bytes (may be dict0)
+    uint32_t *assumed;           // nPieces tables: what piece p assumed at its first block (canonical)
+    uint32_t *finalT;            // nPieces tables: piece p's table after its last block (canonical)
+    int32_t *eq;                 // k_exact_verify: eq[p] = finalT[p-1] == assumed[p]
+    int piece;                   // P: blocks per piece
+    int runin;                   // R: blocks a piece starts early (from a zeroed table)
+    int nPieces;
+};
+
 // small batches: a block's segments are compressed by several waves (kernels.hip, K2 small batches)
 struct EncodeSegArgs {
     EncodeArgs e;
@@ -139,6 +167,12 @@ size_t ptr_ctl_bytes();
 size_t tol_region_bytes();
 void launch_encode(const EncodeArgs &a, bool bigBlocks, hipStream_t s);   // bigBlocks: some block is above 64 KiB
 void launch_encode_hc(const EncodeArgs &a, int level, hipStream_t s);      // compression levels 1..12 (encode_hc.hpp)
+// reference-exact compression (encode_exact.hpp): speculate pieces first..first+count-1, or redo them from their
+// predecessors' tables; compare piece p's assumed table with piece p-1's final one for p = first..first+count-1;
+// save the stream's state
+void launch_exact_chain(const ExactArgs &a, int first, int count, int redo, hipStream_t s);
+void launch_exact_verify(const ExactArgs &a, int first, int count, hipStream_t s);
+void launch_exact_finish(const ExactArgs &a, hipStream_t s);
 void launch_compact(const uint8_t *slots, size_t slotStride, const int32_t *framedLen, int nBlocks,
                     uint8_t *dense, size_t denseCap, uint64_t *denseOff, hipStream_t s);
 void launch_interleave(const uint8_t *local, const uint64_t *localOff, int nLocal, int rank, int nRanks,

@@ -5,6 +5,7 @@
 //       k_decode_fixup_regions / _linked ... its in-order fallbacks (linked_replay.hpp)
 //   K2  k_encode<TabT, DICT>             block encode, independent or linked (encode_wave.hpp)
 //       k_encode_hc                      high-compression levels: hash chains + lazy parse (encode_hc.hpp)
+//       k_exact_chain / _verify / _finish  reference-exact linked stream: speculate, verify, redo (encode_exact.hpp)
 //   K3  k_scan_u64 + k_copy_slots        size scan + compaction into the framed stream
 //       k_header_sizes                   uncompressed-size scan from block headers
 //       k_generate                       synthetic inputs (bench/test support)
@@ -22,6 +23,7 @@
 #include "linked_ptr.hpp"
 #include "encode_wave.hpp"
 #include "encode_hc.hpp"
+#include "encode_exact.hpp"
 #include "checksum.hpp"
 
 using namespace lz4dev;
@@ -230,6 +232,130 @@ void launch_encode_hc(const EncodeArgs &a, int level, hipStream_t s)
     const int depth = 1 << (min(level, 9) - 1);
     const unsigned grid = (unsigned)min(a.nBlocks, max(nc, 1));
     hipLaunchKernelGGL(k_encode_hc, dim3(grid), dim3(HC_THREADS), 0, s, a, depth);
+}
+
+// ---------------------------------------------------------------------------
+// K2, reference-exact compression (encode_exact.hpp).  One wave per piece of a call, its hash table in LDS.
+// ---------------------------------------------------------------------------
+// canonical form of table entry v for a block: the block's renorm applied, entries that no position of the
+// block can use (below start - 65536) read 0
+__device__ __forceinline__ uint32_t exact_canon(uint32_t v, uint32_t start, uint32_t delta)
+{
+    v = (v < delta) ? 0u : v - delta;
+    return (start > 65536u && v < start - 65536u) ? 0u : v;
+}
+
+__device__ __forceinline__ dev_v4 exact_canon4(dev_v4 v, uint32_t start, uint32_t delta)
+{
+    return dev_v4{exact_canon(v.x, start, delta), exact_canon(v.y, start, delta), exact_canon(v.z, start, delta),
+                  exact_canon(v.w, start, delta)};
+}
+
+// the byte range of block j of a call
+__device__ __forceinline__ const uint8_t *exact_src(const EncodeArgs &e, int j)
+{
+    return e.src + (e.srcOff ? e.srcOff[j] : (uint64_t)j * e.blockStride);
+}
+
+// piece p = first + blockIdx.x owns blocks [p*P, min(p*P + P, n)).  Speculating (redo = 0), it starts R blocks early
+// from a zeroed table, or from the stream's state at block 0 when the run-in reaches it (then it is exact by
+// construction), and records assumed[p] at its first block.  Redoing, it starts at its first block from finalT[p-1].
+// Either way it leaves finalT[p] and writes the slots, headers and framedLen of the blocks it owns.
+__global__ __launch_bounds__(LZ4_WAVE) void k_exact_chain(ExactArgs x, int first, int redo)
+{
+    __shared__ dev_v4 tab4[EXACT_TABLE / 4];
+    uint32_t *tab = (uint32_t *)tab4;
+    const int lane = lane_id();
+    const int p = first + (int)blockIdx.x;
+    const int n = x.e.nBlocks;
+    const int own0 = p * x.piece, own1 = min(own0 + x.piece, n);
+    int start = own0;
+    const uint32_t *init = nullptr;
+    if (redo) init = x.finalT + (size_t)(p - 1) * EXACT_TABLE;
+    else if (p == 0 || own0 - x.runin <= 0) { start = 0; init = x.state; }
+    else start = own0 - x.runin;
+    for (int i = lane; i < EXACT_TABLE / 4; i += LZ4_WAVE)
+        tab4[i] = init ? as_global((const dev_v4 *)init)[i] : dev_v4{0u, 0u, 0u, 0u};
+    __syncthreads();
+    for (int j = start; j < own1; j++) {
+        const ExactBlock m = x.meta[j];
+        // LZ4_renormDictT, cbits/lz4.c:1545-1562.  finalT[p-1] is already block own0's table with its renorm applied
+        // (exact_canon4(.., next.delta) below): a redo starts behind that renorm and must not apply it a second time.
+        if (m.delta && !(redo && j == own0)) {
+            for (int i = lane; i < EXACT_TABLE / 4; i += LZ4_WAVE) tab4[i] = exact_canon4(tab4[i], 0u, m.delta);
+            __syncthreads();
+        }
+        if (!redo && j == own0 && p > 0) {
+            dev_v4 *as = (dev_v4 *)(x.assumed + (size_t)p * EXACT_TABLE);
+            for (int i = lane; i < EXACT_TABLE / 4; i += LZ4_WAVE) as_global(as)[i] = exact_canon4(tab4[i], m.start, 0u);
+        }
+        const bool write = j >= own0;
+        const uint8_t *src = exact_src(x.e, j);
+        const uint8_t *dictEnd = j > 0 ? exact_src(x.e, j - 1) + x.meta[j - 1].n : x.dict0 + x.dict0Len;
+        uint8_t *slot = x.e.slots + (size_t)j * x.e.slotStride;
+        const int cap = m.n + m.n / 255 + 16;                           // LZ4_compressBound
+        int c;
+        if (m.n == 0) {                                                 // cbits/lz4.c:1263-1273
+            c = 1;
+            if (write && lane == 0) slot[x.e.headerKind] = 0;
+        } else {
+            c = exact_encode_block(tab, src, m.n, dictEnd, m, (uint32_t)x.e.accel, slot + x.e.headerKind, cap, write);
+        }
+        if (write && lane == 0) {
+            store_le32(slot, c);
+            if (x.e.headerKind == 8) store_le32(slot + 4, m.n);
+            x.e.framedLen[j] = (c > 0) ? x.e.headerKind + c : 0;
+        }
+        __syncthreads();
+    }
+    const ExactBlock next = x.meta[own1];
+    dev_v4 *fin = (dev_v4 *)(x.finalT + (size_t)p * EXACT_TABLE);
+    for (int i = lane; i < EXACT_TABLE / 4; i += LZ4_WAVE) as_global(fin)[i] = exact_canon4(tab4[i], next.start, next.delta);
+}
+
+// eq[p] = (finalT[p-1] == assumed[p]) for p = first + blockIdx.x (first >= 1)
+__global__ __launch_bounds__(LZ4_WAVE) void k_exact_verify(ExactArgs x, int first)
+{
+    const int p = first + (int)blockIdx.x;
+    const dev_v4 *f = (const dev_v4 *)(x.finalT + (size_t)(p - 1) * EXACT_TABLE);
+    const dev_v4 *a = (const dev_v4 *)(x.assumed + (size_t)p * EXACT_TABLE);
+    bool same = true;
+    for (int i = lane_id(); i < EXACT_TABLE / 4; i += LZ4_WAVE) {
+        const dev_v4 u = as_global(f)[i], v = as_global(a)[i];
+        same = same && u.x == v.x && u.y == v.y && u.z == v.z && u.w == v.w;
+    }
+    const bool all = __ballot(!same) == 0;
+    if (lane_id() == 0) x.eq[p] = all ? 1 : 0;
+}
+
+// the stream's state after the call: the last piece's table, and the last array's last bytes (the next call's dictionary)
+__global__ __launch_bounds__(256) void k_exact_finish(ExactArgs x)
+{
+    const dev_v4 *fin = (const dev_v4 *)(x.finalT + (size_t)(x.nPieces - 1) * EXACT_TABLE);
+    for (int i = (int)threadIdx.x; i < EXACT_TABLE / 4; i += (int)blockDim.x) as_global((dev_v4 *)x.state)[i] = as_global(fin)[i];
+    const int last = x.e.nBlocks - 1;
+    const int n = x.meta[last].n;
+    const int keep = n < 65536 ? n : 65536;
+    const uint8_t *from = exact_src(x.e, last) + (n - keep);
+    for (int i = (int)threadIdx.x; i < keep; i += (int)blockDim.x) as_global(x.dictSave)[i] = as_global(from)[i];
+}
+
+void launch_exact_chain(const ExactArgs &a, int first, int count, int redo, hipStream_t s)
+{
+    if (count <= 0) return;
+    hipLaunchKernelGGL(k_exact_chain, dim3((unsigned)count), dim3(LZ4_WAVE), 0, s, a, first, redo);
+}
+
+void launch_exact_verify(const ExactArgs &a, int first, int count, hipStream_t s)
+{
+    if (count <= 0) return;
+    hipLaunchKernelGGL(k_exact_verify, dim3((unsigned)count), dim3(LZ4_WAVE), 0, s, a, first);
+}
+
+void launch_exact_finish(const ExactArgs &a, hipStream_t s)
+{
+    if (a.e.nBlocks <= 0) return;
+    hipLaunchKernelGGL(k_exact_finish, dim3(1), dim3(256), 0, s, a);
 }
 
 // ---------------------------------------------------------------------------

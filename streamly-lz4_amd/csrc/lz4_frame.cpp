@@ -21,6 +21,8 @@
 #include <string>
 #include <vector>
 
+int engine_swap_compress_exact(mi355lz4_ctx *c, int on);   // api.cpp: sets the switch, keeps the stream; returns the old value
+
 namespace streamly_lz4 {
 
 // ---------------------------------------------------------------------------
@@ -104,8 +106,10 @@ Array lz4FrameCompress(const Array &data, int speed, Engine &eng, const Lz4Frame
         size_t outLen = 0;
         const bool was = eng.linkedCompress();
         eng.setLinkedCompress(opt.linkedBlocks);
+        const int exact = engine_swap_compress_exact(eng.ctx(), 0);    // a frame is its own stream: not the exact one's
         const int r = mi355lz4_compress_batch(eng.ctx(), ptrs.data(), lens.data(), (int)nb, speed < 0 ? 0 : speed, 4,
                                               framed.data(), cap, &outLen, flen.data(), status.data());
+        engine_swap_compress_exact(eng.ctx(), exact);
         eng.setLinkedCompress(was);
         if (r != MI355LZ4_OK) throw Error(std::string("lz4FrameCompress: ") + mi355lz4_last_error());
         size_t pos = 0;

@@ -99,6 +99,7 @@ struct PartResult {
 
 int engine_block_checksum(const mi355lz4_ctx *c);   // api.cpp
 int engine_compression_level(const mi355lz4_ctx *c);   // api.cpp
+int engine_compress_exact(const mi355lz4_ctx *c);      // api.cpp
 
 // Block checksums (mi355lz4_set_block_checksum) are a property of the stream a call reads or writes: every engine of the
 // handle must have the same setting.  -1: they disagree.
@@ -131,6 +132,9 @@ extern "C" int mi355lz4_multi_compress_batch(mi355lz4_multi *m, const uint8_t *c
     if (ck < 0) return mfail(MI355LZ4_E_ARG, "mi355lz4_multi_compress_batch: the engines disagree on block checksums");
     if (!multi_same_level(m))
         return mfail(MI355LZ4_E_ARG, "mi355lz4_multi_compress_batch: the engines disagree on the compression level");
+    for (mi355lz4_ctx *e : m->eng)      // one stream cannot be spread over devices
+        if (engine_compress_exact(e))
+            return mfail(MI355LZ4_E_ARG, "mi355lz4_multi_compress_batch: an engine is in the reference-exact compress mode");
     if (nBlocks == 0) return MI355LZ4_OK;
     const std::vector<int> first = cut_ranges(srcLen, nBlocks, (int)m->eng.size());
     const int P = (int)first.size() - 1;

@@ -119,6 +119,10 @@ def _load():
     # compression levels
     sig("mi355lz4_set_compression_level", C.c_int, vp, C.c_int)
     sig("mi355lz4_get_compression_level", C.c_int, vp)
+    sig("mi355lz4_set_compress_exact", C.c_int, vp, C.c_int)
+    sig("mi355lz4_get_compress_exact", C.c_int, vp)
+    sig("mi355lz4_compress_exact_reset", C.c_int, vp)
+    sig("mi355lz4_debug_exact_state", C.c_int, vp, C.POINTER(C.c_int))
     # legacy face (include/lz4.h)
     sig("LZ4_createStream", vp)
     sig("LZ4_freeStream", C.c_int, vp)
@@ -169,6 +173,7 @@ DECLARED_SYMBOLS = [
     "mi355lz4_multi_compress_batch", "mi355lz4_multi_decompress_batch",
     "mi355lz4_set_block_checksum", "mi355lz4_slot_stride_ex", "mi355lz4_index_host_ex", "mi355lz4_xxh32_device",
     "mi355lz4_set_compression_level", "mi355lz4_get_compression_level",
+    "mi355lz4_set_compress_exact", "mi355lz4_get_compress_exact", "mi355lz4_compress_exact_reset",
     "LZ4_createStream", "LZ4_freeStream", "LZ4_createStreamDecode", "LZ4_freeStreamDecode", "LZ4_compressBound",
     "LZ4_compress_fast_continue", "LZ4_decompress_safe_continue",
 ]
@@ -456,6 +461,26 @@ class Engine:
     def compression_level(self):
         """The effective compression level (0..9)."""
         return int(lib.mi355lz4_get_compression_level(self.ctx))
+
+    def set_compress_exact(self, on):
+        """Reference-exact compression: every compress call (device and host calls, compressChunks) appends its blocks to
+        ONE stream whose bytes are LZ4_compress_fast_continue's over separately allocated arrays -- what the reference's
+        compressChunksD writes.  Switching it on starts a new stream (include/mi355lz4.h, mi355lz4_set_compress_exact)."""
+        _check(lib.mi355lz4_set_compress_exact(self.ctx, int(bool(on))), "set_compress_exact")
+
+    @property
+    def compress_exact(self):
+        return bool(lib.mi355lz4_get_compress_exact(self.ctx) == 1)
+
+    def reset_compress_stream(self):
+        """Start a new exact stream (LZ4_createStream); compressChunks does it when it starts."""
+        _check(lib.mi355lz4_compress_exact_reset(self.ctx), "compress_exact_reset")
+
+    def exact_state(self):
+        """Diagnostics of the last exact compress call: (pieces, speculated, kept, redone)."""
+        st = (C.c_int * 4)()
+        _check(lib.mi355lz4_debug_exact_state(self.ctx, st), "debug_exact_state")
+        return tuple(int(v) for v in st)
 
     def xxh32_device(self, base, off, length, n, seed, out):
         """out[i] = xxh32(seed) of base[off[i] : off[i] + length[i]] for i < n (uint8 / int64 / int32 / int32 device
