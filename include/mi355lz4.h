@@ -64,6 +64,28 @@ extern "C" {
 
 typedef struct mi355lz4_ctx mi355lz4_ctx;
 
+/* ---- what a call may write -------------------------------------------
+ * A caller's arrays lie next to other live data, so every call is confined to the ranges below, whatever its blocks'
+ * results (tests/test_write_confinement_gpu.py holds every kernel to it with guard patterns around every range).
+ * Decode calls (_decompress_batch_device, _decompress_streams_device, _decompress_linked_begin / _end / _end_last):
+ *   no byte of `out` outside the union of [outOff[i], outOff[i] + cap_i), where cap_i is outCap[i], else the header's
+ *   uncompLen / fixedUncomp, and 0 when the header is rejected for its uncompLen -- for a block that decodes, one that
+ *   fails with a negative code and one whose header is rejected alike; result[] only in [0, nBlocks) (with lookBack,
+ *   result[-1] and the seam block's output are the caller's: read, never written); framed, blockOff, outOff, outCap
+ *   and streamFirst are never written.
+ * Compress calls (_compress_batch_device: level 0, 1..9, exact; linked or not; segments automatic, forced or off;
+ *   checksums on or off): nothing outside the union of [slots + i*slotStride, slots + i*slotStride +
+ *   mi355lz4_slot_stride_ex(maxBlockLen, headerKind, checksum)), even when the caller's slotStride is larger (the
+ *   rest of a wider stride is the caller's); framedLen[] only in [0, nBlocks); src, srcOff and srcLen never.
+ * _compact_device: dense[0, denseOff[k + 1]) for the last block k that fits (denseOff[k + 1] <= denseCap; nothing
+ *   when none fits), denseOff[0..nBlocks];
+ *   _index_device: outOff[0..nBlocks]; _interleave_device: global + globalOff[j*nRanks + rank] for the local blocks'
+ *   lengths; _generate_device: dst[0, nBlocks * blockLen); _xxh32_device: out[i] for len[i] >= 0.  Inputs never.
+ * Host-buffer calls (_compress_batch, _decompress_batch, _decompress_streams, _multi_*): nothing at or past
+ *   framedOut + cap / out + cap or in front of either pointer; blockFramedLen, status and blockLen only in
+ *   [0, nBlocks) / [0, maxBlocks); inputs never.
+ * Scratch that a call needs is the engine's own. */
+
 /* ---- engine lifecycle ------------------------------------------------ */
 int mi355lz4_version(void);
 /* Thread-local description of the last failure in this library. */

@@ -128,18 +128,41 @@ def test_decode_fuzz_vs_oracle(engine, oracle, decoder):
 def test_decode_huge_length_fields(engine, oracle, decoder):
     """Length fields that are multi-megabyte runs of 0xFF (lengths >= 2^31): same code as the oracle, and
     nothing is written outside the block's output (cbits/lz4.c:1811-1818, 1854-1858, 2064-2065)."""
+    import torch
+    import guarded as G
     from reference_cases import huge_length_blocks
+    dev = torch.device("cuda:0")
+    cases = huge_length_blocks()
+    lay = G.layout([cap for _, _, cap in cases])                                 # every block's output between guards
+    blob, boff = b"", []
+    for _, payload, cap in cases:
+        boff.append(len(blob))
+        blob += len(payload).to_bytes(4, "little") + cap.to_bytes(4, "little") + payload
+    buf = torch.from_numpy(np.frombuffer(blob, dtype=np.uint8).copy()).to(dev)
+    out = G.new_torch(lay.total, 1, dev)
+    res = G.GuardedArray(len(cases), torch.int32, 2, dev)
     engine.set_decoder(decoder)
     try:
-        for name, payload, cap in huge_length_blocks():
+        for name, payload, cap in cases:                                         # the host-buffer call, a block a call
             fr = len(payload).to_bytes(4, "little") + cap.to_bytes(4, "little") + payload
             want_code, want = oracle.decompress_block(payload, cap)
-            out, blen = engine.decompress_batch(fr, raise_on_block_error=False)
+            host_out, blen = engine.decompress_batch(fr, raise_on_block_error=False)
             assert blen == [want_code], (name, blen, want_code)
             if want_code >= 0:
-                assert out == want
+                assert host_out == want
+        engine.decompress_batch_device(buf, len(blob), torch.tensor(boff, dtype=torch.int64, device=dev), len(cases), out,
+                                       torch.tensor(lay.starts, dtype=torch.int64, device=dev), res.view)
+        engine.synchronize()
     finally:
         engine.set_decoder(0)
+    got = res.view.cpu().tolist()
+    for i, (name, payload, cap) in enumerate(cases):
+        want_code, want = oracle.decompress_block(payload, cap)
+        assert got[i] == want_code, (name, got[i], want_code)
+        if want_code >= 0:
+            assert out[lay.starts[i]:lay.starts[i] + want_code].cpu().numpy().tobytes() == want
+    G.assert_confined(out, lay.ranges(), 1, "huge length fields, decoder %d" % decoder)   # whatever the blocks' results
+    res.check(what="result[]")
 
 
 def test_decode_header_rejections(engine, oracle):
@@ -629,7 +652,10 @@ def _decode_streams(engine, frs, linked_mode):
     off = torch.tensor(boff, dtype=torch.int64, device=dev)
     ooff_h = np.concatenate([[0], np.cumsum(ulen)]).astype(np.int64)
     ooff = torch.from_numpy(ooff_h).to(dev)
-    out = torch.zeros(int(ooff_h[-1]) + 64, dtype=torch.uint8, device=dev)
+    import guarded as G
+    total = int(ooff_h[-1])
+    out = G.new_torch(total + G.END_GUARD, 5, dev)                                # the tail holds tests/guarded.py's pattern ...
+    out[:total] = 0
     res = torch.zeros(nb, dtype=torch.int32, device=dev)
     if linked_mode == "streams":
         sf = torch.tensor(first, dtype=torch.int32, device=dev)
@@ -637,7 +663,8 @@ def _decode_streams(engine, frs, linked_mode):
     else:
         engine.decompress_batch_device(buf, len(blob), off, nb, out, ooff, res, linked=(linked_mode == "one"))
     engine.synchronize()
-    return out[: int(ooff_h[-1])].cpu().numpy().tobytes(), res.cpu().tolist(), ulen, first
+    G.assert_confined(out, [(0, total)], 5, "_decode_streams(%s)" % linked_mode)  # ... and still does: nothing past the last block
+    return out[:total].cpu().numpy().tobytes(), res.cpu().tolist(), ulen, first
 
 
 # The second pass of a linked decode has three implementations behind one contract: byte source pointers +
