@@ -35,6 +35,12 @@ module Streamly.Internal.LZ4.GPU
     , setCompressionLevel
     , setCompressExact
     , resetCompressStream
+    , CompressStreams
+    , newCompressStreams
+    , freeCompressStreams
+    , resetCompressStreams
+    , c_compressStreamsDevice
+    , compressChunksMany
     , MultiEngine
     , newMultiEngine
     , freeMultiEngine
@@ -48,7 +54,7 @@ where
 import Control.Monad (forM, forM_, when)
 import Control.Monad.IO.Class (MonadIO(..))
 import Data.Int (Int32)
-import Data.Word (Word8)
+import Data.Word (Word8, Word64)
 import Foreign.C (CInt(..), CSize(..))
 import Foreign.Marshal.Alloc (alloca)
 import Foreign.Marshal.Array (allocaArray, peekArray, pokeArray)
@@ -104,6 +110,30 @@ foreign import ccall safe "mi355lz4.h mi355lz4_compress_batch"
     c_compressBatch
         :: Ptr C_Engine -> Ptr (Ptr Word8) -> Ptr Int32 -> CInt -> CInt -> CInt
         -> Ptr Word8 -> CSize -> Ptr CSize -> Ptr Int32 -> Ptr Int32 -> IO CInt
+
+-- Many reference-exact compress streams in ONE call (include/mi355lz4.h, "many reference-exact streams in one call"): a set
+-- of device-resident @LZ4_stream_t@s, one slot per pipeline; stream s of a call = blocks [streamFirst[s], streamFirst[s+1]),
+-- continuing slot streamSlot[s].  One FFI call for the next arrays of all pipelines instead of one engine per pipeline.
+data C_CStreams
+newtype CompressStreams = CompressStreams (Ptr C_CStreams)
+
+foreign import ccall safe "mi355lz4.h mi355lz4_cstreams_create"
+    c_cstreamsCreate :: Ptr C_Engine -> CInt -> Ptr (Ptr C_CStreams) -> IO CInt
+foreign import ccall safe "mi355lz4.h mi355lz4_cstreams_destroy"
+    c_cstreamsDestroy :: Ptr C_CStreams -> IO ()
+foreign import ccall unsafe "mi355lz4.h mi355lz4_cstreams_count"
+    c_cstreamsCount :: Ptr C_CStreams -> IO CInt
+foreign import ccall safe "mi355lz4.h mi355lz4_cstreams_reset"
+    c_cstreamsReset :: Ptr C_Engine -> Ptr C_CStreams -> Ptr Int32 -> CInt -> IO CInt
+-- device pointers in, device pointers out; only enqueues
+foreign import ccall safe "mi355lz4.h mi355lz4_compress_streams_device"
+    c_compressStreamsDevice
+        :: Ptr C_Engine -> Ptr C_CStreams -> Ptr Word8 -> Ptr Word64 -> Ptr Int32 -> Word64 -> CInt -> CInt
+        -> Ptr Int32 -> Ptr Int32 -> CInt -> CInt -> CInt -> Ptr Word8 -> CSize -> Ptr Int32 -> IO CInt
+foreign import ccall safe "mi355lz4.h mi355lz4_compress_streams"
+    c_compressStreams
+        :: Ptr C_Engine -> Ptr C_CStreams -> Ptr (Ptr Word8) -> Ptr Int32 -> CInt -> Ptr Int32 -> Ptr Int32 -> CInt
+        -> CInt -> CInt -> Ptr Word8 -> CSize -> Ptr CSize -> Ptr Int32 -> Ptr Int32 -> IO CInt
 
 -- replaces c_decompressSafeContinue (Streamly/Internal/LZ4.hs:133-140), N blocks per call
 foreign import ccall safe "mi355lz4.h mi355lz4_decompress_batch"
@@ -205,6 +235,27 @@ resetCompressStream (Engine p) = do
     rc <- c_compressExactReset p
     when (rc /= 0) $ error "mi355lz4_compress_exact_reset failed"
 
+-- | A set of @n@ device-resident compress streams (about 80 KiB each), every one reset.
+newCompressStreams :: Engine -> Int -> IO CompressStreams
+newCompressStreams (Engine p) n = alloca $ \pp -> do
+    rc <- c_cstreamsCreate p (fromIntegral n) pp
+    when (rc /= 0) $ error "mi355lz4_cstreams_create failed"
+    CompressStreams <$> peek pp
+
+freeCompressStreams :: CompressStreams -> IO ()
+freeCompressStreams (CompressStreams p) = c_cstreamsDestroy p
+
+-- | @LZ4_resetStream@ for the listed slots ('Nothing': all of them).
+resetCompressStreams :: Engine -> CompressStreams -> Maybe [Int] -> IO ()
+resetCompressStreams (Engine p) (CompressStreams cs) Nothing = do
+    rc <- c_cstreamsReset p cs nullPtr 0
+    when (rc /= 0) $ error "mi355lz4_cstreams_reset failed"
+resetCompressStreams (Engine p) (CompressStreams cs) (Just slots) =
+    allocaArray (length slots) $ \ps -> do
+        pokeArray ps (map fromIntegral slots)
+        rc <- c_cstreamsReset p cs ps (fromIntegral (length slots))
+        when (rc /= 0) $ error "mi355lz4_cstreams_reset: a slot is out of range"
+
 batchBlocks :: Int
 batchBlocks = 4096
 
@@ -247,6 +298,41 @@ compressBatch (Engine eng) cfg speed arrs = do
         return [ Array.unsafeFreeze (MArray.Array cont dstBegin_ (dstBegin `plusPtr` (o + l)) dstMax)
                    `seq` Array.Array cont (dstBegin `plusPtr` o) (dstBegin `plusPtr` (o + l))
                | (o, l) <- zip offs flens ]
+
+-- | The next arrays of many @compressChunks@ pipelines in one GPU call: @(slot, arrays)@ per pipeline, every pipeline
+-- continuing its slot of the set.  Each pipeline's result is what the reference's @compressChunksD@ yields for those
+-- arrays at this point of its stream (the same bytes, one framed array per input array).
+compressChunksMany
+    :: Engine -> CompressStreams -> BlockConfig -> Int -> [(Int, [Array.Array Word8])] -> IO [[Array.Array Word8]]
+compressChunksMany (Engine eng) (CompressStreams cs) cfg speed pipes = do
+    let arrs = concatMap snd pipes
+        counts = map (length . snd) pipes
+        n = length arrs
+        ns = length pipes
+        meta = metaSizeOf cfg
+        lens = map Array.byteLength arrs
+        cap = sum (map (\l -> fromIntegral (c_bound (fromIntegral l)) + meta + 4) lens)
+    (MArray.Array cont dstBegin_ dstBegin dstMax) <- MArray.newArray (max cap 1)
+    allocaArray n $ \pSrc -> allocaArray n $ \pLen -> allocaArray n $ \pFlen ->
+      allocaArray n $ \pStatus -> allocaArray (ns + 1) $ \pFirst -> allocaArray ns $ \pSlot -> alloca $ \pOutLen -> do
+        let withAll [] k = k []
+            withAll (a:as) k = Array.asPtrUnsafe (Array.unsafeCast a) $ \p -> withAll as (k . (p :))
+        withAll arrs $ \ptrs -> do
+            pokeArray pSrc ptrs
+            pokeArray pLen (map fromIntegral lens)
+            pokeArray pFirst (map fromIntegral (scanl (+) 0 counts))
+            pokeArray pSlot (map (fromIntegral . fst) pipes)
+            rc <- c_compressStreams eng cs pSrc pLen (fromIntegral n) pFirst pSlot (fromIntegral ns)
+                      (fromIntegral speed) (fromIntegral meta) dstBegin (fromIntegral cap) pOutLen pFlen pStatus
+            when (rc /= 0) $ error "compressChunksMany: mi355lz4_compress_streams failed"
+        flens <- map fromIntegral <$> peekArray n pFlen
+        let offs = scanl (+) 0 flens
+            outs = [ Array.unsafeFreeze (MArray.Array cont dstBegin_ (dstBegin `plusPtr` (o + l)) dstMax)
+                       `seq` Array.Array cont (dstBegin `plusPtr` o) (dstBegin `plusPtr` (o + l))
+                   | (o, l) <- zip offs flens ]
+            split [] _ = []
+            split (c : rest) xs = let (h, t) = splitAt c xs in h : split rest t
+        return (split counts outs)
 
 -- | One freshly allocated array holding the given arrays back to back (the reference splices
 -- pairwise with @Array.splice@, Streamly/Internal/LZ4.hs:502; a batch is concatenated in one pass).

@@ -84,6 +84,10 @@ typedef struct mi355lz4_ctx mi355lz4_ctx;
  * Host-buffer calls (_compress_batch, _decompress_batch, _decompress_streams, _multi_*): nothing at or past
  *   framedOut + cap / out + cap or in front of either pointer; blockFramedLen, status and blockLen only in
  *   [0, nBlocks) / [0, maxBlocks); inputs never.
+ * Many exact streams (_compress_streams_device): the slot ranges of _compress_batch_device, framedLen[0, nBlocks)
+ *   (a stream stopped by a bad length leaves its remaining slots untouched and sets their framedLen to 0) and the slots
+ *   of `cs` that streamSlot[] names for a stream with blocks; never a slot of `cs` the call does not name, never src,
+ *   srcOff or srcLen.  _compress_streams is a host-buffer call as above.
  * Scratch that a call needs is the engine's own. */
 
 /* ---- engine lifecycle ------------------------------------------------ */
@@ -411,6 +415,58 @@ int mi355lz4_set_compress_exact(mi355lz4_ctx *ctx, int on);
 int mi355lz4_get_compress_exact(const mi355lz4_ctx *ctx);
 /* Start a new exact stream (LZ4_createStream): the next call's first block has no dictionary and a zeroed table. */
 int mi355lz4_compress_exact_reset(mi355lz4_ctx *ctx);
+/* ---- many reference-exact streams in one call ------------------------------------------------------------------------
+ * The compress-side counterpart of mi355lz4_decompress_streams_device: a host that runs many pipelines at once (files,
+ * connections, shards) keeps one slot per pipeline and compresses the next arrays of all of them in ONE call.
+ *
+ * A mi355lz4_cstreams is an opaque set of nSlots device-resident compress streams, owned by the caller and bound to the
+ * device of the engine it was created with (any engine on that device may use it; one call at a time).  One slot holds
+ * everything LZ4_stream_t holds, all of it on the device: the 4096-entry table, the previous array's last 64 KiB,
+ * currentOffset, dictSize and the number of saved dictionary bytes -- 81984 bytes, about 80 KiB a slot (2560 slots:
+ * 200 MiB).  Nothing of a slot lives on the host, which is what lets the device call return without waiting.
+ * _create leaves every slot reset; _reset is LZ4_resetStream for slots[0..n) (slots == NULL: all of them), enqueued on the
+ * engine's stream; _destroy waits for the device. */
+typedef struct mi355lz4_cstreams mi355lz4_cstreams;
+int mi355lz4_cstreams_create(mi355lz4_ctx *ctx, int nSlots, mi355lz4_cstreams **out);
+void mi355lz4_cstreams_destroy(mi355lz4_cstreams *cs);
+int mi355lz4_cstreams_count(const mi355lz4_cstreams *cs);
+int mi355lz4_cstreams_reset(mi355lz4_ctx *ctx, mi355lz4_cstreams *cs, const int32_t *slots, int n);
+/* Compress nBlocks blocks that belong to nStreams streams.  The block arguments and the outputs are those of
+ * mi355lz4_compress_batch_device (slotStride as mi355lz4_slot_stride_ex says).  Stream s of the call is the blocks
+ * [streamFirst[s], streamFirst[s+1]) and continues the state in slot streamSlot[s]; an empty stream leaves its slot
+ * untouched.  streamFirst (nStreams + 1 entries, streamFirst[0] == 0, streamFirst[nStreams] == nBlocks, ascending) and
+ * streamSlot are small HOST arrays, checked before anything is enqueued and used up before the call returns.
+ * MI355LZ4_E_ARG: a table that is not ascending or does not cover the blocks, a slot out of range, the same slot twice in
+ * one call, `cs` created on another device, a compression level other than 0.
+ * Bytes: every stream's blocks are what LZ4_compress_fast_continue writes on one LZ4_stream_t over separately allocated
+ * arrays (the external-dictionary path, the reference's compressChunksD), for any accel (clamped to 1..65537), lengths
+ * 0..maxBlockLen and placement in memory, across calls and through the 2 GiB renormalisation: a stream given in one call
+ * and the same stream given one block per call give the same bytes.  A block's dictionary is the array before it IN ITS
+ * STREAM -- for a stream's first block in a call, the tail the slot saved -- so a call's source may be overwritten or
+ * freed once the call has run.
+ * Asynchronous: the call only enqueues on the engine's stream; it does not read srcLen on the host and does not wait
+ * (beyond four calls in flight, for the oldest one's stream table).  A length outside 0..maxBlockLen can therefore be no
+ * error code: the stream's wavefront stops there, that block and the rest of that stream's blocks in the call get
+ * framedLen = 0 (no valid block has 0: a zero-length array is the header plus one byte), the slot stays as it was after
+ * the last good block, and the other streams are unaffected.
+ * Switches: block checksums apply; the compression level must be 0; the linked switch and segments are ignored.  The
+ * engine's own exact stream (mi355lz4_set_compress_exact) is separate state that this call never touches, on or off.
+ * One wavefront walks one stream: throughput comes from the number of streams in the call (the chip runs 2560 at a
+ * time), and a stream with many blocks in one call is one serial chain of about 11 ms per 64 KiB block -- a single
+ * long stream belongs in mi355lz4_set_compress_exact, which speculates. */
+int mi355lz4_compress_streams_device(mi355lz4_ctx *ctx, mi355lz4_cstreams *cs, const uint8_t *src,
+                                     const uint64_t *srcOff, const int32_t *srcLen, uint64_t blockStride,
+                                     int maxBlockLen, int nBlocks, const int32_t *streamFirst,
+                                     const int32_t *streamSlot, int nStreams, int accel, int headerKind,
+                                     uint8_t *slots, size_t slotStride, int32_t *framedLen);
+/* Host-buffer form: as mi355lz4_compress_batch (one dense framed stream in block order, blockFramedLen and status per
+ * block, synchronous, the same group pipeline; a group seam inside a stream continues its slot).  The lengths are checked
+ * on the host: a bad one is MI355LZ4_E_ARG and nothing is enqueued. */
+int mi355lz4_compress_streams(mi355lz4_ctx *ctx, mi355lz4_cstreams *cs, const uint8_t *const *src,
+                              const int32_t *srcLen, int nBlocks, const int32_t *streamFirst,
+                              const int32_t *streamSlot, int nStreams, int accel, int headerKind, uint8_t *framedOut,
+                              size_t cap, size_t *outLen, int32_t *blockFramedLen, int32_t *status);
+
 /* mi355lz4_slot_stride with room for the trailer when blockChecksum != 0. */
 size_t mi355lz4_slot_stride_ex(int blockLen, int headerKind, int blockChecksum);
 /* mi355lz4_index_host over a chain whose blocks carry trailers when blockChecksum != 0 (a block spans

@@ -23,6 +23,7 @@
 #include <vector>
 
 struct mi355lz4_ctx;
+struct mi355lz4_cstreams;
 
 namespace streamly_lz4 {
 
@@ -87,10 +88,32 @@ public:
     void setCompressExact(bool on);
     bool compressExact() const;
     void resetCompressStream();
+    // Many exact streams in one call (mi355lz4_compress_streams): streams[s] are the next arrays of the pipeline that owns
+    // slot slots[s] of cs; the result holds, per stream, one framed array per input array -- what compressChunksD yields for
+    // them at this point of that pipeline's stream.  Throws Error.
+    std::vector<std::vector<Array>> compressStreams(const BlockConfig &cfg, int speed, const std::vector<std::vector<Array>> &streams,
+                                                    class CompressStreams &cs, const std::vector<int32_t> &slots);
 private:
     mi355lz4_ctx *ctx_ = nullptr;
     size_t batch_;
     bool linked_ = false;
+};
+
+// A set of nSlots device-resident reference-exact compress streams (mi355lz4_cstreams: about 80 KiB a slot), one per
+// pipeline a host runs at once; Engine::compressStreams compresses the next arrays of many of them in one call.
+class CompressStreams {
+public:
+    CompressStreams(Engine &eng, int nSlots);          // every slot reset; throws Error
+    ~CompressStreams();
+    CompressStreams(const CompressStreams &) = delete;
+    CompressStreams &operator=(const CompressStreams &) = delete;
+    mi355lz4_cstreams *handle() const { return cs_; }
+    int count() const;
+    void reset();                                       // LZ4_resetStream, all slots
+    void reset(const std::vector<int32_t> &slots);      // ... the listed ones
+private:
+    Engine &eng_;
+    mi355lz4_cstreams *cs_ = nullptr;
 };
 
 // ---- Streamly.LZ4 / Streamly.Internal.LZ4 -------------------------------------

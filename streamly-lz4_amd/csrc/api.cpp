@@ -799,6 +799,189 @@ extern "C" int mi355lz4_compress_batch_device(mi355lz4_ctx *c, const uint8_t *sr
                          framedLen, 0);
 }
 
+// ---------------------------------------------------------------------------
+// Many reference-exact streams in one call (mi355lz4_cstreams, mi355lz4_compress_streams_device).  A slot of
+// the set is a whole LZ4_stream_t on the device -- table, scalars, the previous array's last 64 KiB (kernels.h,
+// CSTREAM_*) -- and k_exact_streams follows the scalars itself, so the host never reads a length and never waits.
+// The small per-call table {first block, end block, slot} per stream goes through a ring of pinned buffers: an entry is
+// reused once the launch that read it is done (four calls may be in flight before a call waits for the oldest).
+// ---------------------------------------------------------------------------
+struct mi355lz4_cstreams {
+    int device = 0;
+    int nSlots = 0;
+    uint8_t *state = nullptr;               // nSlots * CSTREAM_SLOT_BYTES
+    struct Ring { DevBuf pin, dev; hipEvent_t ev = nullptr; bool busy = false; } ring[4];
+    int next = 0;
+};
+
+extern "C" int mi355lz4_cstreams_create(mi355lz4_ctx *c, int nSlots, mi355lz4_cstreams **out)
+{
+    if (out) *out = nullptr;
+    if (!c || !out || nSlots < 1) return fail(MI355LZ4_E_ARG, "cstreams_create: bad arguments");
+    HIP_TRY(hipSetDevice(c->device));
+    mi355lz4_cstreams *cs = new (std::nothrow) mi355lz4_cstreams();
+    if (!cs) return fail(MI355LZ4_E_ARG, "out of host memory");
+    cs->device = c->device;
+    cs->nSlots = nSlots;
+    const size_t bytes = (size_t)nSlots * CSTREAM_SLOT_BYTES;
+    hipError_t e = hipMalloc((void **)&cs->state, bytes);
+    if (e == hipSuccess) e = hipMemsetAsync(cs->state, 0, bytes, c->stream);     // LZ4_resetStream, every slot
+    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);                    // (whatever stream the engine is on later)
+    if (e != hipSuccess) {
+        if (cs->state) hipFree(cs->state);
+        delete cs;
+        return fail(MI355LZ4_E_HIP, "cstreams_create: %d slots (%zu bytes): %s", nSlots, bytes, hipGetErrorString(e));
+    }
+    *out = cs;
+    return MI355LZ4_OK;
+}
+
+extern "C" void mi355lz4_cstreams_destroy(mi355lz4_cstreams *cs)
+{
+    if (!cs) return;
+    hipSetDevice(cs->device);
+    hipDeviceSynchronize();                 // calls that still use the slots
+    for (auto &r : cs->ring) {
+        if (r.ev) hipEventDestroy(r.ev);
+        pin_release(r.pin);
+        dev_release(r.dev);
+    }
+    if (cs->state) hipFree(cs->state);
+    delete cs;
+}
+
+extern "C" int mi355lz4_cstreams_count(const mi355lz4_cstreams *cs)
+{
+    if (!cs) return fail(MI355LZ4_E_ARG, "cstreams_count: null set");
+    return cs->nSlots;
+}
+
+extern "C" int mi355lz4_cstreams_reset(mi355lz4_ctx *c, mi355lz4_cstreams *cs, const int32_t *slots, int n)
+{
+    if (!c || !cs) return fail(MI355LZ4_E_ARG, "cstreams_reset: null argument");
+    if (cs->device != c->device) return fail(MI355LZ4_E_ARG, "cstreams_reset: the set lives on device %d, the engine on %d", cs->device, c->device);
+    HIP_TRY(hipSetDevice(c->device));
+    if (!slots) {
+        HIP_TRY(hipMemsetAsync(cs->state, 0, (size_t)cs->nSlots * CSTREAM_SLOT_BYTES, c->stream));
+        return MI355LZ4_OK;
+    }
+    if (n < 0) return fail(MI355LZ4_E_ARG, "cstreams_reset: bad count");
+    for (int i = 0; i < n; i++)
+        if (slots[i] < 0 || slots[i] >= cs->nSlots) return fail(MI355LZ4_E_ARG, "cstreams_reset: slot %d out of range", slots[i]);
+    for (int i = 0; i < n; i++)             // the table and the scalars: a dictionary of 0 bytes needs no bytes cleared
+        HIP_TRY(hipMemsetAsync(cs->state + (size_t)slots[i] * CSTREAM_SLOT_BYTES, 0, CSTREAM_DICT_OFF, c->stream));
+    return MI355LZ4_OK;
+}
+
+// Diagnostic hook (not part of the public header): slot `slot`'s scalars.  get (3 words, may be null): currentOffset, dictSize,
+// saved dictionary bytes, after everything queued on the device has run.  A non-null setCurrentOffset then overwrites
+// currentOffset (the tests reach the 2 GiB renorm with it).
+extern "C" int mi355lz4_debug_cstream_state(mi355lz4_cstreams *cs, int slot, uint32_t *get, const uint32_t *setCurrentOffset)
+{
+    if (!cs || slot < 0 || slot >= cs->nSlots) return fail(MI355LZ4_E_ARG, "debug_cstream_state: bad arguments");
+    HIP_TRY(hipSetDevice(cs->device));
+    HIP_TRY(hipDeviceSynchronize());
+    uint8_t *scal = cs->state + (size_t)slot * CSTREAM_SLOT_BYTES + CSTREAM_SCALAR_OFF;
+    if (get) HIP_TRY(hipMemcpy(get, scal, 12, hipMemcpyDeviceToHost));
+    if (setCurrentOffset) HIP_TRY(hipMemcpy(scal, setCurrentOffset, 4, hipMemcpyHostToDevice));
+    return MI355LZ4_OK;
+}
+
+// the stream table of a call, checked: ascending over [0, nBlocks], every slot in range and named once
+static int streams_check(const mi355lz4_ctx *c, const mi355lz4_cstreams *cs, int nBlocks, const int32_t *streamFirst,
+                         const int32_t *streamSlot, int nStreams, const char *who)
+{
+    if (!c || !cs) return fail(MI355LZ4_E_ARG, "%s: null argument", who);
+    if (cs->device != c->device) return fail(MI355LZ4_E_ARG, "%s: the set lives on device %d, the engine on %d", who, cs->device, c->device);
+    if (c->compLevel != 0)
+        return fail(MI355LZ4_E_ARG, "%s: compression level %d; exact streams are level 0's encoder", who, c->compLevel);
+    if (nBlocks < 0 || nStreams < 0 || !streamFirst || (nStreams > 0 && !streamSlot)) return fail(MI355LZ4_E_ARG, "%s: bad stream table", who);
+    if (streamFirst[0] != 0 || streamFirst[nStreams] != nBlocks)
+        return fail(MI355LZ4_E_ARG, "%s: the streams do not cover blocks 0..%d", who, nBlocks);
+    std::vector<char> seen((size_t)cs->nSlots, 0);
+    for (int s = 0; s < nStreams; s++) {
+        if (streamFirst[s + 1] < streamFirst[s]) return fail(MI355LZ4_E_ARG, "%s: stream table is not ascending at %d", who, s);
+        const int k = streamSlot[s];
+        if (k < 0 || k >= cs->nSlots) return fail(MI355LZ4_E_ARG, "%s: stream %d names slot %d of %d", who, s, k, cs->nSlots);
+        if (seen[(size_t)k]) return fail(MI355LZ4_E_ARG, "%s: slot %d is named twice", who, k);
+        seen[(size_t)k] = 1;
+    }
+    return MI355LZ4_OK;
+}
+
+// Enqueue the streams' parts that fall into blocks [b0, b1) of the table (a.* describes exactly those blocks): a stream cut
+// by b0 or b1 simply continues its slot in the next launch.  Longer parts go first: the launch ends with its longest chain.
+static int streams_enqueue(mi355lz4_ctx *c, mi355lz4_cstreams *cs, const EncodeArgs &a, int b0, int b1,
+                           const int32_t *streamFirst, const int32_t *streamSlot, int nStreams)
+{
+    std::vector<int32_t> work;
+    {
+        std::vector<std::pair<int, int>> order;         // (-blocks, stream)
+        for (int s = 0; s < nStreams; s++) {
+            const int lo = std::max(streamFirst[s], b0), hi = std::min(streamFirst[s + 1], b1);
+            if (hi > lo) order.push_back({lo - hi, s});
+        }
+        std::stable_sort(order.begin(), order.end(), [](const std::pair<int, int> &x, const std::pair<int, int> &y) { return x.first < y.first; });
+        work.reserve(order.size() * 3);
+        for (const auto &o : order) {
+            const int s = o.second;
+            work.push_back(std::max(streamFirst[s], b0) - b0);
+            work.push_back(std::min(streamFirst[s + 1], b1) - b0);
+            work.push_back(streamSlot[s]);
+        }
+    }
+    const int nWork = (int)(work.size() / 3);
+    if (nWork == 0) return MI355LZ4_OK;
+    mi355lz4_cstreams::Ring &r = cs->ring[cs->next];
+    cs->next = (cs->next + 1) & 3;
+    if (r.busy) HIP_TRY(hipEventSynchronize(r.ev));      // the launch that last read this entry (four calls back)
+    r.busy = false;
+    if (!r.ev) HIP_TRY(hipEventCreateWithFlags(&r.ev, hipEventDisableTiming));
+    int rc;
+    if ((rc = pin_reserve(r.pin, work.size() * 4)) || (rc = dev_reserve(r.dev, work.size() * 4))) return rc;
+    memcpy(r.pin.p, work.data(), work.size() * 4);
+    HIP_TRY(hipMemcpyAsync(r.dev.p, r.pin.p, work.size() * 4, hipMemcpyHostToDevice, c->stream));
+    ExactStreamsArgs x;
+    x.e = a;
+    x.work = (const int32_t *)r.dev.p;
+    x.state = cs->state;
+    launch_exact_streams(x, nWork, c->stream);
+    if ((rc = check_launch("exact streams launch"))) return rc;
+    HIP_TRY(hipEventRecord(r.ev, c->stream));
+    r.busy = true;
+    if (c->blockChecksum) {                               // the trailers, behind the encoder (encode_device, finish)
+        launch_xxh32_append(a.slots, a.slotStride, a.headerKind, a.framedLen, a.nBlocks, c->stream);
+        return check_launch("checksum launch");
+    }
+    return MI355LZ4_OK;
+}
+
+extern "C" int mi355lz4_compress_streams_device(mi355lz4_ctx *c, mi355lz4_cstreams *cs, const uint8_t *src,
+                                                const uint64_t *srcOff, const int32_t *srcLen, uint64_t blockStride,
+                                                int maxBlockLen, int nBlocks, const int32_t *streamFirst,
+                                                const int32_t *streamSlot, int nStreams, int accel, int headerKind,
+                                                uint8_t *slots, size_t slotStride, int32_t *framedLen)
+{
+    int r = streams_check(c, cs, nBlocks, streamFirst, streamSlot, nStreams, "compress_streams_device");
+    if (r) return r;
+    if ((headerKind != 4 && headerKind != 8) || maxBlockLen < 0 || (unsigned)maxBlockLen > (unsigned)MI355LZ4_MAX_INPUT_SIZE)
+        return fail(MI355LZ4_E_ARG, "compress_streams_device: bad arguments");
+    if (nBlocks == 0) return MI355LZ4_OK;
+    if (!src && maxBlockLen > 0) return fail(MI355LZ4_E_ARG, "compress_streams_device: null src");
+    if (!slots || !framedLen) return fail(MI355LZ4_E_ARG, "compress_streams_device: null output");
+    if (slotStride < mi355lz4_compress_bound(maxBlockLen) + (size_t)headerKind + (c->blockChecksum ? 4u : 0u))
+        return fail(MI355LZ4_E_CAPACITY, "compress_streams_device: slotStride %zu < bound", slotStride);
+    if (accel < 1) accel = 1;                 // cbits/lz4.c:1577
+    if (accel > 65537) accel = 65537;         // cbits/lz4.c:1578
+    HIP_TRY(hipSetDevice(c->device));
+    EncodeArgs a;
+    a.src = src; a.srcOff = srcOff; a.srcLen = srcLen; a.blockStride = blockStride;
+    a.uniformLen = maxBlockLen; a.nBlocks = nBlocks; a.accel = accel; a.headerKind = headerKind;
+    a.slots = slots; a.slotStride = slotStride; a.framedLen = framedLen;
+    a.stats = nullptr; a.linked = 0; a.lookBack = 0;
+    return streams_enqueue(c, cs, a, 0, nBlocks, streamFirst, streamSlot, nStreams);
+}
+
 extern "C" int mi355lz4_compact_device(mi355lz4_ctx *c, const uint8_t *slots, size_t slotStride,
                                        const int32_t *framedLen, int nBlocks, uint8_t *dense, size_t denseCap,
                                        uint64_t *denseOff)
@@ -1377,9 +1560,16 @@ static inline int32_t host_le32(const uint8_t *p)
     return (int32_t)((uint32_t)p[0] | ((uint32_t)p[1] << 8) | ((uint32_t)p[2] << 16) | ((uint32_t)p[3] << 24));
 }
 
-extern "C" int mi355lz4_compress_batch(mi355lz4_ctx *c, const uint8_t *const *src, const int32_t *srcLen,
-                                       int nBlocks, int accel, int headerKind, uint8_t *framedOut, size_t cap,
-                                       size_t *outLen, int32_t *blockFramedLen, int32_t *status)
+// the streams of a mi355lz4_compress_streams call (null: mi355lz4_compress_batch)
+struct HostStreams {
+    mi355lz4_cstreams *cs;
+    const int32_t *first, *slot;
+    int n;
+};
+
+static int compress_host(mi355lz4_ctx *c, const uint8_t *const *src, const int32_t *srcLen,
+                         int nBlocks, int accel, int headerKind, uint8_t *framedOut, size_t cap,
+                         size_t *outLen, int32_t *blockFramedLen, int32_t *status, const HostStreams *hs)
 {
     if (!c) return fail(MI355LZ4_E_ARG, "null ctx");
     if (nBlocks < 0 || (headerKind != 4 && headerKind != 8) || !outLen)
@@ -1401,7 +1591,7 @@ extern "C" int mi355lz4_compress_batch(mi355lz4_ctx *c, const uint8_t *const *sr
         offs[(size_t)i] = total;
         if (i > 0 && src[i] != src[0] + total) contiguous = false;
         // 16-aligned block starts; back to back for a linked stream (a block's dictionary lies directly in front of it)
-        total += c->linkedCompress ? (size_t)srcLen[i] : (((size_t)srcLen[i] + 15) & ~(size_t)15);
+        total += (c->linkedCompress && !hs) ? (size_t)srcLen[i] : (((size_t)srcLen[i] + 15) & ~(size_t)15);
         if (srcLen[i] > maxLen) maxLen = srcLen[i];
     }
     const size_t stride = mi355lz4_slot_stride_ex(maxLen, headerKind, c->blockChecksum);
@@ -1481,13 +1671,23 @@ extern "C" int mi355lz4_compress_batch(mi355lz4_ctx *c, const uint8_t *const *sr
             }
         }
         HIP_TRY(hipEventRecord(evIn[(size_t)g], c->sIn));
-        StreamSwap on(c, c->sK[c->compExact ? 0 : (g & 1)]);   // an exact stream's groups follow each other
+        StreamSwap on(c, c->sK[(c->compExact || hs) ? 0 : (g & 1)]);   // an exact stream's groups follow each other
         HIP_TRY(hipStreamWaitEvent(c->stream, evIn[(size_t)g], 0));
         PTRACE("compress: group %d H2D enqueued (%zu bytes, direct %d)", g, hi - lo, (int)directIn);
         // (a linked stream: the last block of the group before is this group's first dictionary)
-        r = encode_device(c, (const uint8_t *)c->in.p, (const uint64_t *)c->offA.p + b0,
-                          (const int32_t *)c->lenA.p + b0, 0, maxLen, b1 - b0, accel, headerKind,
-                          (uint8_t *)c->slots.p + (size_t)b0 * stride, stride, (int32_t *)c->lenB.p + b0, b0, srcLen + b0);
+        if (hs) {                                  // (a group seam inside a stream: the slot continues in the next group's launch)
+            EncodeArgs a;
+            a.src = (const uint8_t *)c->in.p; a.srcOff = (const uint64_t *)c->offA.p + b0; a.srcLen = (const int32_t *)c->lenA.p + b0;
+            a.blockStride = 0; a.uniformLen = maxLen; a.nBlocks = b1 - b0;
+            a.accel = accel < 1 ? 1 : (accel > 65537 ? 65537 : accel); a.headerKind = headerKind;
+            a.slots = (uint8_t *)c->slots.p + (size_t)b0 * stride; a.slotStride = stride; a.framedLen = (int32_t *)c->lenB.p + b0;
+            a.stats = nullptr; a.linked = 0; a.lookBack = 0;
+            r = streams_enqueue(c, hs->cs, a, b0, b1, hs->first, hs->slot, hs->n);
+        } else {
+            r = encode_device(c, (const uint8_t *)c->in.p, (const uint64_t *)c->offA.p + b0,
+                              (const int32_t *)c->lenA.p + b0, 0, maxLen, b1 - b0, accel, headerKind,
+                              (uint8_t *)c->slots.p + (size_t)b0 * stride, stride, (int32_t *)c->lenB.p + b0, b0, srcLen + b0);
+        }
         if (r) return r;
         uint64_t *goff = (uint64_t *)c->offB.p + b0 + g;                       // b1 - b0 + 1 offsets of this group
         r = mi355lz4_compact_device(c, (const uint8_t *)c->slots.p + (size_t)b0 * stride, stride,
@@ -1542,6 +1742,28 @@ extern "C" int mi355lz4_compress_batch(mi355lz4_ctx *c, const uint8_t *const *sr
     if (overflow) return fail(MI355LZ4_E_CAPACITY, "compress_batch: need %llu bytes, have %zu", (unsigned long long)outPos, cap);
     *outLen = outPos;
     return MI355LZ4_OK;
+}
+
+extern "C" int mi355lz4_compress_batch(mi355lz4_ctx *c, const uint8_t *const *src, const int32_t *srcLen,
+                                       int nBlocks, int accel, int headerKind, uint8_t *framedOut, size_t cap,
+                                       size_t *outLen, int32_t *blockFramedLen, int32_t *status)
+{
+    return compress_host(c, src, srcLen, nBlocks, accel, headerKind, framedOut, cap, outLen, blockFramedLen, status, nullptr);
+}
+
+// Host-buffer form of mi355lz4_compress_streams_device: the group pipeline of mi355lz4_compress_batch, its groups one behind
+// the other on one compute stream like an exact call's.  The lengths are the caller's host array: checked before anything is queued.
+extern "C" int mi355lz4_compress_streams(mi355lz4_ctx *c, mi355lz4_cstreams *cs, const uint8_t *const *src,
+                                         const int32_t *srcLen, int nBlocks, const int32_t *streamFirst,
+                                         const int32_t *streamSlot, int nStreams, int accel, int headerKind,
+                                         uint8_t *framedOut, size_t cap, size_t *outLen, int32_t *blockFramedLen,
+                                         int32_t *status)
+{
+    if (outLen) *outLen = 0;
+    const int r = streams_check(c, cs, nBlocks, streamFirst, streamSlot, nStreams, "compress_streams");
+    if (r) return r;
+    const HostStreams hs{cs, streamFirst, streamSlot, nStreams};
+    return compress_host(c, src, srcLen, nBlocks, accel, headerKind, framedOut, cap, outLen, blockFramedLen, status, &hs);
 }
 
 extern "C" int mi355lz4_index_host_ex(const uint8_t *framedIn, size_t inLen, int headerKind, int fixedUncomp,

@@ -129,6 +129,18 @@ struct ExactArgs {
     int nPieces;
 };
 
+// many reference-exact streams in one call (mi355lz4_compress_streams_device; kernels.hip, k_exact_streams).  One slot of a
+// mi355lz4_cstreams is the device form of LZ4_stream_t: the table, the previous array's last 64 KiB and the scalars.
+#define CSTREAM_SCALAR_OFF ((size_t)EXACT_TABLE * 4)              // uint32 {currentOffset, dictSize, saved bytes, -}: zeroed with the table
+#define CSTREAM_DICT_OFF   (CSTREAM_SCALAR_OFF + 64)              // the saved dictionary bytes
+#define CSTREAM_SLOT_BYTES (CSTREAM_DICT_OFF + 65536)             // 81984: about 80 KiB a slot
+
+struct ExactStreamsArgs {
+    EncodeArgs e;                // blocks, slots, headers, framedLen, accel (clamped); e.uniformLen bounds every length
+    const int32_t *work;         // per wave of the launch {first block, end block, slot of the set}
+    uint8_t *state;              // the set's slots, CSTREAM_SLOT_BYTES each
+};
+
 // small batches: a block's segments are compressed by several waves (kernels.hip, K2 small batches)
 struct EncodeSegArgs {
     EncodeArgs e;
@@ -173,6 +185,8 @@ void launch_encode_hc(const EncodeArgs &a, int level, hipStream_t s);      // co
 void launch_exact_chain(const ExactArgs &a, int first, int count, int redo, hipStream_t s);
 void launch_exact_verify(const ExactArgs &a, int first, int count, hipStream_t s);
 void launch_exact_finish(const ExactArgs &a, hipStream_t s);
+// many reference-exact streams: one wave per entry of a.work walks its blocks from its slot's state and stores the state back
+void launch_exact_streams(const ExactStreamsArgs &a, int nWork, hipStream_t s);
 void launch_compact(const uint8_t *slots, size_t slotStride, const int32_t *framedLen, int nBlocks,
                     uint8_t *dense, size_t denseCap, uint64_t *denseOff, hipStream_t s);
 void launch_interleave(const uint8_t *local, const uint64_t *localOff, int nLocal, int rank, int nRanks,

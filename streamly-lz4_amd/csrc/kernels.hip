@@ -6,6 +6,7 @@
 //   K2  k_encode<TabT, DICT>             block encode, independent or linked (encode_wave.hpp)
 //       k_encode_hc                      high-compression levels: hash chains + lazy parse (encode_hc.hpp)
 //       k_exact_chain / _verify / _finish  reference-exact linked stream: speculate, verify, redo (encode_exact.hpp)
+//       k_exact_streams                  many reference-exact streams, one wave each, their state in device slots
 //   K3  k_scan_u64 + k_copy_slots        size scan + compaction into the framed stream
 //       k_header_sizes                   uncompressed-size scan from block headers
 //       k_generate                       synthetic inputs (bench/test support)
@@ -356,6 +357,81 @@ void launch_exact_finish(const ExactArgs &a, hipStream_t s)
 {
     if (a.e.nBlocks <= 0) return;
     hipLaunchKernelGGL(k_exact_finish, dim3(1), dim3(256), 0, s, a);
+}
+
+// Many reference-exact streams in one call (mi355lz4_compress_streams_device).  Wave w continues the stream
+// in slot work[3w + 2] with the blocks [work[3w], work[3w + 1]) of the call: every stream starts from its own true state, so
+// nothing is speculated.  The wave follows the scalars itself -- LZ4_compress_fast_continue's statements in front of the
+// encoder (cbits/lz4.c:1565-1627), the ones exact_encode runs on the host for the single stream: wave-uniform, 32-bit.
+// A length outside 0..maxBlockLen ends the stream's part of the call: that block and the ones behind it get framedLen 0,
+// and the slot keeps the state after the last good block.
+__global__ __launch_bounds__(LZ4_WAVE) void k_exact_streams(ExactStreamsArgs x)
+{
+    __shared__ dev_v4 tab4[EXACT_TABLE / 4];
+    uint32_t *tab = (uint32_t *)tab4;
+    const int lane = lane_id();
+    const int32_t *w = x.work + 3 * (size_t)blockIdx.x;
+    const int b0 = uni(w[0]), b1 = uni(w[1]);
+    uint8_t *st = x.state + (size_t)uni(w[2]) * CSTREAM_SLOT_BYTES;
+    uint8_t *dictSave = st + CSTREAM_DICT_OFF;
+    uint32_t *scal = (uint32_t *)(st + CSTREAM_SCALAR_OFF);
+    for (int i = lane; i < EXACT_TABLE / 4; i += LZ4_WAVE) tab4[i] = as_global((const dev_v4 *)st)[i];
+    uint32_t cur = ex_uni(as_global(scal)[0]), dictSize = ex_uni(as_global(scal)[1]);
+    uint32_t dictBytes = ex_uni(as_global(scal)[2]);
+    const uint8_t *dictEnd = dictSave + dictBytes;
+    const uint8_t *lastSrc = nullptr;                                   // the last good array of the call: the next dictionary
+    uint32_t lastN = 0;
+    __syncthreads();
+    for (int j = b0; j < b1; j++) {
+        const int n = uni(x.e.srcLen ? x.e.srcLen[j] : x.e.uniformLen);
+        if (n < 0 || n > x.e.uniformLen) {
+            for (int k = j + lane; k < b1; k += LZ4_WAVE) x.e.framedLen[k] = 0;
+            break;
+        }
+        ExactBlock m;
+        m.delta = 0;
+        if (cur + (uint32_t)n > 0x80000000u) {                          // LZ4_renormDictT, cbits/lz4.c:1545-1562
+            m.delta = cur - 65536u;
+            cur = 65536u;
+            if (dictSize > 65536u) dictSize = 65536u;
+            for (int i = lane; i < EXACT_TABLE / 4; i += LZ4_WAVE) tab4[i] = exact_canon4(tab4[i], 0u, m.delta);
+            __syncthreads();
+        }
+        if (dictSize - 1u < 4u - 1u) dictSize = 0;                      // :1581-1587
+        m.start = cur; m.dictSize = dictSize; m.n = n; m.pad = 0;
+        m.dictSmall = (dictSize < 65536u && dictSize < cur) ? 1 : 0;    // :1627
+        const uint8_t *src = exact_src(x.e, j);
+        uint8_t *slot = x.e.slots + (size_t)j * x.e.slotStride;
+        const int cap = n + n / 255 + 16;                               // LZ4_compressBound
+        int c;
+        if (n == 0) {                                                   // cbits/lz4.c:1263-1273
+            c = 1;
+            if (lane == 0) slot[x.e.headerKind] = 0;
+        } else {
+            c = exact_encode_block(tab, src, n, dictEnd, m, (uint32_t)x.e.accel, slot + x.e.headerKind, cap, true);
+        }
+        if (lane == 0) {
+            store_le32(slot, c);
+            if (x.e.headerKind == 8) store_le32(slot + 4, n);
+            x.e.framedLen[j] = (c > 0) ? x.e.headerKind + c : 0;
+        }
+        cur += (uint32_t)n;                                             // :1633-1634
+        dictSize = (uint32_t)n;
+        dictEnd = src + n;
+        lastSrc = src; lastN = (uint32_t)n;
+        __syncthreads();
+    }
+    if (!lastSrc) return;                                               // no good block: the slot is as it was
+    for (int i = lane; i < EXACT_TABLE / 4; i += LZ4_WAVE) as_global((dev_v4 *)st)[i] = tab4[i];
+    const uint32_t keep = lastN < 65536u ? lastN : 65536u;              // (a zero-length last array: no dictionary)
+    wave_copy_bytes(dictSave, lastSrc + (lastN - keep), keep);
+    if (lane == 0) { as_global(scal)[0] = cur; as_global(scal)[1] = dictSize; as_global(scal)[2] = keep; }
+}
+
+void launch_exact_streams(const ExactStreamsArgs &a, int nWork, hipStream_t s)
+{
+    if (nWork <= 0) return;
+    hipLaunchKernelGGL(k_exact_streams, dim3((unsigned)nWork), dim3(LZ4_WAVE), 0, s, a);
 }
 
 // ---------------------------------------------------------------------------

@@ -18,7 +18,7 @@ import os
 import numpy as np
 
 __all__ = [
-    "lib", "lib_path", "Engine", "LZ4Error", "BlockSize", "BlockConfig", "FrameConfig",
+    "lib", "lib_path", "Engine", "CompressStreams", "LZ4Error", "BlockSize", "BlockConfig", "FrameConfig",
     "defaultBlockConfig", "defaultFrameConfig", "setBlockMaxSize", "setFrameEndMark", "setBlockChecksum",
     "compressChunks", "decompressChunks", "decompressChunksRaw", "resizeChunks",
     "decompressChunksWith", "decompressChunksStream", "simpleFrameParser", "compress_bound", "slot_stride", "slot_stride_ex", "device_count",
@@ -123,6 +123,16 @@ def _load():
     sig("mi355lz4_get_compress_exact", C.c_int, vp)
     sig("mi355lz4_compress_exact_reset", C.c_int, vp)
     sig("mi355lz4_debug_exact_state", C.c_int, vp, C.POINTER(C.c_int))
+    # many exact streams in one call
+    sig("mi355lz4_cstreams_create", C.c_int, vp, C.c_int, C.POINTER(vp))
+    sig("mi355lz4_cstreams_destroy", None, vp)
+    sig("mi355lz4_cstreams_count", C.c_int, vp)
+    sig("mi355lz4_cstreams_reset", C.c_int, vp, vp, _i32p, C.c_int)
+    sig("mi355lz4_debug_cstream_state", C.c_int, vp, C.c_int, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32))
+    sig("mi355lz4_compress_streams_device", C.c_int, vp, vp, vp, vp, vp, C.c_uint64, C.c_int, C.c_int, _i32p, _i32p,
+        C.c_int, C.c_int, C.c_int, vp, C.c_size_t, vp)
+    sig("mi355lz4_compress_streams", C.c_int, vp, vp, C.POINTER(_u8p), _i32p, C.c_int, _i32p, _i32p, C.c_int, C.c_int,
+        C.c_int, _u8p, C.c_size_t, C.POINTER(C.c_size_t), _i32p, _i32p)
     # legacy face (include/lz4.h)
     sig("LZ4_createStream", vp)
     sig("LZ4_freeStream", C.c_int, vp)
@@ -174,6 +184,8 @@ DECLARED_SYMBOLS = [
     "mi355lz4_set_block_checksum", "mi355lz4_slot_stride_ex", "mi355lz4_index_host_ex", "mi355lz4_xxh32_device",
     "mi355lz4_set_compression_level", "mi355lz4_get_compression_level",
     "mi355lz4_set_compress_exact", "mi355lz4_get_compress_exact", "mi355lz4_compress_exact_reset",
+    "mi355lz4_cstreams_create", "mi355lz4_cstreams_destroy", "mi355lz4_cstreams_count", "mi355lz4_cstreams_reset",
+    "mi355lz4_compress_streams_device", "mi355lz4_compress_streams",
     "LZ4_createStream", "LZ4_freeStream", "LZ4_createStreamDecode", "LZ4_freeStreamDecode", "LZ4_compressBound",
     "LZ4_compress_fast_continue", "LZ4_decompress_safe_continue",
 ]
@@ -634,6 +646,47 @@ class Engine:
             _check(rc, "decompress_batch")
         return out[: out_len.value].tobytes(), blen[: got.value].tolist()
 
+    def compress_streams_device(self, cs, src, n_blocks, max_block_len, stream_first, stream_slot, slots, slot_stride_,
+                                framed_len, accel=1, header_kind=8, src_off=None, src_len=None, block_stride=None):
+        """Many reference-exact streams in one call (include/mi355lz4.h, mi355lz4_compress_streams_device): stream s is the
+        blocks [stream_first[s], stream_first[s+1]) and continues slot stream_slot[s] of cs.  The block arguments are those
+        of compress_batch_device (device tensors); stream_first / stream_slot are host sequences.  Only enqueues."""
+        self._follow_torch()
+        sf = np.ascontiguousarray(stream_first, dtype=np.int32)
+        sl = np.ascontiguousarray(stream_slot, dtype=np.int32)
+        if sf.size != sl.size + 1:
+            raise ValueError("stream_first needs one entry more than stream_slot")
+        _check(lib.mi355lz4_compress_streams_device(
+            self.ctx, cs._h, _dptr(src), _dptr(src_off), _dptr(src_len),
+            int(max_block_len if block_stride is None else block_stride), int(max_block_len), int(n_blocks),
+            sf.ctypes.data_as(_i32p), sl.ctypes.data_as(_i32p), int(sl.size), int(accel), int(header_kind), _dptr(slots),
+            int(slot_stride_), _dptr(framed_len)), "compress_streams_device")
+
+    def compress_streams(self, streams, cs, slots=None, accel=1, header_kind=8):
+        """streams: list of lists of bytes-like, stream s continuing slot slots[s] of cs (default: slot s).  Returns
+        (framed bytes of all blocks in order, [framed length per block]); mi355lz4_compress_streams."""
+        if slots is None:
+            slots = list(range(len(streams)))
+        blocks = [b for st in streams for b in st]
+        n = len(blocks)
+        sf = np.cumsum([0] + [len(st) for st in streams]).astype(np.int32)
+        sl = np.ascontiguousarray(slots, dtype=np.int32)
+        if sl.size != len(streams):
+            raise ValueError("one slot per stream")
+        arrs = [np.frombuffer(bytes(b), dtype=np.uint8) if not isinstance(b, np.ndarray) else b for b in blocks]
+        ptrs = (_u8p * max(n, 1))(*[a.ctypes.data_as(_u8p) for a in arrs])
+        lens = np.array([a.size for a in arrs] + [0], dtype=np.int32)
+        cap = int(sum(compress_bound(int(x)) + header_kind + 4 for x in lens[:n])) + 16
+        out = np.empty(cap, dtype=np.uint8)
+        out_len = C.c_size_t()
+        flen = np.zeros(max(n, 1), dtype=np.int32)
+        status = np.zeros(max(n, 1), dtype=np.int32)
+        _check(lib.mi355lz4_compress_streams(self.ctx, cs._h, ptrs, lens.ctypes.data_as(_i32p), n, sf.ctypes.data_as(_i32p),
+                                             sl.ctypes.data_as(_i32p), int(sl.size), int(accel), int(header_kind),
+                                             out.ctypes.data_as(_u8p), cap, C.byref(out_len), flen.ctypes.data_as(_i32p),
+                                             status.ctypes.data_as(_i32p)), "compress_streams")
+        return out[: out_len.value].tobytes(), flen[:n].tolist()
+
     def decompress_streams(self, framed, stream_first, header_kind=8, fixed_uncomp=0, raise_on_block_error=True):
         """Many linked streams, host buffers: stream s = blocks [stream_first[s], stream_first[s+1]).
         Returns (decoded bytes, [decoded length or negative code per block])."""
@@ -657,6 +710,49 @@ class Engine:
         if rc != 0 and (raise_on_block_error or rc != -5):
             _check(rc, "decompress_streams")
         return out[: out_len.value].tobytes(), blen[: got.value].tolist()
+
+
+class CompressStreams:
+    """A set of n_slots device-resident reference-exact compress streams (mi355lz4_cstreams, about 80 KiB a slot), for
+    Engine.compress_streams / compress_streams_device.  Bound to the engine's device; every slot starts reset."""
+
+    def __init__(self, engine, n_slots):
+        self._h = C.c_void_p()
+        self._engine = engine
+        engine._follow_torch()
+        _check(lib.mi355lz4_cstreams_create(engine.ctx, int(n_slots), C.byref(self._h)), "cstreams_create")
+
+    def __len__(self):
+        return int(lib.mi355lz4_cstreams_count(self._h))
+
+    def reset(self, slots=None):
+        """LZ4_resetStream for the listed slots (None: all), enqueued on the engine's stream."""
+        self._engine._follow_torch()
+        if slots is None:
+            _check(lib.mi355lz4_cstreams_reset(self._engine.ctx, self._h, None, 0), "cstreams_reset")
+        else:
+            a = np.ascontiguousarray(slots, dtype=np.int32)
+            _check(lib.mi355lz4_cstreams_reset(self._engine.ctx, self._h, a.ctypes.data_as(_i32p), int(a.size)),
+                   "cstreams_reset")
+
+    def state(self, slot, set_current_offset=None):
+        """Diagnostics: (currentOffset, dictSize, saved dictionary bytes) of a slot, after the device is idle; with
+        set_current_offset the slot's currentOffset is then overwritten."""
+        got = (C.c_uint32 * 3)()
+        new = None if set_current_offset is None else C.byref(C.c_uint32(int(set_current_offset)))
+        _check(lib.mi355lz4_debug_cstream_state(self._h, int(slot), got, new), "debug_cstream_state")
+        return tuple(int(v) for v in got)
+
+    def close(self):
+        if self._h:
+            lib.mi355lz4_cstreams_destroy(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
 
 
 # ---------------------------------------------------------------------------
