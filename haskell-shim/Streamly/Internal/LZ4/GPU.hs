@@ -35,6 +35,8 @@ module Streamly.Internal.LZ4.GPU
     , setCompressionLevel
     , setCompressExact
     , resetCompressStream
+    , c_decodedSizeDevice
+    , decodedSizes
     , CompressStreams
     , newCompressStreams
     , freeCompressStreams
@@ -135,6 +137,14 @@ foreign import ccall safe "mi355lz4.h mi355lz4_compress_streams"
         :: Ptr C_Engine -> Ptr C_CStreams -> Ptr (Ptr Word8) -> Ptr Int32 -> CInt -> Ptr Int32 -> Ptr Int32 -> CInt
         -> CInt -> CInt -> Ptr Word8 -> CSize -> Ptr CSize -> Ptr Int32 -> Ptr Int32 -> IO CInt
 
+-- Decoded sizes without decoding (device pointers in, device pointers out; only enqueues): what every block of a
+-- size-less framing (BlockMax64KB .. BlockMax4MB) decodes to, read off its token chain.  size[i] >= 0, or a negative
+-- per-block code (MI355LZ4_BLK_E_SIZE_UNKNOWN = -0x7F000005); outOff (may be nullPtr) = their exclusive scan.
+foreign import ccall safe "mi355lz4.h mi355lz4_decoded_size_device"
+    c_decodedSizeDevice
+        :: Ptr C_Engine -> Ptr Word8 -> Word64 -> Ptr Word64 -> CInt -> CInt -> CInt -> Ptr Int32 -> Ptr Word64
+        -> IO CInt
+
 -- replaces c_decompressSafeContinue (Streamly/Internal/LZ4.hs:133-140), N blocks per call
 foreign import ccall safe "mi355lz4.h mi355lz4_decompress_batch"
     c_decompressBatch
@@ -191,6 +201,15 @@ newEngine dev = alloca $ \pp -> do
 
 freeEngine :: Engine -> IO ()
 freeEngine (Engine p) = c_destroy p
+
+-- | @decodedSizes eng framed framedLen blockOff nBlocks headerKind maxUncomp size outOff@: enqueues the size pass over
+-- @nBlocks@ framed blocks in device memory (include/mi355lz4.h, @mi355lz4_decoded_size_device@).  A block decoded into
+-- exactly @size[i]@ bytes gives what it gives decoded into @maxUncomp@, so @size@ / @outOff@ are a dense output layout.
+decodedSizes :: Engine -> Ptr Word8 -> Word64 -> Ptr Word64 -> Int -> Int -> Int -> Ptr Int32 -> Ptr Word64 -> IO ()
+decodedSizes (Engine p) framed framedLen blockOff nBlocks headerKind maxUncomp size outOff = do
+    rc <- c_decodedSizeDevice p framed framedLen blockOff (fromIntegral nBlocks) (fromIntegral headerKind)
+                              (fromIntegral maxUncomp) size outOff
+    when (rc /= 0) $ error "mi355lz4_decoded_size_device failed"
 
 -- | 'True': 'compressChunksGPU' writes a linked stream (the block before is a block's
 -- dictionary, what @LZ4_compress_fast_continue@ does with the previous chunk,

@@ -59,6 +59,7 @@ extern "C" {
 #define MI355LZ4_BLK_E_TRUNCATED (-0x7F000002)  /* header/data runs past the framed buffer */
 #define MI355LZ4_BLK_E_UNCOMPLEN (-0x7F000003)  /* negative uncompLen / exceeds output capacity */
 #define MI355LZ4_BLK_E_CHECKSUM (-0x7F000004)   /* data does not match its trailer (mi355lz4_set_block_checksum) */
+#define MI355LZ4_BLK_E_SIZE_UNKNOWN (-0x7F000005) /* mi355lz4_decoded_size_device: the token chain gives no size the call vouches for */
 
 #define MI355LZ4_MAX_INPUT_SIZE 0x7E000000      /* = LZ4_MAX_INPUT_SIZE, cbits/lz4.h:170 */
 
@@ -79,7 +80,7 @@ typedef struct mi355lz4_ctx mi355lz4_ctx;
  *   rest of a wider stride is the caller's); framedLen[] only in [0, nBlocks); src, srcOff and srcLen never.
  * _compact_device: dense[0, denseOff[k + 1]) for the last block k that fits (denseOff[k + 1] <= denseCap; nothing
  *   when none fits), denseOff[0..nBlocks];
- *   _index_device: outOff[0..nBlocks]; _interleave_device: global + globalOff[j*nRanks + rank] for the local blocks'
+ *   _index_device: outOff[0..nBlocks]; _decoded_size_device: size[0..nBlocks), outOff[0..nBlocks]; _interleave_device: global + globalOff[j*nRanks + rank] for the local blocks'
  *   lengths; _generate_device: dst[0, nBlocks * blockLen); _xxh32_device: out[i] for len[i] >= 0.  Inputs never.
  * Host-buffer calls (_compress_batch, _decompress_batch, _decompress_streams, _multi_*): nothing at or past
  *   framedOut + cap / out + cap or in front of either pointer; blockFramedLen, status and blockLen only in
@@ -245,6 +246,39 @@ int mi355lz4_decompress_streams_device(mi355lz4_ctx *ctx, const uint8_t *framed,
 int mi355lz4_index_device(mi355lz4_ctx *ctx, const uint8_t *framed, uint64_t framedLen,
                           const uint64_t *blockOff, int nBlocks, int headerKind, int fixedUncomp,
                           uint64_t *outOff);
+
+/* Decoded sizes without decoding.  Blocks framed without an uncompressed length (headerKind 4) say nowhere what they
+ * decode to; this call reads it off their token chains -- the compressed bytes and nothing else, one wavefront per block --
+ * so that a caller can lay its output out densely instead of at fixedUncomp per block.  It only enqueues on the engine's
+ * stream.  headerKind 8 is accepted too: the data is walked and the header's uncompLen ignored (a cross-check of headers).
+ * size[i] = s >= 0 exactly when
+ *   1. the chain is well formed: every token, extension byte, literal run and offset field lies inside the block's
+ *      compLen bytes, and the chain ends exactly at their end with a sequence of literals only;
+ *   2. the block keeps the end-of-block rules every conforming encoder keeps (cbits/lz4.c:214-221): under 13 bytes no match,
+ *      the last match starts at least 12 bytes before the end, the last 5 bytes are literals;
+ *   3. s <= maxUncomp;
+ *   4. no offset is 0, an empty block is the one byte 0x00, and no match that has length-extension bytes and ends within
+ *      the last 64 bytes of output reaches in front of the block (the code a bad offset gets there depends on the capacity).
+ * Otherwise size[i] = MI355LZ4_BLK_E_SIZE_UNKNOWN; a block whose header is rejected keeps that code
+ * (MI355LZ4_BLK_E_COMPLEN, MI355LZ4_BLK_E_TRUNCATED -- also when block checksums are on and the trailer lies past
+ * framedLen; the checksum itself is not verified here).  Offsets are not judged beyond rule 4: whether a source lies inside
+ * the block or a dictionary is the decoder's business.
+ * What a size vouches for: decoding that block into a capacity of exactly size[i] gives the result and the bytes that
+ * decoding it into any larger capacity gives (capacity enters the reference decoder only through its end-of-output
+ * checks, cbits/lz4.c:1797-1924) -- so outCap = size, outOff = the scan is a drop-in layout for the decode calls.
+ * outOff (optional, nBlocks + 1 entries) = exclusive scan of size[i] >= 0 ? size[i] : 0.
+ * The call writes size[0..nBlocks) and outOff[0..nBlocks] and nothing else; framed and blockOff are never written.
+ * MI355LZ4_E_ARG: null ctx, nBlocks < 0, maxUncomp < 0, a headerKind other than 4 / 8, a null framed / blockOff / size
+ * with nBlocks > 0.  nBlocks == 0 is MI355LZ4_OK (outOff[0] = 0 when given). */
+int mi355lz4_decoded_size_device(mi355lz4_ctx *ctx, const uint8_t *framed, uint64_t framedLen,
+                                 const uint64_t *blockOff, int nBlocks, int headerKind, int maxUncomp,
+                                 int32_t *size, uint64_t *outOff /* optional, nBlocks+1 */);
+
+/* The same for blocks in host memory: framed[0..len) goes to the device, mi355lz4_decoded_size_device runs over it with
+ * host blockOff[], and size[0..nBlocks) (host) comes back.  Synchronous; same argument checks, same per-block codes.
+ * What streamly_lz4::Engine::decodedSizes calls. */
+int mi355lz4_decoded_sizes_host(mi355lz4_ctx *ctx, const uint8_t *framed, size_t len, const uint64_t *blockOff,
+                                int nBlocks, int headerKind, int maxUncomp, int32_t *size);
 
 /* ---- host-buffer batched API (what the Haskell shim binds; synchronous) -
  * A call is pipelined over groups of blocks (MI355LZ4_GROUP_MB, default 64 MiB):

@@ -88,6 +88,11 @@ public:
     void setCompressExact(bool on);
     bool compressExact() const;
     void resetCompressStream();
+    // Decoded sizes without decoding (mi355lz4_decoded_size_device): what every block of the dense framed stream `framed`
+    // (host memory; cfg gives the header kind and whether blocks carry checksum trailers) decodes to, read off the token
+    // chains on the GPU: a size, or a negative per-block code (MI355LZ4_BLK_E_SIZE_UNKNOWN where the chain gives none of
+    // at most maxUncomp bytes).  Throws Error on a malformed header chain or a failed call.
+    std::vector<int32_t> decodedSizes(const BlockConfig &cfg, const Array &framed, int maxUncomp);
     // Many exact streams in one call (mi355lz4_compress_streams): streams[s] are the next arrays of the pipeline that owns
     // slot slots[s] of cs; the result holds, per stream, one framed array per input array -- what compressChunksD yields for
     // them at this point of that pipeline's stream.  Throws Error.

@@ -1395,6 +1395,40 @@ extern "C" int mi355lz4_index_device(mi355lz4_ctx *c, const uint8_t *framed, uin
     return check_launch("index launch");
 }
 
+extern "C" int mi355lz4_decoded_size_device(mi355lz4_ctx *c, const uint8_t *framed, uint64_t framedLen,
+                                            const uint64_t *blockOff, int nBlocks, int headerKind, int maxUncomp,
+                                            int32_t *size, uint64_t *outOff)
+{
+    if (!c || nBlocks < 0 || maxUncomp < 0 || (headerKind != 4 && headerKind != 8) ||
+        (nBlocks > 0 && (!framed || !blockOff || !size)))
+        return fail(MI355LZ4_E_ARG, "decoded_size_device: bad arguments");
+    HIP_TRY(hipSetDevice(c->device));
+    launch_decoded_size(framed, framedLen, blockOff, nBlocks, headerKind, maxUncomp, c->blockChecksum, size, outOff, c->stream);
+    return check_launch("size launch");
+}
+
+// the size pass over blocks in host memory: H2D, mi355lz4_decoded_size_device, sizes back; synchronous
+extern "C" int mi355lz4_decoded_sizes_host(mi355lz4_ctx *c, const uint8_t *framed, size_t len, const uint64_t *blockOff,
+                                           int nBlocks, int headerKind, int maxUncomp, int32_t *size)
+{
+    if (!c || nBlocks < 0 || maxUncomp < 0 || (headerKind != 4 && headerKind != 8) ||
+        (nBlocks > 0 && (!framed || !blockOff || !size)))
+        return fail(MI355LZ4_E_ARG, "decoded_sizes_host: bad arguments");
+    if (nBlocks == 0) return MI355LZ4_OK;
+    HIP_TRY(hipSetDevice(c->device));
+    int r;
+    if ((r = dev_reserve(c->in, len + 16)) || (r = dev_reserve(c->offA, (size_t)nBlocks * 8)) || (r = dev_reserve(c->lenB, (size_t)nBlocks * 4)))
+        return r;
+    if ((r = h2d_staged(c, c->in.p, framed, len))) return r;
+    HIP_TRY(hipMemcpyAsync(c->offA.p, blockOff, (size_t)nBlocks * 8, hipMemcpyHostToDevice, c->stream));
+    r = mi355lz4_decoded_size_device(c, (const uint8_t *)c->in.p, len, (const uint64_t *)c->offA.p, nBlocks, headerKind, maxUncomp,
+                                     (int32_t *)c->lenB.p, nullptr);
+    if (r) return r;
+    HIP_TRY(hipMemcpyAsync(size, c->lenB.p, (size_t)nBlocks * 4, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    return MI355LZ4_OK;
+}
+
 extern "C" int mi355lz4_generate_device(mi355lz4_ctx *c, int kind, uint8_t *dst, int blockLen, int nBlocks,
                                         uint64_t firstBlock, uint64_t blockStep, uint32_t litMax, uint32_t offMax)
 {
@@ -1868,7 +1902,6 @@ static int decompress_host(mi355lz4_ctx *c, const uint8_t *framedIn, size_t inLe
         return decompress_host_pipelined(c, framedIn, inLen, headerKind, fixedUncomp, linked, dict, dictLen, boff, ulen,
                                          ooff, n, out, outLen, blockLen, nBlocksOut);
     if ((r = dev_reserve(c->in, inLen + 16))) return r;
-    if ((r = dev_reserve(c->out, (size_t)total + 16))) return r;
     if ((r = dev_reserve(c->offA, (size_t)n * 8))) return r;
     if ((r = dev_reserve(c->offB, ((size_t)n + 1) * 8))) return r;
     if ((r = dev_reserve(c->res, (size_t)n * 4))) return r;
@@ -1883,6 +1916,30 @@ static int decompress_host(mi355lz4_ctx *c, const uint8_t *framedIn, size_t inLe
     }
     if ((r = h2d_staged(c, c->in.p, framedIn, inLen))) return r;
     HIP_TRY(hipMemcpyAsync(c->offA.p, boff.data(), (size_t)n * 8, hipMemcpyHostToDevice, c->stream));
+    // Blocks without a size in their header: the token chains say what every block decodes to (size_walk.hpp).  When every
+    // size is known the output is laid out back to back at those sizes -- sum(size) device bytes instead of
+    // n * fixedUncomp, one copy back instead of one per block -- and each block is decoded into exactly its size, which
+    // by the size pass's acceptance rule gives what decoding into fixedUncomp gives.  One block without a known size
+    // (malformed, or larger than fixedUncomp) and the whole call is laid out at fixedUncomp, as before.
+    const int32_t *capDev = nullptr;
+    if (headerKind == 4) {
+        if ((r = dev_reserve(c->lenB, (size_t)n * 4))) return r;
+        launch_decoded_size((const uint8_t *)c->in.p, inLen, (const uint64_t *)c->offA.p, n, headerKind, fixedUncomp,
+                            c->blockChecksum, (int32_t *)c->lenB.p, nullptr, c->stream);
+        if ((r = check_launch("size launch"))) return r;
+        std::vector<int32_t> sz((size_t)n);
+        HIP_TRY(hipMemcpyAsync(sz.data(), c->lenB.p, (size_t)n * 4, hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(hipStreamSynchronize(c->stream));
+        bool known = true;
+        for (int i = 0; i < n && known; i++) known = sz[(size_t)i] >= 0;
+        if (known) {
+            total = 0;
+            for (int i = 0; i < n; i++) { ooff[(size_t)i] = total; total += (uint64_t)sz[(size_t)i]; }
+            ooff[(size_t)n] = total;
+            capDev = (const int32_t *)c->lenB.p;
+        }
+    }
+    if ((r = dev_reserve(c->out, (size_t)total + 16))) return r;
     HIP_TRY(hipMemcpyAsync(c->offB.p, ooff.data(), ((size_t)n + 1) * 8, hipMemcpyHostToDevice, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
     const int32_t *sfDev = nullptr;
@@ -1895,7 +1952,7 @@ static int decompress_host(mi355lz4_ctx *c, const uint8_t *framedIn, size_t inLe
         sfDev = (const int32_t *)c->lenA.p;
     }
     DecodeCall d{(const uint8_t *)c->in.p, inLen, (const uint64_t *)c->offA.p, n, headerKind, fixedUncomp, linked,
-                 (uint8_t *)c->out.p, (const uint64_t *)c->offB.p, nullptr, (int32_t *)c->res.p};
+                 (uint8_t *)c->out.p, (const uint64_t *)c->offB.p, capDev, (int32_t *)c->res.p};
     d.dict0 = dlen ? (const uint8_t *)c->scratch.p : nullptr; d.dict0Len = dlen; d.streamFirst = sfDev; d.nStreams = nStreams;
     r = decode_device(c, d);
     if (r) return r;
@@ -1911,6 +1968,9 @@ static int decompress_host(mi355lz4_ctx *c, const uint8_t *framedIn, size_t inLe
         if (res[(size_t)i] < 0) bad++; else need += (uint64_t)res[(size_t)i];
     }
     *nBlocksOut = n;
+    // The capacity is judged after the decode, also where the size pass has already said what the call needs: a size
+    // vouches for the chain, not for the offsets, so a block of known size can still fail in the decoder, and a call with a
+    // failed block returns E_BLOCK with its blockLen[] whether or not the output would have fitted.
     if (bad) return fail(MI355LZ4_E_BLOCK, "decompress_batch: %d block(s) failed", bad);
     if (need > cap) return fail(MI355LZ4_E_CAPACITY, "decompress_batch: need %llu bytes, have %zu", (unsigned long long)need, cap);
     if (need == total) {

@@ -101,6 +101,22 @@ void Engine::resetCompressStream()
 
 Engine::~Engine() { mi355lz4_destroy(ctx_); }
 
+// host bytes -> device, the size pass, sizes back (mi355lz4_decoded_sizes_host)
+std::vector<int32_t> Engine::decodedSizes(const BlockConfig &cfg, const Array &framed, int maxUncomp)
+{
+    const int hk = metaSize(cfg);
+    const BlockChecksumScope scope(ctx_, cfg.blockChecksum);
+    std::vector<uint64_t> off(framed.size() / (size_t)(hk + 1) + 2);
+    int n = 0;
+    if (mi355lz4_index_host_ex(framed.data(), framed.size(), hk, maxUncomp, cfg.blockChecksum ? 1 : 0, off.data(), nullptr,
+                               (int)off.size() - 1, &n) != MI355LZ4_OK)
+        throw Error(std::string("streamly_lz4::Engine::decodedSizes: ") + mi355lz4_last_error());
+    std::vector<int32_t> size((size_t)n);
+    if (n && mi355lz4_decoded_sizes_host(ctx_, framed.data(), framed.size(), off.data(), n, hk, maxUncomp, size.data()) != MI355LZ4_OK)
+        throw Error(std::string("streamly_lz4::Engine::decodedSizes: ") + mi355lz4_last_error());
+    return size;
+}
+
 CompressStreams::CompressStreams(Engine &eng, int nSlots) : eng_(eng)
 {
     if (mi355lz4_cstreams_create(eng.ctx(), nSlots, &cs_) != MI355LZ4_OK)

@@ -10,6 +10,7 @@
 #define BLK_E_TRUNCATED (-0x7F000002)
 #define BLK_E_UNCOMPLEN (-0x7F000003)
 #define BLK_E_CHECKSUM  (-0x7F000004)
+#define BLK_E_SIZE_UNKNOWN (-0x7F000005)
 // LZ4_compressBound(LZ4_MAX_INPUT_SIZE): reference lz4_MAX_OUTPUT_SIZE, Internal/LZ4.hs:145-147
 #define MAX_COMP_LEN 2122219150
 
@@ -193,6 +194,11 @@ void launch_interleave(const uint8_t *local, const uint64_t *localOff, int nLoca
                        uint8_t *global, const uint64_t *globalOff, hipStream_t s);
 void launch_index(const uint8_t *framed, uint64_t framedLen, const uint64_t *blockOff, int nBlocks,
                   int headerKind, int fixedUncomp, int32_t *scratchSizes, uint64_t *outOff, hipStream_t s);
+// decoded sizes (size_walk.hpp): size[i] = what block i decodes to, read off its token chain, or BLK_E_SIZE_UNKNOWN / a
+// header code; outOff (may be null) = exclusive scan of the sizes that are known, nBlocks + 1 entries.  trailer: every
+// block's data is followed by a 4-byte checksum (it must lie inside the framed buffer; it is not verified here).
+void launch_decoded_size(const uint8_t *framed, uint64_t framedLen, const uint64_t *blockOff, int nBlocks, int headerKind,
+                         int maxUncomp, int trailer, int32_t *size, uint64_t *outOff, hipStream_t s);
 // block checksums (checksum.hpp): xxh32(seed) of base + off[i], len[i] bytes -> out[i]; the compress side's trailers
 // (slot i's data hashed, the trailer written behind it, framedLen[i] += 4; failed blocks left alone); the decode side's
 // per-block flags (fail[i] = data does not match its trailer; 0 for blocks whose header or trailer is out of bounds)

@@ -9,6 +9,7 @@
 //       k_exact_streams                  many reference-exact streams, one wave each, their state in device slots
 //   K3  k_scan_u64 + k_copy_slots        size scan + compaction into the framed stream
 //       k_header_sizes                   uncompressed-size scan from block headers
+//       k_decoded_size                   decoded sizes from the token chains alone (size_walk.hpp)
 //       k_generate                       synthetic inputs (bench/test support)
 //   K4  k_xxh32_ranges / _append / _verify  block checksums: xxh32 of many ranges, four lanes per range (checksum.hpp)
 //
@@ -16,6 +17,7 @@
 #include "kernels.h"
 
 #include <algorithm>
+#include <atomic>
 
 #include "decode_seq.hpp"
 #include "decode_par.hpp"
@@ -26,6 +28,7 @@
 #include "encode_hc.hpp"
 #include "encode_exact.hpp"
 #include "checksum.hpp"
+#include "size_walk.hpp"
 
 using namespace lz4dev;
 
@@ -682,6 +685,51 @@ void launch_index(const uint8_t *framed, uint64_t framedLen, const uint64_t *blo
         hipLaunchKernelGGL(k_header_sizes, dim3((unsigned)((nBlocks + 255) / 256)), dim3(256), 0, s, framed,
                            framedLen, blockOff, nBlocks, headerKind, fixedUncomp, scratchSizes);
     hipLaunchKernelGGL(k_scan_u64, dim3(1), dim3(1024), 0, s, scratchSizes, nBlocks, outOff);
+}
+
+// Decoded sizes without decoding (size_walk.hpp): one wavefront per block, a persistent grid.  The header is checked as
+// read_block_header checks it; the header's own uncompLen (headerKind 8) is not looked at.
+static_assert(SIZE_E_UNKNOWN == BLK_E_SIZE_UNKNOWN, "one code");
+__global__ __launch_bounds__(LZ4_WAVE) void k_decoded_size(const uint8_t *framed, uint64_t framedLen, const uint64_t *blockOff,
+                                                           int nBlocks, int headerKind, int maxUncomp, int trailer, int32_t *size)
+{
+    __shared__ SizeLds lds;
+    const int lane = lane_id();
+    if (lane < 4) ((uint32_t *)&lds.win[SW_WIN])[lane] = 0u;
+    if (lane < 2) lds.nz[SW_WIN / 32 + lane] = 0u;
+    wave_fence();
+    for (int blk = (int)blockIdx.x; blk < nBlocks; blk += (int)gridDim.x) {
+        const uint64_t off = blockOff[blk];
+        int r;
+        if (off + (uint64_t)headerKind > framedLen) r = BLK_E_TRUNCATED;
+        else {
+            const int compLen = uni(load_le32(framed + off));
+            const uint64_t end = off + (uint64_t)headerKind + (uint64_t)(uint32_t)max(compLen, 0);
+            if (compLen <= 0 || compLen > MAX_COMP_LEN) r = BLK_E_COMPLEN;
+            else if (end > framedLen || (trailer && end + 4u > framedLen)) r = BLK_E_TRUNCATED;
+            else r = decoded_size_block(framed + off + headerKind, compLen, maxUncomp, framed, framed + framedLen, lds);
+        }
+        if (lane == 0) size[blk] = r;
+    }
+}
+
+void launch_decoded_size(const uint8_t *framed, uint64_t framedLen, const uint64_t *blockOff, int nBlocks, int headerKind,
+                         int maxUncomp, int trailer, int32_t *size, uint64_t *outOff, hipStream_t s)
+{
+    if (nBlocks > 0) {
+        static std::atomic<int> cus[64];                                    // CUs per device, asked for once
+        int dev = 0;
+        (void)hipGetDevice(&dev);
+        int nc = cus[dev & 63].load(std::memory_order_relaxed);
+        if (nc <= 0) {
+            if (hipDeviceGetAttribute(&nc, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || nc <= 0) nc = 256;
+            cus[dev & 63].store(nc, std::memory_order_relaxed);
+        }
+        const unsigned grid = (unsigned)min(nBlocks, max(nc, 1) * 32);      // 8 waves per SIMD
+        hipLaunchKernelGGL(k_decoded_size, dim3(grid), dim3(LZ4_WAVE), 0, s, framed, framedLen, blockOff, nBlocks, headerKind,
+                           maxUncomp, trailer, size);
+    }
+    if (outOff) hipLaunchKernelGGL(k_scan_u64, dim3(1), dim3(1024), 0, s, (const int32_t *)size, nBlocks, outOff);
 }
 
 // ---------------------------------------------------------------------------

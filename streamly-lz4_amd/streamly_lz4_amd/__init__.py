@@ -95,6 +95,8 @@ def _load():
     sig("mi355lz4_decompress_linked_end", C.c_int, vp)
     sig("mi355lz4_decompress_linked_end_last", C.c_int, vp)
     sig("mi355lz4_index_device", C.c_int, vp, vp, C.c_uint64, vp, C.c_int, C.c_int, C.c_int, vp)
+    sig("mi355lz4_decoded_size_device", C.c_int, vp, vp, C.c_uint64, vp, C.c_int, C.c_int, C.c_int, vp, vp)
+    sig("mi355lz4_decoded_sizes_host", C.c_int, vp, _u8p, C.c_size_t, _u64p, C.c_int, C.c_int, C.c_int, _i32p)
     sig("mi355lz4_compress_batch", C.c_int, vp, C.POINTER(_u8p), _i32p, C.c_int, C.c_int, C.c_int, _u8p,
         C.c_size_t, C.POINTER(C.c_size_t), _i32p, _i32p)
     sig("mi355lz4_index_host", C.c_int, _u8p, C.c_size_t, C.c_int, C.c_int, _u64p, _i32p, C.c_int,
@@ -186,6 +188,7 @@ DECLARED_SYMBOLS = [
     "mi355lz4_set_compress_exact", "mi355lz4_get_compress_exact", "mi355lz4_compress_exact_reset",
     "mi355lz4_cstreams_create", "mi355lz4_cstreams_destroy", "mi355lz4_cstreams_count", "mi355lz4_cstreams_reset",
     "mi355lz4_compress_streams_device", "mi355lz4_compress_streams",
+    "mi355lz4_decoded_size_device", "mi355lz4_decoded_sizes_host",
     "LZ4_createStream", "LZ4_freeStream", "LZ4_createStreamDecode", "LZ4_freeStreamDecode", "LZ4_compressBound",
     "LZ4_compress_fast_continue", "LZ4_decompress_safe_continue",
 ]
@@ -598,6 +601,30 @@ class Engine:
         _check(lib.mi355lz4_index_device(self.ctx, _dptr(framed), int(framed_len), _dptr(block_off), int(n_blocks),
                                          int(header_kind), int(fixed_uncomp), _dptr(out_off)), "index_device")
 
+    def decoded_size_device(self, framed, framed_len, block_off, n_blocks, size, out_off=None, header_kind=4, max_uncomp=0):
+        """size[i] (int32, device) = what block i decodes to, read off its token chain, or BLK_E_SIZE_UNKNOWN / a header
+        code; out_off (uint64, n_blocks + 1 entries, optional) = exclusive scan of the known sizes.  Enqueues only."""
+        self._follow_torch()
+        _check(lib.mi355lz4_decoded_size_device(self.ctx, _dptr(framed), int(framed_len), _dptr(block_off), int(n_blocks),
+                                                int(header_kind), int(max_uncomp), _dptr(size),
+                                                _dptr(out_off) if out_off is not None else None), "decoded_size_device")
+
+    def decoded_sizes(self, framed, header_kind=4, max_uncomp=0):
+        """Decoded size of every block of a dense framed stream in host memory, without decoding it: np.int32[], a size or
+        a negative per-block code (BLK_E_SIZE_UNKNOWN where the token chain gives none of at most max_uncomp bytes)."""
+        import torch
+        boff, _ = index_host(framed, header_kind, max_uncomp, self._block_checksum)
+        n = len(boff)
+        if n == 0:
+            return np.zeros(0, dtype=np.int32)
+        dev = "cuda:%d" % self.device
+        src = torch.from_numpy(np.frombuffer(bytes(framed), dtype=np.uint8).copy()).to(dev)
+        off = torch.from_numpy(np.asarray(boff, dtype=np.int64)).to(dev)
+        size = torch.empty(n, dtype=torch.int32, device=dev)
+        self.decoded_size_device(src, src.numel(), off, n, size, None, header_kind, max_uncomp)
+        self.synchronize()
+        return size.cpu().numpy()
+
     def interleave_device(self, local, local_off, n_local, rank, n_ranks, global_buf, global_off):
         self._follow_torch()
         _check(lib.mi355lz4_interleave_device(self.ctx, _dptr(local), _dptr(local_off), int(n_local), int(rank),
@@ -621,8 +648,9 @@ class Engine:
         return out[: out_len.value].tobytes(), flen[:n].tolist()
 
     def decompress_batch(self, framed, header_kind=8, fixed_uncomp=0, linked=False, dict_bytes=None, max_blocks=None,
-                         raise_on_block_error=True):
-        """Returns (decoded bytes, [decoded length or negative code per block])."""
+                         raise_on_block_error=True, cap=None):
+        """Returns (decoded bytes, [decoded length or negative code per block]).  cap: bytes of output buffer to offer
+        (default: every block at its header's size, or at fixed_uncomp)."""
         src = np.frombuffer(bytes(framed), dtype=np.uint8)
         if max_blocks is None:
             max_blocks = src.size // (header_kind + 1) + 1
@@ -632,8 +660,10 @@ class Engine:
         _check(lib.mi355lz4_index_host_ex(src.ctypes.data_as(_u8p), src.size, header_kind, fixed_uncomp,
                                           int(self._block_checksum), boff.ctypes.data_as(_u64p),
                                           ulen.ctypes.data_as(_i32p), max_blocks, C.byref(nb)), "index_host")
-        cap = int(ulen[: nb.value].astype(np.int64).clip(min=0).sum()) + 16
-        out = np.empty(cap, dtype=np.uint8)
+        if cap is None:
+            cap = int(ulen[: nb.value].astype(np.int64).clip(min=0).sum()) + 16
+        cap = int(cap)
+        out = np.empty(max(cap, 1), dtype=np.uint8)
         out_len = C.c_size_t()
         blen = np.zeros(max(nb.value, 1), dtype=np.int32)
         got = C.c_int()
