@@ -37,6 +37,8 @@ module Streamly.Internal.LZ4.GPU
     , resetCompressStream
     , c_decodedSizeDevice
     , decodedSizes
+    , c_decompressPartialDevice
+    , decompressChunksPrefix
     , CompressStreams
     , newCompressStreams
     , freeCompressStreams
@@ -145,6 +147,18 @@ foreign import ccall safe "mi355lz4.h mi355lz4_decoded_size_device"
         :: Ptr C_Engine -> Ptr Word8 -> Word64 -> Ptr Word64 -> CInt -> CInt -> CInt -> Ptr Int32 -> Ptr Word64
         -> IO CInt
 
+-- Partial decode (LZ4_decompress_safe_partial, N blocks per call): the first target[i] bytes of every block.  The device
+-- form takes device pointers and only enqueues; the host form walks a framed chain in host memory and brings back the
+-- prefixes alone, packed back to back.
+foreign import ccall safe "mi355lz4.h mi355lz4_decompress_partial_device"
+    c_decompressPartialDevice
+        :: Ptr C_Engine -> Ptr Word8 -> Word64 -> Ptr Word64 -> CInt -> CInt -> CInt
+        -> Ptr Word8 -> Ptr Word64 -> Ptr Int32 -> Ptr Int32 -> Ptr Int32 -> IO CInt
+foreign import ccall safe "mi355lz4.h mi355lz4_decompress_partial"
+    c_decompressPartial
+        :: Ptr C_Engine -> Ptr Word8 -> CSize -> CInt -> CInt -> Ptr Int32 -> CInt
+        -> Ptr Word8 -> CSize -> Ptr CSize -> Ptr Int32 -> CInt -> Ptr CInt -> IO CInt
+
 -- replaces c_decompressSafeContinue (Streamly/Internal/LZ4.hs:133-140), N blocks per call
 foreign import ccall safe "mi355lz4.h mi355lz4_decompress_batch"
     c_decompressBatch
@@ -210,6 +224,21 @@ decodedSizes (Engine p) framed framedLen blockOff nBlocks headerKind maxUncomp s
     rc <- c_decodedSizeDevice p framed framedLen blockOff (fromIntegral nBlocks) (fromIntegral headerKind)
                               (fromIntegral maxUncomp) size outOff
     when (rc /= 0) $ error "mi355lz4_decoded_size_device failed"
+
+-- | @decompressChunksPrefix eng framed framedLen headerKind fixedUncomp target out cap blockLen maxBlocks@: the first
+-- @target@ bytes of every block of the framed chain @framed@ (host memory), packed back to back into @out@; @blockLen[k]@
+-- is block k's result (what @LZ4_decompress_safe_partial@ returns for it).  Returns (bytes written, blocks).  Only the
+-- prefixes come back from the device (include/mi355lz4.h, @mi355lz4_decompress_partial@).
+decompressChunksPrefix :: Engine -> Ptr Word8 -> Int -> Int -> Int -> Int -> Ptr Word8 -> Int -> Ptr Int32 -> Int -> IO (Int, Int)
+decompressChunksPrefix (Engine p) framed framedLen headerKind fixedUncomp target out cap blockLen maxBlocks =
+    alloca $ \pLen -> alloca $ \pN -> do
+        rc <- c_decompressPartial p framed (fromIntegral framedLen) (fromIntegral headerKind) (fromIntegral fixedUncomp)
+                                  nullPtr (fromIntegral target) out (fromIntegral cap) pLen blockLen
+                                  (fromIntegral maxBlocks) pN
+        when (rc /= 0) $ error "mi355lz4_decompress_partial failed"
+        n <- peek pLen
+        k <- peek pN
+        return (fromIntegral n, fromIntegral k)
 
 -- | 'True': 'compressChunksGPU' writes a linked stream (the block before is a block's
 -- dictionary, what @LZ4_compress_fast_continue@ does with the previous chunk,

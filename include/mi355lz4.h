@@ -74,6 +74,11 @@ typedef struct mi355lz4_ctx mi355lz4_ctx;
  *   fails with a negative code and one whose header is rejected alike; result[] only in [0, nBlocks) (with lookBack,
  *   result[-1] and the seam block's output are the caller's: read, never written); framed, blockOff, outOff, outCap
  *   and streamFirst are never written.
+ * Partial decode (_decompress_partial_device): no byte of `out` outside the union of [outOff[i], outOff[i] +
+ *   min(target[i], cap_i)), cap_i as above -- stricter than the reference, whose wide copies run up to 31 bytes past a
+ *   sequence -- and nothing at all for a block whose header is rejected or whose target is negative; whatever the
+ *   block's result, so prefixes can lie back to back at outOff = scan(min(target, cap)).  result[] only in
+ *   [0, nBlocks); target, framed, blockOff, outOff and outCap are never written.
  * Compress calls (_compress_batch_device: level 0, 1..9, exact; linked or not; segments automatic, forced or off;
  *   checksums on or off): nothing outside the union of [slots + i*slotStride, slots + i*slotStride +
  *   mi355lz4_slot_stride_ex(maxBlockLen, headerKind, checksum)), even when the caller's slotStride is larger (the
@@ -82,7 +87,7 @@ typedef struct mi355lz4_ctx mi355lz4_ctx;
  *   when none fits), denseOff[0..nBlocks];
  *   _index_device: outOff[0..nBlocks]; _decoded_size_device: size[0..nBlocks), outOff[0..nBlocks]; _interleave_device: global + globalOff[j*nRanks + rank] for the local blocks'
  *   lengths; _generate_device: dst[0, nBlocks * blockLen); _xxh32_device: out[i] for len[i] >= 0.  Inputs never.
- * Host-buffer calls (_compress_batch, _decompress_batch, _decompress_streams, _multi_*): nothing at or past
+ * Host-buffer calls (_compress_batch, _decompress_batch, _decompress_partial, _decompress_streams, _multi_*): nothing at or past
  *   framedOut + cap / out + cap or in front of either pointer; blockFramedLen, status and blockLen only in
  *   [0, nBlocks) / [0, maxBlocks); inputs never.
  * Many exact streams (_compress_streams_device): the slot ranges of _compress_batch_device, framedLen[0, nBlocks)
@@ -274,6 +279,32 @@ int mi355lz4_decoded_size_device(mi355lz4_ctx *ctx, const uint8_t *framed, uint6
                                  const uint64_t *blockOff, int nBlocks, int headerKind, int maxUncomp,
                                  int32_t *size, uint64_t *outOff /* optional, nBlocks+1 */);
 
+/* Partial decode: the first target[i] bytes of every block, for time proportional to what is asked for.
+ * result[i] is what LZ4_decompress_safe_partial(data_i, out + outOff[i], compLen_i, target[i], cap_i) returns
+ * (cbits/lz4.c:2179-2185: LZ4_decompress_generic in its partial mode with min(target, cap) as the output end), and
+ * out[outOff[i] .. outOff[i] + result[i]) holds the bytes it writes there.  For a well-formed block of n decoded bytes
+ * that is min(target[i], cap_i, n) and the prefix of the data.  A malformed block often gives a non-negative result
+ * too: the partial mode stops before it reaches the damage and forgives at the output end what the full mode rejects.
+ * (A match with offset 0 that the output end clips copies every byte onto itself, cbits/lz4.c:2112-2113: the bytes
+ * such a block yields there are what lay in `out` before, here as in the reference.)
+ * Block arguments, cap_i and header rejections are those of mi355lz4_decompress_batch_device with linked == 0; the
+ * reference's partial mode has no dictionary, so there is no linked form.  target is a device array of nBlocks entries:
+ * target[i] < 0 gives MI355LZ4_BLK_E_UNCOMPLEN and nothing is written, target[i] == 0 gives 0 whatever the block holds.
+ * The call returns as the full decode does (per-block failures are in result[]); it only enqueues on the engine's
+ * stream, waits for nothing and does not read target on the host.  Block checksums, when on, are verified over the
+ * whole compressed block as in every decode call (the trailer covers the compressed bytes, not the prefix).
+ * What the call may write: see the top of this header.
+ * Decoder variants: the lane-parallel decoder leaves a block after the batch that reaches its target; variant 0 always
+ * takes it (a partial call's work is the prefixes, which only the device knows); variant 4 gives the workgroup form the
+ * blocks whose target does not cut them short and hands the others to the lane-parallel form.
+ * MI355LZ4_E_ARG: null ctx, nBlocks < 0, fixedUncomp < 0, a headerKind other than 4 / 8, a null target / framed /
+ * blockOff / outOff / result with nBlocks > 0, a range begun with mi355lz4_decompress_linked_begin still open.
+ * nBlocks == 0 is MI355LZ4_OK. */
+int mi355lz4_decompress_partial_device(mi355lz4_ctx *ctx, const uint8_t *framed, uint64_t framedLen,
+                                       const uint64_t *blockOff, int nBlocks, int headerKind, int fixedUncomp,
+                                       uint8_t *out, const uint64_t *outOff, const int32_t *outCap /* may be NULL */,
+                                       const int32_t *target /* device, nBlocks entries */, int32_t *result);
+
 /* The same for blocks in host memory: framed[0..len) goes to the device, mi355lz4_decoded_size_device runs over it with
  * host blockOff[], and size[0..nBlocks) (host) comes back.  Synchronous; same argument checks, same per-block codes.
  * What streamly_lz4::Engine::decodedSizes calls. */
@@ -317,6 +348,18 @@ int mi355lz4_index_host(const uint8_t *framedIn, size_t inLen, int headerKind, i
 int mi355lz4_decompress_batch(mi355lz4_ctx *ctx, const uint8_t *framedIn, size_t inLen, int headerKind,
                               int fixedUncomp, int linked, const uint8_t *dict, int dictLen, uint8_t *out,
                               size_t cap, size_t *outLen, int32_t *blockLen, int maxBlocks, int *nBlocks);
+
+/* Partial decode of a chain in host memory: the first target[k] bytes of block k (target == NULL: targetAll bytes of
+ * every block).  The chain is walked as mi355lz4_decompress_batch walks it (with the trailers when block checksums are
+ * on); the prefixes come back packed back to back in out[0 .. *outLen), blockLen[k] holds block k's result
+ * (mi355lz4_decompress_partial_device's result[k]).  Only the prefixes cross the link on the way back -- that is what
+ * this form is for.  Synchronous, and a single group: the whole chain goes to the device, one partial decode, one copy
+ * back (block by block when some block gave fewer bytes than asked); the group pipeline of the full decode is not used.
+ * MI355LZ4_E_BLOCK when a block failed (blockLen[] says which), MI355LZ4_E_CAPACITY when the prefixes need more than
+ * cap bytes (nothing is written then).  The multi-device handle has no partial call. */
+int mi355lz4_decompress_partial(mi355lz4_ctx *ctx, const uint8_t *framedIn, size_t inLen, int headerKind,
+                                int fixedUncomp, const int32_t *target /* host, one per block, or NULL */, int targetAll,
+                                uint8_t *out, size_t cap, size_t *outLen, int32_t *blockLen, int maxBlocks, int *nBlocks);
 
 /* Host-buffer form of mi355lz4_decompress_streams_device: framedIn holds the blocks
  * of nStreams linked streams back to back, stream s = blocks

@@ -93,6 +93,11 @@ public:
     // chains on the GPU: a size, or a negative per-block code (MI355LZ4_BLK_E_SIZE_UNKNOWN where the chain gives none of
     // at most maxUncomp bytes).  Throws Error on a malformed header chain or a failed call.
     std::vector<int32_t> decodedSizes(const BlockConfig &cfg, const Array &framed, int maxUncomp);
+    // Partial decode (mi355lz4_decompress_partial): the first `target` bytes of every block of the dense framed stream
+    // `framed` (host memory), one array per block -- what LZ4_decompress_safe_partial gives for it; only the prefixes come
+    // back from the device.  fixedUncomp: the blocks' capacity when the framing carries no size.  Throws Error on a
+    // malformed header chain, a failed block or a failed call.
+    std::vector<Array> decompressPartial(const BlockConfig &cfg, const Array &framed, int target, int fixedUncomp = 0);
     // Many exact streams in one call (mi355lz4_compress_streams): streams[s] are the next arrays of the pipeline that owns
     // slot slots[s] of cs; the result holds, per stream, one framed array per input array -- what compressChunksD yields for
     // them at this point of that pipeline's stream.  Throws Error.

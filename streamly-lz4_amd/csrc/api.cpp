@@ -1238,6 +1238,12 @@ static int decode_device_impl(mi355lz4_ctx *c, const DecodeCall &d, const int32_
         HIP_TRY(hipMemsetAsync(a.linkStat, 0, 32, c->stream));
         HIP_TRY(hipMemsetAsync(a.linkStat + 1, 0xff, 4, c->stream));
     }
+    if (d.target) {                                  // partial decode: no dictionary, so nothing follows the one pass
+        a.target = d.target;
+        const FirstPass fp = first_pass(d, m, k);
+        launch_decode_partial(a, fp == FirstPass::Seq ? 1 : (fp == FirstPass::Cu ? 4 : 2), c->stream);
+        return check_launch("decode launch");
+    }
     const BigArm big = big_arm(d, m, k);
     const bool bigPre = big == BigArm::BeforeFirstPass && big_scratch(c, a, 1);
     switch (first_pass(d, m, k)) {
@@ -1303,6 +1309,21 @@ extern "C" int mi355lz4_decompress_batch_device(mi355lz4_ctx *c, const uint8_t *
                                                 const int32_t *outCap, int32_t *result)
 {
     return decode_device(c, {framed, framedLen, blockOff, nBlocks, headerKind, fixedUncomp, linked, out, outOff, outCap, result});
+}
+
+extern "C" int mi355lz4_decompress_partial_device(mi355lz4_ctx *c, const uint8_t *framed, uint64_t framedLen,
+                                                  const uint64_t *blockOff, int nBlocks, int headerKind, int fixedUncomp,
+                                                  uint8_t *out, const uint64_t *outOff, const int32_t *outCap,
+                                                  const int32_t *target, int32_t *result)
+{
+    if (!c) return fail(MI355LZ4_E_ARG, "null ctx");
+    if (nBlocks < 0 || (headerKind != 4 && headerKind != 8) || fixedUncomp < 0)
+        return fail(MI355LZ4_E_ARG, "decompress_partial_device: bad arguments");
+    if (nBlocks > 0 && (!target || !framed || !blockOff || !outOff || !result))
+        return fail(MI355LZ4_E_ARG, "decompress_partial_device: null pointer");
+    DecodeCall d{framed, framedLen, blockOff, nBlocks, headerKind, fixedUncomp, 0, out, outOff, outCap, result};
+    d.target = target;
+    return decode_device(c, d);
 }
 
 extern "C" int mi355lz4_decompress_linked_begin(mi355lz4_ctx *c, const uint8_t *framed, uint64_t framedLen,
@@ -1867,6 +1888,80 @@ extern "C" int mi355lz4_decompress_streams(mi355lz4_ctx *c, const uint8_t *frame
             return fail(MI355LZ4_E_ARG, "decompress_streams: stream table is not ascending at %d", s);
     return decompress_host(c, framedIn, inLen, headerKind, fixedUncomp, 1, nullptr, 0, streamFirst, nStreams, out, cap,
                            outLen, blockLen, maxBlocks, nBlocksOut);
+}
+
+// The first target[k] (or targetAll) bytes of every block of a chain in host memory.  One group, synchronous: the whole chain goes up,
+// one partial decode lays the prefixes out back to back at min(target, capacity), and only they come back -- in one copy when every
+// block gave all it was asked for, else block by block.
+extern "C" int mi355lz4_decompress_partial(mi355lz4_ctx *c, const uint8_t *framedIn, size_t inLen, int headerKind,
+                                           int fixedUncomp, const int32_t *target, int targetAll, uint8_t *out, size_t cap,
+                                           size_t *outLen, int32_t *blockLen, int maxBlocks, int *nBlocksOut)
+{
+    if (!c) return fail(MI355LZ4_E_ARG, "null ctx");
+    if (!outLen || !nBlocksOut || maxBlocks < 0 || fixedUncomp < 0 || (headerKind != 4 && headerKind != 8))
+        return fail(MI355LZ4_E_ARG, "decompress_partial: bad arguments");
+    if (c->plan.active) return fail(MI355LZ4_E_ARG, "a linked decode begun with mi355lz4_decompress_linked_begin is still open");
+    *outLen = 0;
+    *nBlocksOut = 0;
+    std::vector<uint64_t> boff((size_t)maxBlocks + 1);
+    std::vector<int32_t> ulen((size_t)maxBlocks + 1);
+    int n = 0;
+    int r = mi355lz4_index_host_ex(framedIn, inLen, headerKind, fixedUncomp, c->blockChecksum, boff.data(), ulen.data(),
+                                   maxBlocks, &n);
+    if (r) return r;
+    if (n == 0) return MI355LZ4_OK;
+    HIP_TRY(hipSetDevice(c->device));
+    // device layout: block k's prefix at scan(min(target, capacity)) -- what the call may write of it and no more
+    std::vector<uint64_t> ooff((size_t)n + 1);
+    std::vector<int32_t> tgt((size_t)n);
+    uint64_t total = 0;
+    for (int i = 0; i < n; i++) {
+        if (ulen[(size_t)i] < 0) return fail(MI355LZ4_E_STREAM, "decompress_partial: block %d has negative size", i);
+        const int32_t t = target ? target[i] : targetAll;
+        tgt[(size_t)i] = t;
+        ooff[(size_t)i] = total;
+        if (t > 0) total += (uint64_t)(t < ulen[(size_t)i] ? t : ulen[(size_t)i]);
+    }
+    ooff[(size_t)n] = total;
+    if ((r = dev_reserve(c->in, inLen + 16)) || (r = dev_reserve(c->offA, (size_t)n * 8)) || (r = dev_reserve(c->offB, ((size_t)n + 1) * 8)) ||
+        (r = dev_reserve(c->res, (size_t)n * 4)) || (r = dev_reserve(c->lenA, (size_t)n * 4)) || (r = dev_reserve(c->out, (size_t)total + 16)))
+        return r;
+    if ((r = h2d_staged(c, c->in.p, framedIn, inLen))) return r;
+    HIP_TRY(hipMemcpyAsync(c->offA.p, boff.data(), (size_t)n * 8, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipMemcpyAsync(c->offB.p, ooff.data(), ((size_t)n + 1) * 8, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipMemcpyAsync(c->lenA.p, tgt.data(), (size_t)n * 4, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));          // (the vectors are pageable memory)
+    r = mi355lz4_decompress_partial_device(c, (const uint8_t *)c->in.p, inLen, (const uint64_t *)c->offA.p, n, headerKind, fixedUncomp,
+                                           (uint8_t *)c->out.p, (const uint64_t *)c->offB.p, nullptr, (const int32_t *)c->lenA.p,
+                                           (int32_t *)c->res.p);
+    if (r) return r;
+    std::vector<int32_t> res((size_t)n);
+    HIP_TRY(hipMemcpyAsync(res.data(), c->res.p, (size_t)n * 4, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    int bad = 0;
+    uint64_t need = 0;
+    for (int i = 0; i < n; i++) {
+        if (blockLen) blockLen[i] = res[(size_t)i];
+        if (res[(size_t)i] < 0) bad++; else need += (uint64_t)res[(size_t)i];
+    }
+    *nBlocksOut = n;
+    if (bad) return fail(MI355LZ4_E_BLOCK, "decompress_partial: %d block(s) failed", bad);
+    if (need > cap) return fail(MI355LZ4_E_CAPACITY, "decompress_partial: need %llu bytes, have %zu", (unsigned long long)need, cap);
+    if (need && !out) return fail(MI355LZ4_E_ARG, "decompress_partial: null output");
+    if (need == total) {
+        if (total && (r = d2h_staged(c, out, c->out.p, (size_t)total))) return r;
+    } else {
+        uint64_t w = 0;
+        for (int i = 0; i < n; i++) {
+            if (res[(size_t)i] > 0)
+                HIP_TRY(hipMemcpyAsync(out + w, (const uint8_t *)c->out.p + ooff[(size_t)i], (size_t)res[(size_t)i],
+                                       hipMemcpyDeviceToHost, c->stream));
+            w += (uint64_t)res[(size_t)i];
+        }
+    }
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    *outLen = (size_t)need;
+    return MI355LZ4_OK;
 }
 
 static int decompress_host(mi355lz4_ctx *c, const uint8_t *framedIn, size_t inLen, int headerKind,

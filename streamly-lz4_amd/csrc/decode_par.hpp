@@ -157,7 +157,13 @@ enum { PS_BATCHES, PS_SEQS, PS_ROUNDS, PS_MATCH_ITERS, PS_LIT_ITERS, PS_HANDOVER
 // list[k] = compressed bytes of sequence k (0 = not known from here on), listLen entries.  The list is a HINT: every
 // position taken from it is checked against the successor the lane in front computes from the token bytes themselves, so
 // a wrong list costs time, never correctness; from the first disagreement on the block falls back to steps 2-3.
-template <bool STATS, bool DICT, bool TOL = false, bool LIST = false>
+// PARTIAL: the first `cap` bytes of the block, cap = min(target, capacity) (LZ4_decompress_safe_partial, decode_seq.hpp).
+// Nothing else changes here: the batch loop takes sequences while their output stays 64 bytes short of `cap` -- the
+// reference is then in its fast loop, which is the same in both modes -- and runs while 128 bytes are left, so a block
+// asked for its first 256 bytes leaves the loop after the batch that reaches them: no further window is staged, no
+// further batch parsed.  The hand-over goes to the sequential decoder's partial mode, which clips the last sequence and
+// returns.  Flushes only ever write bytes below `op`, and op <= cap.
+template <bool STATS, bool DICT, bool TOL = false, bool LIST = false, bool PARTIAL = false>
 __device__ int decode_block_par(const uint8_t *src, int srcLen, uint8_t *dst, int cap, const uint8_t *dict,
                                 uint32_t dictLen, const uint8_t *bufLo, const uint8_t *bufHi, ParLds &L,
                                 unsigned long long *stats, TolCtx *tol = nullptr, const uint8_t *list = nullptr,
@@ -185,7 +191,8 @@ __device__ int decode_block_par(const uint8_t *src, int srcLen, uint8_t *dst, in
             for (int i = 0; i < PS_COUNT; i++) atomicAdd(&stats[i], (unsigned long long)sc[i]);
         }
     };
-    if (cap < 128 || srcLen < 64) return decode_block_seq<TOL>(src, srcLen, dst, cap, dict, dictLen, bufLo, bufHi, tol);
+    static_assert(!PARTIAL || (!DICT && !TOL), "the partial mode has no dictionary");
+    if (cap < 128 || srcLen < 64) return decode_block_seq<TOL, PARTIAL>(src, srcLen, dst, cap, dict, dictLen, bufLo, bufHi, tol);
     // external dictionary (linked streams, cbits/lz4.c:2347-2355): a match that lies ENTIRELY in the
     // previous block's output is a far match with another base pointer; one that straddles the seam
     // (:1883-1911) is left to the sequential decoder
@@ -877,9 +884,9 @@ __device__ int decode_block_par(const uint8_t *src, int srcLen, uint8_t *dst, in
         const bool tail = (iend - ip < 64 || cap - op < 128);
         if (STATS && !tail) sc[PS_HANDOVERS]++;
         lap(PS_T_FLUSH);
-        int r = decode_seq_dispatch<TOL>(st, tail ? 0 : 1, src, srcLen, dst, cap, dict, dictLen, bufLo, bufHi, tol);
+        int r = decode_seq_dispatch<TOL, PARTIAL>(st, tail ? 0 : 1, src, srcLen, dst, cap, dict, dictLen, bufLo, bufHi, tol);
         if (r == SEQ_CONTINUE && (!st.fast || iend - st.ip < 64 || cap - st.op < 128))
-            r = decode_seq_dispatch<TOL>(st, 0, src, srcLen, dst, cap, dict, dictLen, bufLo, bufHi, tol);
+            r = decode_seq_dispatch<TOL, PARTIAL>(st, 0, src, srcLen, dst, cap, dict, dictLen, bufLo, bufHi, tol);
         lap(PS_T_SEQ);
         r = uni(r);
         if (r != SEQ_CONTINUE) { publish(); return r; }

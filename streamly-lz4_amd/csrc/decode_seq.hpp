@@ -159,7 +159,24 @@ struct SeqState {
 // (reads outside return 0 instead of faulting).
 // TOL is a template parameter (not a run-time test of tol) so that the strict instantiation keeps the register
 // footprint the lane-parallel kernel's occupancy is built around (it is the one non-inlined call of that kernel).
-template <bool TOL>
+//
+// PARTIAL: LZ4_decompress_safe_partial (cbits/lz4.c:2179-2185), i.e. LZ4_decompress_generic instantiated
+// (endOnInputSize, partial_decode, noDict); `cap` is min(targetOutputSize, dstCapacity) (:2181).  The block may end
+// anywhere: the output end clips the sequence that reaches it instead of rejecting it.  The rules, with the loop the
+// reference is in when it meets them:
+//   :1781-1783  an empty output gives 0, whatever the block holds (decode_block_seq, before either loop)
+//   :1999-2022  safe loop, or the fast loop leaving through safe_literal_copy (:1818, :1831): a literal run that comes
+//               within MFLIMIT of the output end or within 8 bytes of the input end is clipped to the input and the
+//               output that are left (the full mode demands the exact end of the block here, :2031)
+//   :2046       ... and ends the block only if the output is full or fewer than 3 input bytes follow (no offset can);
+//               otherwise its match is decoded like any other
+//   :2077       clipping a match that starts in a dictionary: not reachable (noDict), such a match is an error (:2073)
+//   :2108-2120  safe loop, or the fast loop leaving through safe_match_copy (:1858, :1863): a match that comes within
+//               MATCH_SAFEGUARD_DISTANCE of the output end is clipped to it and copied byte by byte (an overlapping
+//               copy; offset 0 copies every byte onto itself: the bytes stay what they were); a full output ends the
+//               block.  The full mode's LASTLITERALS rule (:2139) is never reached.
+// The fast loop itself (:1797-1924) is the same in both modes.  No byte at or behind dst + cap is written.
+template <bool TOL, bool PARTIAL = false>
 __device__ __forceinline__ int decode_seq_body(SeqState &st, int maxSeq, const uint8_t *src, int srcLen, uint8_t *dst, int cap,
                               const uint8_t *dict, uint32_t dictLen, const uint8_t *bufLo, const uint8_t *bufHi,
                               TolCtx *tol)
@@ -266,13 +283,21 @@ __device__ __forceinline__ int decode_seq_body(SeqState &st, int maxSeq, const u
         }
     safe_literal_copy:
         if (op + ll > (int64_t)oend - LZ4_MFLIMIT || ip + ll > (int64_t)iend - (2 + 1 + LZ4_LASTLITERALS)) { // :1991
-            if (ip + ll != (int64_t)iend || op + ll > (int64_t)oend) goto error; // :2031-2036
+            if (PARTIAL) {
+                if (ip + ll > (int64_t)iend) ll = (int64_t)(iend - ip);       // :2011-2014
+                if (op + ll > (int64_t)oend) ll = (int64_t)(oend - op);       // :2018-2022
+                if (ll < 0) ll = 0;                                           // (ip <= iend and op <= oend hold; nothing is copied if they ever did not)
+            } else {
+                if (ip + ll != (int64_t)iend || op + ll > (int64_t)oend) goto error; // :2031-2036
+            }
             wave_copy_bytes(dst + op, src + ip, (uint32_t)ll);
             ip += (int)ll; op += (int)ll;
-            break;                                                            // :2046
+            if (!PARTIAL || op == oend || ip >= iend - 2) break;              // :2046
+            goto get_offset;
         }
         wave_copy_bytes(dst + op, src + ip, (uint32_t)ll);                    // :2050
         ip += (int)ll; op += (int)ll;
+    get_offset:
         offset = rd(ip) | (rd(ip + 1) << 8); ip += 2;                         // :2055
         match = op - (int)offset;
         ml = token & 15;
@@ -288,6 +313,12 @@ __device__ __forceinline__ int decode_seq_body(SeqState &st, int maxSeq, const u
         if (match < 0) {
             if (!useDict) goto error;
             if (op + ml > (int64_t)oend - LZ4_LASTLITERALS) goto error;       // :2076-2079
+        } else if (PARTIAL && op + ml > (int64_t)oend - 12) {                 // :2108
+            const uint32_t mlen = (uint32_t)min(ml, (int64_t)(oend - op));    // :2109
+            if (offset != 0) wave_copy_match(dst, op, match, mlen, offset, dict, dictLen);   // :2112-2116 (offset 0: every byte onto itself)
+            op += (int)mlen;
+            if (op == oend) break;                                            // :2118
+            continue;
         } else if (op + ml > (int64_t)oend - 12) {                            // :2137
             if (op + ml > (int64_t)oend - LZ4_LASTLITERALS) goto error;       // :2139
         }
@@ -312,21 +343,29 @@ __device__ SEQ_RUN_ATTR int decode_seq_run(SeqState &st, int maxSeq, const uint8
 {
     return decode_seq_body<false>(st, maxSeq, src, srcLen, dst, cap, dict, dictLen, bufLo, bufHi, nullptr);
 }
+// partial mode (no dictionary: LZ4_decompress_safe_partial has none); cap = min(target, capacity)
+__device__ __attribute__((noinline)) int decode_seq_run_partial(SeqState &st, int maxSeq, const uint8_t *src, int srcLen, uint8_t *dst, int cap,
+                              const uint8_t *bufLo, const uint8_t *bufHi)
+{
+    return decode_seq_body<false, true>(st, maxSeq, src, srcLen, dst, cap, nullptr, 0, bufLo, bufHi, nullptr);
+}
 __device__ __attribute__((noinline)) int decode_seq_run_tol(SeqState &st, int maxSeq, const uint8_t *src, int srcLen, uint8_t *dst, int cap,
                               const uint8_t *bufLo, const uint8_t *bufHi, TolCtx *tol)
 {
     return decode_seq_body<true>(st, maxSeq, src, srcLen, dst, cap, nullptr, 0, bufLo, bufHi, tol);
 }
-template <bool TOL>
+template <bool TOL, bool PARTIAL = false>
 __device__ __forceinline__ int decode_seq_dispatch(SeqState &st, int maxSeq, const uint8_t *src, int srcLen, uint8_t *dst, int cap,
                               const uint8_t *dict, uint32_t dictLen, const uint8_t *bufLo, const uint8_t *bufHi, TolCtx *tol)
 {
-    if constexpr (TOL) return decode_seq_run_tol(st, maxSeq, src, srcLen, dst, cap, bufLo, bufHi, tol);
+    static_assert(!(TOL && PARTIAL), "the partial mode has no dictionary, so no tolerant form");
+    if constexpr (PARTIAL) return decode_seq_run_partial(st, maxSeq, src, srcLen, dst, cap, bufLo, bufHi);
+    else if constexpr (TOL) return decode_seq_run_tol(st, maxSeq, src, srcLen, dst, cap, bufLo, bufHi, tol);
     else return decode_seq_run(st, maxSeq, src, srcLen, dst, cap, dict, dictLen, bufLo, bufHi);
 }
 
-// Decode one whole block.  All arguments are wave-uniform.
-template <bool TOL = false>
+// Decode one whole block (PARTIAL: its first `cap` bytes, cap = min(target, capacity)).  All arguments are wave-uniform.
+template <bool TOL = false, bool PARTIAL = false>
 #ifndef SEQ_BLOCK_ATTR
 #define SEQ_BLOCK_ATTR
 #endif
@@ -335,6 +374,7 @@ __device__ SEQ_BLOCK_ATTR int decode_block_seq(const uint8_t *src, int srcLen, u
                                 const uint8_t *bufHi, TolCtx *tol = nullptr)
 {
     if (cap == 0) {                                              // :1781-1785
+        if (PARTIAL) return 0;                                   // :1783
         InWindow w0; w0.lo = bufLo; w0.hi = bufHi; w0.load(src);
         return (srcLen == 1 && w0.byte_at(src) == 0) ? 0 : -1;
     }
@@ -342,7 +382,7 @@ __device__ SEQ_BLOCK_ATTR int decode_block_seq(const uint8_t *src, int srcLen, u
     SeqState st;
     st.ip = 0; st.op = 0;
     st.fast = cap >= 64;                                         // :1791
-    return decode_seq_dispatch<TOL>(st, 0, src, srcLen, dst, cap, dict, dictLen, bufLo, bufHi, tol);
+    return decode_seq_dispatch<TOL, PARTIAL>(st, 0, src, srcLen, dst, cap, dict, dictLen, bufLo, bufHi, tol);
 }
 
 } // namespace lz4dev

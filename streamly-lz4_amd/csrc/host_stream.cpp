@@ -117,6 +117,36 @@ std::vector<int32_t> Engine::decodedSizes(const BlockConfig &cfg, const Array &f
     return size;
 }
 
+// host bytes -> device, one partial decode, the prefixes back (mi355lz4_decompress_partial).  The chain is indexed first, so the
+// buffer the prefixes come back in is sum(min(target, capacity)) bytes and not a worst case.
+std::vector<Array> Engine::decompressPartial(const BlockConfig &cfg, const Array &framed, int target, int fixedUncomp)
+{
+    const int hk = metaSize(cfg);
+    const BlockChecksumScope scope(ctx_, cfg.blockChecksum);
+    std::vector<uint64_t> off(framed.size() / (size_t)(hk + 1) + 2);
+    std::vector<int32_t> len(off.size());
+    int n = 0;
+    if (mi355lz4_index_host_ex(framed.data(), framed.size(), hk, fixedUncomp, cfg.blockChecksum ? 1 : 0, off.data(), len.data(),
+                               (int)off.size() - 1, &n) != MI355LZ4_OK)
+        throw Error(std::string("streamly_lz4::Engine::decompressPartial: ") + mi355lz4_last_error());
+    size_t room = 0;
+    for (int k = 0; k < n; k++)
+        if (target > 0 && len[(size_t)k] > 0) room += (size_t)(target < len[(size_t)k] ? target : len[(size_t)k]);
+    Array packed(room + 16);
+    size_t outLen = 0;
+    int got = 0;
+    if (mi355lz4_decompress_partial(ctx_, framed.data(), framed.size(), hk, fixedUncomp, nullptr, target, packed.data(), room,
+                                    &outLen, len.data(), n, &got) != MI355LZ4_OK)
+        throw Error(std::string("streamly_lz4::Engine::decompressPartial: ") + mi355lz4_last_error());
+    std::vector<Array> out((size_t)got);
+    size_t pos = 0;
+    for (int k = 0; k < got; k++) {
+        out[(size_t)k].assign(packed.begin() + (ptrdiff_t)pos, packed.begin() + (ptrdiff_t)(pos + (size_t)len[(size_t)k]));
+        pos += (size_t)len[(size_t)k];
+    }
+    return out;
+}
+
 CompressStreams::CompressStreams(Engine &eng, int nSlots) : eng_(eng)
 {
     if (mi355lz4_cstreams_create(eng.ctx(), nSlots, &cs_) != MI355LZ4_OK)

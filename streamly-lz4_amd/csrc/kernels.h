@@ -83,6 +83,9 @@ struct DecodeArgs {
     // block checksums (mi355lz4_set_block_checksum): every block's data is followed by a 4-byte xxh32 trailer, and
     // ckFail[blk] != 0 says k_xxh32_verify found that they do not match; null = no trailers (read_block_header)
     const int32_t *ckFail = nullptr;
+    // partial decode (mi355lz4_decompress_partial_device): target[blk] = how many bytes of block blk are wanted; the block is
+    // decoded as LZ4_decompress_safe_partial does with min(target, capacity) as its output end.  null = full decode (every other call)
+    const int32_t *target = nullptr;
 };
 
 struct EncodeArgs {
@@ -157,6 +160,9 @@ void launch_encode_seg(const EncodeSegArgs &a, hipStream_t s);
 void launch_decode_seq(const DecodeArgs &a, hipStream_t s);
 void launch_decode_par(const DecodeArgs &a, unsigned long long *stats, hipStream_t s);
 void launch_decode_cu(const DecodeArgs &a, hipStream_t s);       // one workgroup per block (decode_cu.hpp): calls that do not fill the GPU
+// partial decode (a.target set): form 1 = one wavefront per block, sequence at a time; 4 = one workgroup per block for the blocks
+// their target does not cut short, the others left to the lane-parallel form; anything else = the lane-parallel form
+void launch_decode_partial(const DecodeArgs &a, int form, hipStream_t s);
 #ifdef MI355LZ4_EXPERIMENTS
 void launch_decode_tok(const DecodeArgs &a, hipStream_t s);      // token lists (a.tokList / a.tokCnt), then the list-driven decoder
 #endif

@@ -66,6 +66,7 @@ struct DecodeCall {
     const int32_t *streamFirst = nullptr; int nStreams = 0;    // stream table (null: one stream)
     int lookBack = 0;                                          // blocks of the same stream in front of block 0
     bool splitOk = false, deferEnd = false;                    // mi355lz4_decompress_linked_begin
+    const int32_t *target = nullptr;                           // mi355lz4_decompress_partial_device: bytes wanted per block (device memory)
 };
 // What the engine is set to: mi355lz4_set_decoder, mi355lz4_debug_stats, LINKED_ASYNC else mi355lz4_set_linked_async
 struct EngineMode { int decoder = 0; bool stats = false; int asyncCap = 0; };
@@ -98,6 +99,11 @@ inline FirstPass first_pass(const DecodeCall &d, const EngineMode &m, const Deco
 {
     if (m.decoder == 1) return FirstPass::Seq;
     if (m.decoder == 3) return FirstPass::Tok;  // experiment builds only (the lane-parallel form when its scratch cannot be had)
+    // A partial call's work is sum(min(target, capacity)), not the blocks' sizes, and the targets are device memory the call does not
+    // read: 200 blocks of 64 KiB asked for 100 bytes each are 20 KB of work, a fraction of a segment per workgroup.  Variant 0 takes the
+    // lane-parallel form, whose cost follows the prefix; variant 4 (the tests) the workgroup form, which hands every block its target
+    // cuts short to the lane-parallel one (kernels.hip, k_decode_cu_partial).  There is no token-list form of it.
+    if (d.target && m.decoder != 4) return FirstPass::Par;
     if (!m.stats && (m.decoder == 4 || (m.decoder == 0 && cu_auto(k, d.nBlocks, d.framedLen)))) return FirstPass::Cu;
     return FirstPass::Par;
 }

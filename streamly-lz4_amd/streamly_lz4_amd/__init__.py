@@ -97,6 +97,10 @@ def _load():
     sig("mi355lz4_index_device", C.c_int, vp, vp, C.c_uint64, vp, C.c_int, C.c_int, C.c_int, vp)
     sig("mi355lz4_decoded_size_device", C.c_int, vp, vp, C.c_uint64, vp, C.c_int, C.c_int, C.c_int, vp, vp)
     sig("mi355lz4_decoded_sizes_host", C.c_int, vp, _u8p, C.c_size_t, _u64p, C.c_int, C.c_int, C.c_int, _i32p)
+    # partial decode
+    sig("mi355lz4_decompress_partial_device", C.c_int, vp, vp, C.c_uint64, vp, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp, vp)
+    sig("mi355lz4_decompress_partial", C.c_int, vp, _u8p, C.c_size_t, C.c_int, C.c_int, _i32p, C.c_int, _u8p, C.c_size_t,
+        C.POINTER(C.c_size_t), _i32p, C.c_int, C.POINTER(C.c_int))
     sig("mi355lz4_compress_batch", C.c_int, vp, C.POINTER(_u8p), _i32p, C.c_int, C.c_int, C.c_int, _u8p,
         C.c_size_t, C.POINTER(C.c_size_t), _i32p, _i32p)
     sig("mi355lz4_index_host", C.c_int, _u8p, C.c_size_t, C.c_int, C.c_int, _u64p, _i32p, C.c_int,
@@ -189,6 +193,7 @@ DECLARED_SYMBOLS = [
     "mi355lz4_cstreams_create", "mi355lz4_cstreams_destroy", "mi355lz4_cstreams_count", "mi355lz4_cstreams_reset",
     "mi355lz4_compress_streams_device", "mi355lz4_compress_streams",
     "mi355lz4_decoded_size_device", "mi355lz4_decoded_sizes_host",
+    "mi355lz4_decompress_partial_device", "mi355lz4_decompress_partial",
     "LZ4_createStream", "LZ4_freeStream", "LZ4_createStreamDecode", "LZ4_freeStreamDecode", "LZ4_compressBound",
     "LZ4_compress_fast_continue", "LZ4_decompress_safe_continue",
 ]
@@ -560,6 +565,17 @@ class Engine:
             int(fixed_uncomp), int(bool(linked)), _dptr(out), _dptr(out_off), _dptr(out_cap), _dptr(result)),
             "decompress_batch_device")
 
+    def decompress_partial_device(self, framed, framed_len, block_off, n_blocks, out, out_off, target, result, header_kind=8,
+                                  fixed_uncomp=0, out_cap=None):
+        """The first target[i] bytes of every block (int32 device tensor): result[i] and the bytes are those of
+        LZ4_decompress_safe_partial; nothing outside [out_off[i], out_off[i] + min(target[i], cap_i)) is written.
+        Enqueues only (include/mi355lz4.h, mi355lz4_decompress_partial_device)."""
+        self._follow_torch()
+        _check(lib.mi355lz4_decompress_partial_device(
+            self.ctx, _dptr(framed), int(framed_len), _dptr(block_off), int(n_blocks), int(header_kind),
+            int(fixed_uncomp), _dptr(out), _dptr(out_off), _dptr(out_cap), _dptr(target), _dptr(result)),
+            "decompress_partial_device")
+
     def decompress_streams_device(self, framed, framed_len, block_off, n_blocks, stream_first, n_streams, out,
                                   out_off, result, header_kind=8, fixed_uncomp=0, out_cap=None):
         self._follow_torch()
@@ -674,6 +690,40 @@ class Engine:
                                            C.byref(out_len), blen.ctypes.data_as(_i32p), max(nb.value, 1), C.byref(got))
         if rc != 0 and (raise_on_block_error or rc != -5):
             _check(rc, "decompress_batch")
+        return out[: out_len.value].tobytes(), blen[: got.value].tolist()
+
+    def decompress_partial(self, framed, target, header_kind=8, fixed_uncomp=0, max_blocks=None, raise_on_block_error=True,
+                           cap=None):
+        """The first `target` bytes of every block of a framed chain in host memory (an int for all blocks, or one per
+        block).  Returns (the prefixes packed back to back, [result per block]); mi355lz4_decompress_partial.  cap: bytes of
+        output buffer to offer (default: what the targets can ask for)."""
+        src = np.frombuffer(bytes(framed), dtype=np.uint8)
+        if max_blocks is None:
+            max_blocks = src.size // (header_kind + 1) + 1
+        per_block = not isinstance(target, (int, np.integer))
+        tarr = np.ascontiguousarray(target, dtype=np.int32) if per_block else None
+        if cap is None:
+            boff, ulen = index_host(framed, header_kind, fixed_uncomp, self._block_checksum)
+            u = np.asarray(ulen, dtype=np.int64).clip(min=0)
+            t = tarr[: len(u)].astype(np.int64) if per_block else np.full(len(u), int(target), dtype=np.int64)
+            if per_block and tarr.size < len(u):
+                raise ValueError("decompress_partial: %d targets for %d blocks" % (tarr.size, len(u)))
+            cap = int(np.minimum(u, t.clip(min=0)).sum()) + 16
+        elif per_block:
+            boff, _ = index_host(framed, header_kind, fixed_uncomp, self._block_checksum)
+            if tarr.size < len(boff):
+                raise ValueError("decompress_partial: %d targets for %d blocks" % (tarr.size, len(boff)))
+        cap = int(cap)
+        out = np.empty(max(cap, 1), dtype=np.uint8)
+        out_len = C.c_size_t()
+        blen = np.zeros(max(max_blocks, 1), dtype=np.int32)
+        got = C.c_int()
+        rc = lib.mi355lz4_decompress_partial(self.ctx, src.ctypes.data_as(_u8p), src.size, int(header_kind), int(fixed_uncomp),
+                                             tarr.ctypes.data_as(_i32p) if per_block else None, 0 if per_block else int(target),
+                                             out.ctypes.data_as(_u8p), cap, C.byref(out_len), blen.ctypes.data_as(_i32p),
+                                             int(max_blocks), C.byref(got))
+        if rc != 0 and (raise_on_block_error or rc != -5):
+            _check(rc, "decompress_partial")
         return out[: out_len.value].tobytes(), blen[: got.value].tolist()
 
     def compress_streams_device(self, cs, src, n_blocks, max_block_len, stream_first, stream_slot, slots, slot_stride_,
