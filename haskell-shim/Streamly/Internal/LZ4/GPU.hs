@@ -45,6 +45,13 @@ module Streamly.Internal.LZ4.GPU
     , resetCompressStreams
     , c_compressStreamsDevice
     , compressChunksMany
+    , DecompressStreams
+    , newDecompressStreams
+    , freeDecompressStreams
+    , resetDecompressStreams
+    , c_dstreamsSetDict
+    , c_decompressDStreamsDevice
+    , decompressChunksMany
     , MultiEngine
     , newMultiEngine
     , freeMultiEngine
@@ -176,6 +183,34 @@ foreign import ccall safe "mi355lz4.h mi355lz4_decompress_streams"
         :: Ptr C_Engine -> Ptr Word8 -> CSize -> CInt -> CInt -> Ptr Int32 -> CInt
         -> Ptr Word8 -> CSize -> Ptr CSize -> Ptr Int32 -> CInt -> Ptr CInt -> IO CInt
 
+-- Many linked decode streams continued across calls (include/mi355lz4.h, "many linked decode streams, continued across
+-- calls"): a set of device-resident @LZ4_streamDecode_t@s, one slot per pipeline -- the last block's last 64 KiB and their
+-- count.  Stream s of a call = blocks [streamFirst[s], streamFirst[s+1]), continuing slot streamSlot[s]: the next blocks of
+-- all pipelines in one FFI call, as they arrive, instead of one engine call per stream with a host-side dictionary.
+data C_DStreams
+newtype DecompressStreams = DecompressStreams (Ptr C_DStreams)
+
+foreign import ccall safe "mi355lz4.h mi355lz4_dstreams_create"
+    c_dstreamsCreate :: Ptr C_Engine -> CInt -> Ptr (Ptr C_DStreams) -> IO CInt
+foreign import ccall safe "mi355lz4.h mi355lz4_dstreams_destroy"
+    c_dstreamsDestroy :: Ptr C_DStreams -> IO ()
+foreign import ccall unsafe "mi355lz4.h mi355lz4_dstreams_count"
+    c_dstreamsCount :: Ptr C_DStreams -> IO CInt
+foreign import ccall safe "mi355lz4.h mi355lz4_dstreams_reset"
+    c_dstreamsReset :: Ptr C_Engine -> Ptr C_DStreams -> Ptr Int32 -> CInt -> IO CInt
+-- LZ4_setStreamDecode: the dictionary is DEVICE memory; enqueued
+foreign import ccall safe "mi355lz4.h mi355lz4_dstreams_set_dict"
+    c_dstreamsSetDict :: Ptr C_Engine -> Ptr C_DStreams -> CInt -> Ptr Word8 -> CInt -> IO CInt
+-- device pointers in, device pointers out; only enqueues (no host wait: per-block codes are in result[])
+foreign import ccall safe "mi355lz4.h mi355lz4_decompress_dstreams_device"
+    c_decompressDStreamsDevice
+        :: Ptr C_Engine -> Ptr C_DStreams -> Ptr Word8 -> Word64 -> Ptr Word64 -> CInt -> CInt -> CInt
+        -> Ptr Int32 -> Ptr Int32 -> CInt -> Ptr Word8 -> Ptr Word64 -> Ptr Int32 -> Ptr Int32 -> IO CInt
+foreign import ccall safe "mi355lz4.h mi355lz4_decompress_dstreams"
+    c_decompressDStreams
+        :: Ptr C_Engine -> Ptr C_DStreams -> Ptr Word8 -> CSize -> CInt -> CInt -> Ptr Int32 -> Ptr Int32 -> CInt
+        -> Ptr Word8 -> CSize -> Ptr CSize -> Ptr Int32 -> CInt -> Ptr CInt -> IO CInt
+
 -- Several GPUs behind one handle (one process, host buffers: a host caller is bound by PCIe, one link per GPU).  The two
 -- batch calls take the arguments of c_compressBatch / c_decompressBatch (independent blocks) and give the same bytes; the
 -- batch is cut into one contiguous block range per device and the results lie in order in the caller's buffer
@@ -304,6 +339,27 @@ resetCompressStreams (Engine p) (CompressStreams cs) (Just slots) =
         rc <- c_cstreamsReset p cs ps (fromIntegral (length slots))
         when (rc /= 0) $ error "mi355lz4_cstreams_reset: a slot is out of range"
 
+-- | A set of @n@ device-resident decode streams (about 64 KiB each), every one reset.
+newDecompressStreams :: Engine -> Int -> IO DecompressStreams
+newDecompressStreams (Engine p) n = alloca $ \pp -> do
+    rc <- c_dstreamsCreate p (fromIntegral n) pp
+    when (rc /= 0) $ error "mi355lz4_dstreams_create failed"
+    DecompressStreams <$> peek pp
+
+freeDecompressStreams :: DecompressStreams -> IO ()
+freeDecompressStreams (DecompressStreams p) = c_dstreamsDestroy p
+
+-- | Forget the dictionaries of the listed slots ('Nothing': all of them): the next block of such a stream starts one.
+resetDecompressStreams :: Engine -> DecompressStreams -> Maybe [Int] -> IO ()
+resetDecompressStreams (Engine p) (DecompressStreams ds) Nothing = do
+    rc <- c_dstreamsReset p ds nullPtr 0
+    when (rc /= 0) $ error "mi355lz4_dstreams_reset failed"
+resetDecompressStreams (Engine p) (DecompressStreams ds) (Just slots) =
+    allocaArray (length slots) $ \ps -> do
+        pokeArray ps (map fromIntegral slots)
+        rc <- c_dstreamsReset p ds ps (fromIntegral (length slots))
+        when (rc /= 0) $ error "mi355lz4_dstreams_reset: a slot is out of range"
+
 batchBlocks :: Int
 batchBlocks = 4096
 
@@ -381,6 +437,39 @@ compressChunksMany (Engine eng) (CompressStreams cs) cfg speed pipes = do
             split [] _ = []
             split (c : rest) xs = let (h, t) = splitAt c xs in h : split rest t
         return (split counts outs)
+
+-- | The next resized blocks of many @decompressChunksRaw@ pipelines in one GPU call, the counterpart of
+-- 'compressChunksMany': @(slot, blocks)@ per pipeline, every pipeline continuing its slot of the set -- what the
+-- reference's @decompressChunksRawD@ threads through as the previous output array lives in the slot, on the device.
+-- Each pipeline's result is one decoded array per block.
+decompressChunksMany
+    :: Engine -> DecompressStreams -> BlockConfig -> [(Int, [Array.Array Word8])] -> IO [[Array.Array Word8]]
+decompressChunksMany (Engine eng) (DecompressStreams ds) cfg pipes = do
+    let blocks = concatMap snd pipes
+        counts = map (length . snd) pipes
+        n = length blocks
+        ns = length pipes
+        meta = metaSizeOf cfg
+    framed <- concatArrays blocks                         -- blocks back to back, pipeline after pipeline
+    cap <- sum <$> forM blocks (\a -> Array.asPtrUnsafe (Array.unsafeCast a) $ \p ->
+               if meta == 8 then fromIntegral <$> (peek (castPtr p `plusPtr` 4) :: IO Int32)
+                            else return (fixedUncompOf cfg))
+    (MArray.Array cont _ b _) <- MArray.newArray (max cap 1)
+    allocaArray (max n 1) $ \pBlen -> allocaArray (ns + 1) $ \pFirst -> allocaArray (max ns 1) $ \pSlot ->
+      alloca $ \pOutLen -> alloca $ \pN ->
+        Array.asPtrUnsafe (Array.unsafeCast framed) $ \pIn -> do
+            pokeArray pFirst (map fromIntegral (scanl (+) 0 counts))
+            pokeArray pSlot (map (fromIntegral . fst) pipes)
+            rc <- c_decompressDStreams eng ds pIn (fromIntegral (Array.byteLength framed)) (fromIntegral meta)
+                      (fromIntegral (fixedUncompOf cfg)) pFirst pSlot (fromIntegral ns)
+                      b (fromIntegral cap) pOutLen pBlen (fromIntegral n) pN
+            when (rc /= 0) $ error "decompressChunksMany: mi355lz4_decompress_dstreams failed"
+            lens <- map fromIntegral <$> peekArray n pBlen
+            let offs = scanl (+) 0 lens
+                outs = [ Array.Array cont (b `plusPtr` o) (b `plusPtr` (o + l)) | (o, l) <- zip offs lens ]
+                split [] _ = []
+                split (c : rest) xs = let (h, t) = splitAt c xs in h : split rest t
+            return (split counts outs)
 
 -- | One freshly allocated array holding the given arrays back to back (the reference splices
 -- pairwise with @Array.splice@, Streamly/Internal/LZ4.hs:502; a batch is concatenated in one pass).

@@ -94,6 +94,11 @@ typedef struct mi355lz4_ctx mi355lz4_ctx;
  *   (a stream stopped by a bad length leaves its remaining slots untouched and sets their framedLen to 0) and the slots
  *   of `cs` that streamSlot[] names for a stream with blocks; never a slot of `cs` the call does not name, never src,
  *   srcOff or srcLen.  _compress_streams is a host-buffer call as above.
+ * Many decode streams (_decompress_dstreams_device): no byte of `out` outside the union of [outOff[i], outOff[i] + cap_i),
+ *   cap_i as for the decode calls, whatever the blocks' results; result[] only in [0, nBlocks); of `ds` only the slots that
+ *   streamSlot[] names for a stream with blocks -- never a slot the call does not name, never framed, blockOff, outOff or
+ *   outCap.  _dstreams_reset / _dstreams_set_dict write the slots they name and nothing else (never the dictionary handed
+ *   in).  _decompress_dstreams is a host-buffer call as above.
  * Scratch that a call needs is the engine's own. */
 
 /* ---- engine lifecycle ------------------------------------------------ */
@@ -132,7 +137,7 @@ int mi355lz4_synchronize(mi355lz4_ctx *ctx);
  * the first pass found nothing to do (about a dozen empty launches per 4096 blocks).  The call can then be captured in
  * a graph and no longer serialises a caller's pipeline; it costs more than the wait on big batches of independent
  * blocks (measured in DESIGN.md), which is why it is opt-in.  0 restores the default.  The streams call
- * (mi355lz4_decompress_streams_device) always waits.
+ * (mi355lz4_decompress_streams_device) always waits; mi355lz4_decompress_dstreams_device never does.
  * Before capturing such a call in a graph, make ONE warm-up call with the largest batch the graph will see: the
  * scratch is sized for ALL blocks of the call whether or not any is dependent (lists: one byte per output byte, up
  * to 16384 blocks' worth; source pointers: four bytes per output byte of a 4096-block segment, about 1 GiB) and is
@@ -456,7 +461,7 @@ int mi355lz4_interleave_device(mi355lz4_ctx *ctx, const uint8_t *local, const ui
  *   needs slotStride >= LZ4_compressBound(maxBlockLen) + headerKind + 4 (mi355lz4_slot_stride_ex) or returns
  *   MI355LZ4_E_CAPACITY;
  *   every decode call (_decompress_batch_device, _decompress_streams_device, _decompress_linked_begin / _end / _end_last,
- *   _decompress_batch, _decompress_streams) expects the trailer: each block's data is hashed on the device before the block
+ *   _decompress_batch, _decompress_streams, _decompress_dstreams_device, _decompress_dstreams) expects the trailer: each block's data is hashed on the device before the block
  *   is decoded; a trailer that lies past the framed buffer gives MI355LZ4_BLK_E_TRUNCATED, a mismatch
  *   MI355LZ4_BLK_E_CHECKSUM (the call returns MI355LZ4_E_BLOCK).  Such a block is a header-rejected block: in a linked
  *   stream the block after it sees what it sees after any rejected block.  The host-buffer calls walk the chain with the
@@ -543,6 +548,69 @@ int mi355lz4_compress_streams(mi355lz4_ctx *ctx, mi355lz4_cstreams *cs, const ui
                               const int32_t *srcLen, int nBlocks, const int32_t *streamFirst,
                               const int32_t *streamSlot, int nStreams, int accel, int headerKind, uint8_t *framedOut,
                               size_t cap, size_t *outLen, int32_t *blockFramedLen, int32_t *status);
+
+/* ---- many linked decode streams, continued across calls ---------------------------------------------------------------
+ * The decode-side counterpart of mi355lz4_cstreams, and the device-resident form of the reference's one LZ4_streamDecode_t
+ * per stream (Internal/LZ4.hs:539-567 -> cbits/lz4.c:2322-2359): a host that runs many pipelines keeps one slot per
+ * pipeline and decodes the next blocks of all of them in ONE call, as they arrive -- every stream written by
+ * compressChunksD or by mi355lz4_compress_streams_device is such a stream.
+ *
+ * A mi355lz4_dstreams is an opaque set of nSlots device-resident decode streams, owned by the caller and bound to the
+ * device of the engine it was created with (any engine on that device may use it; one call at a time).  One slot holds
+ * what LZ4_streamDecode_t amounts to for separately allocated blocks: the last min(r, 65536) bytes of the stream's last
+ * block that decoded to r > 0 bytes, and that count -- 65600 bytes, about 64 KiB a slot (2560 slots: about 160 MiB).  No
+ * other state, all of it on the device; nothing of a slot lives on the host.
+ * _create leaves every slot reset (no dictionary); _reset does that for slots[0..n) (slots == NULL: all of them), enqueued
+ * on the engine's stream; _destroy waits for the device.
+ * _set_dict is LZ4_setStreamDecode: slot `slot`'s state becomes the last 64 KiB of dictDevice[0, len) (device memory; the
+ * slot keeps its own copy); len == 0 equals a reset.  Enqueued; nothing is read after the call has run on the device. */
+typedef struct mi355lz4_dstreams mi355lz4_dstreams;
+int mi355lz4_dstreams_create(mi355lz4_ctx *ctx, int nSlots, mi355lz4_dstreams **out);
+void mi355lz4_dstreams_destroy(mi355lz4_dstreams *ds);
+int mi355lz4_dstreams_count(const mi355lz4_dstreams *ds);
+int mi355lz4_dstreams_reset(mi355lz4_ctx *ctx, mi355lz4_dstreams *ds, const int32_t *slots, int n);
+int mi355lz4_dstreams_set_dict(mi355lz4_ctx *ctx, mi355lz4_dstreams *ds, int slot, const uint8_t *dictDevice, int len);
+/* Decode nBlocks blocks that belong to nStreams linked streams.  The block arguments, cap_i, the header rejections and the
+ * per-block codes are those of mi355lz4_decompress_streams_device.  Stream s of the call is the blocks
+ * [streamFirst[s], streamFirst[s+1]) and continues slot streamSlot[s]; streamFirst (nStreams + 1 entries, streamFirst[0] == 0,
+ * streamFirst[nStreams] == nBlocks, ascending) and streamSlot are small HOST arrays with the rules of
+ * mi355lz4_compress_streams_device, checked before anything is enqueued and used up before the call returns.
+ * Semantics (cbits/lz4.c:2331-2333, 2347-2355): a stream's first block in the call has the slot's bytes as its dictionary;
+ * every later block has the output, in `out`, of the last block before it in the stream that decoded to more than 0 bytes,
+ * and the slot when there is none.  A block with a result <= 0 or a rejected header leaves that state alone.  After the
+ * stream's last block the slot takes the tail of the last block with r > 0 if the call had one, else it stays as it was;
+ * an empty stream leaves its slot untouched.  The slot owns its copy: `out` and `framed` may be overwritten or freed once
+ * the call has run.  (The reference takes its prefix path when outputs happen to lie back to back; that mode is not
+ * restated, here or elsewhere in this engine.)  However a stream is cut into calls, result[] and the bytes are those of ONE
+ * mi355lz4_decompress_streams_device call on the whole stream.
+ * Enqueue only: no host wait, no read of device memory on the host, no standalone first pass -- every block is decoded
+ * once, with its dictionary.  The call returns MI355LZ4_OK once it is enqueued (beyond four calls in flight it waits for
+ * the oldest one's stream table); per-block failures are in result[], as with the partial call.  This is the first linked
+ * decode form that can sit in a caller's pipeline without a synchronisation.
+ * Block checksums, when on, are verified first as in every decode call; a mismatching block is a header-rejected block
+ * (MI355LZ4_BLK_E_CHECKSUM) and the stream goes on as after any rejected block.
+ * MI355LZ4_E_ARG: a table that is not ascending or does not cover the blocks, a slot out of range, the same slot twice in
+ * one call, `ds` created on another device, null pointers with nBlocks > 0, a range begun with
+ * mi355lz4_decompress_linked_begin still open.  nBlocks == 0 is MI355LZ4_OK.  What the call may write: see the top.
+ * One wavefront walks one stream: throughput comes from the number of streams in the call (the chip runs 2560 at a
+ * time), and a stream with many blocks in one call is one serial chain -- a single long stream belongs in
+ * mi355lz4_decompress_batch_device(linked != 0).  Rates: unmeasured until scripts/dstreams_rate.py has written
+ * profiles/dstreams_rate.json. */
+int mi355lz4_decompress_dstreams_device(mi355lz4_ctx *ctx, mi355lz4_dstreams *ds, const uint8_t *framed,
+                                        uint64_t framedLen, const uint64_t *blockOff, int nBlocks, int headerKind,
+                                        int fixedUncomp, const int32_t *streamFirst, const int32_t *streamSlot,
+                                        int nStreams, uint8_t *out, const uint64_t *outOff, const int32_t *outCap,
+                                        int32_t *result);
+/* Host-buffer form: as mi355lz4_decompress_batch (a dense framed chain in, the decoded blocks back to back out, blockLen per
+ * block, synchronous, the same group pipeline with the slots in place of `dict`; a group seam inside a stream continues
+ * through its slot).  Stream s is blocks [streamFirst[s], streamFirst[s+1]) of the chain and the table must cover it.  The
+ * chain is walked on the host: a length that does not fit it (compLen <= 0, a block cut short, a negative uncompLen) is
+ * MI355LZ4_E_ARG and nothing is enqueued.  Every block is written at its header's size (fixedUncomp for headerKind 4)
+ * before its result is known: cap below their sum is MI355LZ4_E_CAPACITY, nothing enqueued. */
+int mi355lz4_decompress_dstreams(mi355lz4_ctx *ctx, mi355lz4_dstreams *ds, const uint8_t *framedIn, size_t inLen,
+                                 int headerKind, int fixedUncomp, const int32_t *streamFirst, const int32_t *streamSlot,
+                                 int nStreams, uint8_t *out, size_t cap, size_t *outLen, int32_t *blockLen, int maxBlocks,
+                                 int *nBlocks);
 
 /* mi355lz4_slot_stride with room for the trailer when blockChecksum != 0. */
 size_t mi355lz4_slot_stride_ex(int blockLen, int headerKind, int blockChecksum);

@@ -24,6 +24,7 @@
 
 struct mi355lz4_ctx;
 struct mi355lz4_cstreams;
+struct mi355lz4_dstreams;
 
 namespace streamly_lz4 {
 
@@ -103,6 +104,12 @@ public:
     // them at this point of that pipeline's stream.  Throws Error.
     std::vector<std::vector<Array>> compressStreams(const BlockConfig &cfg, int speed, const std::vector<std::vector<Array>> &streams,
                                                     class CompressStreams &cs, const std::vector<int32_t> &slots);
+    // Many linked decode streams continued across calls (mi355lz4_decompress_dstreams): streams[s] are the next resized
+    // blocks (header + data each) of the pipeline that owns slot slots[s] of ds; the result holds, per stream, one decoded
+    // array per block -- what decompressChunksRawD yields for them at this point of that pipeline's stream; the previous
+    // output it threads through lives in the slot, on the device.  Throws Error (a failed block included).
+    std::vector<std::vector<Array>> decompressStreams(const BlockConfig &cfg, const std::vector<std::vector<Array>> &streams,
+                                                      class DecompressStreams &ds, const std::vector<int32_t> &slots);
 private:
     mi355lz4_ctx *ctx_ = nullptr;
     size_t batch_;
@@ -124,6 +131,26 @@ public:
 private:
     Engine &eng_;
     mi355lz4_cstreams *cs_ = nullptr;
+};
+
+// A set of nSlots device-resident linked decode streams (mi355lz4_dstreams: about 64 KiB a slot -- the last block's last
+// 64 KiB and their count), one per pipeline a host runs at once; Engine::decompressStreams decodes the next blocks of many
+// of them in one call.
+class DecompressStreams {
+public:
+    DecompressStreams(Engine &eng, int nSlots);        // every slot reset; throws Error
+    ~DecompressStreams();
+    DecompressStreams(const DecompressStreams &) = delete;
+    DecompressStreams &operator=(const DecompressStreams &) = delete;
+    mi355lz4_dstreams *handle() const { return ds_; }
+    int count() const;
+    void reset();                                       // no dictionary, all slots
+    void reset(const std::vector<int32_t> &slots);      // ... the listed ones
+    // LZ4_setStreamDecode: the slot's state becomes the last 64 KiB of dictDevice[0, len) (DEVICE memory); enqueued
+    void setDict(int slot, const uint8_t *dictDevice, int len);
+private:
+    Engine &eng_;
+    mi355lz4_dstreams *ds_ = nullptr;
 };
 
 // ---- Streamly.LZ4 / Streamly.Internal.LZ4 -------------------------------------

@@ -20,6 +20,7 @@
 #include <condition_variable>
 #include <mutex>
 #include <new>
+#include <string>
 #include <thread>
 #include <vector>
 
@@ -806,12 +807,25 @@ extern "C" int mi355lz4_compress_batch_device(mi355lz4_ctx *c, const uint8_t *sr
 // The small per-call table {first block, end block, slot} per stream goes through a ring of pinned buffers: an entry is
 // reused once the launch that read it is done (four calls may be in flight before a call waits for the oldest).
 // ---------------------------------------------------------------------------
+struct StreamTableRing {                    // (shared with mi355lz4_dstreams, the decode side's set)
+    struct Ring { DevBuf pin, dev; hipEvent_t ev = nullptr; bool busy = false; } ring[4];
+    int next = 0;
+    void release()
+    {
+        for (auto &r : ring) {
+            if (r.ev) hipEventDestroy(r.ev);
+            r.ev = nullptr; r.busy = false;
+            pin_release(r.pin);
+            dev_release(r.dev);
+        }
+    }
+};
+
 struct mi355lz4_cstreams {
     int device = 0;
     int nSlots = 0;
     uint8_t *state = nullptr;               // nSlots * CSTREAM_SLOT_BYTES
-    struct Ring { DevBuf pin, dev; hipEvent_t ev = nullptr; bool busy = false; } ring[4];
-    int next = 0;
+    StreamTableRing table;
 };
 
 extern "C" int mi355lz4_cstreams_create(mi355lz4_ctx *c, int nSlots, mi355lz4_cstreams **out)
@@ -841,11 +855,7 @@ extern "C" void mi355lz4_cstreams_destroy(mi355lz4_cstreams *cs)
     if (!cs) return;
     hipSetDevice(cs->device);
     hipDeviceSynchronize();                 // calls that still use the slots
-    for (auto &r : cs->ring) {
-        if (r.ev) hipEventDestroy(r.ev);
-        pin_release(r.pin);
-        dev_release(r.dev);
-    }
+    cs->table.release();
     if (cs->state) hipFree(cs->state);
     delete cs;
 }
@@ -888,6 +898,23 @@ extern "C" int mi355lz4_debug_cstream_state(mi355lz4_cstreams *cs, int slot, uin
 }
 
 // the stream table of a call, checked: ascending over [0, nBlocks], every slot in range and named once
+static int stream_table_check(int nSlots, int nBlocks, const int32_t *streamFirst, const int32_t *streamSlot, int nStreams,
+                              const char *who)
+{
+    if (nBlocks < 0 || nStreams < 0 || !streamFirst || (nStreams > 0 && !streamSlot)) return fail(MI355LZ4_E_ARG, "%s: bad stream table", who);
+    if (streamFirst[0] != 0 || streamFirst[nStreams] != nBlocks)
+        return fail(MI355LZ4_E_ARG, "%s: the streams do not cover blocks 0..%d", who, nBlocks);
+    std::vector<char> seen((size_t)nSlots, 0);
+    for (int s = 0; s < nStreams; s++) {
+        if (streamFirst[s + 1] < streamFirst[s]) return fail(MI355LZ4_E_ARG, "%s: stream table is not ascending at %d", who, s);
+        const int k = streamSlot[s];
+        if (k < 0 || k >= nSlots) return fail(MI355LZ4_E_ARG, "%s: stream %d names slot %d of %d", who, s, k, nSlots);
+        if (seen[(size_t)k]) return fail(MI355LZ4_E_ARG, "%s: slot %d is named twice", who, k);
+        seen[(size_t)k] = 1;
+    }
+    return MI355LZ4_OK;
+}
+
 static int streams_check(const mi355lz4_ctx *c, const mi355lz4_cstreams *cs, int nBlocks, const int32_t *streamFirst,
                          const int32_t *streamSlot, int nStreams, const char *who)
 {
@@ -895,25 +922,17 @@ static int streams_check(const mi355lz4_ctx *c, const mi355lz4_cstreams *cs, int
     if (cs->device != c->device) return fail(MI355LZ4_E_ARG, "%s: the set lives on device %d, the engine on %d", who, cs->device, c->device);
     if (c->compLevel != 0)
         return fail(MI355LZ4_E_ARG, "%s: compression level %d; exact streams are level 0's encoder", who, c->compLevel);
-    if (nBlocks < 0 || nStreams < 0 || !streamFirst || (nStreams > 0 && !streamSlot)) return fail(MI355LZ4_E_ARG, "%s: bad stream table", who);
-    if (streamFirst[0] != 0 || streamFirst[nStreams] != nBlocks)
-        return fail(MI355LZ4_E_ARG, "%s: the streams do not cover blocks 0..%d", who, nBlocks);
-    std::vector<char> seen((size_t)cs->nSlots, 0);
-    for (int s = 0; s < nStreams; s++) {
-        if (streamFirst[s + 1] < streamFirst[s]) return fail(MI355LZ4_E_ARG, "%s: stream table is not ascending at %d", who, s);
-        const int k = streamSlot[s];
-        if (k < 0 || k >= cs->nSlots) return fail(MI355LZ4_E_ARG, "%s: stream %d names slot %d of %d", who, s, k, cs->nSlots);
-        if (seen[(size_t)k]) return fail(MI355LZ4_E_ARG, "%s: slot %d is named twice", who, k);
-        seen[(size_t)k] = 1;
-    }
-    return MI355LZ4_OK;
+    return stream_table_check(cs->nSlots, nBlocks, streamFirst, streamSlot, nStreams, who);
 }
 
-// Enqueue the streams' parts that fall into blocks [b0, b1) of the table (a.* describes exactly those blocks): a stream cut
-// by b0 or b1 simply continues its slot in the next launch.  Longer parts go first: the launch ends with its longest chain.
-static int streams_enqueue(mi355lz4_ctx *c, mi355lz4_cstreams *cs, const EncodeArgs &a, int b0, int b1,
-                           const int32_t *streamFirst, const int32_t *streamSlot, int nStreams)
+// The upload: {first block, end block, slot} per stream with blocks in [b0, b1), relative to b0, longer parts first, through
+// the next entry of the set's ring.
+// *nWork = 0: nothing to launch.  The caller launches the kernel that reads *workDev, then calls stream_table_launched.
+static int stream_table_upload(mi355lz4_ctx *c, StreamTableRing &t, int b0, int b1, const int32_t *streamFirst,
+                               const int32_t *streamSlot, int nStreams, const int32_t **workDev, int *nWorkOut,
+                               StreamTableRing::Ring **used)
 {
+    *nWorkOut = 0;
     std::vector<int32_t> work;
     {
         std::vector<std::pair<int, int>> order;         // (-blocks, stream)
@@ -932,8 +951,8 @@ static int streams_enqueue(mi355lz4_ctx *c, mi355lz4_cstreams *cs, const EncodeA
     }
     const int nWork = (int)(work.size() / 3);
     if (nWork == 0) return MI355LZ4_OK;
-    mi355lz4_cstreams::Ring &r = cs->ring[cs->next];
-    cs->next = (cs->next + 1) & 3;
+    StreamTableRing::Ring &r = t.ring[t.next];
+    t.next = (t.next + 1) & 3;
     if (r.busy) HIP_TRY(hipEventSynchronize(r.ev));      // the launch that last read this entry (four calls back)
     r.busy = false;
     if (!r.ev) HIP_TRY(hipEventCreateWithFlags(&r.ev, hipEventDisableTiming));
@@ -941,14 +960,33 @@ static int streams_enqueue(mi355lz4_ctx *c, mi355lz4_cstreams *cs, const EncodeA
     if ((rc = pin_reserve(r.pin, work.size() * 4)) || (rc = dev_reserve(r.dev, work.size() * 4))) return rc;
     memcpy(r.pin.p, work.data(), work.size() * 4);
     HIP_TRY(hipMemcpyAsync(r.dev.p, r.pin.p, work.size() * 4, hipMemcpyHostToDevice, c->stream));
+    *workDev = (const int32_t *)r.dev.p;
+    *nWorkOut = nWork;
+    *used = &r;
+    return MI355LZ4_OK;
+}
+static int stream_table_launched(mi355lz4_ctx *c, StreamTableRing::Ring *r)
+{
+    HIP_TRY(hipEventRecord(r->ev, c->stream));
+    r->busy = true;
+    return MI355LZ4_OK;
+}
+
+// Enqueue the streams' parts that fall into blocks [b0, b1) of the table (a.* describes exactly those blocks): a stream cut
+// by b0 or b1 simply continues its slot in the next launch.  Longer parts go first: the launch ends with its longest chain.
+static int streams_enqueue(mi355lz4_ctx *c, mi355lz4_cstreams *cs, const EncodeArgs &a, int b0, int b1,
+                           const int32_t *streamFirst, const int32_t *streamSlot, int nStreams)
+{
     ExactStreamsArgs x;
+    int nWork = 0, rc;
+    StreamTableRing::Ring *used = nullptr;
+    if ((rc = stream_table_upload(c, cs->table, b0, b1, streamFirst, streamSlot, nStreams, &x.work, &nWork, &used))) return rc;
+    if (nWork == 0) return MI355LZ4_OK;
     x.e = a;
-    x.work = (const int32_t *)r.dev.p;
     x.state = cs->state;
     launch_exact_streams(x, nWork, c->stream);
     if ((rc = check_launch("exact streams launch"))) return rc;
-    HIP_TRY(hipEventRecord(r.ev, c->stream));
-    r.busy = true;
+    if ((rc = stream_table_launched(c, used))) return rc;
     if (c->blockChecksum) {                               // the trailers, behind the encoder (encode_device, finish)
         launch_xxh32_append(a.slots, a.slotStride, a.headerKind, a.framedLen, a.nBlocks, c->stream);
         return check_launch("checksum launch");
@@ -1388,6 +1426,162 @@ extern "C" int mi355lz4_decompress_streams_device(mi355lz4_ctx *c, const uint8_t
     DecodeCall d{framed, framedLen, blockOff, nBlocks, headerKind, fixedUncomp, nStreams > 0, out, outOff, outCap, result};
     if (nStreams > 0) { d.streamFirst = streamFirst; d.nStreams = nStreams; }   // (no streams: every block is decoded on its own)
     return decode_device(c, d);
+}
+
+// ---------------------------------------------------------------------------
+// Many linked decode streams continued across calls (mi355lz4_dstreams, mi355lz4_decompress_dstreams_device):
+// the decode side's counterpart of mi355lz4_cstreams.  A slot is LZ4_streamDecode_t for separately allocated blocks, on the
+// device -- the last block's last 64 KiB and their count (kernels.h, DSTREAM_*) -- and k_decode_dstreams decodes every block
+// once, with its dictionary, so there is no first pass whose verdict the host would wait for: the call only enqueues.  The
+// per-call table goes through the same ring as the compress side's (stream_table_upload).
+// ---------------------------------------------------------------------------
+struct mi355lz4_dstreams {
+    int device = 0;
+    int nSlots = 0;
+    uint8_t *state = nullptr;               // nSlots * DSTREAM_SLOT_BYTES
+    StreamTableRing table;
+};
+
+extern "C" int mi355lz4_dstreams_create(mi355lz4_ctx *c, int nSlots, mi355lz4_dstreams **out)
+{
+    if (out) *out = nullptr;
+    if (!c || !out || nSlots < 1) return fail(MI355LZ4_E_ARG, "dstreams_create: bad arguments");
+    HIP_TRY(hipSetDevice(c->device));
+    mi355lz4_dstreams *ds = new (std::nothrow) mi355lz4_dstreams();
+    if (!ds) return fail(MI355LZ4_E_ARG, "out of host memory");
+    ds->device = c->device;
+    ds->nSlots = nSlots;
+    const size_t bytes = (size_t)nSlots * DSTREAM_SLOT_BYTES;
+    hipError_t e = hipMalloc((void **)&ds->state, bytes);
+    if (e == hipSuccess) e = hipMemsetAsync(ds->state, 0, bytes, c->stream);     // every slot reset: no dictionary
+    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);                    // (whatever stream the engine is on later)
+    if (e != hipSuccess) {
+        if (ds->state) hipFree(ds->state);
+        delete ds;
+        return fail(MI355LZ4_E_HIP, "dstreams_create: %d slots (%zu bytes): %s", nSlots, bytes, hipGetErrorString(e));
+    }
+    *out = ds;
+    return MI355LZ4_OK;
+}
+
+extern "C" void mi355lz4_dstreams_destroy(mi355lz4_dstreams *ds)
+{
+    if (!ds) return;
+    hipSetDevice(ds->device);
+    hipDeviceSynchronize();                 // calls that still use the slots
+    ds->table.release();
+    if (ds->state) hipFree(ds->state);
+    delete ds;
+}
+
+extern "C" int mi355lz4_dstreams_count(const mi355lz4_dstreams *ds)
+{
+    if (!ds) return fail(MI355LZ4_E_ARG, "dstreams_count: null set");
+    return ds->nSlots;
+}
+
+extern "C" int mi355lz4_dstreams_reset(mi355lz4_ctx *c, mi355lz4_dstreams *ds, const int32_t *slots, int n)
+{
+    if (!c || !ds) return fail(MI355LZ4_E_ARG, "dstreams_reset: null argument");
+    if (ds->device != c->device) return fail(MI355LZ4_E_ARG, "dstreams_reset: the set lives on device %d, the engine on %d", ds->device, c->device);
+    HIP_TRY(hipSetDevice(c->device));
+    if (!slots) {
+        launch_dstreams_set(ds->state, 0, ds->nSlots, nullptr, 0, c->stream);
+        return check_launch("dstreams reset launch");
+    }
+    if (n < 0) return fail(MI355LZ4_E_ARG, "dstreams_reset: bad count");
+    for (int i = 0; i < n; i++)
+        if (slots[i] < 0 || slots[i] >= ds->nSlots) return fail(MI355LZ4_E_ARG, "dstreams_reset: slot %d out of range", slots[i]);
+    for (int i = 0; i < n; i++)             // the count: a dictionary of 0 bytes needs no bytes cleared
+        HIP_TRY(hipMemsetAsync(ds->state + (size_t)slots[i] * DSTREAM_SLOT_BYTES + DSTREAM_COUNT_OFF, 0, 4, c->stream));
+    return MI355LZ4_OK;
+}
+
+// LZ4_setStreamDecode (cbits/lz4.c:2292-2300) for one slot: only the last 64 KiB of a dictionary can be referenced
+extern "C" int mi355lz4_dstreams_set_dict(mi355lz4_ctx *c, mi355lz4_dstreams *ds, int slot, const uint8_t *dictDevice, int len)
+{
+    if (!c || !ds) return fail(MI355LZ4_E_ARG, "dstreams_set_dict: null argument");
+    if (ds->device != c->device) return fail(MI355LZ4_E_ARG, "dstreams_set_dict: the set lives on device %d, the engine on %d", ds->device, c->device);
+    if (slot < 0 || slot >= ds->nSlots) return fail(MI355LZ4_E_ARG, "dstreams_set_dict: slot %d of %d", slot, ds->nSlots);
+    if (len < 0 || (len > 0 && !dictDevice)) return fail(MI355LZ4_E_ARG, "dstreams_set_dict: bad dictionary");
+    HIP_TRY(hipSetDevice(c->device));
+    const int keep = len > DSTREAM_DICT_BYTES ? DSTREAM_DICT_BYTES : len;
+    launch_dstreams_set(ds->state, slot, 1, keep ? dictDevice + (len - keep) : nullptr, (uint32_t)keep, c->stream);
+    return check_launch("dstreams set_dict launch");
+}
+
+// Diagnostic hook (not part of the public header): slot `slot` as it is after everything queued on the device has run --
+// *count = its dictionary bytes, bytes (may be null, 65536 bytes of host memory) = the slot's whole dictionary area.  A
+// non-null setBytes (65536 bytes) then overwrites that area, the count stays (the tests put guard patterns into unused slots).
+extern "C" int mi355lz4_debug_dstream_state(mi355lz4_dstreams *ds, int slot, uint32_t *count, uint8_t *bytes, const uint8_t *setBytes)
+{
+    if (!ds || slot < 0 || slot >= ds->nSlots) return fail(MI355LZ4_E_ARG, "debug_dstream_state: bad arguments");
+    HIP_TRY(hipSetDevice(ds->device));
+    HIP_TRY(hipDeviceSynchronize());
+    uint8_t *st = ds->state + (size_t)slot * DSTREAM_SLOT_BYTES;
+    if (count) HIP_TRY(hipMemcpy(count, st + DSTREAM_COUNT_OFF, 4, hipMemcpyDeviceToHost));
+    if (bytes) HIP_TRY(hipMemcpy(bytes, st, DSTREAM_DICT_BYTES, hipMemcpyDeviceToHost));
+    if (setBytes) HIP_TRY(hipMemcpy(st, setBytes, DSTREAM_DICT_BYTES, hipMemcpyHostToDevice));
+    return MI355LZ4_OK;
+}
+
+static int dstreams_check(const mi355lz4_ctx *c, const mi355lz4_dstreams *ds, int nBlocks, const int32_t *streamFirst,
+                          const int32_t *streamSlot, int nStreams, const char *who)
+{
+    if (!c || !ds) return fail(MI355LZ4_E_ARG, "%s: null argument", who);
+    if (ds->device != c->device) return fail(MI355LZ4_E_ARG, "%s: the set lives on device %d, the engine on %d", who, ds->device, c->device);
+    if (c->plan.active) return fail(MI355LZ4_E_ARG, "%s: a linked decode begun with mi355lz4_decompress_linked_begin is still open", who);
+    return stream_table_check(ds->nSlots, nBlocks, streamFirst, streamSlot, nStreams, who);
+}
+
+// Enqueue the streams' parts that fall into blocks [b0, b1) of the table (d.* describes exactly those blocks, as a.* does in
+// streams_enqueue): the checksum flags first, as in decode_device, then one wave per stream with blocks.
+static int dstreams_enqueue(mi355lz4_ctx *c, mi355lz4_dstreams *ds, const DecodeCall &d, int b0, int b1,
+                            const int32_t *streamFirst, const int32_t *streamSlot, int nStreams)
+{
+    if (d.nBlocks <= 0) return MI355LZ4_OK;
+    DStreamsArgs x{};
+    x.d.framed = d.framed; x.d.framedLen = d.framedLen; x.d.blockOff = d.blockOff; x.d.nBlocks = d.nBlocks; x.d.segEnd = d.nBlocks;
+    x.d.headerKind = d.headerKind; x.d.fixedUncomp = d.fixedUncomp; x.d.linked = 1;
+    x.d.out = d.out; x.d.outOff = d.outOff; x.d.outCap = d.outCap; x.d.result = d.result; x.d.onlyBlk = -1;
+    int rc;
+    if (c->blockChecksum) {
+        if (c->ckEvent && c->ckStream != c->stream) HIP_TRY(hipStreamWaitEvent(c->stream, c->ckEvent, 0));
+        if ((rc = dev_reserve(c->ckBuf, (size_t)d.nBlocks * 4))) return rc;
+        launch_xxh32_verify(x.d, (int32_t *)c->ckBuf.p, c->stream);
+        if ((rc = check_launch("checksum launch"))) return rc;
+        x.d.ckFail = (const int32_t *)c->ckBuf.p;
+    }
+    int nWork = 0;
+    StreamTableRing::Ring *used = nullptr;
+    if ((rc = stream_table_upload(c, ds->table, b0, b1, streamFirst, streamSlot, nStreams, &x.work, &nWork, &used))) return rc;
+    if (nWork > 0) {
+        x.state = ds->state;
+        launch_decode_dstreams(x, nWork, c->stream);
+        if ((rc = check_launch("decode streams launch"))) return rc;
+        if ((rc = stream_table_launched(c, used))) return rc;
+    }
+    if (c->blockChecksum) {
+        if (!c->ckEvent && hipEventCreateWithFlags(&c->ckEvent, hipEventDisableTiming) != hipSuccess) c->ckEvent = nullptr;
+        if (c->ckEvent && hipEventRecord(c->ckEvent, c->stream) == hipSuccess) c->ckStream = c->stream;
+    }
+    return MI355LZ4_OK;
+}
+
+extern "C" int mi355lz4_decompress_dstreams_device(mi355lz4_ctx *c, mi355lz4_dstreams *ds, const uint8_t *framed,
+                                                   uint64_t framedLen, const uint64_t *blockOff, int nBlocks, int headerKind,
+                                                   int fixedUncomp, const int32_t *streamFirst, const int32_t *streamSlot,
+                                                   int nStreams, uint8_t *out, const uint64_t *outOff, const int32_t *outCap,
+                                                   int32_t *result)
+{
+    int r = dstreams_check(c, ds, nBlocks, streamFirst, streamSlot, nStreams, "decompress_dstreams_device");
+    if (r) return r;
+    if ((headerKind != 4 && headerKind != 8) || fixedUncomp < 0) return fail(MI355LZ4_E_ARG, "decompress_dstreams_device: bad arguments");
+    if (nBlocks == 0) return MI355LZ4_OK;
+    if (!framed || !blockOff || !outOff || !result) return fail(MI355LZ4_E_ARG, "decompress_dstreams_device: null pointer");
+    HIP_TRY(hipSetDevice(c->device));
+    const DecodeCall d{framed, framedLen, blockOff, nBlocks, headerKind, fixedUncomp, 1, out, outOff, outCap, result};
+    return dstreams_enqueue(c, ds, d, 0, nBlocks, streamFirst, streamSlot, nStreams);
 }
 
 extern "C" int mi355lz4_xxh32_device(mi355lz4_ctx *c, const uint8_t *base, const uint64_t *off, const int32_t *len, int n,
@@ -1856,6 +2050,12 @@ extern "C" int mi355lz4_index_host_ex(const uint8_t *framedIn, size_t inLen, int
     return MI355LZ4_OK;
 }
 
+// mi355lz4_decompress_dstreams: the group pipeline with the set's slots in place of dict0
+struct HostDStreams {
+    mi355lz4_dstreams *ds;
+    const int32_t *first, *slot;
+    int n;
+};
 static int decompress_host(mi355lz4_ctx *c, const uint8_t *framedIn, size_t inLen, int headerKind,
                            int fixedUncomp, int linked, const uint8_t *dict, int dictLen,
                            const int32_t *streamFirst, int nStreams,
@@ -1865,7 +2065,7 @@ static int decompress_host_pipelined(mi355lz4_ctx *c, const uint8_t *framedIn, s
                                      int fixedUncomp, int linked, const uint8_t *dict, int dictLen,
                                      const std::vector<uint64_t> &boff, const std::vector<int32_t> &ulen,
                                      const std::vector<uint64_t> &ooff, int n, uint8_t *out, size_t *outLen,
-                                     int32_t *blockLen, int *nBlocksOut);
+                                     int32_t *blockLen, int *nBlocksOut, const HostDStreams *hs = nullptr);
 
 extern "C" int mi355lz4_decompress_batch(mi355lz4_ctx *c, const uint8_t *framedIn, size_t inLen, int headerKind,
                                          int fixedUncomp, int linked, const uint8_t *dict, int dictLen,
@@ -1888,6 +2088,43 @@ extern "C" int mi355lz4_decompress_streams(mi355lz4_ctx *c, const uint8_t *frame
             return fail(MI355LZ4_E_ARG, "decompress_streams: stream table is not ascending at %d", s);
     return decompress_host(c, framedIn, inLen, headerKind, fixedUncomp, 1, nullptr, 0, streamFirst, nStreams, out, cap,
                            outLen, blockLen, maxBlocks, nBlocksOut);
+}
+
+// Host-buffer form of mi355lz4_decompress_dstreams_device: the group pipeline of mi355lz4_decompress_batch, every group's
+// streams continuing their slots.  The chain is walked on the host: a bad length is MI355LZ4_E_ARG before anything is queued.
+extern "C" int mi355lz4_decompress_dstreams(mi355lz4_ctx *c, mi355lz4_dstreams *ds, const uint8_t *framedIn, size_t inLen,
+                                            int headerKind, int fixedUncomp, const int32_t *streamFirst,
+                                            const int32_t *streamSlot, int nStreams, uint8_t *out, size_t cap, size_t *outLen,
+                                            int32_t *blockLen, int maxBlocks, int *nBlocksOut)
+{
+    if (outLen) *outLen = 0;
+    if (nBlocksOut) *nBlocksOut = 0;
+    if (!c || !ds) return fail(MI355LZ4_E_ARG, "decompress_dstreams: null argument");
+    if (!outLen || !nBlocksOut || maxBlocks < 0 || fixedUncomp < 0 || (headerKind != 4 && headerKind != 8))
+        return fail(MI355LZ4_E_ARG, "decompress_dstreams: bad arguments");
+    std::vector<uint64_t> boff((size_t)maxBlocks + 1);
+    std::vector<int32_t> ulen((size_t)maxBlocks + 1);
+    int n = 0;
+    int r = mi355lz4_index_host_ex(framedIn, inLen, headerKind, fixedUncomp, c->blockChecksum, boff.data(), ulen.data(), maxBlocks, &n);
+    if (r == MI355LZ4_E_STREAM) return fail(MI355LZ4_E_ARG, "decompress_dstreams: %s", std::string(g_err).c_str());
+    if (r) return r;
+    std::vector<uint64_t> ooff((size_t)n + 1);
+    uint64_t total = 0;
+    for (int i = 0; i < n; i++) {
+        if (ulen[(size_t)i] < 0) return fail(MI355LZ4_E_ARG, "decompress_dstreams: block %d has negative size", i);
+        ooff[(size_t)i] = total;
+        total += (uint64_t)ulen[(size_t)i];
+    }
+    ooff[(size_t)n] = total;
+    if ((r = dstreams_check(c, ds, n, streamFirst, streamSlot, nStreams, "decompress_dstreams"))) return r;
+    if (n == 0) return MI355LZ4_OK;
+    // every block is written at its capacity offset (the header's size, or fixedUncomp) before the results are known
+    if (cap < total) return fail(MI355LZ4_E_CAPACITY, "decompress_dstreams: need %llu bytes, have %zu", (unsigned long long)total, cap);
+    if (total && !out) return fail(MI355LZ4_E_ARG, "decompress_dstreams: null output");
+    HIP_TRY(hipSetDevice(c->device));
+    const HostDStreams hs{ds, streamFirst, streamSlot, nStreams};
+    return decompress_host_pipelined(c, framedIn, inLen, headerKind, fixedUncomp, 0, nullptr, 0, boff, ulen, ooff, n, out, outLen,
+                                     blockLen, nBlocksOut, &hs);
 }
 
 // The first target[k] (or targetAll) bytes of every block of a chain in host memory.  One group, synchronous: the whole chain goes up,
@@ -2091,7 +2328,7 @@ static int decompress_host_pipelined(mi355lz4_ctx *c, const uint8_t *framedIn, s
                                      int fixedUncomp, int linked, const uint8_t *dict, int dictLen,
                                      const std::vector<uint64_t> &boff, const std::vector<int32_t> &ulen,
                                      const std::vector<uint64_t> &ooff, int n, uint8_t *out, size_t *outLen,
-                                     int32_t *blockLen, int *nBlocksOut)
+                                     int32_t *blockLen, int *nBlocksOut, const HostDStreams *hs)
 {
     const uint64_t total = ooff[(size_t)n];
     std::vector<int> gFirst;
@@ -2173,7 +2410,8 @@ static int decompress_host_pipelined(mi355lz4_ctx *c, const uint8_t *framedIn, s
             DecodeCall d{(const uint8_t *)c->in.p, inLen, (const uint64_t *)c->offA.p + b0, b1 - b0, headerKind, fixedUncomp, linked,
                          (uint8_t *)c->out.p, (const uint64_t *)c->offB.p + b0, nullptr, (int32_t *)c->res.p + b0};
             d.dict0 = dlen ? (const uint8_t *)c->scratch.p : nullptr; d.dict0Len = dlen; d.lookBack = b0;
-            r = decode_device(c, d);
+            // (many streams: each continues through its slot, so a group seam inside a stream needs no look-back)
+            r = hs ? dstreams_enqueue(c, hs->ds, d, b0, b1, hs->first, hs->slot, hs->n) : decode_device(c, d);
             if (r) return r;
             HIP_TRY(hipMemcpyAsync(resPin + b0, (const int32_t *)c->res.p + b0, (size_t)(b1 - b0) * 4, hipMemcpyDeviceToHost, c->stream));
             HIP_TRY(hipEventRecord(evK[(size_t)g], c->stream));

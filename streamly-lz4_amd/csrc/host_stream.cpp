@@ -205,6 +205,72 @@ std::vector<std::vector<Array>> Engine::compressStreams(const BlockConfig &cfg, 
     return out;
 }
 
+DecompressStreams::DecompressStreams(Engine &eng, int nSlots) : eng_(eng)
+{
+    if (mi355lz4_dstreams_create(eng.ctx(), nSlots, &ds_) != MI355LZ4_OK)
+        throw Error(std::string("streamly_lz4::DecompressStreams: ") + mi355lz4_last_error());
+}
+DecompressStreams::~DecompressStreams() { mi355lz4_dstreams_destroy(ds_); }
+int DecompressStreams::count() const { return mi355lz4_dstreams_count(ds_); }
+void DecompressStreams::reset()
+{
+    if (mi355lz4_dstreams_reset(eng_.ctx(), ds_, nullptr, 0) != MI355LZ4_OK)
+        throw Error(std::string("streamly_lz4::DecompressStreams::reset: ") + mi355lz4_last_error());
+}
+void DecompressStreams::reset(const std::vector<int32_t> &slots)
+{
+    if (slots.empty()) return;
+    if (mi355lz4_dstreams_reset(eng_.ctx(), ds_, slots.data(), (int)slots.size()) != MI355LZ4_OK)
+        throw Error(std::string("streamly_lz4::DecompressStreams::reset: ") + mi355lz4_last_error());
+}
+void DecompressStreams::setDict(int slot, const uint8_t *dictDevice, int len)
+{
+    if (mi355lz4_dstreams_set_dict(eng_.ctx(), ds_, slot, dictDevice, len) != MI355LZ4_OK)
+        throw Error(std::string("streamly_lz4::DecompressStreams::setDict: ") + mi355lz4_last_error());
+}
+
+std::vector<std::vector<Array>> Engine::decompressStreams(const BlockConfig &cfg, const std::vector<std::vector<Array>> &streams,
+                                                          DecompressStreams &ds, const std::vector<int32_t> &slots)
+{
+    if (slots.size() != streams.size()) throw Error("decompressStreams: one slot per stream");
+    const int meta = metaSize(cfg);
+    const BlockChecksumScope scope(ctx_, cfg.blockChecksum);
+    Array framed;
+    std::vector<int32_t> first{0};
+    size_t cap = 16;
+    int n = 0;
+    for (const auto &st : streams) {
+        for (const Array &a : st) {
+            if (a.size() < (size_t)meta) throw Error("decompressStreams: an array shorter than a block header");
+            const int64_t u = (meta == 8) ? (int64_t)(int32_t)((uint32_t)a[4] | ((uint32_t)a[5] << 8) | ((uint32_t)a[6] << 16) |
+                                                               ((uint32_t)a[7] << 24))
+                                          : (int64_t)fixedUncompSize(cfg);
+            if (u > 0) cap += (size_t)u;
+            framed.insert(framed.end(), a.begin(), a.end());
+            n++;
+        }
+        first.push_back((int32_t)n);
+    }
+    Array out(cap);
+    std::vector<int32_t> blen((size_t)n + 1);
+    std::vector<int32_t> slot(slots);
+    slot.push_back(0);
+    size_t outLen = 0;
+    int got = 0;
+    if (mi355lz4_decompress_dstreams(ctx_, ds.handle(), framed.data(), framed.size(), meta, fixedUncompSize(cfg), first.data(),
+                                     slot.data(), (int)streams.size(), out.data(), cap, &outLen, blen.data(), n, &got) != MI355LZ4_OK)
+        throw Error(std::string("decompressStreams: ") + mi355lz4_last_error());
+    std::vector<std::vector<Array>> res(streams.size());
+    size_t pos = 0;
+    int k = 0;
+    for (size_t s = 0; s < streams.size(); s++)
+        for (size_t i = 0; i < streams[s].size(); i++, k++) {
+            res[s].emplace_back(out.begin() + (long)pos, out.begin() + (long)(pos + (size_t)blen[(size_t)k]));
+            pos += (size_t)blen[(size_t)k];
+        }
+    return res;
+}
+
 // ---------------------------------------------------------------------------
 // compressChunksD (:353-394) + compressChunk (:226-281)
 // ---------------------------------------------------------------------------

@@ -145,6 +145,19 @@ struct ExactStreamsArgs {
     uint8_t *state;              // the set's slots, CSTREAM_SLOT_BYTES each
 };
 
+// many linked decode streams continued across calls (mi355lz4_decompress_dstreams_device; kernels.hip, k_decode_dstreams).
+// One slot of a mi355lz4_dstreams is the device form of LZ4_streamDecode_t for separately allocated blocks: the last
+// min(r, 65536) bytes of the stream's last block that decoded to r > 0 bytes, at the slot's start, and that count.
+#define DSTREAM_DICT_BYTES 65536
+#define DSTREAM_COUNT_OFF  ((size_t)DSTREAM_DICT_BYTES)           // uint32 count (the rest of the 64 bytes is unused)
+#define DSTREAM_SLOT_BYTES (DSTREAM_COUNT_OFF + 64)               // 65600: about 64 KiB a slot
+
+struct DStreamsArgs {
+    DecodeArgs d;                // blocks, headers, outputs, result, ckFail; nothing of the linked second pass is used
+    const int32_t *work;         // per wave of the launch {first block, end block, slot of the set}
+    uint8_t *state;              // the set's slots, DSTREAM_SLOT_BYTES each
+};
+
 // small batches: a block's segments are compressed by several waves (kernels.hip, K2 small batches)
 struct EncodeSegArgs {
     EncodeArgs e;
@@ -194,6 +207,10 @@ void launch_exact_verify(const ExactArgs &a, int first, int count, hipStream_t s
 void launch_exact_finish(const ExactArgs &a, hipStream_t s);
 // many reference-exact streams: one wave per entry of a.work walks its blocks from its slot's state and stores the state back
 void launch_exact_streams(const ExactStreamsArgs &a, int nWork, hipStream_t s);
+// many linked decode streams: one wave per entry of a.work walks its blocks from its slot's dictionary and stores the tail back;
+// launch_dstreams_set: slots [first, first + count) take the keep <= 65536 bytes at src as their dictionary (0: reset)
+void launch_decode_dstreams(const DStreamsArgs &a, int nWork, hipStream_t s);
+void launch_dstreams_set(uint8_t *state, int first, int count, const uint8_t *src, uint32_t keep, hipStream_t s);
 void launch_compact(const uint8_t *slots, size_t slotStride, const int32_t *framedLen, int nBlocks,
                     uint8_t *dense, size_t denseCap, uint64_t *denseOff, hipStream_t s);
 void launch_interleave(const uint8_t *local, const uint64_t *localOff, int nLocal, int rank, int nRanks,

@@ -3,6 +3,7 @@
 //   K1  k_decode_par / k_decode_seq      block decode (decode_par.hpp, decode_seq.hpp)
 //       k_decode_tolerant, k_ptr_*       linked streams, second pass (linked_ptr.hpp)
 //       k_decode_fixup_regions / _linked ... its in-order fallbacks (linked_replay.hpp)
+//       k_decode_dstreams                many linked streams continued across calls, one wave each, their state in device slots
 //   K2  k_encode<TabT, DICT>             block encode, independent or linked (encode_wave.hpp)
 //       k_encode_hc                      high-compression levels: hash chains + lazy parse (encode_hc.hpp)
 //       k_exact_chain / _verify / _finish  reference-exact linked stream: speculate, verify, redo (encode_exact.hpp)
@@ -1232,6 +1233,65 @@ __global__ PAR_OCC void k_decode_fixup_linked(DecodeArgs a)
         if (r > 0) { dict = dst; dictLen = (uint32_t)r; }          // :2331-2333, :2353-2355
         wave_fence();       // (the next block reads this one through the pipeline that wrote it: no write-back, see k_runin_decode)
     }
+}
+
+// Many linked decode streams continued across calls (mi355lz4_decompress_dstreams_device).  Wave w continues the
+// stream in slot work[3w + 2] with the blocks [work[3w], work[3w + 1]) of the call.  A slot is what LZ4_streamDecode_t amounts
+// to for separately allocated blocks: the last min(r, 65536) bytes of the stream's last block that decoded to r > 0 bytes,
+// and that count.  Every block is decoded once, with the dictionary in force (:2347-2355) -- there is no standalone pass
+// whose verdict a host would have to read.  A block with a result <= 0 or a rejected header leaves the dictionary alone
+// (:2331-2333); after the last block the slot takes the tail of the last block with r > 0, if the call had one.
+__global__ PAR_OCC void k_decode_dstreams(DStreamsArgs x)
+{
+    __shared__ ParLds lds;
+    const int32_t *w = x.work + 3 * (size_t)blockIdx.x;
+    const int b0 = uni(w[0]), b1 = uni(w[1]);
+    uint8_t *slot = x.state + (size_t)uni(w[2]) * DSTREAM_SLOT_BYTES;
+    uint32_t *count = (uint32_t *)(slot + DSTREAM_COUNT_OFF);
+    const uint8_t *dict = slot;
+    uint32_t dictLen = min((uint32_t)uni((int)as_global(count)[0]), (uint32_t)DSTREAM_DICT_BYTES);
+    const uint8_t *last = nullptr;                                  // the call's last block with r > 0: the slot's next content
+    uint32_t lastN = 0;
+    for (int blk = b0; blk < b1; blk++) {
+        const uint8_t *data = nullptr;
+        int compLen = 0, cap = 0;
+        uint8_t *dst = x.d.out + x.d.outOff[blk];
+        int r = read_block_header(x.d, blk, data, compLen, cap);
+        if (r == 0)
+            r = decode_block_par<false, true>(data, compLen, dst, cap, dict, dictLen, x.d.framed,
+                                              x.d.framed + x.d.framedLen, lds, nullptr);
+        r = uni(r);
+        if (lane_id() == 0) x.d.result[blk] = r;
+        if (r > 0) { dict = dst; dictLen = (uint32_t)r; last = dst; lastN = (uint32_t)r; }
+        wave_fence();       // (the next block reads this one through the pipeline that wrote it, see k_decode_fixup_linked)
+    }
+    if (!last) return;                                              // no block with output: the slot is as it was
+    // (the slot was read by the blocks up to the first one with r > 0, whose loads have returned: wave order)
+    const uint32_t keep = lastN < (uint32_t)DSTREAM_DICT_BYTES ? lastN : (uint32_t)DSTREAM_DICT_BYTES;
+    wave_copy_bytes(slot, last + (lastN - keep), keep);
+    if (lane_id() == 0) as_global(count)[0] = keep;
+}
+
+void launch_decode_dstreams(const DStreamsArgs &a, int nWork, hipStream_t s)
+{
+    if (nWork <= 0) return;
+    hipLaunchKernelGGL(k_decode_dstreams, dim3((unsigned)nWork), dim3(64), 0, s, a);
+}
+
+// LZ4_setStreamDecode for `count` slots from `first` on (one wave each): the slot's state becomes the keep <= 65536 bytes at
+// src (none: a reset).  dstreams_set_dict and dstreams_reset; nothing of the host is read.
+__global__ __launch_bounds__(LZ4_WAVE) void k_dstreams_set(uint8_t *state, int first, const uint8_t *src, uint32_t keep)
+{
+    uint8_t *slot = state + (size_t)(first + (int)blockIdx.x) * DSTREAM_SLOT_BYTES;
+    if (keep) wave_copy_bytes(slot, src, keep);
+    if (lane_id() == 0) as_global((uint32_t *)(slot + DSTREAM_COUNT_OFF))[0] = keep;
+}
+
+void launch_dstreams_set(uint8_t *state, int first, int count, const uint8_t *src, uint32_t keep, hipStream_t s)
+{
+    if (count <= 0) return;
+    hipLaunchKernelGGL(k_dstreams_set, dim3((unsigned)count), dim3(LZ4_WAVE), 0, s, state, first, src,
+                       keep > (uint32_t)DSTREAM_DICT_BYTES ? (uint32_t)DSTREAM_DICT_BYTES : keep);
 }
 
 // One stream in which FEW blocks need their dictionary (a reference-written stream of data whose matches rarely reach

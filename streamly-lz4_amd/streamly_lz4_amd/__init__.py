@@ -18,7 +18,7 @@ import os
 import numpy as np
 
 __all__ = [
-    "lib", "lib_path", "Engine", "CompressStreams", "LZ4Error", "BlockSize", "BlockConfig", "FrameConfig",
+    "lib", "lib_path", "Engine", "CompressStreams", "DecompressStreams", "LZ4Error", "BlockSize", "BlockConfig", "FrameConfig",
     "defaultBlockConfig", "defaultFrameConfig", "setBlockMaxSize", "setFrameEndMark", "setBlockChecksum",
     "compressChunks", "decompressChunks", "decompressChunksRaw", "resizeChunks",
     "decompressChunksWith", "decompressChunksStream", "simpleFrameParser", "compress_bound", "slot_stride", "slot_stride_ex", "device_count",
@@ -139,6 +139,17 @@ def _load():
         C.c_int, C.c_int, C.c_int, vp, C.c_size_t, vp)
     sig("mi355lz4_compress_streams", C.c_int, vp, vp, C.POINTER(_u8p), _i32p, C.c_int, _i32p, _i32p, C.c_int, C.c_int,
         C.c_int, _u8p, C.c_size_t, C.POINTER(C.c_size_t), _i32p, _i32p)
+    # many linked decode streams, continued across calls
+    sig("mi355lz4_dstreams_create", C.c_int, vp, C.c_int, C.POINTER(vp))
+    sig("mi355lz4_dstreams_destroy", None, vp)
+    sig("mi355lz4_dstreams_count", C.c_int, vp)
+    sig("mi355lz4_dstreams_reset", C.c_int, vp, vp, _i32p, C.c_int)
+    sig("mi355lz4_dstreams_set_dict", C.c_int, vp, vp, C.c_int, vp, C.c_int)
+    sig("mi355lz4_debug_dstream_state", C.c_int, vp, C.c_int, C.POINTER(C.c_uint32), _u8p, _u8p)
+    sig("mi355lz4_decompress_dstreams_device", C.c_int, vp, vp, vp, C.c_uint64, vp, C.c_int, C.c_int, C.c_int, _i32p, _i32p,
+        C.c_int, vp, vp, vp, vp)
+    sig("mi355lz4_decompress_dstreams", C.c_int, vp, vp, _u8p, C.c_size_t, C.c_int, C.c_int, _i32p, _i32p, C.c_int,
+        _u8p, C.c_size_t, C.POINTER(C.c_size_t), _i32p, C.c_int, C.POINTER(C.c_int))
     # legacy face (include/lz4.h)
     sig("LZ4_createStream", vp)
     sig("LZ4_freeStream", C.c_int, vp)
@@ -194,6 +205,8 @@ DECLARED_SYMBOLS = [
     "mi355lz4_compress_streams_device", "mi355lz4_compress_streams",
     "mi355lz4_decoded_size_device", "mi355lz4_decoded_sizes_host",
     "mi355lz4_decompress_partial_device", "mi355lz4_decompress_partial",
+    "mi355lz4_dstreams_create", "mi355lz4_dstreams_destroy", "mi355lz4_dstreams_count", "mi355lz4_dstreams_reset",
+    "mi355lz4_dstreams_set_dict", "mi355lz4_decompress_dstreams_device", "mi355lz4_decompress_dstreams",
     "LZ4_createStream", "LZ4_freeStream", "LZ4_createStreamDecode", "LZ4_freeStreamDecode", "LZ4_compressBound",
     "LZ4_compress_fast_continue", "LZ4_decompress_safe_continue",
 ]
@@ -791,6 +804,54 @@ class Engine:
             _check(rc, "decompress_streams")
         return out[: out_len.value].tobytes(), blen[: got.value].tolist()
 
+    def decompress_dstreams_device(self, ds, framed, framed_len, block_off, n_blocks, stream_first, stream_slot, out, out_off,
+                                   result, header_kind=8, fixed_uncomp=0, out_cap=None):
+        """Many linked decode streams continued across calls (include/mi355lz4.h, mi355lz4_decompress_dstreams_device):
+        stream s is the blocks [stream_first[s], stream_first[s+1]) and continues slot stream_slot[s] of ds.  The block
+        arguments are those of decompress_streams_device (device tensors); stream_first / stream_slot are host sequences.
+        Only enqueues: per-block codes are in result."""
+        self._follow_torch()
+        sf = np.ascontiguousarray(stream_first, dtype=np.int32)
+        sl = np.ascontiguousarray(stream_slot, dtype=np.int32)
+        if sf.size != sl.size + 1:
+            raise ValueError("stream_first needs one entry more than stream_slot")
+        _check(lib.mi355lz4_decompress_dstreams_device(
+            self.ctx, ds._h, _dptr(framed), int(framed_len), _dptr(block_off), int(n_blocks), int(header_kind),
+            int(fixed_uncomp), sf.ctypes.data_as(_i32p), sl.ctypes.data_as(_i32p), int(sl.size), _dptr(out), _dptr(out_off),
+            _dptr(out_cap), _dptr(result)), "decompress_dstreams_device")
+
+    def decompress_dstreams(self, framed, stream_first, ds, slots=None, header_kind=8, fixed_uncomp=0,
+                            raise_on_block_error=True, cap=None):
+        """Host buffers: framed holds the next blocks of len(stream_first) - 1 linked streams back to back, stream s =
+        blocks [stream_first[s], stream_first[s+1]) continuing slot slots[s] of ds (default: slot s).  Returns (decoded
+        bytes, [decoded length or negative code per block]); mi355lz4_decompress_dstreams."""
+        src = np.frombuffer(bytes(framed), dtype=np.uint8)
+        sf = np.ascontiguousarray(stream_first, dtype=np.int32)
+        if slots is None:
+            slots = list(range(sf.size - 1))
+        sl = np.ascontiguousarray(list(slots) + [0], dtype=np.int32)
+        if sl.size != sf.size:
+            raise ValueError("one slot per stream")
+        max_blocks = src.size // (header_kind + 1) + 1
+        if cap is None:
+            try:
+                _, ulen = index_host(framed, header_kind, fixed_uncomp, self._block_checksum)
+            except LZ4Error:
+                ulen = []                                   # (the call reports the chain itself)
+            cap = int(np.asarray(ulen, dtype=np.int64).clip(min=0).sum()) + 16
+        cap = int(cap)
+        out = np.empty(max(cap, 1), dtype=np.uint8)
+        out_len = C.c_size_t()
+        blen = np.zeros(max(max_blocks, 1), dtype=np.int32)
+        got = C.c_int()
+        rc = lib.mi355lz4_decompress_dstreams(self.ctx, ds._h, src.ctypes.data_as(_u8p) if src.size else None, src.size,
+                                              int(header_kind), int(fixed_uncomp), sf.ctypes.data_as(_i32p),
+                                              sl.ctypes.data_as(_i32p), int(sf.size - 1), out.ctypes.data_as(_u8p), cap,
+                                              C.byref(out_len), blen.ctypes.data_as(_i32p), int(max_blocks), C.byref(got))
+        if rc != 0 and (raise_on_block_error or rc != -5):
+            _check(rc, "decompress_dstreams")
+        return out[: out_len.value].tobytes(), blen[: got.value].tolist()
+
 
 class CompressStreams:
     """A set of n_slots device-resident reference-exact compress streams (mi355lz4_cstreams, about 80 KiB a slot), for
@@ -826,6 +887,63 @@ class CompressStreams:
     def close(self):
         if self._h:
             lib.mi355lz4_cstreams_destroy(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class DecompressStreams:
+    """A set of n_slots device-resident linked decode streams (mi355lz4_dstreams, about 64 KiB a slot), for
+    Engine.decompress_dstreams / decompress_dstreams_device.  Bound to the engine's device; every slot starts reset."""
+
+    def __init__(self, engine, n_slots):
+        self._h = C.c_void_p()
+        self._engine = engine
+        engine._follow_torch()
+        _check(lib.mi355lz4_dstreams_create(engine.ctx, int(n_slots), C.byref(self._h)), "dstreams_create")
+
+    def __len__(self):
+        return int(lib.mi355lz4_dstreams_count(self._h))
+
+    def reset(self, slots=None):
+        """Forget the listed slots' dictionaries (None: all), enqueued on the engine's stream."""
+        self._engine._follow_torch()
+        if slots is None:
+            _check(lib.mi355lz4_dstreams_reset(self._engine.ctx, self._h, None, 0), "dstreams_reset")
+        else:
+            a = np.ascontiguousarray(slots, dtype=np.int32)
+            _check(lib.mi355lz4_dstreams_reset(self._engine.ctx, self._h, a.ctypes.data_as(_i32p), int(a.size)),
+                   "dstreams_reset")
+
+    def set_dict(self, slot, dict_device, length=None):
+        """LZ4_setStreamDecode: the slot's state becomes the last 64 KiB of dict_device[:length] (a uint8 device tensor;
+        length defaults to all of it, 0 equals a reset).  Enqueued; the slot keeps its own copy."""
+        self._engine._follow_torch()
+        n = int(dict_device.numel() if length is None else length) if dict_device is not None else 0
+        _check(lib.mi355lz4_dstreams_set_dict(self._engine.ctx, self._h, int(slot), _dptr(dict_device) if n else None, n),
+               "dstreams_set_dict")
+
+    def state(self, slot, set_bytes=None):
+        """Diagnostics: (dictionary bytes held, the slot's whole 64 KiB area as bytes), after the device is idle; with
+        set_bytes (65536 bytes) the area is then overwritten, the count stays."""
+        cnt = C.c_uint32()
+        buf = np.empty(65536, dtype=np.uint8)
+        new = None
+        if set_bytes is not None:
+            new = np.frombuffer(bytes(set_bytes), dtype=np.uint8)
+            if new.size != 65536:
+                raise ValueError("set_bytes must be 65536 bytes")
+        _check(lib.mi355lz4_debug_dstream_state(self._h, int(slot), C.byref(cnt), buf.ctypes.data_as(_u8p),
+                                                new.ctypes.data_as(_u8p) if new is not None else None), "debug_dstream_state")
+        return int(cnt.value), buf.tobytes()
+
+    def close(self):
+        if self._h:
+            lib.mi355lz4_dstreams_destroy(self._h)
             self._h = C.c_void_p()
 
     def __del__(self):
