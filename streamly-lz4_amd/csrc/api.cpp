@@ -3,33 +3,26 @@
 // Host-side plumbing only: argument checks, device workspaces, copies and
 // kernel launches.  All arithmetic of the hot path happens in kernels.hip.
 // There is no CPU code path: without a gfx950 device every call fails.
-#include "../../include/mi355lz4.h"
-#include "../../include/lz4.h"
-
-#include "kernels.h"
-#include "linked_plan.hpp"
-
-#include <hip/hip_runtime.h>
+#include "engine.hpp"
 
 #include <algorithm>
 #include <cstdarg>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
-#include <chrono>
 #include <condition_variable>
 #include <mutex>
 #include <new>
-#include <string>
 #include <thread>
-#include <vector>
+
+using namespace mi355lz4_detail;
 
 // ---------------------------------------------------------------------------
 // errors
 // ---------------------------------------------------------------------------
-static thread_local char g_err[512] = "";
+static thread_local char g_err[512] = "";      // one per thread for the whole library: the other files write it through fail()
 
-static int fail(int code, const char *fmt, ...)
+int mi355lz4_detail::fail(int code, const char *fmt, ...)
 {
     va_list ap;
     va_start(ap, fmt);
@@ -38,22 +31,12 @@ static int fail(int code, const char *fmt, ...)
     return code;
 }
 
-#define HIP_TRY(expr)                                                                          \
-    do {                                                                                       \
-        hipError_t e_ = (expr);                                                                \
-        if (e_ != hipSuccess)                                                                  \
-            return fail(MI355LZ4_E_HIP, "%s failed: %s (%s:%d)", #expr, hipGetErrorString(e_), \
-                        __FILE__, __LINE__);                                                   \
-    } while (0)
-
 // ---------------------------------------------------------------------------
 // Host copy pool: the staging copies between pageable caller memory and the
 // pinned buffers are what bounds the host-buffer API (one thread moves ~10 GB/s,
 // the Gen5 x16 link ~55 GB/s), so they are spread over a few threads.
 // MI355LZ4_COPY_THREADS overrides the count (default 8, 1 = no helper threads).
 // ---------------------------------------------------------------------------
-struct CopyTask { uint8_t *dst; const uint8_t *src; size_t n; };
-
 class CopyPool {
 public:
     CopyPool()
@@ -136,64 +119,13 @@ static CopyPool &copy_pool()
     static CopyPool *pool = new CopyPool();     // leaked on purpose: no thread joins during process teardown
     return *pool;
 }
+void mi355lz4_detail::pool_run(const std::vector<CopyTask> &tasks) { copy_pool().run(tasks); }
+void mi355lz4_detail::pool_copy(uint8_t *dst, const uint8_t *src, size_t n) { copy_pool().copy(dst, src, n); }
 
 // ---------------------------------------------------------------------------
 // engine
 // ---------------------------------------------------------------------------
-struct DevBuf {
-    void *p = nullptr;
-    size_t cap = 0;
-};
-
-struct mi355lz4_ctx {
-    int device = 0;
-    hipStream_t stream = nullptr;
-    bool ownStream = false;
-    int decoder = 0;
-    int linkedCompress = 0;                 // compress calls treat their blocks as consecutive blocks of one stream
-    int blockChecksum = 0;                  // every block's data is followed by its xxh32 (mi355lz4_set_block_checksum)
-    int compLevel = 0;                      // 0: k_encode (fast); 1..9: k_encode_hc (mi355lz4_set_compression_level)
-    int compExact = 0;                      // compress calls continue ONE reference-exact stream (mi355lz4_set_compress_exact)
-    // ... that stream's state (the device counterpart of LZ4_stream_t): currentOffset and dictSize here, the table and
-    // the previous array's last bytes in exState; fresh = the table is still to be zeroed (a new stream)
-    struct ExactStream { uint32_t cur = 0, dictSize = 0; int dictBytes = 0; bool fresh = true; int last[4] = {0, 0, 0, 0}; } ex;
-    DevBuf exState, exMeta, exTabs, exFlags;
-    DevBuf ckBuf;                           // ... the decode side's per-block verdicts (k_xxh32_verify)
-    hipEvent_t ckEvent = nullptr;           // ... end of the last decode that read them, and the stream it ran on
-    hipStream_t ckStream = nullptr;
-    // workspaces of the host-buffer API (grown on demand, reused across calls)
-    DevBuf in, slots, dense, out, offA, offB, lenA, lenB, res, scratch;
-    DevBuf tokBuf;                          // decoder variant 3: token lists
-    DevBuf tolPool, tolMeta;                // deferred-copy decode of a long linked stream (linked_replay.hpp)
-    DevBuf linkBuf, ptrBuf, pinStat;        // ... its failure count, control block and source pointers (linked_ptr.hpp)
-    DevBuf pinIn, pinOut;   // pinned host staging
-    DevBuf pinMeta;         // pinned: per-group sizes coming back from the device
-    hipStream_t sIn = nullptr, sOut = nullptr;   // copy streams of the pipelined host-buffer API (created on first use)
-    hipStream_t sK[2] = {nullptr, nullptr};   // compute streams: kernels of consecutive groups overlap
-    // a linked decode whose data half is still to be issued (mi355lz4_decompress_linked_begin / _end)
-    struct LinkedPlan {
-        bool active = false, split = false;
-        DecodeArgs a;
-        int first = 0, last = -1, pool = 0, seg = 0;
-    } plan;
-    // small-batch compression: per-segment sequence lists, one scratch buffer per stream the engine has been used on
-    // (the host pipelines run two groups at a time on two compute streams; work on ONE stream is ordered)
-    struct SegScratch { hipStream_t s = nullptr; DevBuf b; unsigned long long tick = 0; } seg[4];
-    int nSeg = 0;
-    unsigned long long segTick = 0;
-    int linkedAsyncCap = 0;                // > 0: linked device decodes do not wait on the host (mi355lz4_set_linked_async)
-    RuninState runin;                      // the run-in decode's adaptive state (linked_plan.hpp)
-    int linkedPath = -1;                   // diagnostics: how the last linked call was finished (LinkedPath; mi355lz4_debug_runin_state)
-    int runinShareE6 = -1;                 // diagnostics: the dictionary share the last linked call sampled, in millionths (-1: none)
-    int segMode = -1;                      // small-batch segments per block: -1 auto, 0 off, k forced (mi355lz4_set_segments)
-    hipEvent_t linkEvent = nullptr;        // end of the last linked decode's use of linkBuf / tolPool / tolMeta / ptrBuf
-    hipStream_t linkStream = nullptr;      // ... and the stream it ran on
-    bool linkBusy = false;
-    unsigned long long *stats = nullptr;   // diagnostics: device counters of the lane-parallel decoder (off by default)
-    uint32_t *cuDbg = nullptr;             // diagnostics: 16 words per block from the workgroup-per-block decoder (mi355lz4_debug_cu)
-};
-
-static int dev_reserve(DevBuf &b, size_t bytes)
+int mi355lz4_detail::dev_reserve(DevBuf &b, size_t bytes)
 {
     if (bytes <= b.cap) return 0;
     if (b.p) { hipFree(b.p); b.p = nullptr; b.cap = 0; }
@@ -202,7 +134,7 @@ static int dev_reserve(DevBuf &b, size_t bytes)
     b.cap = want;
     return 0;
 }
-static int pin_reserve(DevBuf &b, size_t bytes)
+int mi355lz4_detail::pin_reserve(DevBuf &b, size_t bytes)
 {
     if (bytes <= b.cap) return 0;
     if (b.p) { hipHostFree(b.p); b.p = nullptr; b.cap = 0; }
@@ -211,8 +143,8 @@ static int pin_reserve(DevBuf &b, size_t bytes)
     b.cap = want;
     return 0;
 }
-static void dev_release(DevBuf &b) { if (b.p) hipFree(b.p); b.p = nullptr; b.cap = 0; }
-static void pin_release(DevBuf &b) { if (b.p) hipHostFree(b.p); b.p = nullptr; b.cap = 0; }
+void mi355lz4_detail::dev_release(DevBuf &b) { if (b.p) hipFree(b.p); b.p = nullptr; b.cap = 0; }
+void mi355lz4_detail::pin_release(DevBuf &b) { if (b.p) hipHostFree(b.p); b.p = nullptr; b.cap = 0; }
 
 // ---------------------------------------------------------------------------
 // Host <-> device transfers of pageable memory, pipelined through pinned staging:
@@ -230,7 +162,7 @@ static size_t stage_chunk()
 }
 #define kStageChunk (stage_chunk())
 
-static int h2d_staged(mi355lz4_ctx *c, void *dstDev, const uint8_t *srcHost, size_t bytes)
+int mi355lz4_detail::h2d_staged(mi355lz4_ctx *c, void *dstDev, const uint8_t *srcHost, size_t bytes)
 {
     if (!bytes) return 0;
     int r = pin_reserve(c->pinIn, bytes);
@@ -244,7 +176,7 @@ static int h2d_staged(mi355lz4_ctx *c, void *dstDev, const uint8_t *srcHost, siz
     return 0;
 }
 
-static int d2h_staged(mi355lz4_ctx *c, uint8_t *dstHost, const void *srcDev, size_t bytes)
+int mi355lz4_detail::d2h_staged(mi355lz4_ctx *c, uint8_t *dstHost, const void *srcDev, size_t bytes)
 {
     if (!bytes) return 0;
     int r = pin_reserve(c->pinOut, bytes);
@@ -409,7 +341,7 @@ extern "C" int mi355lz4_set_block_checksum(mi355lz4_ctx *c, int on)
 }
 
 // the switch as the multi handle sees it (multi_device.cpp): its engines must agree
-int engine_block_checksum(const mi355lz4_ctx *c) { return c ? c->blockChecksum : 0; }
+int mi355lz4_detail::engine_block_checksum(const mi355lz4_ctx *c) { return c ? c->blockChecksum : 0; }
 
 extern "C" int mi355lz4_set_compression_level(mi355lz4_ctx *c, int level)
 {
@@ -425,7 +357,7 @@ extern "C" int mi355lz4_get_compression_level(const mi355lz4_ctx *c)
     return c->compLevel;
 }
 
-int engine_compression_level(const mi355lz4_ctx *c) { return c ? c->compLevel : 0; }
+int mi355lz4_detail::engine_compression_level(const mi355lz4_ctx *c) { return c ? c->compLevel : 0; }
 
 extern "C" int mi355lz4_set_compress_exact(mi355lz4_ctx *c, int on)
 {
@@ -448,8 +380,8 @@ extern "C" int mi355lz4_compress_exact_reset(mi355lz4_ctx *c)
     return MI355LZ4_OK;
 }
 
-int engine_compress_exact(const mi355lz4_ctx *c) { return c ? c->compExact : 0; }
-int engine_swap_compress_exact(mi355lz4_ctx *c, int on)
+int mi355lz4_detail::engine_compress_exact(const mi355lz4_ctx *c) { return c ? c->compExact : 0; }
+int mi355lz4_detail::engine_swap_compress_exact(mi355lz4_ctx *c, int on)
 {
     if (!c) return 0;
     const int was = c->compExact;
@@ -556,7 +488,7 @@ extern "C" size_t mi355lz4_slot_stride_ex(int blockLen, int headerKind, int bloc
     return (b + 15) & ~(size_t)15;
 }
 
-static int check_launch(const char *what)
+int mi355lz4_detail::check_launch(const char *what)
 {
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return fail(MI355LZ4_E_HIP, "%s: %s", what, hipGetErrorString(e));
@@ -565,14 +497,13 @@ static int check_launch(const char *what)
 
 // ---------------------------------------------------------------------------
 // device-resident batched API
-// ---------------------------------------------------------------------------
-// ---------------------------------------------------------------------------
+//
 // Reference-exact compression (mi355lz4_set_compress_exact; encode_exact.hpp).  The host follows the
 // stream's scalar state (currentOffset, dictSize, renorms) from the lengths alone; the device holds the table and the
 // dictionary bytes.  Pieces of P blocks are speculated from a zeroed table R blocks early and verified in parallel; the
 // ones whose assumption failed are redone from their predecessor's true table, serially and in order.
 // ---------------------------------------------------------------------------
-static int env_int(const char *name, int dflt)
+int mi355lz4_detail::env_int(const char *name, int dflt)
 {
     const char *e = getenv(name);
     return (e && *e) ? atoi(e) : dflt;
@@ -684,9 +615,19 @@ static int exact_encode(mi355lz4_ctx *c, EncodeArgs a, const int32_t *hostLen)
     return MI355LZ4_OK;
 }
 
-static int encode_device(mi355lz4_ctx *c, const uint8_t *src, const uint64_t *srcOff, const int32_t *srcLen,
-                         uint64_t blockStride, int maxBlockLen, int nBlocks, int accel, int headerKind, uint8_t *slots,
-                         size_t slotStride, int32_t *framedLen, int lookBack, const int32_t *hostLen = nullptr)
+EncodeArgs mi355lz4_detail::make_encode_args(const uint8_t *src, const uint64_t *srcOff, const int32_t *srcLen, uint64_t blockStride,
+                                             int maxBlockLen, int nBlocks, int accel, int headerKind, uint8_t *slots,
+                                             size_t slotStride, int32_t *framedLen)
+{
+    if (accel < 1) accel = 1;                 // cbits/lz4.c:1577
+    if (accel > 65537) accel = 65537;         // cbits/lz4.c:1578
+    return EncodeArgs{src, srcOff, srcLen, blockStride, maxBlockLen, nBlocks, accel, headerKind, slots, slotStride, framedLen,
+                      nullptr, 0, 0};
+}
+
+int mi355lz4_detail::encode_device(mi355lz4_ctx *c, const uint8_t *src, const uint64_t *srcOff, const int32_t *srcLen,
+                                   uint64_t blockStride, int maxBlockLen, int nBlocks, int accel, int headerKind, uint8_t *slots,
+                                   size_t slotStride, int32_t *framedLen, int lookBack, const int32_t *hostLen)
 {
     if (!c) return fail(MI355LZ4_E_ARG, "null ctx");
     if (nBlocks < 0 || (headerKind != 4 && headerKind != 8) || maxBlockLen < 0 ||
@@ -698,15 +639,9 @@ static int encode_device(mi355lz4_ctx *c, const uint8_t *src, const uint64_t *sr
     const size_t trailer = c->blockChecksum ? 4u : 0u;
     if (slotStride < (size_t)mi355lz4_compress_bound(maxBlockLen) + (size_t)headerKind + trailer)
         return fail(MI355LZ4_E_CAPACITY, "compress_batch_device: slotStride %zu < bound", slotStride);
-    if (accel < 1) accel = 1;                 // cbits/lz4.c:1577
-    if (accel > 65537) accel = 65537;         // cbits/lz4.c:1578
     HIP_TRY(hipSetDevice(c->device));
-    EncodeArgs a;
-    a.src = src; a.srcOff = srcOff; a.srcLen = srcLen; a.blockStride = blockStride;
-    a.uniformLen = maxBlockLen; a.nBlocks = nBlocks; a.accel = accel; a.headerKind = headerKind;
-    a.slots = slots; a.slotStride = slotStride; a.framedLen = framedLen;
-    a.stats = c->stats;
-    a.linked = c->linkedCompress; a.lookBack = lookBack;
+    EncodeArgs a = make_encode_args(src, srcOff, srcLen, blockStride, maxBlockLen, nBlocks, accel, headerKind, slots, slotStride, framedLen);
+    a.stats = c->stats; a.linked = c->linkedCompress; a.lookBack = lookBack;
     // block checksums: the trailers go behind the encoder's output, on the same stream, before anything reads framedLen
     auto finish = [&]() -> int {
         int r = check_launch("encode launch");
@@ -821,63 +756,82 @@ struct StreamTableRing {                    // (shared with mi355lz4_dstreams, t
     }
 };
 
-struct mi355lz4_cstreams {
+// A set of slots on one device, written once for both sides: the compress side's slot is CSTREAM_SLOT_BYTES, the decode side's
+// (mi355lz4_dstreams, below) DSTREAM_SLOT_BYTES.  `who` names the calling entry point in the messages.
+struct SlotSet {
     int device = 0;
     int nSlots = 0;
-    uint8_t *state = nullptr;               // nSlots * CSTREAM_SLOT_BYTES
+    uint8_t *state = nullptr;               // nSlots * the side's slot size
     StreamTableRing table;
 };
+struct mi355lz4_cstreams : SlotSet {};
+struct mi355lz4_dstreams : SlotSet {};
 
-extern "C" int mi355lz4_cstreams_create(mi355lz4_ctx *c, int nSlots, mi355lz4_cstreams **out)
+template <class Set>
+static int slots_create(mi355lz4_ctx *c, int nSlots, size_t slotBytes, Set **out, const char *who)
 {
     if (out) *out = nullptr;
-    if (!c || !out || nSlots < 1) return fail(MI355LZ4_E_ARG, "cstreams_create: bad arguments");
+    if (!c || !out || nSlots < 1) return fail(MI355LZ4_E_ARG, "%s: bad arguments", who);
     HIP_TRY(hipSetDevice(c->device));
-    mi355lz4_cstreams *cs = new (std::nothrow) mi355lz4_cstreams();
-    if (!cs) return fail(MI355LZ4_E_ARG, "out of host memory");
-    cs->device = c->device;
-    cs->nSlots = nSlots;
-    const size_t bytes = (size_t)nSlots * CSTREAM_SLOT_BYTES;
-    hipError_t e = hipMalloc((void **)&cs->state, bytes);
-    if (e == hipSuccess) e = hipMemsetAsync(cs->state, 0, bytes, c->stream);     // LZ4_resetStream, every slot
+    Set *s = new (std::nothrow) Set();
+    if (!s) return fail(MI355LZ4_E_ARG, "out of host memory");
+    s->device = c->device;
+    s->nSlots = nSlots;
+    const size_t bytes = (size_t)nSlots * slotBytes;
+    hipError_t e = hipMalloc((void **)&s->state, bytes);
+    if (e == hipSuccess) e = hipMemsetAsync(s->state, 0, bytes, c->stream);      // every slot reset (LZ4_resetStream; no dictionary)
     if (e == hipSuccess) e = hipStreamSynchronize(c->stream);                    // (whatever stream the engine is on later)
     if (e != hipSuccess) {
-        if (cs->state) hipFree(cs->state);
-        delete cs;
-        return fail(MI355LZ4_E_HIP, "cstreams_create: %d slots (%zu bytes): %s", nSlots, bytes, hipGetErrorString(e));
+        if (s->state) hipFree(s->state);
+        delete s;
+        return fail(MI355LZ4_E_HIP, "%s: %d slots (%zu bytes): %s", who, nSlots, bytes, hipGetErrorString(e));
     }
-    *out = cs;
+    *out = s;
+    return MI355LZ4_OK;
+}
+template <class Set>
+static void slots_destroy(Set *s)
+{
+    if (!s) return;
+    hipSetDevice(s->device);
+    hipDeviceSynchronize();                 // calls that still use the slots
+    s->table.release();
+    if (s->state) hipFree(s->state);
+    delete s;
+}
+static int slots_count(const SlotSet *s, const char *who) { return s ? s->nSlots : fail(MI355LZ4_E_ARG, "%s: null set", who); }
+static int slots_same_device(const mi355lz4_ctx *c, const SlotSet *s, const char *who)
+{
+    if (!c || !s) return fail(MI355LZ4_E_ARG, "%s: null argument", who);
+    if (s->device != c->device) return fail(MI355LZ4_E_ARG, "%s: the set lives on device %d, the engine on %d", who, s->device, c->device);
+    return MI355LZ4_OK;
+}
+// the arguments of a _reset: the set on the engine's device and, with a list, every slot of it in range
+static int slots_reset_check(const mi355lz4_ctx *c, const SlotSet *s, const int32_t *slots, int n, const char *who)
+{
+    if (int r = slots_same_device(c, s, who)) return r;
+    HIP_TRY(hipSetDevice(c->device));
+    if (!slots) return MI355LZ4_OK;
+    if (n < 0) return fail(MI355LZ4_E_ARG, "%s: bad count", who);
+    for (int i = 0; i < n; i++)
+        if (slots[i] < 0 || slots[i] >= s->nSlots) return fail(MI355LZ4_E_ARG, "%s: slot %d out of range", who, slots[i]);
     return MI355LZ4_OK;
 }
 
-extern "C" void mi355lz4_cstreams_destroy(mi355lz4_cstreams *cs)
+extern "C" int mi355lz4_cstreams_create(mi355lz4_ctx *c, int nSlots, mi355lz4_cstreams **out)
 {
-    if (!cs) return;
-    hipSetDevice(cs->device);
-    hipDeviceSynchronize();                 // calls that still use the slots
-    cs->table.release();
-    if (cs->state) hipFree(cs->state);
-    delete cs;
+    return slots_create(c, nSlots, CSTREAM_SLOT_BYTES, out, "cstreams_create");
 }
-
-extern "C" int mi355lz4_cstreams_count(const mi355lz4_cstreams *cs)
-{
-    if (!cs) return fail(MI355LZ4_E_ARG, "cstreams_count: null set");
-    return cs->nSlots;
-}
+extern "C" void mi355lz4_cstreams_destroy(mi355lz4_cstreams *cs) { slots_destroy(cs); }
+extern "C" int mi355lz4_cstreams_count(const mi355lz4_cstreams *cs) { return slots_count(cs, "cstreams_count"); }
 
 extern "C" int mi355lz4_cstreams_reset(mi355lz4_ctx *c, mi355lz4_cstreams *cs, const int32_t *slots, int n)
 {
-    if (!c || !cs) return fail(MI355LZ4_E_ARG, "cstreams_reset: null argument");
-    if (cs->device != c->device) return fail(MI355LZ4_E_ARG, "cstreams_reset: the set lives on device %d, the engine on %d", cs->device, c->device);
-    HIP_TRY(hipSetDevice(c->device));
+    if (int r = slots_reset_check(c, cs, slots, n, "cstreams_reset")) return r;
     if (!slots) {
         HIP_TRY(hipMemsetAsync(cs->state, 0, (size_t)cs->nSlots * CSTREAM_SLOT_BYTES, c->stream));
         return MI355LZ4_OK;
     }
-    if (n < 0) return fail(MI355LZ4_E_ARG, "cstreams_reset: bad count");
-    for (int i = 0; i < n; i++)
-        if (slots[i] < 0 || slots[i] >= cs->nSlots) return fail(MI355LZ4_E_ARG, "cstreams_reset: slot %d out of range", slots[i]);
     for (int i = 0; i < n; i++)             // the table and the scalars: a dictionary of 0 bytes needs no bytes cleared
         HIP_TRY(hipMemsetAsync(cs->state + (size_t)slots[i] * CSTREAM_SLOT_BYTES, 0, CSTREAM_DICT_OFF, c->stream));
     return MI355LZ4_OK;
@@ -915,11 +869,10 @@ static int stream_table_check(int nSlots, int nBlocks, const int32_t *streamFirs
     return MI355LZ4_OK;
 }
 
-static int streams_check(const mi355lz4_ctx *c, const mi355lz4_cstreams *cs, int nBlocks, const int32_t *streamFirst,
-                         const int32_t *streamSlot, int nStreams, const char *who)
+int mi355lz4_detail::streams_check(const mi355lz4_ctx *c, const mi355lz4_cstreams *cs, int nBlocks, const int32_t *streamFirst,
+                                   const int32_t *streamSlot, int nStreams, const char *who)
 {
-    if (!c || !cs) return fail(MI355LZ4_E_ARG, "%s: null argument", who);
-    if (cs->device != c->device) return fail(MI355LZ4_E_ARG, "%s: the set lives on device %d, the engine on %d", who, cs->device, c->device);
+    if (int r = slots_same_device(c, cs, who)) return r;
     if (c->compLevel != 0)
         return fail(MI355LZ4_E_ARG, "%s: compression level %d; exact streams are level 0's encoder", who, c->compLevel);
     return stream_table_check(cs->nSlots, nBlocks, streamFirst, streamSlot, nStreams, who);
@@ -974,8 +927,8 @@ static int stream_table_launched(mi355lz4_ctx *c, StreamTableRing::Ring *r)
 
 // Enqueue the streams' parts that fall into blocks [b0, b1) of the table (a.* describes exactly those blocks): a stream cut
 // by b0 or b1 simply continues its slot in the next launch.  Longer parts go first: the launch ends with its longest chain.
-static int streams_enqueue(mi355lz4_ctx *c, mi355lz4_cstreams *cs, const EncodeArgs &a, int b0, int b1,
-                           const int32_t *streamFirst, const int32_t *streamSlot, int nStreams)
+int mi355lz4_detail::streams_enqueue(mi355lz4_ctx *c, mi355lz4_cstreams *cs, const EncodeArgs &a, int b0, int b1,
+                                     const int32_t *streamFirst, const int32_t *streamSlot, int nStreams)
 {
     ExactStreamsArgs x;
     int nWork = 0, rc;
@@ -1009,14 +962,8 @@ extern "C" int mi355lz4_compress_streams_device(mi355lz4_ctx *c, mi355lz4_cstrea
     if (!slots || !framedLen) return fail(MI355LZ4_E_ARG, "compress_streams_device: null output");
     if (slotStride < mi355lz4_compress_bound(maxBlockLen) + (size_t)headerKind + (c->blockChecksum ? 4u : 0u))
         return fail(MI355LZ4_E_CAPACITY, "compress_streams_device: slotStride %zu < bound", slotStride);
-    if (accel < 1) accel = 1;                 // cbits/lz4.c:1577
-    if (accel > 65537) accel = 65537;         // cbits/lz4.c:1578
     HIP_TRY(hipSetDevice(c->device));
-    EncodeArgs a;
-    a.src = src; a.srcOff = srcOff; a.srcLen = srcLen; a.blockStride = blockStride;
-    a.uniformLen = maxBlockLen; a.nBlocks = nBlocks; a.accel = accel; a.headerKind = headerKind;
-    a.slots = slots; a.slotStride = slotStride; a.framedLen = framedLen;
-    a.stats = nullptr; a.linked = 0; a.lookBack = 0;
+    const EncodeArgs a = make_encode_args(src, srcOff, srcLen, blockStride, maxBlockLen, nBlocks, accel, headerKind, slots, slotStride, framedLen);
     return streams_enqueue(c, cs, a, 0, nBlocks, streamFirst, streamSlot, nStreams);
 }
 
@@ -1321,7 +1268,7 @@ static int decode_device_impl(mi355lz4_ctx *c, const DecodeCall &d, const int32_
 // Every decode of the engine.  With block checksums on, the blocks' data is hashed first (k_xxh32_verify, one flag per
 // block in ckBuf) and read_block_header turns a mismatch into MI355LZ4_BLK_E_CHECKSUM: to every decode path a block
 // that fails its checksum is a header-rejected block, so linked streams treat it as they treat any other.
-static int decode_device(mi355lz4_ctx *c, const DecodeCall &d)
+int mi355lz4_detail::decode_device(mi355lz4_ctx *c, const DecodeCall &d)
 {
     if (!c || !c->blockChecksum || d.nBlocks <= 0 || c->plan.active || !d.framed || !d.blockOff ||
         (d.headerKind != 4 && d.headerKind != 8))
@@ -1435,63 +1382,20 @@ extern "C" int mi355lz4_decompress_streams_device(mi355lz4_ctx *c, const uint8_t
 // once, with its dictionary, so there is no first pass whose verdict the host would wait for: the call only enqueues.  The
 // per-call table goes through the same ring as the compress side's (stream_table_upload).
 // ---------------------------------------------------------------------------
-struct mi355lz4_dstreams {
-    int device = 0;
-    int nSlots = 0;
-    uint8_t *state = nullptr;               // nSlots * DSTREAM_SLOT_BYTES
-    StreamTableRing table;
-};
-
 extern "C" int mi355lz4_dstreams_create(mi355lz4_ctx *c, int nSlots, mi355lz4_dstreams **out)
 {
-    if (out) *out = nullptr;
-    if (!c || !out || nSlots < 1) return fail(MI355LZ4_E_ARG, "dstreams_create: bad arguments");
-    HIP_TRY(hipSetDevice(c->device));
-    mi355lz4_dstreams *ds = new (std::nothrow) mi355lz4_dstreams();
-    if (!ds) return fail(MI355LZ4_E_ARG, "out of host memory");
-    ds->device = c->device;
-    ds->nSlots = nSlots;
-    const size_t bytes = (size_t)nSlots * DSTREAM_SLOT_BYTES;
-    hipError_t e = hipMalloc((void **)&ds->state, bytes);
-    if (e == hipSuccess) e = hipMemsetAsync(ds->state, 0, bytes, c->stream);     // every slot reset: no dictionary
-    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);                    // (whatever stream the engine is on later)
-    if (e != hipSuccess) {
-        if (ds->state) hipFree(ds->state);
-        delete ds;
-        return fail(MI355LZ4_E_HIP, "dstreams_create: %d slots (%zu bytes): %s", nSlots, bytes, hipGetErrorString(e));
-    }
-    *out = ds;
-    return MI355LZ4_OK;
+    return slots_create(c, nSlots, DSTREAM_SLOT_BYTES, out, "dstreams_create");
 }
-
-extern "C" void mi355lz4_dstreams_destroy(mi355lz4_dstreams *ds)
-{
-    if (!ds) return;
-    hipSetDevice(ds->device);
-    hipDeviceSynchronize();                 // calls that still use the slots
-    ds->table.release();
-    if (ds->state) hipFree(ds->state);
-    delete ds;
-}
-
-extern "C" int mi355lz4_dstreams_count(const mi355lz4_dstreams *ds)
-{
-    if (!ds) return fail(MI355LZ4_E_ARG, "dstreams_count: null set");
-    return ds->nSlots;
-}
+extern "C" void mi355lz4_dstreams_destroy(mi355lz4_dstreams *ds) { slots_destroy(ds); }
+extern "C" int mi355lz4_dstreams_count(const mi355lz4_dstreams *ds) { return slots_count(ds, "dstreams_count"); }
 
 extern "C" int mi355lz4_dstreams_reset(mi355lz4_ctx *c, mi355lz4_dstreams *ds, const int32_t *slots, int n)
 {
-    if (!c || !ds) return fail(MI355LZ4_E_ARG, "dstreams_reset: null argument");
-    if (ds->device != c->device) return fail(MI355LZ4_E_ARG, "dstreams_reset: the set lives on device %d, the engine on %d", ds->device, c->device);
-    HIP_TRY(hipSetDevice(c->device));
+    if (int r = slots_reset_check(c, ds, slots, n, "dstreams_reset")) return r;
     if (!slots) {
         launch_dstreams_set(ds->state, 0, ds->nSlots, nullptr, 0, c->stream);
         return check_launch("dstreams reset launch");
     }
-    if (n < 0) return fail(MI355LZ4_E_ARG, "dstreams_reset: bad count");
-    for (int i = 0; i < n; i++)
-        if (slots[i] < 0 || slots[i] >= ds->nSlots) return fail(MI355LZ4_E_ARG, "dstreams_reset: slot %d out of range", slots[i]);
     for (int i = 0; i < n; i++)             // the count: a dictionary of 0 bytes needs no bytes cleared
         HIP_TRY(hipMemsetAsync(ds->state + (size_t)slots[i] * DSTREAM_SLOT_BYTES + DSTREAM_COUNT_OFF, 0, 4, c->stream));
     return MI355LZ4_OK;
@@ -1500,8 +1404,7 @@ extern "C" int mi355lz4_dstreams_reset(mi355lz4_ctx *c, mi355lz4_dstreams *ds, c
 // LZ4_setStreamDecode (cbits/lz4.c:2292-2300) for one slot: only the last 64 KiB of a dictionary can be referenced
 extern "C" int mi355lz4_dstreams_set_dict(mi355lz4_ctx *c, mi355lz4_dstreams *ds, int slot, const uint8_t *dictDevice, int len)
 {
-    if (!c || !ds) return fail(MI355LZ4_E_ARG, "dstreams_set_dict: null argument");
-    if (ds->device != c->device) return fail(MI355LZ4_E_ARG, "dstreams_set_dict: the set lives on device %d, the engine on %d", ds->device, c->device);
+    if (int r = slots_same_device(c, ds, "dstreams_set_dict")) return r;
     if (slot < 0 || slot >= ds->nSlots) return fail(MI355LZ4_E_ARG, "dstreams_set_dict: slot %d of %d", slot, ds->nSlots);
     if (len < 0 || (len > 0 && !dictDevice)) return fail(MI355LZ4_E_ARG, "dstreams_set_dict: bad dictionary");
     HIP_TRY(hipSetDevice(c->device));
@@ -1525,19 +1428,18 @@ extern "C" int mi355lz4_debug_dstream_state(mi355lz4_dstreams *ds, int slot, uin
     return MI355LZ4_OK;
 }
 
-static int dstreams_check(const mi355lz4_ctx *c, const mi355lz4_dstreams *ds, int nBlocks, const int32_t *streamFirst,
-                          const int32_t *streamSlot, int nStreams, const char *who)
+int mi355lz4_detail::dstreams_check(const mi355lz4_ctx *c, const mi355lz4_dstreams *ds, int nBlocks, const int32_t *streamFirst,
+                                    const int32_t *streamSlot, int nStreams, const char *who)
 {
-    if (!c || !ds) return fail(MI355LZ4_E_ARG, "%s: null argument", who);
-    if (ds->device != c->device) return fail(MI355LZ4_E_ARG, "%s: the set lives on device %d, the engine on %d", who, ds->device, c->device);
+    if (int r = slots_same_device(c, ds, who)) return r;
     if (c->plan.active) return fail(MI355LZ4_E_ARG, "%s: a linked decode begun with mi355lz4_decompress_linked_begin is still open", who);
     return stream_table_check(ds->nSlots, nBlocks, streamFirst, streamSlot, nStreams, who);
 }
 
 // Enqueue the streams' parts that fall into blocks [b0, b1) of the table (d.* describes exactly those blocks, as a.* does in
 // streams_enqueue): the checksum flags first, as in decode_device, then one wave per stream with blocks.
-static int dstreams_enqueue(mi355lz4_ctx *c, mi355lz4_dstreams *ds, const DecodeCall &d, int b0, int b1,
-                            const int32_t *streamFirst, const int32_t *streamSlot, int nStreams)
+int mi355lz4_detail::dstreams_enqueue(mi355lz4_ctx *c, mi355lz4_dstreams *ds, const DecodeCall &d, int b0, int b1,
+                                      const int32_t *streamFirst, const int32_t *streamSlot, int nStreams)
 {
     if (d.nBlocks <= 0) return MI355LZ4_OK;
     DStreamsArgs x{};
@@ -1622,28 +1524,6 @@ extern "C" int mi355lz4_decoded_size_device(mi355lz4_ctx *c, const uint8_t *fram
     return check_launch("size launch");
 }
 
-// the size pass over blocks in host memory: H2D, mi355lz4_decoded_size_device, sizes back; synchronous
-extern "C" int mi355lz4_decoded_sizes_host(mi355lz4_ctx *c, const uint8_t *framed, size_t len, const uint64_t *blockOff,
-                                           int nBlocks, int headerKind, int maxUncomp, int32_t *size)
-{
-    if (!c || nBlocks < 0 || maxUncomp < 0 || (headerKind != 4 && headerKind != 8) ||
-        (nBlocks > 0 && (!framed || !blockOff || !size)))
-        return fail(MI355LZ4_E_ARG, "decoded_sizes_host: bad arguments");
-    if (nBlocks == 0) return MI355LZ4_OK;
-    HIP_TRY(hipSetDevice(c->device));
-    int r;
-    if ((r = dev_reserve(c->in, len + 16)) || (r = dev_reserve(c->offA, (size_t)nBlocks * 8)) || (r = dev_reserve(c->lenB, (size_t)nBlocks * 4)))
-        return r;
-    if ((r = h2d_staged(c, c->in.p, framed, len))) return r;
-    HIP_TRY(hipMemcpyAsync(c->offA.p, blockOff, (size_t)nBlocks * 8, hipMemcpyHostToDevice, c->stream));
-    r = mi355lz4_decoded_size_device(c, (const uint8_t *)c->in.p, len, (const uint64_t *)c->offA.p, nBlocks, headerKind, maxUncomp,
-                                     (int32_t *)c->lenB.p, nullptr);
-    if (r) return r;
-    HIP_TRY(hipMemcpyAsync(size, c->lenB.p, (size_t)nBlocks * 4, hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    return MI355LZ4_OK;
-}
-
 extern "C" int mi355lz4_generate_device(mi355lz4_ctx *c, int kind, uint8_t *dst, int blockLen, int nBlocks,
                                         uint64_t firstBlock, uint64_t blockStep, uint32_t litMax, uint32_t offMax)
 {
@@ -1699,979 +1579,3 @@ extern "C" int mi355lz4_event_elapsed_ms(void *start, void *stop, float *ms)
     return MI355LZ4_OK;
 }
 
-
-// ---------------------------------------------------------------------------
-// Pipelined host-buffer calls.  A call is cut into groups of blocks; the H2D copy of
-// group i+1, the kernels of group i and the D2H copy of group i-1 run on three streams, and the CPU copies
-// between pageable caller memory and the pinned staging slots run meanwhile on the copy pool.  Caller
-// memory that is already page-locked (hipHostMalloc / hipHostRegister, e.g. a torch pinned tensor) is
-// handed to the DMA engines directly.
-// ---------------------------------------------------------------------------
-// The pipelined calls keep the caller's stream, two copy streams and two compute streams busy; HIP multiplexes
-// streams onto GPU_MAX_HW_QUEUES hardware queues (default 4), and streams that share a queue serialize
-// (measured: compress 33 -> 41 GB/s with 8).  The variable is the process's: the library does not set it.
-
-static bool pipe_trace()
-{
-    static const bool v = [] { const char *e = getenv("MI355LZ4_TRACE"); return e && atoi(e); }();
-    return v;
-}
-static double now_ms()
-{
-    using namespace std::chrono;
-    return duration<double, std::milli>(steady_clock::now().time_since_epoch()).count();
-}
-#define PTRACE(...) do { if (pipe_trace()) { fprintf(stderr, "[%10.3f] ", now_ms()); fprintf(stderr, __VA_ARGS__); fputc('\n', stderr); } } while (0)
-
-// Staging copies of a call of one or two groups go in pieces (decompress_host_pipelined): how many, and where piece q begins
-static size_t sub_pieces(int groups, size_t bytes)
-{
-    static const int forced = [] { const char *e = getenv("MI355LZ4_STAGE_PIECES"); return e ? atoi(e) : 0; }();
-    if (forced > 0) return (size_t)forced;
-    // (measured, 10 MiB out / 3.6 MB in, ms per call: 1 piece 0.613, 2: 0.584, 4: 0.611, 8: 0.809 -- a piece costs ~30 us of calls and waits)
-    return (groups > 2 || bytes < ((size_t)1 << 20)) ? 1 : 2;
-}
-static size_t piece_cut(size_t bytes, size_t q, size_t pieces)
-{
-    if (q >= pieces) return bytes;
-    return (bytes / pieces * q) & ~(size_t)4095;
-}
-
-static size_t group_bytes()
-{
-    static const size_t v = [] {
-        const char *e = getenv("MI355LZ4_GROUP_MB");
-        const long mb = e ? atol(e) : 64;
-        return (size_t)((mb < 1) ? 1 : (mb > 4096 ? 4096 : mb)) << 20;
-    }();
-    return v;
-}
-
-static bool host_range_is_pinned(const void *p, size_t n)
-{
-    if (!p || !n) return false;
-    if (const char *e = getenv("MI355LZ4_NO_DIRECT")) if (atoi(e)) return false;
-    hipPointerAttribute_t at;
-    for (const uint8_t *q : {(const uint8_t *)p, (const uint8_t *)p + (n - 1)}) {
-        if (hipPointerGetAttributes(&at, q) != hipSuccess) { (void)hipGetLastError(); return false; }
-        if (at.type != hipMemoryTypeHost) return false;
-    }
-    return true;
-}
-
-static int pipe_streams(mi355lz4_ctx *c)
-{
-    if (!c->sIn) HIP_TRY(hipStreamCreateWithFlags(&c->sIn, hipStreamNonBlocking));
-    if (!c->sOut) HIP_TRY(hipStreamCreateWithFlags(&c->sOut, hipStreamNonBlocking));
-    for (hipStream_t &k : c->sK) if (!k) HIP_TRY(hipStreamCreateWithFlags(&k, hipStreamNonBlocking));
-    return 0;
-}
-
-// run the device-API entry points on another stream of the same engine for the duration of a scope
-struct StreamSwap {
-    mi355lz4_ctx *c;
-    hipStream_t saved;
-    StreamSwap(mi355lz4_ctx *ctx, hipStream_t s) : c(ctx), saved(ctx->stream) { c->stream = s; }
-    ~StreamSwap() { c->stream = saved; }
-};
-
-// events of one pipelined call, destroyed together
-struct EventSet {
-    std::vector<hipEvent_t> ev;
-    ~EventSet() { for (hipEvent_t e : ev) if (e) hipEventDestroy(e); }
-    int make(hipEvent_t *out)
-    {
-        hipEvent_t e = nullptr;
-        HIP_TRY(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-        ev.push_back(e);
-        *out = e;
-        return 0;
-    }
-};
-
-// never return from a pipelined call with work in flight that still references caller or ctx buffers
-struct DrainOnExit {
-    mi355lz4_ctx *c;
-    ~DrainOnExit()
-    {
-        if (c->sIn) hipStreamSynchronize(c->sIn);
-        hipStreamSynchronize(c->stream);
-        for (hipStream_t k : c->sK) if (k) hipStreamSynchronize(k);
-        if (c->sOut) hipStreamSynchronize(c->sOut);
-    }
-};
-
-// ---------------------------------------------------------------------------
-// host-buffer batched API
-// ---------------------------------------------------------------------------
-static inline int32_t host_le32(const uint8_t *p)
-{
-    return (int32_t)((uint32_t)p[0] | ((uint32_t)p[1] << 8) | ((uint32_t)p[2] << 16) | ((uint32_t)p[3] << 24));
-}
-
-// the streams of a mi355lz4_compress_streams call (null: mi355lz4_compress_batch)
-struct HostStreams {
-    mi355lz4_cstreams *cs;
-    const int32_t *first, *slot;
-    int n;
-};
-
-static int compress_host(mi355lz4_ctx *c, const uint8_t *const *src, const int32_t *srcLen,
-                         int nBlocks, int accel, int headerKind, uint8_t *framedOut, size_t cap,
-                         size_t *outLen, int32_t *blockFramedLen, int32_t *status, const HostStreams *hs)
-{
-    if (!c) return fail(MI355LZ4_E_ARG, "null ctx");
-    if (nBlocks < 0 || (headerKind != 4 && headerKind != 8) || !outLen)
-        return fail(MI355LZ4_E_ARG, "compress_batch: bad arguments");
-    *outLen = 0;
-    if (nBlocks == 0) return MI355LZ4_OK;
-    if (!src || !srcLen || !framedOut) return fail(MI355LZ4_E_ARG, "compress_batch: null pointer");
-    HIP_TRY(hipSetDevice(c->device));
-
-    size_t total = 0;
-    int maxLen = 0;
-    bool contiguous = true;                    // blocks back to back in caller memory, every start 16-aligned
-    std::vector<uint64_t> offs((size_t)nBlocks);
-    for (int i = 0; i < nBlocks; i++) {
-        // compressChunk's size check, Internal/LZ4.hs:237-241 (BlockHasSize limit = LZ4_MAX_INPUT_SIZE)
-        if (srcLen[i] < 0 || (unsigned)srcLen[i] > (unsigned)MI355LZ4_MAX_INPUT_SIZE)
-            return fail(MI355LZ4_E_ARG, "compress_batch: block %d length %d exceeds the maximum block size", i, srcLen[i]);
-        if (srcLen[i] > 0 && !src[i]) return fail(MI355LZ4_E_ARG, "compress_batch: block %d is null", i);
-        offs[(size_t)i] = total;
-        if (i > 0 && src[i] != src[0] + total) contiguous = false;
-        // 16-aligned block starts; back to back for a linked stream (a block's dictionary lies directly in front of it)
-        total += (c->linkedCompress && !hs) ? (size_t)srcLen[i] : (((size_t)srcLen[i] + 15) & ~(size_t)15);
-        if (srcLen[i] > maxLen) maxLen = srcLen[i];
-    }
-    const size_t stride = mi355lz4_slot_stride_ex(maxLen, headerKind, c->blockChecksum);
-    const int trailer = c->blockChecksum ? 4 : 0;
-
-    // groups of consecutive blocks, about group_bytes() of input each
-    std::vector<int> gFirst;
-    {
-        size_t acc = 0;
-        for (int i = 0; i < nBlocks; i++) {
-            if (i == 0 || acc >= group_bytes()) { gFirst.push_back(i); acc = 0; }
-            acc += (size_t)srcLen[i];
-        }
-        gFirst.push_back(nBlocks);
-    }
-    const int G = (int)gFirst.size() - 1;
-    size_t maxIn = 0, maxBlocksG = 0;
-    for (int g = 0; g < G; g++) {
-        const size_t lo = offs[(size_t)gFirst[g]], hi = (gFirst[g + 1] < nBlocks) ? offs[(size_t)gFirst[g + 1]] : total;
-        if (hi - lo > maxIn) maxIn = hi - lo;
-        if ((size_t)(gFirst[g + 1] - gFirst[g]) > maxBlocksG) maxBlocksG = (size_t)(gFirst[g + 1] - gFirst[g]);
-    }
-    const bool directIn = contiguous && host_range_is_pinned(src[0], total);
-    const bool directOut = host_range_is_pinned(framedOut, cap);
-
-    int r;
-    if ((r = pipe_streams(c))) return r;
-    if (!directIn && (r = pin_reserve(c->pinIn, 2 * (maxIn + 16)))) return r;
-    if (!directOut && (r = pin_reserve(c->pinOut, 2 * maxBlocksG * stride))) return r;
-    if ((r = pin_reserve(c->pinMeta, (size_t)nBlocks * 4 + (size_t)G * 8))) return r;
-    if ((r = dev_reserve(c->in, total + 16))) return r;
-    if ((r = dev_reserve(c->offA, (size_t)nBlocks * 8))) return r;
-    if ((r = dev_reserve(c->lenA, (size_t)nBlocks * 4))) return r;
-    if ((r = dev_reserve(c->lenB, (size_t)nBlocks * 4))) return r;
-    if ((r = dev_reserve(c->slots, (size_t)nBlocks * stride))) return r;
-    if ((r = dev_reserve(c->dense, (size_t)nBlocks * stride))) return r;
-    if ((r = dev_reserve(c->offB, ((size_t)nBlocks + (size_t)G) * 8))) return r;
-
-    DrainOnExit drain{c};
-    EventSet evs;
-    HIP_TRY(hipMemcpyAsync(c->offA.p, offs.data(), (size_t)nBlocks * 8, hipMemcpyHostToDevice, c->stream));
-    HIP_TRY(hipMemcpyAsync(c->lenA.p, srcLen, (size_t)nBlocks * 4, hipMemcpyHostToDevice, c->stream));
-    // offs / srcLen are pageable: make sure the copies have consumed them before they go away
-    HIP_TRY(hipStreamSynchronize(c->stream));
-
-    int32_t *flenPin = (int32_t *)c->pinMeta.p;                              // framed length of every block
-    uint64_t *totPin = (uint64_t *)((uint8_t *)c->pinMeta.p + (size_t)nBlocks * 4);   // compressed bytes of every group
-    std::vector<hipEvent_t> evIn((size_t)G), evK((size_t)G), evOut((size_t)G);
-    std::vector<size_t> outAt((size_t)G, 0), outN((size_t)G, 0);
-    size_t outPos = 0;
-    int bad = 0;
-    bool overflow = false;
-
-    // Phase 1 -- input.  A block takes the encoder ~2 ms whatever else runs (it is latency-bound), and a
-    // group of a few hundred blocks fills a fraction of the chip, so the kernels of consecutive groups go to
-    // different compute streams and overlap each other as well as the copies.
-    for (int g = 0; g < G; g++) {
-        const int b0 = gFirst[g], b1 = gFirst[g + 1];
-        const size_t lo = offs[(size_t)b0], hi = (b1 < nBlocks) ? offs[(size_t)b1] : total;
-        if ((r = evs.make(&evIn[(size_t)g])) || (r = evs.make(&evK[(size_t)g])) || (r = evs.make(&evOut[(size_t)g]))) return r;
-        if (directIn) {
-            HIP_TRY(hipMemcpyAsync((uint8_t *)c->in.p + lo, src[0] + lo, hi - lo, hipMemcpyHostToDevice, c->sIn));
-        } else {
-            uint8_t *slot = (uint8_t *)c->pinIn.p + (size_t)(g & 1) * (maxIn + 16);
-            if (g >= 2) HIP_TRY(hipEventSynchronize(evIn[(size_t)g - 2]));   // the copy that last read this slot
-            // (in pieces for a call of one or two groups: the copy engine moves one while the host copies the next, sub_pieces)
-            const int pieces = (int)sub_pieces(G, hi - lo);
-            for (int q = 0; q < pieces; q++) {
-                const int q0 = b0 + (int)((int64_t)(b1 - b0) * q / pieces), q1 = b0 + (int)((int64_t)(b1 - b0) * (q + 1) / pieces);
-                if (q1 <= q0) continue;
-                const size_t plo = offs[(size_t)q0], phi = (q1 < nBlocks) ? offs[(size_t)q1] : total;
-                std::vector<CopyTask> tasks;
-                for (int i = q0; i < q1; i++)
-                    if (srcLen[i] > 0) tasks.push_back({slot + (offs[(size_t)i] - lo), src[i], (size_t)srcLen[i]});
-                copy_pool().run(tasks);
-                if (phi > plo) HIP_TRY(hipMemcpyAsync((uint8_t *)c->in.p + plo, slot + (plo - lo), phi - plo, hipMemcpyHostToDevice, c->sIn));
-            }
-        }
-        HIP_TRY(hipEventRecord(evIn[(size_t)g], c->sIn));
-        StreamSwap on(c, c->sK[(c->compExact || hs) ? 0 : (g & 1)]);   // an exact stream's groups follow each other
-        HIP_TRY(hipStreamWaitEvent(c->stream, evIn[(size_t)g], 0));
-        PTRACE("compress: group %d H2D enqueued (%zu bytes, direct %d)", g, hi - lo, (int)directIn);
-        // (a linked stream: the last block of the group before is this group's first dictionary)
-        if (hs) {                                  // (a group seam inside a stream: the slot continues in the next group's launch)
-            EncodeArgs a;
-            a.src = (const uint8_t *)c->in.p; a.srcOff = (const uint64_t *)c->offA.p + b0; a.srcLen = (const int32_t *)c->lenA.p + b0;
-            a.blockStride = 0; a.uniformLen = maxLen; a.nBlocks = b1 - b0;
-            a.accel = accel < 1 ? 1 : (accel > 65537 ? 65537 : accel); a.headerKind = headerKind;
-            a.slots = (uint8_t *)c->slots.p + (size_t)b0 * stride; a.slotStride = stride; a.framedLen = (int32_t *)c->lenB.p + b0;
-            a.stats = nullptr; a.linked = 0; a.lookBack = 0;
-            r = streams_enqueue(c, hs->cs, a, b0, b1, hs->first, hs->slot, hs->n);
-        } else {
-            r = encode_device(c, (const uint8_t *)c->in.p, (const uint64_t *)c->offA.p + b0,
-                              (const int32_t *)c->lenA.p + b0, 0, maxLen, b1 - b0, accel, headerKind,
-                              (uint8_t *)c->slots.p + (size_t)b0 * stride, stride, (int32_t *)c->lenB.p + b0, b0, srcLen + b0);
-        }
-        if (r) return r;
-        uint64_t *goff = (uint64_t *)c->offB.p + b0 + g;                       // b1 - b0 + 1 offsets of this group
-        r = mi355lz4_compact_device(c, (const uint8_t *)c->slots.p + (size_t)b0 * stride, stride,
-                                    (const int32_t *)c->lenB.p + b0, b1 - b0, (uint8_t *)c->dense.p + (size_t)b0 * stride,
-                                    (size_t)(b1 - b0) * stride, goff);
-        if (r) return r;
-        HIP_TRY(hipMemcpyAsync(flenPin + b0, (const int32_t *)c->lenB.p + b0, (size_t)(b1 - b0) * 4, hipMemcpyDeviceToHost, c->stream));
-        HIP_TRY(hipMemcpyAsync(totPin + g, goff + (b1 - b0), 8, hipMemcpyDeviceToHost, c->stream));
-        HIP_TRY(hipEventRecord(evK[(size_t)g], c->stream));
-    }
-    // Phase 2 -- output, once the last input copy is through: on this link both directions together run
-    // at ~39 GB/s each against 57 GB/s for one alone (scripts/pcie_rate.py) and the output is the small
-    // side, so it only overlaps the tail of the kernels.  D2H of group t while the pool copies group t-1 out.
-    // The output copies go to the INPUT copy stream, behind the last input copy: HIP multiplexes streams onto four
-    // hardware queues by default, and the caller's stream, one copy stream and two compute streams use them up.
-    // Data that barely compresses sends back as much as it took in: then the two directions do overlap (own stream).
-    hipStream_t so = c->sIn;
-    for (int t = 0; t < G + 1; t++) {
-        if (t < G) {
-            const int g = t, b0 = gFirst[g], b1 = gFirst[g + 1];
-            HIP_TRY(hipEventSynchronize(evK[(size_t)g]));
-            if (g == 0) {
-                const size_t in0 = ((gFirst[1] < nBlocks) ? offs[(size_t)gFirst[1]] : total) - offs[0];
-                if ((size_t)totPin[0] * 8 > in0 * 5) so = c->sOut;
-            }
-            PTRACE("compress: group %d kernels done", g);
-            for (int i = b0; i < b1; i++) {
-                const int32_t f = flenPin[i];
-                if (blockFramedLen) blockFramedLen[i] = f;
-                if (status) status[i] = (f > headerKind) ? f - headerKind - trailer : 0;
-                if (f <= headerKind) bad++;
-            }
-            outAt[(size_t)g] = outPos;
-            outN[(size_t)g] = (size_t)totPin[g];
-            outPos += outN[(size_t)g];
-            if (outPos > cap) overflow = true;
-            if (!bad && !overflow && outN[(size_t)g]) {
-                uint8_t *dst = directOut ? framedOut + outAt[(size_t)g] : (uint8_t *)c->pinOut.p + (size_t)(g & 1) * maxBlocksG * stride;
-                HIP_TRY(hipMemcpyAsync(dst, (const uint8_t *)c->dense.p + (size_t)b0 * stride, outN[(size_t)g], hipMemcpyDeviceToHost, so));
-            }
-            HIP_TRY(hipEventRecord(evOut[(size_t)g], so));
-        }
-        if (t >= 1) {
-            const int g = t - 1;
-            HIP_TRY(hipEventSynchronize(evOut[(size_t)g]));
-            PTRACE("compress: group %d D2H done (%zu bytes)", g, outN[(size_t)g]);
-            if (!directOut && !bad && !overflow && outN[(size_t)g])
-                copy_pool().copy(framedOut + outAt[(size_t)g], (const uint8_t *)c->pinOut.p + (size_t)(g & 1) * maxBlocksG * stride, outN[(size_t)g]);
-        }
-    }
-    if (bad) return fail(MI355LZ4_E_BLOCK, "compress_batch: %d block(s) failed", bad);
-    if (overflow) return fail(MI355LZ4_E_CAPACITY, "compress_batch: need %llu bytes, have %zu", (unsigned long long)outPos, cap);
-    *outLen = outPos;
-    return MI355LZ4_OK;
-}
-
-extern "C" int mi355lz4_compress_batch(mi355lz4_ctx *c, const uint8_t *const *src, const int32_t *srcLen,
-                                       int nBlocks, int accel, int headerKind, uint8_t *framedOut, size_t cap,
-                                       size_t *outLen, int32_t *blockFramedLen, int32_t *status)
-{
-    return compress_host(c, src, srcLen, nBlocks, accel, headerKind, framedOut, cap, outLen, blockFramedLen, status, nullptr);
-}
-
-// Host-buffer form of mi355lz4_compress_streams_device: the group pipeline of mi355lz4_compress_batch, its groups one behind
-// the other on one compute stream like an exact call's.  The lengths are the caller's host array: checked before anything is queued.
-extern "C" int mi355lz4_compress_streams(mi355lz4_ctx *c, mi355lz4_cstreams *cs, const uint8_t *const *src,
-                                         const int32_t *srcLen, int nBlocks, const int32_t *streamFirst,
-                                         const int32_t *streamSlot, int nStreams, int accel, int headerKind,
-                                         uint8_t *framedOut, size_t cap, size_t *outLen, int32_t *blockFramedLen,
-                                         int32_t *status)
-{
-    if (outLen) *outLen = 0;
-    const int r = streams_check(c, cs, nBlocks, streamFirst, streamSlot, nStreams, "compress_streams");
-    if (r) return r;
-    const HostStreams hs{cs, streamFirst, streamSlot, nStreams};
-    return compress_host(c, src, srcLen, nBlocks, accel, headerKind, framedOut, cap, outLen, blockFramedLen, status, &hs);
-}
-
-extern "C" int mi355lz4_index_host_ex(const uint8_t *framedIn, size_t inLen, int headerKind, int fixedUncomp,
-                                      int blockChecksum, uint64_t *blockOff, int32_t *uncompLen, int maxBlocks, int *nBlocks);
-extern "C" int mi355lz4_index_host(const uint8_t *framedIn, size_t inLen, int headerKind, int fixedUncomp,
-                                   uint64_t *blockOff, int32_t *uncompLen, int maxBlocks, int *nBlocks)
-{
-    return mi355lz4_index_host_ex(framedIn, inLen, headerKind, fixedUncomp, 0, blockOff, uncompLen, maxBlocks, nBlocks);
-}
-
-extern "C" int mi355lz4_index_host_ex(const uint8_t *framedIn, size_t inLen, int headerKind, int fixedUncomp,
-                                      int blockChecksum, uint64_t *blockOff, int32_t *uncompLen, int maxBlocks, int *nBlocks)
-{
-    const size_t trailer = blockChecksum ? 4u : 0u;
-    if (!nBlocks || (headerKind != 4 && headerKind != 8) || maxBlocks < 0 || (inLen && !framedIn))
-        return fail(MI355LZ4_E_ARG, "index_host: bad arguments");
-    size_t pos = 0;
-    int k = 0;
-    *nBlocks = 0;
-    while (pos < inLen) {
-        if (pos + (size_t)headerKind > inLen)
-            return fail(MI355LZ4_E_STREAM, "index_host: incomplete block header at offset %zu", pos);
-        const int32_t cl = host_le32(framedIn + pos);
-        const int32_t ul = (headerKind == 8) ? host_le32(framedIn + pos + 4) : fixedUncomp;
-        if (cl <= 0) return fail(MI355LZ4_E_STREAM, "index_host: block %d has compressed length %d", k, cl);
-        if (pos + (size_t)headerKind + (size_t)cl + trailer > inLen)
-            return fail(MI355LZ4_E_STREAM, "index_host: incomplete block %d (needs %zu bytes)", k, (size_t)cl + trailer);
-        if (k >= maxBlocks) return fail(MI355LZ4_E_CAPACITY, "index_host: more than %d blocks", maxBlocks);
-        if (blockOff) blockOff[k] = pos;
-        if (uncompLen) uncompLen[k] = ul;
-        pos += (size_t)headerKind + (size_t)cl + trailer;
-        k++;
-    }
-    *nBlocks = k;
-    return MI355LZ4_OK;
-}
-
-// mi355lz4_decompress_dstreams: the group pipeline with the set's slots in place of dict0
-struct HostDStreams {
-    mi355lz4_dstreams *ds;
-    const int32_t *first, *slot;
-    int n;
-};
-static int decompress_host(mi355lz4_ctx *c, const uint8_t *framedIn, size_t inLen, int headerKind,
-                           int fixedUncomp, int linked, const uint8_t *dict, int dictLen,
-                           const int32_t *streamFirst, int nStreams,
-                           uint8_t *out, size_t cap, size_t *outLen, int32_t *blockLen,
-                           int maxBlocks, int *nBlocksOut);
-static int decompress_host_pipelined(mi355lz4_ctx *c, const uint8_t *framedIn, size_t inLen, int headerKind,
-                                     int fixedUncomp, int linked, const uint8_t *dict, int dictLen,
-                                     const std::vector<uint64_t> &boff, const std::vector<int32_t> &ulen,
-                                     const std::vector<uint64_t> &ooff, int n, uint8_t *out, size_t *outLen,
-                                     int32_t *blockLen, int *nBlocksOut, const HostDStreams *hs = nullptr);
-
-extern "C" int mi355lz4_decompress_batch(mi355lz4_ctx *c, const uint8_t *framedIn, size_t inLen, int headerKind,
-                                         int fixedUncomp, int linked, const uint8_t *dict, int dictLen,
-                                         uint8_t *out, size_t cap, size_t *outLen, int32_t *blockLen,
-                                         int maxBlocks, int *nBlocksOut)
-{
-    return decompress_host(c, framedIn, inLen, headerKind, fixedUncomp, linked, dict, dictLen, nullptr, 0, out, cap,
-                           outLen, blockLen, maxBlocks, nBlocksOut);
-}
-
-extern "C" int mi355lz4_decompress_streams(mi355lz4_ctx *c, const uint8_t *framedIn, size_t inLen, int headerKind,
-                                           int fixedUncomp, const int32_t *streamFirst, int nStreams,
-                                           uint8_t *out, size_t cap, size_t *outLen, int32_t *blockLen,
-                                           int maxBlocks, int *nBlocksOut)
-{
-    if (nStreams < 0 || (nStreams > 0 && !streamFirst))
-        return fail(MI355LZ4_E_ARG, "decompress_streams: bad stream table");
-    for (int s = 0; s < nStreams; s++)
-        if (streamFirst[s] < 0 || streamFirst[s + 1] < streamFirst[s])
-            return fail(MI355LZ4_E_ARG, "decompress_streams: stream table is not ascending at %d", s);
-    return decompress_host(c, framedIn, inLen, headerKind, fixedUncomp, 1, nullptr, 0, streamFirst, nStreams, out, cap,
-                           outLen, blockLen, maxBlocks, nBlocksOut);
-}
-
-// Host-buffer form of mi355lz4_decompress_dstreams_device: the group pipeline of mi355lz4_decompress_batch, every group's
-// streams continuing their slots.  The chain is walked on the host: a bad length is MI355LZ4_E_ARG before anything is queued.
-extern "C" int mi355lz4_decompress_dstreams(mi355lz4_ctx *c, mi355lz4_dstreams *ds, const uint8_t *framedIn, size_t inLen,
-                                            int headerKind, int fixedUncomp, const int32_t *streamFirst,
-                                            const int32_t *streamSlot, int nStreams, uint8_t *out, size_t cap, size_t *outLen,
-                                            int32_t *blockLen, int maxBlocks, int *nBlocksOut)
-{
-    if (outLen) *outLen = 0;
-    if (nBlocksOut) *nBlocksOut = 0;
-    if (!c || !ds) return fail(MI355LZ4_E_ARG, "decompress_dstreams: null argument");
-    if (!outLen || !nBlocksOut || maxBlocks < 0 || fixedUncomp < 0 || (headerKind != 4 && headerKind != 8))
-        return fail(MI355LZ4_E_ARG, "decompress_dstreams: bad arguments");
-    std::vector<uint64_t> boff((size_t)maxBlocks + 1);
-    std::vector<int32_t> ulen((size_t)maxBlocks + 1);
-    int n = 0;
-    int r = mi355lz4_index_host_ex(framedIn, inLen, headerKind, fixedUncomp, c->blockChecksum, boff.data(), ulen.data(), maxBlocks, &n);
-    if (r == MI355LZ4_E_STREAM) return fail(MI355LZ4_E_ARG, "decompress_dstreams: %s", std::string(g_err).c_str());
-    if (r) return r;
-    std::vector<uint64_t> ooff((size_t)n + 1);
-    uint64_t total = 0;
-    for (int i = 0; i < n; i++) {
-        if (ulen[(size_t)i] < 0) return fail(MI355LZ4_E_ARG, "decompress_dstreams: block %d has negative size", i);
-        ooff[(size_t)i] = total;
-        total += (uint64_t)ulen[(size_t)i];
-    }
-    ooff[(size_t)n] = total;
-    if ((r = dstreams_check(c, ds, n, streamFirst, streamSlot, nStreams, "decompress_dstreams"))) return r;
-    if (n == 0) return MI355LZ4_OK;
-    // every block is written at its capacity offset (the header's size, or fixedUncomp) before the results are known
-    if (cap < total) return fail(MI355LZ4_E_CAPACITY, "decompress_dstreams: need %llu bytes, have %zu", (unsigned long long)total, cap);
-    if (total && !out) return fail(MI355LZ4_E_ARG, "decompress_dstreams: null output");
-    HIP_TRY(hipSetDevice(c->device));
-    const HostDStreams hs{ds, streamFirst, streamSlot, nStreams};
-    return decompress_host_pipelined(c, framedIn, inLen, headerKind, fixedUncomp, 0, nullptr, 0, boff, ulen, ooff, n, out, outLen,
-                                     blockLen, nBlocksOut, &hs);
-}
-
-// The first target[k] (or targetAll) bytes of every block of a chain in host memory.  One group, synchronous: the whole chain goes up,
-// one partial decode lays the prefixes out back to back at min(target, capacity), and only they come back -- in one copy when every
-// block gave all it was asked for, else block by block.
-extern "C" int mi355lz4_decompress_partial(mi355lz4_ctx *c, const uint8_t *framedIn, size_t inLen, int headerKind,
-                                           int fixedUncomp, const int32_t *target, int targetAll, uint8_t *out, size_t cap,
-                                           size_t *outLen, int32_t *blockLen, int maxBlocks, int *nBlocksOut)
-{
-    if (!c) return fail(MI355LZ4_E_ARG, "null ctx");
-    if (!outLen || !nBlocksOut || maxBlocks < 0 || fixedUncomp < 0 || (headerKind != 4 && headerKind != 8))
-        return fail(MI355LZ4_E_ARG, "decompress_partial: bad arguments");
-    if (c->plan.active) return fail(MI355LZ4_E_ARG, "a linked decode begun with mi355lz4_decompress_linked_begin is still open");
-    *outLen = 0;
-    *nBlocksOut = 0;
-    std::vector<uint64_t> boff((size_t)maxBlocks + 1);
-    std::vector<int32_t> ulen((size_t)maxBlocks + 1);
-    int n = 0;
-    int r = mi355lz4_index_host_ex(framedIn, inLen, headerKind, fixedUncomp, c->blockChecksum, boff.data(), ulen.data(),
-                                   maxBlocks, &n);
-    if (r) return r;
-    if (n == 0) return MI355LZ4_OK;
-    HIP_TRY(hipSetDevice(c->device));
-    // device layout: block k's prefix at scan(min(target, capacity)) -- what the call may write of it and no more
-    std::vector<uint64_t> ooff((size_t)n + 1);
-    std::vector<int32_t> tgt((size_t)n);
-    uint64_t total = 0;
-    for (int i = 0; i < n; i++) {
-        if (ulen[(size_t)i] < 0) return fail(MI355LZ4_E_STREAM, "decompress_partial: block %d has negative size", i);
-        const int32_t t = target ? target[i] : targetAll;
-        tgt[(size_t)i] = t;
-        ooff[(size_t)i] = total;
-        if (t > 0) total += (uint64_t)(t < ulen[(size_t)i] ? t : ulen[(size_t)i]);
-    }
-    ooff[(size_t)n] = total;
-    if ((r = dev_reserve(c->in, inLen + 16)) || (r = dev_reserve(c->offA, (size_t)n * 8)) || (r = dev_reserve(c->offB, ((size_t)n + 1) * 8)) ||
-        (r = dev_reserve(c->res, (size_t)n * 4)) || (r = dev_reserve(c->lenA, (size_t)n * 4)) || (r = dev_reserve(c->out, (size_t)total + 16)))
-        return r;
-    if ((r = h2d_staged(c, c->in.p, framedIn, inLen))) return r;
-    HIP_TRY(hipMemcpyAsync(c->offA.p, boff.data(), (size_t)n * 8, hipMemcpyHostToDevice, c->stream));
-    HIP_TRY(hipMemcpyAsync(c->offB.p, ooff.data(), ((size_t)n + 1) * 8, hipMemcpyHostToDevice, c->stream));
-    HIP_TRY(hipMemcpyAsync(c->lenA.p, tgt.data(), (size_t)n * 4, hipMemcpyHostToDevice, c->stream));
-    HIP_TRY(hipStreamSynchronize(c->stream));          // (the vectors are pageable memory)
-    r = mi355lz4_decompress_partial_device(c, (const uint8_t *)c->in.p, inLen, (const uint64_t *)c->offA.p, n, headerKind, fixedUncomp,
-                                           (uint8_t *)c->out.p, (const uint64_t *)c->offB.p, nullptr, (const int32_t *)c->lenA.p,
-                                           (int32_t *)c->res.p);
-    if (r) return r;
-    std::vector<int32_t> res((size_t)n);
-    HIP_TRY(hipMemcpyAsync(res.data(), c->res.p, (size_t)n * 4, hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    int bad = 0;
-    uint64_t need = 0;
-    for (int i = 0; i < n; i++) {
-        if (blockLen) blockLen[i] = res[(size_t)i];
-        if (res[(size_t)i] < 0) bad++; else need += (uint64_t)res[(size_t)i];
-    }
-    *nBlocksOut = n;
-    if (bad) return fail(MI355LZ4_E_BLOCK, "decompress_partial: %d block(s) failed", bad);
-    if (need > cap) return fail(MI355LZ4_E_CAPACITY, "decompress_partial: need %llu bytes, have %zu", (unsigned long long)need, cap);
-    if (need && !out) return fail(MI355LZ4_E_ARG, "decompress_partial: null output");
-    if (need == total) {
-        if (total && (r = d2h_staged(c, out, c->out.p, (size_t)total))) return r;
-    } else {
-        uint64_t w = 0;
-        for (int i = 0; i < n; i++) {
-            if (res[(size_t)i] > 0)
-                HIP_TRY(hipMemcpyAsync(out + w, (const uint8_t *)c->out.p + ooff[(size_t)i], (size_t)res[(size_t)i],
-                                       hipMemcpyDeviceToHost, c->stream));
-            w += (uint64_t)res[(size_t)i];
-        }
-    }
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    *outLen = (size_t)need;
-    return MI355LZ4_OK;
-}
-
-static int decompress_host(mi355lz4_ctx *c, const uint8_t *framedIn, size_t inLen, int headerKind,
-                           int fixedUncomp, int linked, const uint8_t *dict, int dictLen,
-                           const int32_t *streamFirst, int nStreams,
-                           uint8_t *out, size_t cap, size_t *outLen, int32_t *blockLen,
-                           int maxBlocks, int *nBlocksOut)
-{
-    if (!c) return fail(MI355LZ4_E_ARG, "null ctx");
-    if (!outLen || !nBlocksOut || maxBlocks < 0) return fail(MI355LZ4_E_ARG, "decompress_batch: bad arguments");
-    *outLen = 0;
-    *nBlocksOut = 0;
-    std::vector<uint64_t> boff((size_t)maxBlocks + 1);
-    std::vector<int32_t> ulen((size_t)maxBlocks + 1);
-    int n = 0;
-    int r = mi355lz4_index_host_ex(framedIn, inLen, headerKind, fixedUncomp, c->blockChecksum, boff.data(), ulen.data(),
-                                   maxBlocks, &n);
-    if (r) return r;
-    if (n == 0) return MI355LZ4_OK;
-    HIP_TRY(hipSetDevice(c->device));
-
-    // output layout: blocks back to back at their header (or fixed) capacity
-    std::vector<uint64_t> ooff((size_t)n + 1);
-    uint64_t total = 0;
-    for (int i = 0; i < n; i++) {
-        if (ulen[(size_t)i] < 0) return fail(MI355LZ4_E_STREAM, "decompress_batch: block %d has negative size", i);
-        ooff[(size_t)i] = total;
-        total += (uint64_t)ulen[(size_t)i];
-    }
-    ooff[(size_t)n] = total;
-    // the pipelined path writes every block at its capacity offset: it needs room for that layout and one stream
-    if (!streamFirst && cap >= total && total > 0)
-        return decompress_host_pipelined(c, framedIn, inLen, headerKind, fixedUncomp, linked, dict, dictLen, boff, ulen,
-                                         ooff, n, out, outLen, blockLen, nBlocksOut);
-    if ((r = dev_reserve(c->in, inLen + 16))) return r;
-    if ((r = dev_reserve(c->offA, (size_t)n * 8))) return r;
-    if ((r = dev_reserve(c->offB, ((size_t)n + 1) * 8))) return r;
-    if ((r = dev_reserve(c->res, (size_t)n * 4))) return r;
-    // dictionary in force before block 0: only its last 64 KiB can be referenced, and
-    // keeping exactly 64 KiB preserves the reference's "dictSize >= 64 KB => no offset
-    // check" behaviour (cbits/lz4.c:1764)
-    uint32_t dlen = 0;
-    if (linked && dict && dictLen > 0) {
-        dlen = (dictLen > 65536) ? 65536u : (uint32_t)dictLen;
-        if ((r = dev_reserve(c->scratch, 65536 + 16))) return r;
-        HIP_TRY(hipMemcpyAsync(c->scratch.p, dict + (dictLen - (int)dlen), dlen, hipMemcpyHostToDevice, c->stream));
-    }
-    if ((r = h2d_staged(c, c->in.p, framedIn, inLen))) return r;
-    HIP_TRY(hipMemcpyAsync(c->offA.p, boff.data(), (size_t)n * 8, hipMemcpyHostToDevice, c->stream));
-    // Blocks without a size in their header: the token chains say what every block decodes to (size_walk.hpp).  When every
-    // size is known the output is laid out back to back at those sizes -- sum(size) device bytes instead of
-    // n * fixedUncomp, one copy back instead of one per block -- and each block is decoded into exactly its size, which
-    // by the size pass's acceptance rule gives what decoding into fixedUncomp gives.  One block without a known size
-    // (malformed, or larger than fixedUncomp) and the whole call is laid out at fixedUncomp, as before.
-    const int32_t *capDev = nullptr;
-    if (headerKind == 4) {
-        if ((r = dev_reserve(c->lenB, (size_t)n * 4))) return r;
-        launch_decoded_size((const uint8_t *)c->in.p, inLen, (const uint64_t *)c->offA.p, n, headerKind, fixedUncomp,
-                            c->blockChecksum, (int32_t *)c->lenB.p, nullptr, c->stream);
-        if ((r = check_launch("size launch"))) return r;
-        std::vector<int32_t> sz((size_t)n);
-        HIP_TRY(hipMemcpyAsync(sz.data(), c->lenB.p, (size_t)n * 4, hipMemcpyDeviceToHost, c->stream));
-        HIP_TRY(hipStreamSynchronize(c->stream));
-        bool known = true;
-        for (int i = 0; i < n && known; i++) known = sz[(size_t)i] >= 0;
-        if (known) {
-            total = 0;
-            for (int i = 0; i < n; i++) { ooff[(size_t)i] = total; total += (uint64_t)sz[(size_t)i]; }
-            ooff[(size_t)n] = total;
-            capDev = (const int32_t *)c->lenB.p;
-        }
-    }
-    if ((r = dev_reserve(c->out, (size_t)total + 16))) return r;
-    HIP_TRY(hipMemcpyAsync(c->offB.p, ooff.data(), ((size_t)n + 1) * 8, hipMemcpyHostToDevice, c->stream));
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    const int32_t *sfDev = nullptr;
-    if (streamFirst) {
-        if (nStreams == 0 || streamFirst[nStreams] > n)
-            return fail(MI355LZ4_E_ARG, "decompress_streams: the stream table names block %d of %d", nStreams ? streamFirst[nStreams] : 0, n);
-        if ((r = dev_reserve(c->lenA, ((size_t)nStreams + 1) * 4))) return r;
-        HIP_TRY(hipMemcpyAsync(c->lenA.p, streamFirst, ((size_t)nStreams + 1) * 4, hipMemcpyHostToDevice, c->stream));
-        HIP_TRY(hipStreamSynchronize(c->stream));
-        sfDev = (const int32_t *)c->lenA.p;
-    }
-    DecodeCall d{(const uint8_t *)c->in.p, inLen, (const uint64_t *)c->offA.p, n, headerKind, fixedUncomp, linked,
-                 (uint8_t *)c->out.p, (const uint64_t *)c->offB.p, capDev, (int32_t *)c->res.p};
-    d.dict0 = dlen ? (const uint8_t *)c->scratch.p : nullptr; d.dict0Len = dlen; d.streamFirst = sfDev; d.nStreams = nStreams;
-    r = decode_device(c, d);
-    if (r) return r;
-    std::vector<int32_t> res((size_t)n);
-    HIP_TRY(hipMemcpyAsync(res.data(), c->res.p, (size_t)n * 4, hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(hipStreamSynchronize(c->stream));
-
-    // pack the decoded blocks back to back (a block may decode to fewer bytes than its capacity)
-    int bad = 0;
-    uint64_t need = 0;
-    for (int i = 0; i < n; i++) {
-        if (blockLen) blockLen[i] = res[(size_t)i];
-        if (res[(size_t)i] < 0) bad++; else need += (uint64_t)res[(size_t)i];
-    }
-    *nBlocksOut = n;
-    // The capacity is judged after the decode, also where the size pass has already said what the call needs: a size
-    // vouches for the chain, not for the offsets, so a block of known size can still fail in the decoder, and a call with a
-    // failed block returns E_BLOCK with its blockLen[] whether or not the output would have fitted.
-    if (bad) return fail(MI355LZ4_E_BLOCK, "decompress_batch: %d block(s) failed", bad);
-    if (need > cap) return fail(MI355LZ4_E_CAPACITY, "decompress_batch: need %llu bytes, have %zu", (unsigned long long)need, cap);
-    if (need == total) {
-        if ((r = d2h_staged(c, out, c->out.p, (size_t)total))) return r;
-    } else {
-        uint64_t w = 0;
-        for (int i = 0; i < n; i++) {
-            if (res[(size_t)i] > 0)
-                HIP_TRY(hipMemcpyAsync(out + w, (const uint8_t *)c->out.p + ooff[(size_t)i], (size_t)res[(size_t)i],
-                                       hipMemcpyDeviceToHost, c->stream));
-            w += (uint64_t)res[(size_t)i];
-        }
-    }
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    *outLen = (size_t)need;
-    return MI355LZ4_OK;
-}
-
-
-// One stream, output laid out at capacity offsets: groups of blocks flow through H2D -> decode (-> linked
-// fixup of the group, which looks back into the groups before it) -> D2H on three streams.
-static int decompress_host_pipelined(mi355lz4_ctx *c, const uint8_t *framedIn, size_t inLen, int headerKind,
-                                     int fixedUncomp, int linked, const uint8_t *dict, int dictLen,
-                                     const std::vector<uint64_t> &boff, const std::vector<int32_t> &ulen,
-                                     const std::vector<uint64_t> &ooff, int n, uint8_t *out, size_t *outLen,
-                                     int32_t *blockLen, int *nBlocksOut, const HostDStreams *hs)
-{
-    const uint64_t total = ooff[(size_t)n];
-    std::vector<int> gFirst;
-    {
-        size_t acc = 0;
-        for (int i = 0; i < n; i++) {
-            if (i == 0 || acc >= group_bytes()) { gFirst.push_back(i); acc = 0; }
-            acc += (size_t)ulen[(size_t)i];
-        }
-        gFirst.push_back(n);
-    }
-    const int G = (int)gFirst.size() - 1;
-    auto in_lo = [&](int b) -> size_t { return (b < n) ? (size_t)boff[(size_t)b] : inLen; };
-    size_t maxIn = 0, maxOut = 0;
-    for (int g = 0; g < G; g++) {
-        maxIn = std::max(maxIn, in_lo(gFirst[g + 1]) - in_lo(gFirst[g]));
-        maxOut = std::max(maxOut, (size_t)(ooff[(size_t)gFirst[g + 1]] - ooff[(size_t)gFirst[g]]));
-    }
-    const bool directIn = host_range_is_pinned(framedIn, inLen);
-    const bool directOut = host_range_is_pinned(out, (size_t)total);
-    int r;
-    if ((r = pipe_streams(c))) return r;
-    if (!directIn && (r = pin_reserve(c->pinIn, 2 * (maxIn + 16)))) return r;
-    if (!directOut && (r = pin_reserve(c->pinOut, 2 * (maxOut + 16)))) return r;
-    if ((r = pin_reserve(c->pinMeta, (size_t)n * 4))) return r;
-    if ((r = dev_reserve(c->in, inLen + 16))) return r;
-    if ((r = dev_reserve(c->out, (size_t)total + 16))) return r;
-    if ((r = dev_reserve(c->offA, (size_t)n * 8))) return r;
-    if ((r = dev_reserve(c->offB, ((size_t)n + 1) * 8))) return r;
-    if ((r = dev_reserve(c->res, (size_t)n * 4))) return r;
-
-    DrainOnExit drain{c};
-    EventSet evs;
-    uint32_t dlen = 0;
-    if (linked && dict && dictLen > 0) {                    // see decompress_host: only the last 64 KiB matter
-        dlen = (dictLen > 65536) ? 65536u : (uint32_t)dictLen;
-        if ((r = dev_reserve(c->scratch, 65536 + 16))) return r;
-        HIP_TRY(hipMemcpyAsync(c->scratch.p, dict + (dictLen - (int)dlen), dlen, hipMemcpyHostToDevice, c->stream));
-    }
-    // (boff / ooff outlive everything this call enqueues -- it drains its streams before it returns --, and the kernels that read the
-    // device copies are ordered behind these on the same stream: no wait here)
-    HIP_TRY(hipMemcpyAsync(c->offA.p, boff.data(), (size_t)n * 8, hipMemcpyHostToDevice, c->stream));
-    HIP_TRY(hipMemcpyAsync(c->offB.p, ooff.data(), ((size_t)n + 1) * 8, hipMemcpyHostToDevice, c->stream));
-
-    int32_t *resPin = (int32_t *)c->pinMeta.p;
-    std::vector<hipEvent_t> evIn((size_t)G), evK((size_t)G), evOut((size_t)G);
-    std::vector<std::vector<hipEvent_t>> evPiece((size_t)G);      // device-to-host copy in pieces (small calls): an event behind every piece but the last
-    // input copy of group g: enqueued one group AHEAD of its kernels, because a linked decode waits on the
-    // host for its first pass (decode_device) and the copy engine should be busy meanwhile
-    auto stage_in = [&](int g) -> int {
-        const int b0 = gFirst[g], b1 = gFirst[g + 1];
-        const size_t lo = in_lo(b0), hi = in_lo(b1);
-        int rr;
-        if ((rr = evs.make(&evIn[(size_t)g])) || (rr = evs.make(&evK[(size_t)g])) || (rr = evs.make(&evOut[(size_t)g]))) return rr;
-        if (directIn) {
-            HIP_TRY(hipMemcpyAsync((uint8_t *)c->in.p + lo, framedIn + lo, hi - lo, hipMemcpyHostToDevice, c->sIn));
-        } else {
-            uint8_t *slot = (uint8_t *)c->pinIn.p + (size_t)(g & 1) * (maxIn + 16);
-            if (g >= 2) HIP_TRY(hipEventSynchronize(evIn[(size_t)g - 2]));
-            // (a call of one or two groups has no other group's copies to hide its own staging behind: in pieces, so that the
-            // copy engine moves one piece while the host copies the next)
-            const size_t pieces = sub_pieces(G, hi - lo);
-            for (size_t q = 0; q < pieces; q++) {
-                const size_t a = piece_cut(hi - lo, q, pieces), b = piece_cut(hi - lo, q + 1, pieces);
-                copy_pool().copy(slot + a, framedIn + lo + a, b - a);
-                HIP_TRY(hipMemcpyAsync((uint8_t *)c->in.p + lo + a, slot + a, b - a, hipMemcpyHostToDevice, c->sIn));
-            }
-        }
-        HIP_TRY(hipEventRecord(evIn[(size_t)g], c->sIn));
-        return 0;
-    };
-    if (G > 0 && (r = stage_in(0))) return r;
-    for (int t = 0; t < G + 1; t++) {
-        if (t < G) {                                                           // ---- stage A, group t
-            const int g = t, b0 = gFirst[g], b1 = gFirst[g + 1];
-            if (linked && g + 1 < G && (r = stage_in(g + 1))) return r;
-            HIP_TRY(hipStreamWaitEvent(c->stream, evIn[(size_t)g], 0));
-            // the group's blocks, with the whole framed buffer as bounds and the blocks before it as look-back
-            DecodeCall d{(const uint8_t *)c->in.p, inLen, (const uint64_t *)c->offA.p + b0, b1 - b0, headerKind, fixedUncomp, linked,
-                         (uint8_t *)c->out.p, (const uint64_t *)c->offB.p + b0, nullptr, (int32_t *)c->res.p + b0};
-            d.dict0 = dlen ? (const uint8_t *)c->scratch.p : nullptr; d.dict0Len = dlen; d.lookBack = b0;
-            // (many streams: each continues through its slot, so a group seam inside a stream needs no look-back)
-            r = hs ? dstreams_enqueue(c, hs->ds, d, b0, b1, hs->first, hs->slot, hs->n) : decode_device(c, d);
-            if (r) return r;
-            HIP_TRY(hipMemcpyAsync(resPin + b0, (const int32_t *)c->res.p + b0, (size_t)(b1 - b0) * 4, hipMemcpyDeviceToHost, c->stream));
-            HIP_TRY(hipEventRecord(evK[(size_t)g], c->stream));
-            HIP_TRY(hipStreamWaitEvent(c->sOut, evK[(size_t)g], 0));
-            const size_t olo = (size_t)ooff[(size_t)b0], ohi = (size_t)ooff[(size_t)b1];
-            if (ohi > olo) {
-                if (directOut) {
-                    HIP_TRY(hipMemcpyAsync(out + olo, (const uint8_t *)c->out.p + olo, ohi - olo, hipMemcpyDeviceToHost, c->sOut));
-                } else {
-                    // slot g & 1 was emptied by stage C of group g - 2, one iteration ago
-                    uint8_t *slot = (uint8_t *)c->pinOut.p + (size_t)(g & 1) * (maxOut + 16);
-                    const size_t pieces = sub_pieces(G, ohi - olo);
-                    for (size_t q = 0; q < pieces; q++) {
-                        const size_t a = piece_cut(ohi - olo, q, pieces), b = piece_cut(ohi - olo, q + 1, pieces);
-                        HIP_TRY(hipMemcpyAsync(slot + a, (const uint8_t *)c->out.p + olo + a, b - a, hipMemcpyDeviceToHost, c->sOut));
-                        if (q + 1 < pieces) {
-                            hipEvent_t e;
-                            if ((r = evs.make(&e))) return r;
-                            HIP_TRY(hipEventRecord(e, c->sOut));
-                            evPiece[(size_t)g].push_back(e);
-                        }
-                    }
-                }
-            }
-            HIP_TRY(hipEventRecord(evOut[(size_t)g], c->sOut));
-        }
-        if (t >= 1) {                                                          // ---- stage C, group t-1
-            const int g = t - 1, b0 = gFirst[g], b1 = gFirst[g + 1];
-            const size_t olo = (size_t)ooff[(size_t)b0], ohi = (size_t)ooff[(size_t)b1];
-            const size_t pieces = evPiece[(size_t)g].size() + 1;
-            for (size_t q = 0; q < pieces; q++) {
-                // (the last piece's event is the group's: the results' copy and every piece lie in front of it)
-                HIP_TRY(hipEventSynchronize(q + 1 < pieces ? evPiece[(size_t)g][q] : evOut[(size_t)g]));
-                if (!directOut && ohi > olo) {
-                    const uint8_t *slot = (const uint8_t *)c->pinOut.p + (size_t)(g & 1) * (maxOut + 16);
-                    const size_t a = piece_cut(ohi - olo, q, pieces), b = piece_cut(ohi - olo, q + 1, pieces);
-                    if (b > a) copy_pool().copy(out + olo + a, slot + a, b - a);
-                }
-            }
-        }
-        if (!linked && t + 1 < G && (r = stage_in(t + 1))) return r;
-    }
-    HIP_TRY(hipStreamSynchronize(c->stream));
-
-    int bad = 0;
-    bool full = true;
-    uint64_t need = 0;
-    for (int i = 0; i < n; i++) {
-        const int32_t ri = resPin[i];
-        if (blockLen) blockLen[i] = ri;
-        if (ri < 0) bad++; else need += (uint64_t)ri;
-        if (ri != ulen[(size_t)i]) full = false;
-    }
-    *nBlocksOut = n;
-    if (bad) return fail(MI355LZ4_E_BLOCK, "decompress_batch: %d block(s) failed", bad);
-    if (!full) {
-        // a block may decode to fewer bytes than its capacity: pack the blocks back to back, in place
-        uint64_t w = 0;
-        for (int i = 0; i < n; i++) {
-            const uint64_t len = (uint64_t)resPin[i];
-            if (len && w != ooff[(size_t)i]) memmove(out + w, out + ooff[(size_t)i], (size_t)len);
-            w += len;
-        }
-    }
-    *outLen = (size_t)need;
-    return MI355LZ4_OK;
-}
-
-// ===========================================================================
-// Legacy face: the 7 symbols Streamly.Internal.LZ4 imports today
-// (src/Streamly/Internal/LZ4.hs:105-143).  One block per call: source
-// compatible, correct, and slow by construction (a PCIe round trip per block) --
-// the batched calls above are what INTEGRATION.md binds instead.
-// ===========================================================================
-static std::mutex g_engineMu;
-static mi355lz4_ctx *g_engine = nullptr;
-
-static mi355lz4_ctx *legacy_engine()
-{
-    std::lock_guard<std::mutex> lk(g_engineMu);
-    if (!g_engine) {
-        int dev = 0;
-        if (const char *e = getenv("MI355LZ4_DEVICE")) dev = atoi(e);
-        if (mi355lz4_create(&g_engine, dev) != MI355LZ4_OK) {
-            fprintf(stderr, "mi355lz4: %s\n", g_err);
-            g_engine = nullptr;
-        }
-    }
-    return g_engine;
-}
-
-// One call = one block.  Since round 4 a call is ONE host-to-device copy (staged in page-locked memory), ONE kernel
-// launch, ONE device-to-host copy (the output with its size word behind it) and ONE synchronisation.  The decoder keeps
-// the previous block's output where it was decoded -- the next call decodes into the other of two buffers -- so the
-// dictionary is never copied.  (Round 3: a heap-allocated frame or output vector, three or four synchronisations and a
-// device-to-device copy of the dictionary per block.)  Still one PCIe round trip per block: compatibility, not speed.
-struct LegacyBuf { void *p = nullptr; size_t cap = 0; };
-static bool legacy_dev(LegacyBuf &b, size_t n)
-{
-    if (n <= b.cap) return true;
-    if (b.p) (void)hipFree(b.p);
-    b.p = nullptr; b.cap = 0;
-    if (hipMalloc(&b.p, n * 2) != hipSuccess) { b.p = nullptr; return false; }
-    b.cap = n * 2;
-    return true;
-}
-static bool legacy_pin(LegacyBuf &b, size_t n)
-{
-    if (n <= b.cap) return true;
-    if (b.p) (void)hipHostFree(b.p);
-    b.p = nullptr; b.cap = 0;
-    if (hipHostMalloc(&b.p, n * 2, hipHostMallocDefault) != hipSuccess) { b.p = nullptr; return false; }
-    b.cap = n * 2;
-    return true;
-}
-struct LZ4_stream_u {
-    uint32_t magic;
-    LegacyBuf inDev, slotDev, inPin, outPin;
-};
-struct LZ4_streamDecode_u {
-    uint32_t magic;
-    const uint8_t *dictDev;       // last <= 64 KiB of the previous block's output, inside outDev[1 - cur]
-    uint32_t dictLen;
-    int cur;
-    LegacyBuf inDev, outDev[2], inPin, outPin;
-};
-// [blockOff = 0 | outOff = 0 | result | pad] travels in front of the framed block
-#define LEGACY_PRE 32
-
-extern "C" LZ4_stream_t *LZ4_createStream(void)
-{
-    LZ4_stream_u *s = new (std::nothrow) LZ4_stream_u();
-    if (s) s->magic = 0x4C5A3443u;
-    return (LZ4_stream_t *)s;
-}
-extern "C" int LZ4_freeStream(LZ4_stream_t *p)
-{
-    LZ4_stream_u *s = (LZ4_stream_u *)p;
-    if (!s) return 0;
-    if (s->inDev.p) (void)hipFree(s->inDev.p);
-    if (s->slotDev.p) (void)hipFree(s->slotDev.p);
-    if (s->inPin.p) (void)hipHostFree(s->inPin.p);
-    if (s->outPin.p) (void)hipHostFree(s->outPin.p);
-    delete s;
-    return 0;
-}
-
-extern "C" LZ4_streamDecode_t *LZ4_createStreamDecode(void)
-{
-    LZ4_streamDecode_u *s = new (std::nothrow) LZ4_streamDecode_u();
-    if (s) { s->magic = 0x4C5A3444u; s->dictDev = nullptr; s->dictLen = 0; s->cur = 0; }
-    return (LZ4_streamDecode_t *)s;
-}
-extern "C" int LZ4_freeStreamDecode(LZ4_streamDecode_t *p)
-{
-    LZ4_streamDecode_u *s = (LZ4_streamDecode_u *)p;
-    if (!s) return 0;
-    if (s->inDev.p) (void)hipFree(s->inDev.p);
-    for (int k = 0; k < 2; k++) if (s->outDev[k].p) (void)hipFree(s->outDev[k].p);
-    if (s->inPin.p) (void)hipHostFree(s->inPin.p);
-    if (s->outPin.p) (void)hipHostFree(s->outPin.p);
-    delete s;
-    return 0;
-}
-
-extern "C" int LZ4_compressBound(int inputSize) { return mi355lz4_compress_bound(inputSize); }
-
-// Emits an independent block (never references earlier blocks), which the
-// reference's linked decoder accepts.  Returns 0 on failure like the reference.
-extern "C" int LZ4_compress_fast_continue(LZ4_stream_t *streamPtr, const char *src, char *dst, int srcSize,
-                                          int dstCapacity, int acceleration)
-{
-    LZ4_stream_u *s = (LZ4_stream_u *)streamPtr;
-    mi355lz4_ctx *c = legacy_engine();
-    if (!c || !s || srcSize < 0 || dstCapacity <= 0 || !dst || (!src && srcSize > 0)) return 0;
-    if ((unsigned)srcSize > (unsigned)MI355LZ4_MAX_INPUT_SIZE) return 0;          // cbits/lz4.c:1254
-    std::lock_guard<std::mutex> lk(g_engineMu);
-    if (hipSetDevice(c->device) != hipSuccess) return 0;
-    const size_t stride = mi355lz4_slot_stride(srcSize, 4);
-    if (!legacy_dev(s->inDev, (size_t)srcSize + 16) || !legacy_dev(s->slotDev, stride + 16) ||
-        !legacy_pin(s->inPin, (size_t)srcSize + 16) || !legacy_pin(s->outPin, stride + 16))
-        return 0;
-    if (srcSize) {
-        memcpy(s->inPin.p, src, (size_t)srcSize);
-        if (hipMemcpyAsync(s->inDev.p, s->inPin.p, (size_t)srcSize, hipMemcpyHostToDevice, c->stream) != hipSuccess) return 0;
-    }
-    int32_t *lenDev = (int32_t *)((uint8_t *)s->slotDev.p + stride);
-    if (encode_device(c, (const uint8_t *)s->inDev.p, nullptr, nullptr, (uint64_t)srcSize, srcSize, 1, acceleration, 4,
-                      (uint8_t *)s->slotDev.p, stride, lenDev, 0) != MI355LZ4_OK)
-        return 0;
-    if (hipMemcpyAsync(s->outPin.p, s->slotDev.p, stride + 4, hipMemcpyDeviceToHost, c->stream) != hipSuccess) return 0;
-    if (hipStreamSynchronize(c->stream) != hipSuccess) return 0;
-    int32_t framed = 0;
-    memcpy(&framed, (const uint8_t *)s->outPin.p + stride, 4);
-    const int st = framed - 4;
-    if (st <= 0 || st > dstCapacity) return 0;   // limitedOutput: cbits/lz4.c:1024-1027
-    memcpy(dst, (const uint8_t *)s->outPin.p + 4, (size_t)st);
-    return st;
-}
-
-// Linked semantics of cbits/lz4.c:2322-2359 for separately allocated blocks: the
-// previous block's output stays on the device as the external dictionary.
-extern "C" int LZ4_decompress_safe_continue(LZ4_streamDecode_t *p, const char *src, char *dst, int srcSize,
-                                            int dstCapacity)
-{
-    LZ4_streamDecode_u *s = (LZ4_streamDecode_u *)p;
-    mi355lz4_ctx *c = legacy_engine();
-    if (!c || !s) return -1;
-    if (!src) return -1;                                          // cbits/lz4.c:1752
-    if (srcSize < 0 || dstCapacity < 0) return -1;
-    if (srcSize == 0) return -1;                                   // cbits/lz4.c:1787 (and :1781 for cap==0)
-    std::lock_guard<std::mutex> lk(g_engineMu);
-    if (hipSetDevice(c->device) != hipSuccess) return -1;
-    const size_t inBytes = LEGACY_PRE + 4 + (size_t)srcSize;
-    const size_t outPad = ((size_t)dstCapacity + 15) & ~(size_t)15;      // the result word sits behind the output
-    LegacyBuf &outDev = s->outDev[s->cur];
-    if (!legacy_dev(s->inDev, inBytes + 16) || !legacy_dev(outDev, outPad + 32) || !legacy_pin(s->inPin, inBytes) ||
-        !legacy_pin(s->outPin, outPad + 16))
-        return -1;
-    // (growing outDev[cur] cannot move the dictionary: that lies in the OTHER buffer)
-    uint8_t *hp = (uint8_t *)s->inPin.p;
-    memset(hp, 0, LEGACY_PRE);
-    const int32_t preset = s->dictLen ? -1 : 0;                    // a codec error: "this block wants its dictionary"
-    memcpy(hp + 16, &preset, 4);
-    hp[LEGACY_PRE + 0] = (uint8_t)srcSize; hp[LEGACY_PRE + 1] = (uint8_t)(srcSize >> 8);
-    hp[LEGACY_PRE + 2] = (uint8_t)(srcSize >> 16); hp[LEGACY_PRE + 3] = (uint8_t)(srcSize >> 24);
-    memcpy(hp + LEGACY_PRE + 4, src, (size_t)srcSize);
-    if (hipMemcpyAsync(s->inDev.p, hp, inBytes, hipMemcpyHostToDevice, c->stream) != hipSuccess) return -1;
-    int32_t *resDev = (int32_t *)((uint8_t *)outDev.p + outPad);
-    DecodeArgs a;
-    a.framed = (const uint8_t *)s->inDev.p + LEGACY_PRE; a.framedLen = 4 + (uint64_t)srcSize;
-    a.blockOff = (const uint64_t *)s->inDev.p; a.nBlocks = 1;
-    a.headerKind = 4; a.fixedUncomp = dstCapacity; a.linked = 1;
-    a.out = (uint8_t *)outDev.p; a.outOff = (const uint64_t *)s->inDev.p + 1; a.outCap = nullptr; a.result = resDev;
-    a.dict0 = s->dictLen ? s->dictDev : nullptr; a.dict0Len = s->dictLen;
-    a.streamFirst = nullptr; a.nStreams = 0; a.lookBack = 0;
-    a.tolPool = nullptr; a.tolRegions = 0; a.tolPer = 0; a.tolCounter = nullptr; a.tolRegion = a.tolCount = a.tolSize = nullptr;
-    a.linkStat = nullptr; a.segFirst = 0; a.segEnd = 1; a.ptr = nullptr; a.ptrCap = 0; a.ptrCtl = nullptr;
-    a.ptrBad = nullptr; a.asyncGate = 0; a.onlyBlk = -1; a.tokList = nullptr; a.tokCnt = nullptr; a.runList = nullptr; a.runCap = 0;
-    a.cuDbg = nullptr; a.cuBail = 0; a.cuSnap = nullptr; a.cuFlags = nullptr; a.cuRes = nullptr; a.cuPass = 0;
-    a.ring = nullptr; a.ringStride = 0; a.zeroPage = nullptr; a.runPiece = 0; a.runIn = 0; a.runSpin = 0; a.runRound = 0;
-    a.runRes = nullptr; a.runInfo = nullptr; a.runDirty = nullptr; a.runCtl = nullptr;
-    if (s->dictLen) {
-        // the exact decoder with the dictionary in force, at once (a block that does not reach back decodes the same)
-        if (hipMemcpyAsync(resDev, (const uint8_t *)s->inDev.p + 16, 4, hipMemcpyDeviceToDevice, c->stream) != hipSuccess) return -1;
-        launch_linked_runs(a, c->stream);
-    } else {
-        launch_decode_par(a, nullptr, c->stream);
-    }
-    if (check_launch("decode launch") != MI355LZ4_OK) return -1;
-    if (hipMemcpyAsync(s->outPin.p, outDev.p, outPad + 4, hipMemcpyDeviceToHost, c->stream) != hipSuccess) return -1;
-    if (hipStreamSynchronize(c->stream) != hipSuccess) return -1;
-    int32_t res = -1;
-    memcpy(&res, (const uint8_t *)s->outPin.p + outPad, 4);
-    if (res <= 0) return res;                                      // :2331 / :2353: context unchanged
-    if (res > dstCapacity) return -1;
-    memcpy(dst, s->outPin.p, (size_t)res);
-    const uint32_t keep = (res > 65536) ? 65536u : (uint32_t)res;
-    s->dictDev = (const uint8_t *)outDev.p + ((size_t)res - keep);
-    s->dictLen = keep;
-    s->cur ^= 1;
-    return res;
-}

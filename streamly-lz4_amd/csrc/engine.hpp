@@ -1,0 +1,124 @@
+// engine.hpp -- what the layers of the C ABI share (internal, not installed): api.cpp holds the engine and the device-pointer
+// calls, host_batch.cpp the host-buffer calls on top of them, legacy.cpp the LZ4_* face; multi_device.cpp, lz4_frame.cpp and
+// host_stream.cpp read an engine's switches.  Everything that is not extern "C" lives in mi355lz4_detail.
+#pragma once
+
+#include "../../include/mi355lz4.h"
+
+#include "kernels.h"
+#include "linked_plan.hpp"
+
+#include <hip/hip_runtime.h>
+
+#include <vector>
+
+namespace mi355lz4_detail {
+
+// The message mi355lz4_last_error returns: ONE buffer per thread for the whole library (api.cpp), written through fail() only.
+int fail(int code, const char *fmt, ...) __attribute__((format(printf, 2, 3)));
+int check_launch(const char *what);
+int env_int(const char *name, int dflt);
+
+#define HIP_TRY(expr)                                                                          \
+    do {                                                                                       \
+        hipError_t e_ = (expr);                                                                \
+        if (e_ != hipSuccess)                                                                  \
+            return mi355lz4_detail::fail(MI355LZ4_E_HIP, "%s failed: %s (%s:%d)", #expr, hipGetErrorString(e_), \
+                                         __FILE__, __LINE__);                                  \
+    } while (0)
+
+struct DevBuf {
+    void *p = nullptr;
+    size_t cap = 0;
+};
+int dev_reserve(DevBuf &b, size_t bytes);
+int pin_reserve(DevBuf &b, size_t bytes);
+void dev_release(DevBuf &b);
+void pin_release(DevBuf &b);
+
+// The host copy pool (api.cpp): run all tasks, the calling thread working too; one large range, cut into slices.  Both return
+// when every byte is copied.
+struct CopyTask { uint8_t *dst; const uint8_t *src; size_t n; };
+void pool_run(const std::vector<CopyTask> &tasks);
+void pool_copy(uint8_t *dst, const uint8_t *src, size_t n);
+
+}  // namespace mi355lz4_detail
+
+struct mi355lz4_ctx {
+    using DevBuf = mi355lz4_detail::DevBuf;
+    int device = 0;
+    hipStream_t stream = nullptr;
+    bool ownStream = false;
+    int decoder = 0;
+    int linkedCompress = 0;                 // compress calls treat their blocks as consecutive blocks of one stream
+    int blockChecksum = 0;                  // every block's data is followed by its xxh32 (mi355lz4_set_block_checksum)
+    int compLevel = 0;                      // 0: k_encode (fast); 1..9: k_encode_hc (mi355lz4_set_compression_level)
+    int compExact = 0;                      // compress calls continue ONE reference-exact stream (mi355lz4_set_compress_exact)
+    // ... that stream's state (the device counterpart of LZ4_stream_t): currentOffset and dictSize here, the table and
+    // the previous array's last bytes in exState; fresh = the table is still to be zeroed (a new stream)
+    struct ExactStream { uint32_t cur = 0, dictSize = 0; int dictBytes = 0; bool fresh = true; int last[4] = {0, 0, 0, 0}; } ex;
+    DevBuf exState, exMeta, exTabs, exFlags;
+    DevBuf ckBuf;                           // ... the decode side's per-block verdicts (k_xxh32_verify)
+    hipEvent_t ckEvent = nullptr;           // ... end of the last decode that read them, and the stream it ran on
+    hipStream_t ckStream = nullptr;
+    // workspaces of the host-buffer API (grown on demand, reused across calls)
+    DevBuf in, slots, dense, out, offA, offB, lenA, lenB, res, scratch;
+    DevBuf tokBuf;                          // decoder variant 3: token lists
+    DevBuf tolPool, tolMeta;                // deferred-copy decode of a long linked stream (linked_replay.hpp)
+    DevBuf linkBuf, ptrBuf, pinStat;        // ... its failure count, control block and source pointers (linked_ptr.hpp)
+    DevBuf pinIn, pinOut;   // pinned host staging
+    DevBuf pinMeta;         // pinned: per-group sizes coming back from the device
+    hipStream_t sIn = nullptr, sOut = nullptr;   // copy streams of the pipelined host-buffer API (created on first use)
+    hipStream_t sK[2] = {nullptr, nullptr};   // compute streams: kernels of consecutive groups overlap
+    // a linked decode whose data half is still to be issued (mi355lz4_decompress_linked_begin / _end)
+    struct LinkedPlan {
+        bool active = false, split = false;
+        DecodeArgs a;
+        int first = 0, last = -1, pool = 0, seg = 0;
+    } plan;
+    // small-batch compression: per-segment sequence lists, one scratch buffer per stream the engine has been used on
+    // (the host pipelines run two groups at a time on two compute streams; work on ONE stream is ordered)
+    struct SegScratch { hipStream_t s = nullptr; DevBuf b; unsigned long long tick = 0; } seg[4];
+    int nSeg = 0;
+    unsigned long long segTick = 0;
+    int linkedAsyncCap = 0;                // > 0: linked device decodes do not wait on the host (mi355lz4_set_linked_async)
+    RuninState runin;                      // the run-in decode's adaptive state (linked_plan.hpp)
+    int linkedPath = -1;                   // diagnostics: how the last linked call was finished (LinkedPath; mi355lz4_debug_runin_state)
+    int runinShareE6 = -1;                 // diagnostics: the dictionary share the last linked call sampled, in millionths (-1: none)
+    int segMode = -1;                      // small-batch segments per block: -1 auto, 0 off, k forced (mi355lz4_set_segments)
+    hipEvent_t linkEvent = nullptr;        // end of the last linked decode's use of linkBuf / tolPool / tolMeta / ptrBuf
+    hipStream_t linkStream = nullptr;      // ... and the stream it ran on
+    bool linkBusy = false;
+    unsigned long long *stats = nullptr;   // diagnostics: device counters of the lane-parallel decoder (off by default)
+    uint32_t *cuDbg = nullptr;             // diagnostics: 16 words per block from the workgroup-per-block decoder (mi355lz4_debug_cu)
+};
+
+namespace mi355lz4_detail {
+
+// pageable host memory <-> device through pinned staging, on the engine's stream (api.cpp)
+int h2d_staged(mi355lz4_ctx *c, void *dstDev, const uint8_t *srcHost, size_t bytes);
+int d2h_staged(mi355lz4_ctx *c, uint8_t *dstHost, const void *srcDev, size_t bytes);
+
+// an engine's switches as the code above the C ABI sees them; _swap_ sets the switch, keeps the stream and returns the old value
+int engine_block_checksum(const mi355lz4_ctx *c);
+int engine_compression_level(const mi355lz4_ctx *c);
+int engine_compress_exact(const mi355lz4_ctx *c);
+int engine_swap_compress_exact(mi355lz4_ctx *c, int on);
+
+// the device layer as the host-buffer and legacy layers call it (api.cpp); accel is clamped to 1..65537
+EncodeArgs make_encode_args(const uint8_t *src, const uint64_t *srcOff, const int32_t *srcLen, uint64_t blockStride, int maxBlockLen,
+                            int nBlocks, int accel, int headerKind, uint8_t *slots, size_t slotStride, int32_t *framedLen);
+int encode_device(mi355lz4_ctx *c, const uint8_t *src, const uint64_t *srcOff, const int32_t *srcLen, uint64_t blockStride,
+                  int maxBlockLen, int nBlocks, int accel, int headerKind, uint8_t *slots, size_t slotStride, int32_t *framedLen,
+                  int lookBack, const int32_t *hostLen = nullptr);
+int decode_device(mi355lz4_ctx *c, const DecodeCall &d);
+int streams_check(const mi355lz4_ctx *c, const mi355lz4_cstreams *cs, int nBlocks, const int32_t *streamFirst,
+                  const int32_t *streamSlot, int nStreams, const char *who);
+int streams_enqueue(mi355lz4_ctx *c, mi355lz4_cstreams *cs, const EncodeArgs &a, int b0, int b1, const int32_t *streamFirst,
+                    const int32_t *streamSlot, int nStreams);
+int dstreams_check(const mi355lz4_ctx *c, const mi355lz4_dstreams *ds, int nBlocks, const int32_t *streamFirst,
+                   const int32_t *streamSlot, int nStreams, const char *who);
+int dstreams_enqueue(mi355lz4_ctx *c, mi355lz4_dstreams *ds, const DecodeCall &d, int b0, int b1, const int32_t *streamFirst,
+                     const int32_t *streamSlot, int nStreams);
+
+}  // namespace mi355lz4_detail

@@ -21,7 +21,7 @@
 #include <string>
 #include <vector>
 
-int engine_swap_compress_exact(mi355lz4_ctx *c, int on);   // api.cpp: sets the switch, keeps the stream; returns the old value
+using mi355lz4_detail::engine_swap_compress_exact;
 
 namespace streamly_lz4 {
 

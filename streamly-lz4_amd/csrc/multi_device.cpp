@@ -20,7 +20,9 @@
 #include <thread>
 #include <vector>
 
-#include "../../include/mi355lz4.h"
+#include "engine.hpp"
+
+using namespace mi355lz4_detail;
 
 struct mi355lz4_multi {
     std::vector<mi355lz4_ctx *> eng;
@@ -96,10 +98,6 @@ struct PartResult {
     size_t outLen = 0;
     int got = 0;
 };
-
-int engine_block_checksum(const mi355lz4_ctx *c);   // api.cpp
-int engine_compression_level(const mi355lz4_ctx *c);   // api.cpp
-int engine_compress_exact(const mi355lz4_ctx *c);      // api.cpp
 
 // Block checksums (mi355lz4_set_block_checksum) are a property of the stream a call reads or writes: every engine of the
 // handle must have the same setting.  -1: they disagree.

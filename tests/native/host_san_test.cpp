@@ -1,11 +1,12 @@
-// host_san_test.cpp -- sanitizer driver for the HOST side of libmi355lz4 (api.cpp + host_stream.cpp).
+// host_san_test.cpp -- sanitizer driver for the HOST side of libmi355lz4 (api.cpp, host_batch.cpp, legacy.cpp, host_stream.cpp).
 //
 // Built by `make asan` / `make tsan` (CPU only: the kernel launchers are stubbed by san_stubs.cpp, and
 // without a gfx950 device every engine call stops at MI355LZ4_E_NO_DEVICE).  What runs under the sanitizers:
 //   * the staging copy pool (api.cpp) hammered from several caller threads at once;
 //   * the stream state machines that need no codec: resizeChunks at every split size the reference tests
 //     (test/Main.hs:217-224), end mark, the frame-header parser, and their error paths;
-//   * the legacy LZ4_* entry points' no-device behaviour (create/free, compressBound, 0 / -1 returns);
+//   * the legacy LZ4_* entry points' (legacy.cpp) no-device behaviour (create/free, compressBound, 0 / -1 returns);
+//   * the one error message per thread that api.cpp keeps for every layer (host_batch.cpp's argument checks);
 //   * the decode planner (linked_plan.hpp): a table of call shape -> path.
 #include "../../include/lz4.h"
 #include "../../include/mi355lz4.h"
@@ -139,6 +140,27 @@ static void legacy_no_device()
     bool threw = false;
     try { streamly_lz4::Engine e(0); } catch (const streamly_lz4::Error &) { threw = true; }
     CHECK(threw);
+}
+
+// mi355lz4_last_error is ONE buffer per thread for the whole library: after a host-buffer call (host_batch.cpp) fails its argument
+// check, the message is that call's and no longer the one an engine call (api.cpp) left before it -- on every thread.
+static void one_last_error()
+{
+    auto check = [] {
+        CHECK(mi355lz4_create(nullptr, 0) == MI355LZ4_E_ARG && strstr(mi355lz4_last_error(), "mi355lz4_create") != nullptr);
+        const uint8_t cut[3] = {9, 0, 0};                          // a chain that ends inside its first header
+        int n = -1;
+        CHECK(mi355lz4_index_host(cut, sizeof(cut), 4, 65536, nullptr, nullptr, 8, &n) == MI355LZ4_E_STREAM && n == 0);
+        CHECK(strstr(mi355lz4_last_error(), "index_host: incomplete block header at offset 0") != nullptr);
+        CHECK(mi355lz4_create(nullptr, 0) == MI355LZ4_E_ARG);
+        size_t outLen = 0;
+        int got = 0;
+        CHECK(mi355lz4_decompress_partial(nullptr, cut, sizeof(cut), 4, 65536, nullptr, 16, nullptr, 0, &outLen, nullptr, -1, &got) == MI355LZ4_E_ARG);
+        CHECK(strcmp(mi355lz4_last_error(), "null ctx") == 0);
+    };
+    check();
+    std::thread other(check);
+    other.join();
 }
 
 // the frame reader's host half on valid, damaged and truncated frames: it either parses or throws, nothing else
@@ -551,6 +573,7 @@ int main()
     pool_stress();
     resize_checks();
     legacy_no_device();
+    one_last_error();
     if (failures) { fprintf(stderr, "host_san_test: %d failure(s)\n", failures); return 1; }
     printf("host_san_test ok\n");
     return 0;
