@@ -1,6 +1,6 @@
 #!/bin/bash
 # Development aid: build the library of a given commit (default HEAD) into streamly-lz4_amd/lib/variants/<name>.so so that
-# scripts/ab_time.py can time it beside the working tree's build.   usage: scripts/ab_base.sh [commit] [name] [extra flags]
+# scripts/ab_time.py can time it beside the working tree's build (kernels.hip includes its family files, csrc/kernels/*.inc, itself).   usage: scripts/ab_base.sh [commit] [name] [extra flags]
 set -e
 cd "$(dirname "$0")/.."
 C=${1:-HEAD}; N=${2:-base}; F=${3:-}

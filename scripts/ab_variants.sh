@@ -1,5 +1,5 @@
 #!/bin/bash
-# Development aid: build variants of the library with different -D settings into
+# Development aid: build variants of the library (kernels.hip includes its family files, csrc/kernels/*.inc, itself) with different -D settings into
 # streamly-lz4_amd/lib/variants/<name>.so   usage: scripts/ab_variants.sh name "-DPAR_RING=6144 ..." [name flags]...
 set -e
 cd "$(dirname "$0")/.."

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Development aid (CPU only): how many blocks a decode that starts WITHOUT its dictionary needs until a block comes
-out exact -- the run-in of the linked decode's pieces (kernels.hip, "RUN-IN DECODE").  A reference-written linked stream
+out exact -- the run-in of the linked decode's pieces (kernels/runin.inc, "RUN-IN DECODE").  A reference-written linked stream
 (oracle compressor == reference's, byte for byte); for every block as a starting point, the bytes that derive from the
 missing dictionary are followed block by block (byte-exact) until a block has none.
 usage: runin_sim.py [kind=text|lzsynth|pysrc|periodic] [blocks=120] [block_len=65536]"""

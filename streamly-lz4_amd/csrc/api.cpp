@@ -1,7 +1,7 @@
 // api.cpp -- C ABI of the MI355X LZ4 block engine (include/mi355lz4.h, include/lz4.h).
 //
 // Host-side plumbing only: argument checks, device workspaces, copies and
-// kernel launches.  All arithmetic of the hot path happens in kernels.hip.
+// kernel launches.  All arithmetic of the hot path happens in the kernels (kernels.hip, kernels/*.inc).
 // There is no CPU code path: without a gfx950 device every call fails.
 #include "engine.hpp"
 
@@ -664,7 +664,7 @@ int mi355lz4_detail::encode_device(mi355lz4_ctx *c, const uint8_t *src, const ui
         return finish();
     }
     // Small batches: with fewer blocks than the chip has wave slots (256 CUs x 16), a block is cut into segments that
-    // several waves compress at once (kernels.hip, "K2, small batches").  Segments of >= 4 KiB, at most 64 per block,
+    // several waves compress at once (kernels/encode.inc, "K2, small batches").  Segments of >= 4 KiB, at most 64 per block,
     // about two waves per slot in all; blocks of up to 4 MiB (24-bit positions in the records); independent blocks only.
     // MI355LZ4_SEG=0 turns it off, MI355LZ4_SEG=k forces k segments (tests).
     {
@@ -1021,7 +1021,7 @@ static int linked_finish(mi355lz4_ctx *c)
 }
 
 // The steps of a linked decode return STEP_NEXT or what the call returns; ending, they order the link scratch behind what they queued.
-// pinStat words: 0-7 the summary, 8-9 the share sample, 10-11 big-pass flags, 12-13 runCtl; _linked_end_last: 8-11 its own (below).
+// pinStat words: 0-7 the summary, 8-9 the share sample, 10-11 big-pass flags, 12-13 run.ctl; _linked_end_last: 8-11 its own (below).
 constexpr int STEP_NEXT = 1;
 static int link_done(mi355lz4_ctx *c) { link_scratch_release(c); return check_launch("decode launch"); }
 static int link_fail(mi355lz4_ctx *c, int rc) { link_scratch_release(c); return rc; }
@@ -1044,8 +1044,8 @@ static bool big_scratch(mi355lz4_ctx *c, DecodeArgs &a, int pass)
     (void)hipGetLastError();
     if (!ok) return false;
     uint8_t *meta = (uint8_t *)c->tolMeta.p;
-    a.zeroPage = meta; a.cuSnap = (uint8_t *)c->ptrBuf.p; a.cuPass = pass;
-    a.cuFlags = (uint32_t *)(meta + 65536); a.cuRes = (int32_t *)(meta + 65536 + ((size_t)a.nBlocks + 4) * sizeof(uint32_t));
+    a.run.zeroPage = meta;
+    a.cu = {(uint8_t *)c->ptrBuf.p, (uint32_t *)(meta + 65536), (int32_t *)(meta + 65536 + ((size_t)a.nBlocks + 4) * sizeof(uint32_t)), pass};   // snap, flags, res, pass
     return true;
 }
 // Big blocks (big_arm): every dependent block by the workgroup form against a GUESS of its dictionary -- zeros, then its predecessor's
@@ -1064,11 +1064,11 @@ static int linked_big(mi355lz4_ctx *c, DecodeArgs &a, const DecodeKnobs &k, cons
         uint32_t *flags = (uint32_t *)c->pinStat.p + 10;
         bool settled = false; int passes = 0;
         for (int pass = 1; pass <= BIG_PASSES && !settled; pass++) {
-            a.cuPass = pass; passes = pass;
+            a.cu.pass = pass; passes = pass;
             launch_cu_linked(a, pass > 1 || late, c->stream);
             if (hipGetLastError() != hipSuccess) break;
             if (pass == 1) continue;                                  // (every snapshot is new after the first pass)
-            LINK_TRY(hipMemcpyAsync(flags, a.cuFlags, 8, hipMemcpyDeviceToHost, c->stream));
+            LINK_TRY(hipMemcpyAsync(flags, a.cu.flags, 8, hipMemcpyDeviceToHost, c->stream));
             LINK_TRY(hipStreamSynchronize(c->stream));
             if (flags[1] != 0) break;                                 // a block this form cannot take
             settled = flags[0] == 0;
@@ -1080,7 +1080,7 @@ static int linked_big(mi355lz4_ctx *c, DecodeArgs &a, const DecodeKnobs &k, cons
         }
         (void)hipGetLastError();
     }
-    a.zeroPage = nullptr; a.cuSnap = nullptr; a.cuFlags = nullptr; a.cuRes = nullptr; a.cuPass = 0;
+    a.cu = {}; a.run.zeroPage = nullptr;
     return STEP_NEXT;
 }
 // Short runs (runs_take): every run walked by a wave of its own with the exact decoder and its dictionary, from a list of their starts
@@ -1089,8 +1089,8 @@ static int linked_runs(mi355lz4_ctx *c, DecodeArgs &a, const DecodeCall &d, cons
     if (!runs_take(d, m, k, st)) return STEP_NEXT;
     const int runs = (int)st.runs > 0 ? (int)st.runs : 1;
     if (int r = dev_reserve(c->tolMeta, ((size_t)runs + 1) * sizeof(int32_t))) return link_fail(c, r);
-    a.runList = (int32_t *)c->tolMeta.p; a.runCap = runs;
-    if (hipMemsetAsync(a.runList, 0, sizeof(int32_t), c->stream) != hipSuccess)
+    a.runs.list = (int32_t *)c->tolMeta.p; a.runs.cap = runs;
+    if (hipMemsetAsync(a.runs.list, 0, sizeof(int32_t), c->stream) != hipSuccess)
         return link_fail(c, fail(MI355LZ4_E_HIP, "decompress: the run list could not be cleared"));
     a.segFirst = (int)st.first; a.segEnd = (int)st.last + 1;
     launch_linked_runs(a, c->stream);
@@ -1098,8 +1098,8 @@ static int linked_runs(mi355lz4_ctx *c, DecodeArgs &a, const DecodeCall &d, cons
     return link_done(c);
 }
 // Long runs of dependent blocks (a reference-written stream is ONE) in pieces, every piece decoded from a few blocks in front of it
-// ("run-in": by then the dictionary is the true one; checked against what the piece in front wrote, redone where not: kernels.hip,
-// "RUN-IN DECODE").  Serial chain: run-in + piece blocks (0.53 ms per 64 KiB of text); one wave and a ring of two blocks per piece.
+// ("run-in": by then the dictionary is the true one; checked against what the piece in front wrote, redone where not:
+// kernels/runin.inc, "RUN-IN DECODE").  Serial chain: run-in + piece blocks (0.53 ms per 64 KiB of text); one wave and a ring of two blocks per piece.
 // Not finished (a broken block, rounds that run out, no scratch): finished segments are final, st is taken again for the rest.
 static int linked_runin(mi355lz4_ctx *c, DecodeArgs &a, const DecodeCall &d, const EngineMode &m, const DecodeKnobs &k, LinkStat &st)
 {
@@ -1119,29 +1119,29 @@ static int linked_runin(mi355lz4_ctx *c, DecodeArgs &a, const DecodeCall &d, con
     }
     if (p.use) runin_after_sample(p, k, span0, share);
     if (!p.use) return STEP_NEXT;
-    a.runSpin = k.runinSpin;
+    a.run.spin = k.runinSpin;
     const size_t nPiecesMax = ((size_t)p.segBlocks + p.piece - 1) / p.piece, metaBytes = 65536 + (size_t)p.segBlocks * 4 + nPiecesMax * 20 + 64;
     bool done = false;
     if (dev_reserve(c->ptrBuf, nPiecesMax * 2u * p.stride) == 0 && dev_reserve(c->tolMeta, metaBytes) == 0) {
         uint8_t *meta = (uint8_t *)c->tolMeta.p, *tail = meta + 65536 + (size_t)p.segBlocks * 4;
-        a.zeroPage = meta; a.ring = (uint8_t *)c->ptrBuf.p; a.ringStride = p.stride; a.runPiece = p.piece; a.runIn = p.runIn;
-        a.runRes = (int32_t *)(meta + 65536); a.runInfo = (int32_t *)tail;
-        a.runDirty = (uint32_t *)(tail + nPiecesMax * 16); a.runCtl = (uint32_t *)(tail + nPiecesMax * 20);
-        // (a kernel that did not launch must not read as "nothing left to do": runCtl was zeroed by the host)
+        a.run.zeroPage = meta; a.run.ring = (uint8_t *)c->ptrBuf.p; a.run.stride = p.stride; a.run.piece = p.piece; a.run.in = p.runIn;
+        a.run.res = (int32_t *)(meta + 65536); a.run.info = (int32_t *)tail;
+        a.run.dirty = (uint32_t *)(tail + nPiecesMax * 16); a.run.ctl = (uint32_t *)(tail + nPiecesMax * 20);
+        // (a kernel that did not launch must not read as "nothing left to do": run.ctl was zeroed by the host)
         uint32_t *ctl = pin + 12;
         LINK_TRY(hipMemsetAsync(meta, 0x00, 65536, c->stream));
         done = true;
         for (int s0 = first; s0 <= last && done; s0 += p.segBlocks) {
             a.segFirst = s0; a.segEnd = (s0 + p.segBlocks < last + 1) ? s0 + p.segBlocks : last + 1;
-            LINK_TRY(hipMemsetAsync(a.runCtl, 0, 8, c->stream));
+            LINK_TRY(hipMemsetAsync(a.run.ctl, 0, 8, c->stream));
             launch_runin_decode(a, c->stream);
             bool segDone = false, launched = hipGetLastError() == hipSuccess;
             for (int round = 0; round < RUNIN_ROUNDS && !segDone && launched; round++) {
-                a.runRound = round;
-                if (round) LINK_TRY(hipMemsetAsync(a.runCtl, 0, 4, c->stream));
+                a.run.round = round;
+                if (round) LINK_TRY(hipMemsetAsync(a.run.ctl, 0, 4, c->stream));
                 launch_runin_fix(a, c->stream);
                 if (hipGetLastError() != hipSuccess) { launched = false; break; }
-                LINK_TRY(hipMemcpyAsync(ctl, a.runCtl, 8, hipMemcpyDeviceToHost, c->stream));
+                LINK_TRY(hipMemcpyAsync(ctl, a.run.ctl, 8, hipMemcpyDeviceToHost, c->stream));
                 LINK_TRY(hipStreamSynchronize(c->stream));
                 if (ctl[1] != 0) break;                 // a block failed with the dictionary it got, or a chain of dirty pieces
                 segDone = ctl[0] == 0;
@@ -1152,8 +1152,7 @@ static int linked_runin(mi355lz4_ctx *c, DecodeArgs &a, const DecodeCall &d, con
         }
     }
     (void)hipGetLastError();                             // (only a failed reservation is left to swallow here)
-    a.ring = nullptr; a.zeroPage = nullptr; a.runRes = nullptr; a.runCtl = nullptr; a.runInfo = nullptr; a.runDirty = nullptr;
-    a.runPiece = 0; a.runIn = 0;
+    a.run = {};
     c->linkedPath = (int)(done ? (p.longRun ? LinkedPath::RunInLong : LinkedPath::RunIn) : LinkedPath::RunInGivenUp);
     if (done) return link_done(c);
     a.segFirst = 0; a.segEnd = a.nBlocks;
@@ -1174,20 +1173,20 @@ static int linked_pointer(mi355lz4_ctx *c, DecodeArgs &a, const DecodeCall &d, c
     int seg = p.pool;
     if (p.lists && dev_reserve(c->tolPool, (size_t)p.pool * p.per * tol_region_bytes()) == 0 &&
         dev_reserve(c->tolMeta, ((size_t)a.nBlocks * 3 + 4) * sizeof(int32_t)) == 0) {
-        a.tolPool = c->tolPool.p; a.tolRegions = p.pool * p.per; a.tolPer = p.per;
-        a.tolCounter = (uint32_t *)c->tolMeta.p; a.tolRegion = (int32_t *)c->tolMeta.p + 4;
-        a.tolCount = a.tolRegion + a.nBlocks; a.tolSize = a.tolCount + a.nBlocks;
+        a.tol.pool = c->tolPool.p; a.tol.regions = p.pool * p.per; a.tol.per = p.per;
+        a.tol.counter = (uint32_t *)c->tolMeta.p; a.tol.region = (int32_t *)c->tolMeta.p + 4;
+        a.tol.count = a.tol.region + a.nBlocks; a.tol.size = a.tol.count + a.nBlocks;
         if (p.usePtr && dev_reserve(c->ptrBuf, p.ptrs * sizeof(uint32_t)) == 0) {
-            a.ptr = (uint32_t *)c->ptrBuf.p; a.ptrCap = p.ptrs;
-            a.ptrCtl = (uint8_t *)c->linkBuf.p + 64;
-            a.ptrBad = (uint32_t *)((uint8_t *)c->linkBuf.p + 64 + ptr_ctl_bytes());
+            a.ptr.buf = (uint32_t *)c->ptrBuf.p; a.ptr.cap = p.ptrs;
+            a.ptr.ctl = (uint8_t *)c->linkBuf.p + 64;
+            a.ptr.bad = (uint32_t *)((uint8_t *)c->linkBuf.p + 64 + ptr_ctl_bytes());
             seg = p.seg;
         }
     }
     (void)hipGetLastError();          // scratch that could not be had is not an error: the serial walk needs none
     c->plan.active = true;
     c->plan.a = a; c->plan.first = first; c->plan.last = last; c->plan.pool = p.pool; c->plan.seg = seg;
-    c->plan.split = linked_split(d.splitOk, a.ptr != nullptr, span, seg, p.pool);
+    c->plan.split = linked_split(d.splitOk, a.ptr.buf != nullptr, span, seg, p.pool);
     if (c->plan.split) {
         a.segFirst = first; a.segEnd = last + 1;
         launch_linked_tolerant(a, c->stream);
@@ -1237,8 +1236,8 @@ static int decode_device_impl(mi355lz4_ctx *c, const DecodeCall &d, const int32_
 #ifdef MI355LZ4_EXPERIMENTS
     case FirstPass::Tok:   // experiment: the parse as a pass of its own (token lists), then the list-driven decoder
         if (dev_reserve(c->tokBuf, (size_t)(d.framedLen >> 1) + 192 + ((size_t)d.nBlocks + 1) * sizeof(int32_t)) == 0) {
-            a.tokCnt = (int32_t *)c->tokBuf.p;
-            a.tokList = (uint8_t *)c->tokBuf.p + ((((size_t)d.nBlocks + 1) * sizeof(int32_t) + 63) & ~(size_t)63);
+            a.tok.cnt = (int32_t *)c->tokBuf.p;
+            a.tok.list = (uint8_t *)c->tokBuf.p + ((((size_t)d.nBlocks + 1) * sizeof(int32_t) + 63) & ~(size_t)63);
             launch_decode_tok(a, c->stream);
             break;
         }
@@ -1336,22 +1335,22 @@ extern "C" int mi355lz4_decompress_linked_end_last(mi355lz4_ctx *c)
     if (!c) return fail(MI355LZ4_E_ARG, "null ctx");
     HIP_TRY(hipSetDevice(c->device));
     if (!c->plan.active) return 1;                           // no block of the range needed its dictionary: all final
-    if (!c->plan.split || !c->plan.a.ptrCtl || c->plan.a.streamFirst) return 0;
+    if (!c->plan.split || !c->plan.a.ptr.ctl || c->plan.a.streamFirst) return 0;
     DecodeArgs a = c->plan.a;
     const int last = a.nBlocks - 1;
     int r;
     if ((r = pin_reserve(c->pinStat, 48))) return r;
     // {lastOpen, the stream's flag, the last block's standalone result, whether it has a list}
     uint32_t *stat = (uint32_t *)c->pinStat.p + 8;
-    uint8_t *ctl = (uint8_t *)a.ptrCtl;
+    uint8_t *ctl = (uint8_t *)a.ptr.ctl;
     stat[0] = stat[1] = 0; stat[3] = 0;
     if (last >= a.segFirst && last < a.segEnd) {
         HIP_TRY(hipMemsetAsync(ctl + ptr_ctl_last_open_offset(), 0, sizeof(uint32_t), c->stream));
         a.onlyBlk = last;
         launch_linked_fetch_block(a, c->stream);
         HIP_TRY(hipMemcpyAsync(&stat[0], ctl + ptr_ctl_last_open_offset(), 4, hipMemcpyDeviceToHost, c->stream));
-        HIP_TRY(hipMemcpyAsync(&stat[1], a.ptrBad, 4, hipMemcpyDeviceToHost, c->stream));
-        HIP_TRY(hipMemcpyAsync(&stat[3], a.tolRegion + last, 4, hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(hipMemcpyAsync(&stat[1], a.ptr.bad, 4, hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(hipMemcpyAsync(&stat[3], a.tol.region + last, 4, hipMemcpyDeviceToHost, c->stream));
     }
     HIP_TRY(hipMemcpyAsync(&stat[2], a.result + last, 4, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));

@@ -152,7 +152,7 @@ enum { PS_BATCHES, PS_SEQS, PS_ROUNDS, PS_MATCH_ITERS, PS_LIT_ITERS, PS_HANDOVER
 // TOL: tolerant (deferred-copy) decode of a block of a linked stream without its dictionary, see TolCtx in
 // decode_seq.hpp: matches that start before the block, or whose source touches a tainted granule, are
 // recorded in tol->list instead of being copied.
-// LIST: the token positions of a batch come from a list made by a separate pass (kernels.hip, k_walk_tokens: one LANE per
+// LIST: the token positions of a batch come from a list made by a separate pass (kernels/decode_tok.inc, k_walk_tokens: one LANE per
 // block walks the token chain, which costs a fraction of finding 64 tokens at once by speculation) instead of steps 2-3.
 // list[k] = compressed bytes of sequence k (0 = not known from here on), listLen entries.  The list is a HINT: every
 // position taken from it is checked against the successor the lane in front computes from the token bytes themselves, so

@@ -78,7 +78,7 @@ __device__ __forceinline__ void wave_copy_match(uint8_t *dstGeneric, int op, int
 // appended to the block's deferred list and its destination is marked in a taint bitmap (one bit per
 // granule of output).  A match whose source touches a tainted granule is deferred too, and taints its own
 // destination.  Everything else is copied as usual.  A later pass walks the stream in order and replays each
-// block's list with the previous block's final output beside it (kernels.hip: k_decode_fixup_regions).
+// block's list with the previous block's final output beside it (kernels/linked_tolerant.inc: k_decode_fixup_regions).
 // ---------------------------------------------------------------------------
 // One deferred match in 8 bytes: destination (22 bits), length (22 bits), offset (16 bits; the source is
 // destination - offset and is negative when the match starts in the previous block's output).  Blocks of up to

@@ -9,7 +9,7 @@
 // LZ4_count (256 bytes per step), literal copies, length runs, and the table passes of the chain driver (zero, renorm,
 // canonicalise, load, store).
 //
-// Chain driver (k_exact_chain / k_exact_verify / k_exact_finish in kernels.hip): a call's blocks are cut into pieces of
+// Chain driver (k_exact_chain / k_exact_verify / k_exact_finish in kernels/encode.inc): a call's blocks are cut into pieces of
 // P blocks.  Piece p > 0 starts R blocks early from a zeroed table (the run-in), records the canonical table it assumed
 // at its first block and the canonical table after its last block; a piece is exact when its predecessor is and the two
 // tables agree (api.cpp, exact_encode).  Canonical: an entry no position of the next block can use -- below

@@ -1,4 +1,5 @@
-// kernels.h -- launch interface between the C-ABI layer (api.cpp) and kernels.hip.
+// kernels.h -- launch interface between the host layers (api.cpp, host_batch.cpp, legacy.cpp, host_stream.cpp, multi_device.cpp)
+// and the kernels (kernels.hip and its family files, kernels/*.inc).
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -32,54 +33,69 @@ struct DecodeArgs {
     int nStreams;
     int lookBack;                 // linked, one stream: blocks of the SAME stream that precede block 0 in result[] /
                                   // outOff[] (already final); lets a long stream be decoded range by range
-    // deferred-copy decode of one long linked stream (linked_replay.hpp): per-block state of the tolerant pass
-    // and the pool its deferred lists live in; all null when the pool is not available
-    void *tolPool;                // TolEntry[tolRegions][TOL_LIST_CAP]
-    int tolRegions;
-    int tolPer;                   // list regions per block of a tolerant launch: block segFirst + i owns regions [i * tolPer, (i + 1) * tolPer)
-    uint32_t *tolCounter;         // regions handed out so far
-    int32_t *tolRegion;           // per block: region index, or -1 (no list: serial path)
-    int32_t *tolCount;            // per block: entries appended (may exceed the capacity: overflow)
-    int32_t *tolSize;             // per block: result of the tolerant decode
+    // Below, the fields one decode path alone arms are grouped by that path (a group is reset with `a.tol = {}`); what several
+    // paths read stays flat.  The groups sit where their fields always sat: the layout of the kernel argument is part of the build.
+    // deferred-copy decode of one long linked stream (linked_replay.hpp; kernels/linked_tolerant.inc, read by the pointer passes
+    // too): per-block state of the tolerant pass and the pool its deferred lists live in; all null when the pool is not available
+    struct {
+        void *pool;               // TolEntry[regions][TOL_LIST_CAP]
+        int regions;
+        int per;                  // list regions per block of a tolerant launch: block segFirst + i owns regions [i * per, (i + 1) * per)
+        uint32_t *counter;        // regions handed out so far
+        int32_t *region;          // per block: region index, or -1 (no list: serial path)
+        int32_t *count;           // per block: entries appended (may exceed the capacity: overflow)
+        int32_t *size;            // per block: result of the tolerant decode
+    } tol;
     // one long linked stream, data-parallel second pass (linked_ptr.hpp)
     uint32_t *linkStat;           // filled by the standalone pass: {blocks with a codec error, first, last}
     int segFirst, segEnd;         // blocks the second-pass kernels cover in this launch
-    uint32_t *ptr;                // source pointers of the segment's bytes
-    uint64_t ptrCap;              // ... capacity in pointers
-    void *ptrCtl;                 // PtrCtl
-    uint32_t *ptrBad;             // per stream (one entry without streamFirst): left to the serial walk
+    struct {                      // the pointer passes (kernels/linked_ptr.inc)
+        uint32_t *buf;            // source pointers of the segment's bytes
+        uint64_t cap;             // ... capacity in pointers
+        void *ctl;                // PtrCtl
+        uint32_t *bad;            // per stream (one entry without streamFirst): left to the serial walk
+    } ptr;
     int asyncGate;                // second-pass kernels return at once when linkStat[0] == 0 (asynchronous linked decode)
     int onlyBlk;                  // >= 0: the fetch covers this block alone (mi355lz4_decompress_linked_end_last); -1: all
-    // run starts of a linked stream's dependent blocks (k_run_starts -> k_decode_fixup_runs): runList[0] = count,
-    // runList[1..] = first block of each run, at most runCap of them; null: the launch covers one run that starts at segFirst
-    int32_t *runList;
-    int runCap;
-    // long linked streams, run-in decode (kernels.hip, k_runin_*): pieces of runPiece consecutive blocks of [segFirst, segEnd)
-    uint8_t *ring;                // scratch: two blocks per piece (piece p at ring + p * 2 * ringStride)
-    uint64_t ringStride;          // >= the largest block capacity
-    const uint8_t *zeroPage;      // 64 KiB of 0x00: the stand-in for the dictionary of the block a run-in starts at
-    int runPiece;                 // blocks per piece
-    int runIn;                    // blocks a piece decodes in front of its own (<= 64)
-    int runSpin;                  // k_runin_fix: how many times a piece polls for the piece in front of it before it leaves itself to the next round
-    int runRound;                 // k_runin_fix: the round this launch is
-    int32_t *runRes;              // per block of the segment: its result (result[] is written when everything is final)
-    int32_t *runInfo;             // per piece {block the run-in's dictionary came from | -1 | -2 exact, its length, its ring slot, -}
-    uint32_t *runDirty;           // per piece: the round in which it is to be redone, 0xffffffff = none
-    uint32_t *runCtl;             // [0] pieces marked for the next round, [1] give the call up (1: a block failed, 2: a chain of dirty pieces)
-    // experiment builds only (MI355LZ4_EXPERIMENTS; decode_par.hpp, LIST): block blk's token list lives at tokList +
-    // blockOff[blk] / 2 (a sequence is at least three compressed bytes), tokCnt[blk] entries; both null without the list pass
-    uint8_t *tokList;
-    int32_t *tokCnt;
+    // run starts of a linked stream's dependent blocks (k_run_starts -> k_decode_fixup_runs, kernels/linked_walk.inc): list[0] = count,
+    // list[1..] = first block of each run, at most cap of them; null: the launch covers one run that starts at segFirst
+    struct {
+        int32_t *list;
+        int cap;
+    } runs;
+    // long linked streams, run-in decode (kernels/runin.inc, k_runin_*): pieces of `piece` consecutive blocks of [segFirst, segEnd)
+    struct {
+        uint8_t *ring;            // scratch: two blocks per piece (piece p at ring + p * 2 * stride)
+        uint64_t stride;          // >= the largest block capacity
+        const uint8_t *zeroPage;  // 64 KiB of 0x00: the stand-in for the dictionary of the block a run-in starts at.  The big linked
+                                  // blocks (cu, below) read it too, for their first pass: that path sets and clears it beside its own group
+        int piece;                // blocks per piece
+        int in;                   // blocks a piece decodes in front of its own (<= 64)
+        int spin;                 // k_runin_fix: how many times a piece polls for the piece in front of it before it leaves itself to the next round
+        int round;                // k_runin_fix: the round this launch is
+        int32_t *res;             // per block of the segment: its result (result[] is written when everything is final)
+        int32_t *info;            // per piece {block the run-in's dictionary came from | -1 | -2 exact, its length, its ring slot, -}
+        uint32_t *dirty;          // per piece: the round in which it is to be redone, 0xffffffff = none
+        uint32_t *ctl;            // [0] pieces marked for the next round, [1] give the call up (1: a block failed, 2: a chain of dirty pieces)
+    } run;
+    // experiment builds only (MI355LZ4_EXPERIMENTS; decode_par.hpp, LIST; kernels/decode_tok.inc): block blk's token list lives at list +
+    // blockOff[blk] / 2 (a sequence is at least three compressed bytes), cnt[blk] entries; both null without the list pass
+    struct {
+        uint8_t *list;
+        int32_t *cnt;
+    } tok;
     // diagnostics of the workgroup-per-block decoder (mi355lz4_debug_cu): 16 words per block, null = off
     uint32_t *cuDbg;
     int cuBail;                 // workgroup-per-block decoder: leave blocks that do not suit it (hardly compressible; long literal runs) to the lane-parallel one at once (decoder variant 0; variant 4 keeps them)
-    // big linked blocks by the workgroup-per-block decoder (launch_cu_linked): every dependent block decoded with a guess of its
-    // dictionary -- zeros in pass 1, from pass 2 on a snapshot of the last 64 KiB its predecessor decoded to in the pass before --
-    // until no snapshot changes any more
-    uint8_t *cuSnap;            // [nBlocks][65536]
-    uint32_t *cuFlags;          // [0] snapshots that changed in the last launch_cu_tails, [1] blocks the form cannot take, [2 + k] block k's snapshot changed
-    int32_t *cuRes;             // [nBlocks] results of the passes (published by the caller when the snapshots have settled)
-    int cuPass;
+    // big linked blocks by the workgroup-per-block decoder (launch_cu_linked, kernels/decode_par_cu.inc): every dependent block decoded with
+    // a guess of its dictionary -- zeros (run.zeroPage) in pass 1, from pass 2 on a snapshot of the last 64 KiB its predecessor decoded to in
+    // the pass before -- until no snapshot changes any more
+    struct {
+        uint8_t *snap;          // [nBlocks][65536]
+        uint32_t *flags;        // [0] snapshots that changed in the last launch_cu_tails, [1] blocks the form cannot take, [2 + k] block k's snapshot changed
+        int32_t *res;           // [nBlocks] results of the passes (published by the caller when the snapshots have settled)
+        int pass;
+    } cu;
     // block checksums (mi355lz4_set_block_checksum): every block's data is followed by a 4-byte xxh32 trailer, and
     // ckFail[blk] != 0 says k_xxh32_verify found that they do not match; null = no trailers (read_block_header)
     const int32_t *ckFail = nullptr;
@@ -133,7 +149,7 @@ struct ExactArgs {
     int nPieces;
 };
 
-// many reference-exact streams in one call (mi355lz4_compress_streams_device; kernels.hip, k_exact_streams).  One slot of a
+// many reference-exact streams in one call (mi355lz4_compress_streams_device; kernels/encode.inc, k_exact_streams).  One slot of a
 // mi355lz4_cstreams is the device form of LZ4_stream_t: the table, the previous array's last 64 KiB and the scalars.
 #define CSTREAM_SCALAR_OFF ((size_t)EXACT_TABLE * 4)              // uint32 {currentOffset, dictSize, saved bytes, -}: zeroed with the table
 #define CSTREAM_DICT_OFF   (CSTREAM_SCALAR_OFF + 64)              // the saved dictionary bytes
@@ -145,7 +161,7 @@ struct ExactStreamsArgs {
     uint8_t *state;              // the set's slots, CSTREAM_SLOT_BYTES each
 };
 
-// many linked decode streams continued across calls (mi355lz4_decompress_dstreams_device; kernels.hip, k_decode_dstreams).
+// many linked decode streams continued across calls (mi355lz4_decompress_dstreams_device; kernels/linked_walk.inc, k_decode_dstreams).
 // One slot of a mi355lz4_dstreams is the device form of LZ4_streamDecode_t for separately allocated blocks: the last
 // min(r, 65536) bytes of the stream's last block that decoded to r > 0 bytes, at the slot's start, and that count.
 #define DSTREAM_DICT_BYTES 65536
@@ -158,7 +174,7 @@ struct DStreamsArgs {
     uint8_t *state;              // the set's slots, DSTREAM_SLOT_BYTES each
 };
 
-// small batches: a block's segments are compressed by several waves (kernels.hip, K2 small batches)
+// small batches: a block's segments are compressed by several waves (kernels/encode.inc, "K2, small batches")
 struct EncodeSegArgs {
     EncodeArgs e;
     int segs;                    // segments per block
@@ -177,7 +193,7 @@ void launch_decode_cu(const DecodeArgs &a, hipStream_t s);       // one workgrou
 // their target does not cut short, the others left to the lane-parallel form; anything else = the lane-parallel form
 void launch_decode_partial(const DecodeArgs &a, int form, hipStream_t s);
 #ifdef MI355LZ4_EXPERIMENTS
-void launch_decode_tok(const DecodeArgs &a, hipStream_t s);      // token lists (a.tokList / a.tokCnt), then the list-driven decoder
+void launch_decode_tok(const DecodeArgs &a, hipStream_t s);      // token lists (a.tok.list / a.tok.cnt), then the list-driven decoder
 #endif
 #define PAR_STATS_COUNT 32
 void launch_linked_tolerant(const DecodeArgs &a, hipStream_t s);   // both cover blocks [a.segFirst, a.segEnd)
@@ -187,12 +203,12 @@ void launch_linked_resolve_b(const DecodeArgs &a, hipStream_t s);   // data: fet
 void launch_linked_fetch_block(const DecodeArgs &a, hipStream_t s);  // data: the fetch of block a.onlyBlk alone; PtrCtl::lastOpen tells whether it is complete
 size_t ptr_ctl_last_open_offset();
 void launch_longest_stream(const DecodeArgs &a, hipStream_t s);   // linkStat[3]
-void launch_cu_linked(const DecodeArgs &a, bool decode, hipStream_t s);   // one pass over the dependent blocks (a.cuPass; decode = false: the first launch has made it), then the snapshots
-void launch_cu_publish(const DecodeArgs &a, hipStream_t s);      // a.cuRes -> a.result for the dependent blocks
+void launch_cu_linked(const DecodeArgs &a, bool decode, hipStream_t s);   // one pass over the dependent blocks (a.cu.pass; decode = false: the first launch has made it), then the snapshots
+void launch_cu_publish(const DecodeArgs &a, hipStream_t s);      // a.cu.res -> a.result for the dependent blocks
 void launch_dict_share(const DecodeArgs &a, int step, int count, hipStream_t s);   // linkStat[8], [9]: bytes taken directly from the dictionary / bytes walked, over `count` blocks from a.segFirst on
 void launch_link_stat(const DecodeArgs &a, hipStream_t s);       // linkStat from result[] (the decode launchers call it themselves)
 void launch_runin_decode(const DecodeArgs &a, hipStream_t s);    // long linked stream: every piece with its run-in + the comparison
-void launch_runin_fix(const DecodeArgs &a, hipStream_t s);       // ... one round (a.runRound) of pieces to be redone
+void launch_runin_fix(const DecodeArgs &a, hipStream_t s);       // ... one round (a.run.round) of pieces to be redone
 void launch_runin_publish(const DecodeArgs &a, hipStream_t s);   // ... results into result[]
 void launch_linked_runs(const DecodeArgs &a, hipStream_t s);      // one stream, short runs of dependent blocks: one wave per run, exact decoder with dictionary
 size_t ptr_ctl_bytes();

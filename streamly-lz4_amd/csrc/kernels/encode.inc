@@ -1,0 +1,437 @@
+// kernels/encode.inc -- the encoders: k_encode, k_encode_hc, the reference-exact chain and streams, the segment encoder of small batches.
+// A part of kernels.hip, the one device translation unit: included there, in this order, and not compiled on its own.
+// ---------------------------------------------------------------------------
+// K2: encode
+// ---------------------------------------------------------------------------
+// MOD: table entries are positions modulo 64 Ki (encode_wave.hpp, tab_candidate): needed when positions run beyond
+// 64 Ki -- blocks above 64 KiB, or a dictionary in front of the block (linked compression).  The table is the same
+// size either way, so every block size runs at the same occupancy (a table of 32-bit positions would halve it).
+#ifndef ENC_WAVES_PER_EU
+#define ENC_WAVES_PER_EU 4
+#endif
+// PAIR: two dense windows per step (encode_wave.hpp): blocks of up to 64 KiB, independent or linked (measured: +6 % /
+// +5 %); blocks above 64 KiB run one window per step (-9 % with pairs).
+template <bool MOD, bool PAIR>
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(ENC_WAVES_PER_EU, ENC_WAVES_PER_EU))) void k_encode(EncodeArgs a)
+{
+#ifndef ENC_LDS_PAD
+#define ENC_LDS_PAD 0
+#endif
+    // positions + tags (encode_wave.hpp): 10 KiB, 16 waves per CU (the ENC_STAGE experiment's 256 bytes behind them make it 15)
+    __shared__ __attribute__((aligned(16))) uint16_t table[ENC_TABLE_ENTRIES + ENC_LDS_PAD + ((PAIR && ENC_STAGE) ? 128 : 0)];
+    const int blk = (int)blockIdx.x;
+    const uint64_t off = a.srcOff ? a.srcOff[blk] : (uint64_t)blk * a.blockStride;
+    const int n = a.srcLen ? a.srcLen[blk] : a.uniformLen;
+    uint8_t *slot = a.slots + (size_t)blk * a.slotStride;
+    int dictLen = 0;
+    if (MOD && a.linked && (blk > 0 || a.lookBack > 0)) {
+        // linked stream: the block before is the dictionary when it lies directly in front of this one
+        const uint64_t poff = a.srcOff ? a.srcOff[blk - 1] : (uint64_t)(blk - 1) * a.blockStride;
+        const int pn = a.srcLen ? a.srcLen[blk - 1] : a.uniformLen;
+        if (pn > 0 && poff + (uint64_t)pn == off) dictLen = min(pn, 65536);
+    }
+    int c = 0;
+    if (n >= 0 && (MOD || n <= 65536))
+        c = encode_block_wave<uint16_t, MOD, false, PAIR>(a.src + off, n, slot + a.headerKind, a.accel, table, a.stats, dictLen);
+    if (lane_id() == 0) {
+        store_le32(slot, c);                                   // Internal/LZ4.hs:262
+        if (a.headerKind == 8) store_le32(slot + 4, n);        // Internal/LZ4.hs:261
+        a.framedLen[blk] = (c > 0) ? a.headerKind + c : 0;
+    }
+}
+
+void launch_encode(const EncodeArgs &a, bool bigBlocks, hipStream_t s)
+{
+    if (a.nBlocks <= 0) return;
+    const dim3 grid((unsigned)a.nBlocks), wg(64);
+    if (bigBlocks) hipLaunchKernelGGL((k_encode<true, false>), grid, wg, 0, s, a);
+    else if (a.linked) hipLaunchKernelGGL((k_encode<true, true>), grid, wg, 0, s, a);
+#ifdef ENC_EXP_NOPAIR
+    else hipLaunchKernelGGL((k_encode<false, false>), grid, wg, 0, s, a);
+#else
+    else hipLaunchKernelGGL((k_encode<false, true>), grid, wg, 0, s, a);
+#endif
+}
+
+// ---------------------------------------------------------------------------
+// K2, high-compression levels (encode_hc.hpp): one workgroup of HC_THREADS per block, all of a CU's LDS, a persistent grid
+// of one workgroup per CU striding over the blocks.  Same slots, headers, framedLen and dictionary as k_encode.
+// ---------------------------------------------------------------------------
+__global__ __launch_bounds__(HC_THREADS) void k_encode_hc(EncodeArgs a, int depth)
+{
+    __shared__ HcLds L;
+    for (int blk = (int)blockIdx.x; blk < a.nBlocks; blk += (int)gridDim.x) {
+        const uint64_t off = a.srcOff ? a.srcOff[blk] : (uint64_t)blk * a.blockStride;
+        const int n = a.srcLen ? a.srcLen[blk] : a.uniformLen;
+        uint8_t *slot = a.slots + (size_t)blk * a.slotStride;
+        int dictLen = 0;
+        if (a.linked && (blk > 0 || a.lookBack > 0)) {           // k_encode's dictionary: the block directly in front
+            const uint64_t poff = a.srcOff ? a.srcOff[blk - 1] : (uint64_t)(blk - 1) * a.blockStride;
+            const int pn = a.srcLen ? a.srcLen[blk - 1] : a.uniformLen;
+            if (pn > 0 && poff + (uint64_t)pn == off) dictLen = min(pn, 65536);
+        }
+        int c = 0;
+        if (n >= 0) c = encode_block_hc(L, a.src + off, n, dictLen, slot + a.headerKind, depth);
+        if (threadIdx.x == 0) {
+            store_le32(slot, c);
+            if (a.headerKind == 8) store_le32(slot + 4, n);
+            a.framedLen[blk] = (c > 0) ? a.headerKind + c : 0;
+        }
+    }
+}
+
+void launch_encode_hc(const EncodeArgs &a, int level, hipStream_t s)
+{
+    if (a.nBlocks <= 0) return;
+    static int cus[64];
+    int dev = 0;
+    (void)hipGetDevice(&dev);
+    int &nc = cus[dev & 63];
+    if (nc <= 0 && hipDeviceGetAttribute(&nc, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) nc = 256;
+    const int depth = 1 << (min(level, 9) - 1);
+    const unsigned grid = (unsigned)min(a.nBlocks, max(nc, 1));
+    hipLaunchKernelGGL(k_encode_hc, dim3(grid), dim3(HC_THREADS), 0, s, a, depth);
+}
+
+// ---------------------------------------------------------------------------
+// K2, reference-exact compression (encode_exact.hpp, DESIGN.md 7d).  One wave per piece of a call, its hash table in LDS.
+// ---------------------------------------------------------------------------
+// canonical form of table entry v for a block (DESIGN 7d): the block's renorm applied, entries that no position of the
+// block can use (below start - 65536) read 0
+__device__ __forceinline__ uint32_t exact_canon(uint32_t v, uint32_t start, uint32_t delta)
+{
+    v = (v < delta) ? 0u : v - delta;
+    return (start > 65536u && v < start - 65536u) ? 0u : v;
+}
+
+__device__ __forceinline__ dev_v4 exact_canon4(dev_v4 v, uint32_t start, uint32_t delta)
+{
+    return dev_v4{exact_canon(v.x, start, delta), exact_canon(v.y, start, delta), exact_canon(v.z, start, delta),
+                  exact_canon(v.w, start, delta)};
+}
+
+// the byte range of block j of a call
+__device__ __forceinline__ const uint8_t *exact_src(const EncodeArgs &e, int j)
+{
+    return e.src + (e.srcOff ? e.srcOff[j] : (uint64_t)j * e.blockStride);
+}
+
+// piece p = first + blockIdx.x owns blocks [p*P, min(p*P + P, n)).  Speculating (redo = 0), it starts R blocks early
+// from a zeroed table, or from the stream's state at block 0 when the run-in reaches it (then it is exact by
+// construction), and records assumed[p] at its first block.  Redoing, it starts at its first block from finalT[p-1].
+// Either way it leaves finalT[p] and writes the slots, headers and framedLen of the blocks it owns.
+__global__ __launch_bounds__(LZ4_WAVE) void k_exact_chain(ExactArgs x, int first, int redo)
+{
+    __shared__ dev_v4 tab4[EXACT_TABLE / 4];
+    uint32_t *tab = (uint32_t *)tab4;
+    const int lane = lane_id();
+    const int p = first + (int)blockIdx.x;
+    const int n = x.e.nBlocks;
+    const int own0 = p * x.piece, own1 = min(own0 + x.piece, n);
+    int start = own0;
+    const uint32_t *init = nullptr;
+    if (redo) init = x.finalT + (size_t)(p - 1) * EXACT_TABLE;
+    else if (p == 0 || own0 - x.runin <= 0) { start = 0; init = x.state; }
+    else start = own0 - x.runin;
+    for (int i = lane; i < EXACT_TABLE / 4; i += LZ4_WAVE)
+        tab4[i] = init ? as_global((const dev_v4 *)init)[i] : dev_v4{0u, 0u, 0u, 0u};
+    __syncthreads();
+    for (int j = start; j < own1; j++) {
+        const ExactBlock m = x.meta[j];
+        // LZ4_renormDictT, cbits/lz4.c:1545-1562.  finalT[p-1] is already block own0's table with its renorm applied
+        // (exact_canon4(.., next.delta) below): a redo starts behind that renorm and must not apply it a second time.
+        if (m.delta && !(redo && j == own0)) {
+            for (int i = lane; i < EXACT_TABLE / 4; i += LZ4_WAVE) tab4[i] = exact_canon4(tab4[i], 0u, m.delta);
+            __syncthreads();
+        }
+        if (!redo && j == own0 && p > 0) {
+            dev_v4 *as = (dev_v4 *)(x.assumed + (size_t)p * EXACT_TABLE);
+            for (int i = lane; i < EXACT_TABLE / 4; i += LZ4_WAVE) as_global(as)[i] = exact_canon4(tab4[i], m.start, 0u);
+        }
+        const bool write = j >= own0;
+        const uint8_t *src = exact_src(x.e, j);
+        const uint8_t *dictEnd = j > 0 ? exact_src(x.e, j - 1) + x.meta[j - 1].n : x.dict0 + x.dict0Len;
+        uint8_t *slot = x.e.slots + (size_t)j * x.e.slotStride;
+        const int cap = m.n + m.n / 255 + 16;                           // LZ4_compressBound
+        int c;
+        if (m.n == 0) {                                                 // cbits/lz4.c:1263-1273
+            c = 1;
+            if (write && lane == 0) slot[x.e.headerKind] = 0;
+        } else {
+            c = exact_encode_block(tab, src, m.n, dictEnd, m, (uint32_t)x.e.accel, slot + x.e.headerKind, cap, write);
+        }
+        if (write && lane == 0) {
+            store_le32(slot, c);
+            if (x.e.headerKind == 8) store_le32(slot + 4, m.n);
+            x.e.framedLen[j] = (c > 0) ? x.e.headerKind + c : 0;
+        }
+        __syncthreads();
+    }
+    const ExactBlock next = x.meta[own1];
+    dev_v4 *fin = (dev_v4 *)(x.finalT + (size_t)p * EXACT_TABLE);
+    for (int i = lane; i < EXACT_TABLE / 4; i += LZ4_WAVE) as_global(fin)[i] = exact_canon4(tab4[i], next.start, next.delta);
+}
+
+// eq[p] = (finalT[p-1] == assumed[p]) for p = first + blockIdx.x (first >= 1)
+__global__ __launch_bounds__(LZ4_WAVE) void k_exact_verify(ExactArgs x, int first)
+{
+    const int p = first + (int)blockIdx.x;
+    const dev_v4 *f = (const dev_v4 *)(x.finalT + (size_t)(p - 1) * EXACT_TABLE);
+    const dev_v4 *a = (const dev_v4 *)(x.assumed + (size_t)p * EXACT_TABLE);
+    bool same = true;
+    for (int i = lane_id(); i < EXACT_TABLE / 4; i += LZ4_WAVE) {
+        const dev_v4 u = as_global(f)[i], v = as_global(a)[i];
+        same = same && u.x == v.x && u.y == v.y && u.z == v.z && u.w == v.w;
+    }
+    const bool all = __ballot(!same) == 0;
+    if (lane_id() == 0) x.eq[p] = all ? 1 : 0;
+}
+
+// the stream's state after the call: the last piece's table, and the last array's last bytes (the next call's dictionary)
+__global__ __launch_bounds__(256) void k_exact_finish(ExactArgs x)
+{
+    const dev_v4 *fin = (const dev_v4 *)(x.finalT + (size_t)(x.nPieces - 1) * EXACT_TABLE);
+    for (int i = (int)threadIdx.x; i < EXACT_TABLE / 4; i += (int)blockDim.x) as_global((dev_v4 *)x.state)[i] = as_global(fin)[i];
+    const int last = x.e.nBlocks - 1;
+    const int n = x.meta[last].n;
+    const int keep = n < 65536 ? n : 65536;
+    const uint8_t *from = exact_src(x.e, last) + (n - keep);
+    for (int i = (int)threadIdx.x; i < keep; i += (int)blockDim.x) as_global(x.dictSave)[i] = as_global(from)[i];
+}
+
+void launch_exact_chain(const ExactArgs &a, int first, int count, int redo, hipStream_t s)
+{
+    if (count <= 0) return;
+    hipLaunchKernelGGL(k_exact_chain, dim3((unsigned)count), dim3(LZ4_WAVE), 0, s, a, first, redo);
+}
+
+void launch_exact_verify(const ExactArgs &a, int first, int count, hipStream_t s)
+{
+    if (count <= 0) return;
+    hipLaunchKernelGGL(k_exact_verify, dim3((unsigned)count), dim3(LZ4_WAVE), 0, s, a, first);
+}
+
+void launch_exact_finish(const ExactArgs &a, hipStream_t s)
+{
+    if (a.e.nBlocks <= 0) return;
+    hipLaunchKernelGGL(k_exact_finish, dim3(1), dim3(256), 0, s, a);
+}
+
+// Many reference-exact streams in one call (mi355lz4_compress_streams_device, DESIGN.md 7e).  Wave w continues the stream
+// in slot work[3w + 2] with the blocks [work[3w], work[3w + 1]) of the call: every stream starts from its own true state, so
+// nothing is speculated.  The wave follows the scalars itself -- LZ4_compress_fast_continue's statements in front of the
+// encoder (cbits/lz4.c:1565-1627), the ones exact_encode runs on the host for the single stream: wave-uniform, 32-bit.
+// A length outside 0..maxBlockLen ends the stream's part of the call: that block and the ones behind it get framedLen 0,
+// and the slot keeps the state after the last good block.
+__global__ __launch_bounds__(LZ4_WAVE) void k_exact_streams(ExactStreamsArgs x)
+{
+    __shared__ dev_v4 tab4[EXACT_TABLE / 4];
+    uint32_t *tab = (uint32_t *)tab4;
+    const int lane = lane_id();
+    const int32_t *w = x.work + 3 * (size_t)blockIdx.x;
+    const int b0 = uni(w[0]), b1 = uni(w[1]);
+    uint8_t *st = x.state + (size_t)uni(w[2]) * CSTREAM_SLOT_BYTES;
+    uint8_t *dictSave = st + CSTREAM_DICT_OFF;
+    uint32_t *scal = (uint32_t *)(st + CSTREAM_SCALAR_OFF);
+    for (int i = lane; i < EXACT_TABLE / 4; i += LZ4_WAVE) tab4[i] = as_global((const dev_v4 *)st)[i];
+    uint32_t cur = ex_uni(as_global(scal)[0]), dictSize = ex_uni(as_global(scal)[1]);
+    uint32_t dictBytes = ex_uni(as_global(scal)[2]);
+    const uint8_t *dictEnd = dictSave + dictBytes;
+    const uint8_t *lastSrc = nullptr;                                   // the last good array of the call: the next dictionary
+    uint32_t lastN = 0;
+    __syncthreads();
+    for (int j = b0; j < b1; j++) {
+        const int n = uni(x.e.srcLen ? x.e.srcLen[j] : x.e.uniformLen);
+        if (n < 0 || n > x.e.uniformLen) {
+            for (int k = j + lane; k < b1; k += LZ4_WAVE) x.e.framedLen[k] = 0;
+            break;
+        }
+        ExactBlock m;
+        m.delta = 0;
+        if (cur + (uint32_t)n > 0x80000000u) {                          // LZ4_renormDictT, cbits/lz4.c:1545-1562
+            m.delta = cur - 65536u;
+            cur = 65536u;
+            if (dictSize > 65536u) dictSize = 65536u;
+            for (int i = lane; i < EXACT_TABLE / 4; i += LZ4_WAVE) tab4[i] = exact_canon4(tab4[i], 0u, m.delta);
+            __syncthreads();
+        }
+        if (dictSize - 1u < 4u - 1u) dictSize = 0;                      // :1581-1587
+        m.start = cur; m.dictSize = dictSize; m.n = n; m.pad = 0;
+        m.dictSmall = (dictSize < 65536u && dictSize < cur) ? 1 : 0;    // :1627
+        const uint8_t *src = exact_src(x.e, j);
+        uint8_t *slot = x.e.slots + (size_t)j * x.e.slotStride;
+        const int cap = n + n / 255 + 16;                               // LZ4_compressBound
+        int c;
+        if (n == 0) {                                                   // cbits/lz4.c:1263-1273
+            c = 1;
+            if (lane == 0) slot[x.e.headerKind] = 0;
+        } else {
+            c = exact_encode_block(tab, src, n, dictEnd, m, (uint32_t)x.e.accel, slot + x.e.headerKind, cap, true);
+        }
+        if (lane == 0) {
+            store_le32(slot, c);
+            if (x.e.headerKind == 8) store_le32(slot + 4, n);
+            x.e.framedLen[j] = (c > 0) ? x.e.headerKind + c : 0;
+        }
+        cur += (uint32_t)n;                                             // :1633-1634
+        dictSize = (uint32_t)n;
+        dictEnd = src + n;
+        lastSrc = src; lastN = (uint32_t)n;
+        __syncthreads();
+    }
+    if (!lastSrc) return;                                               // no good block: the slot is as it was
+    for (int i = lane; i < EXACT_TABLE / 4; i += LZ4_WAVE) as_global((dev_v4 *)st)[i] = tab4[i];
+    const uint32_t keep = lastN < 65536u ? lastN : 65536u;              // (a zero-length last array: no dictionary)
+    wave_copy_bytes(dictSave, lastSrc + (lastN - keep), keep);
+    if (lane == 0) { as_global(scal)[0] = cur; as_global(scal)[1] = dictSize; as_global(scal)[2] = keep; }
+}
+
+void launch_exact_streams(const ExactStreamsArgs &a, int nWork, hipStream_t s)
+{
+    if (nWork <= 0) return;
+    hipLaunchKernelGGL(k_exact_streams, dim3((unsigned)nWork), dim3(LZ4_WAVE), 0, s, a);
+}
+
+// ---------------------------------------------------------------------------
+// K2, small batches: several waves per block (encode_wave.hpp, SEG).  One wavefront per block cannot be faster than
+// one block (1.5 ms for 64 KiB), however empty the chip is: a call of 160 blocks -- the reference's own benchmark
+// protocol, 10 MiB per file -- left 97 % of it idle, and 16 arrays of 640 KiB took 51 ms.  Here a block is cut into
+// segments; wave (b, j) seeds its table from the bytes in front of segment j (what linked compression does between
+// blocks) and writes sequence records; k_emit_seg then stitches a block's lists into one valid LZ4 block: a segment's
+// trailing literals simply become the first literals of the next segment's first sequence.
+// ---------------------------------------------------------------------------
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(ENC_WAVES_PER_EU, ENC_WAVES_PER_EU))) void k_encode_seg(EncodeSegArgs a)
+{
+    __shared__ uint16_t table[ENC_TABLE_ENTRIES + ENC_LDS_PAD];
+    const int blk = (int)(blockIdx.x / (unsigned)a.segs), j = (int)(blockIdx.x % (unsigned)a.segs);
+    const uint64_t off = a.e.srcOff ? a.e.srcOff[blk] : (uint64_t)blk * a.e.blockStride;
+    const int n = a.e.srcLen ? a.e.srcLen[blk] : a.e.uniformLen;
+    uint32_t count = 0;
+    if (n > 0) {
+        const int s0 = min(n, j * a.segLen), s1 = (j == a.segs - 1) ? n : min(n, (j + 1) * a.segLen);
+        if (s1 > s0) {
+            SegOut so;
+            so.list = a.lists + (size_t)blk * a.listStride + (size_t)(s0 / 4 + j);     // a segment has at most len/4 + 1 records
+            so.count = 0;
+            const int dictLen = min(s0, 65536);
+            so.base = s0 - dictLen;
+            so.last = s1 >= n;
+            so.tail = n - s1;
+            (void)encode_block_wave<uint16_t, true, true>(a.e.src + off + s0, s1 - s0, nullptr, a.e.accel, table, a.e.stats, dictLen, &so);
+            count = so.count;
+        }
+    }
+    if (lane_id() == 0) a.segCount[(size_t)blk * a.segs + j] = count;
+}
+
+// Emission of a segmented block, every segment by a wave of its own, in two steps: k_seg_sizes measures what each
+// segment's records come to in bytes (a segment's first sequence takes its literals from where the last sequence
+// BEFORE the segment ends), k_emit_seg places every segment behind the ones in front of it.  (One wave per block did
+// this in round 3's first version: 8 ms for a 4 MiB block.)
+__device__ __forceinline__ int seg_prev_end(const EncodeSegArgs &a, int blk, int j, int n)
+{
+    // end of the last sequence in front of segment j (0 when there is none)
+    for (int i = j - 1; i >= 0; i--) {
+        const int cnt = (int)a.segCount[(size_t)blk * a.segs + i];
+        if (cnt > 0) {
+            const int s0 = min(n, i * a.segLen);
+            int start, len, mo;
+            seg_unpack(a.lists[(size_t)blk * a.listStride + (size_t)(s0 / 4 + i) + (size_t)(cnt - 1)], start, len, mo);
+            return start + len;
+        }
+    }
+    return 0;
+}
+
+__global__ __launch_bounds__(64) void k_seg_sizes(EncodeSegArgs a)
+{
+    const int blk = (int)(blockIdx.x / (unsigned)a.segs), j = (int)(blockIdx.x % (unsigned)a.segs);
+    const int lane = lane_id();
+    const int n = a.e.srcLen ? a.e.srcLen[blk] : a.e.uniformLen;
+    const int cnt = (n > 0) ? (int)a.segCount[(size_t)blk * a.segs + j] : 0;
+    const int s0 = min(max(n, 0), j * a.segLen);
+    const uint64_t *list = a.lists + (size_t)blk * a.listStride + (size_t)(s0 / 4 + j);
+    int prevEnd = (n > 0) ? seg_prev_end(a, blk, j, n) : 0;
+    const int prev0 = prevEnd;
+    uint32_t bytes = 0;
+    for (int i0 = 0; i0 < cnt; i0 += LZ4_WAVE) {
+        const int k = min(LZ4_WAVE, cnt - i0);
+        int start = 0, len = 0, mo = 0;
+        if (lane < k) seg_unpack(list[i0 + lane], start, len, mo);
+        const int end = start + len;
+        int qPrev = __builtin_amdgcn_update_dpp(prevEnd, end, 0x138 /* wave_shr:1 */, 0xf, 0xf, false);
+        if (lane == 0) qPrev = prevEnd;
+        const uint32_t lit = (uint32_t)(start - qPrev), mc = (uint32_t)(len - LZ4_MINMATCH);
+        const uint32_t esz = (lane < k) ? 1u + lit + ext_len_bytes(lit) + 2u + ext_len_bytes(mc) : 0u;
+        bytes += (uint32_t)__builtin_amdgcn_readlane(enc_scan_incl((int)esz), 63);
+        prevEnd = __builtin_amdgcn_readlane(end, k - 1);
+    }
+    if (lane == 0) {
+        a.segBytes[(size_t)blk * a.segs + j] = bytes;
+        a.segPrevEnd[(size_t)blk * a.segs + j] = prev0;
+    }
+}
+
+__global__ __launch_bounds__(64) void k_emit_seg(EncodeSegArgs a)
+{
+    const int blk = (int)(blockIdx.x / (unsigned)a.segs), j = (int)(blockIdx.x % (unsigned)a.segs);
+    const int lane = lane_id();
+    const uint64_t off = a.e.srcOff ? a.e.srcOff[blk] : (uint64_t)blk * a.e.blockStride;
+    const int n = a.e.srcLen ? a.e.srcLen[blk] : a.e.uniformLen;
+    uint8_t *slot = a.e.slots + (size_t)blk * a.e.slotStride;
+    uint8_t *op0 = slot + a.e.headerKind;
+    const uint8_t *src = a.e.src + off;
+    const bool lastSeg = j == a.segs - 1;
+    if (n <= 0) {
+        if (lastSeg && lane == 0) {
+            int c = 0;
+            if (n == 0) { op0[0] = 0; c = 1; }                 // cbits/lz4.c:1263-1273: empty input -> single 0 token
+            store_le32(slot, c);
+            if (a.e.headerKind == 8) store_le32(slot + 4, n);
+            a.e.framedLen[blk] = (c > 0) ? a.e.headerKind + c : 0;
+        }
+        return;
+    }
+    // where this segment's bytes go: behind the segments in front of it (at most 64: one per lane)
+    const uint32_t mine = (lane < j) ? a.segBytes[(size_t)blk * a.segs + lane] : 0u;
+    const uint32_t before = (uint32_t)__builtin_amdgcn_readlane(enc_scan_incl((int)mine), 63);
+    uint8_t *op = op0 + before;
+    const int cnt = (int)a.segCount[(size_t)blk * a.segs + j];
+    const int s0 = min(n, j * a.segLen);
+    const uint64_t *list = a.lists + (size_t)blk * a.listStride + (size_t)(s0 / 4 + j);
+    int prevEnd = a.segPrevEnd[(size_t)blk * a.segs + j];
+    for (int i0 = 0; i0 < cnt; i0 += LZ4_WAVE) {
+        const int k = min(LZ4_WAVE, cnt - i0);
+        int start = 0, len = 0, mo = 0;
+        if (lane < k) seg_unpack(list[i0 + lane], start, len, mo);
+        const int end = start + len;
+        // my literals start where the sequence before me ends (lane 0: the one before this batch)
+        int qPrev = __builtin_amdgcn_update_dpp(prevEnd, end, 0x138 /* wave_shr:1 */, 0xf, 0xf, false);
+        if (lane == 0) qPrev = prevEnd;
+        op = emit_sequences(src, op, qPrev, start, len, mo, k);
+        prevEnd = __builtin_amdgcn_readlane(end, k - 1);
+    }
+    if (!lastSeg) return;
+    // ---- the block's last segment: last literals (:1204-1231), header ----
+    const uint32_t lastRun = (uint32_t)(n - prevEnd);
+    uint8_t *tok = op++;
+    if (lane == 0) *tok = (uint8_t)(min(lastRun, 15u) << 4);
+    if (lastRun >= 15) op = emit_ext_len(op, lastRun - 15);
+    wave_copy_bytes(op, src + prevEnd, lastRun);
+    op += lastRun;
+    const int c = (int)(op - op0);
+    if (lane == 0) {
+        store_le32(slot, c);                                   // Internal/LZ4.hs:262
+        if (a.e.headerKind == 8) store_le32(slot + 4, n);      // Internal/LZ4.hs:261
+        a.e.framedLen[blk] = (c > 0) ? a.e.headerKind + c : 0;
+    }
+}
+
+void launch_encode_seg(const EncodeSegArgs &a, hipStream_t s)
+{
+    if (a.e.nBlocks <= 0) return;
+    const dim3 grid((unsigned)a.e.nBlocks * (unsigned)a.segs);
+    hipLaunchKernelGGL(k_encode_seg, grid, dim3(64), 0, s, a);
+    hipLaunchKernelGGL(k_seg_sizes, grid, dim3(64), 0, s, a);
+    hipLaunchKernelGGL(k_emit_seg, grid, dim3(64), 0, s, a);
+}

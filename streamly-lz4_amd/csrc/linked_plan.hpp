@@ -102,7 +102,7 @@ inline FirstPass first_pass(const DecodeCall &d, const EngineMode &m, const Deco
     // A partial call's work is sum(min(target, capacity)), not the blocks' sizes, and the targets are device memory the call does not
     // read: 200 blocks of 64 KiB asked for 100 bytes each are 20 KB of work, a fraction of a segment per workgroup.  Variant 0 takes the
     // lane-parallel form, whose cost follows the prefix; variant 4 (the tests) the workgroup form, which hands every block its target
-    // cuts short to the lane-parallel one (kernels.hip, k_decode_cu_partial).  There is no token-list form of it.
+    // cuts short to the lane-parallel one (kernels/decode_partial.inc, k_decode_cu_partial).  There is no token-list form of it.
     if (d.target && m.decoder != 4) return FirstPass::Par;
     if (!m.stats && (m.decoder == 4 || (m.decoder == 0 && cu_auto(k, d.nBlocks, d.framedLen)))) return FirstPass::Cu;
     return FirstPass::Par;
@@ -179,7 +179,7 @@ inline void runin_after_sample(RuninPlan &p, const DecodeKnobs &k, int span0, do
     if (p.piece < 1) p.piece = 1;
     p.segBlocks = (int)((p.maxPieces * (uint64_t)p.piece < (uint64_t)span0) ? p.maxPieces * (uint64_t)p.piece : (uint64_t)span0);
 }
-// A segment the run-in did not finish (runCtl[1]; a kernel that did not launch counts as a broken block).  Given up for what the DATA
+// A segment the run-in did not finish (run.ctl[1]; a kernel that did not launch counts as a broken block).  Given up for what the DATA
 // is like (chains of pieces to redo, rounds that do not end), not for a broken block: the engine's next calls take the long run-in,
 // or -- that was the long one -- RUNIN_BACKOFF of them do not try.  A forced run-in teaches nothing.
 inline void runin_given_up(RuninState &st, const RuninPlan &p, const DecodeKnobs &k, uint32_t why)

@@ -484,7 +484,7 @@ static void plan_pointer()
     // 64 KiB)); walkStreams = streamFirst && !PTR set && 0.42 * (stat[3] > 0 ? stat[3] - 1 : 0) * (1 + nStreams / 5000) < 0.55 +
     // 1.15e-3 * stat[0]; poolBlocks = POOL_BLOCKS set ? poolMax : max(1, poolMax / per); ptrBlocks = PTR_BLOCKS > 0 ? ptrMax :
     // max(1, ptrMax / per); pool = (poolMax > 0 && !walkStreams) ? min(span, poolBlocks) : span; pointers when usePtr and
-    // (min(pool, ptrBlocks) + 1) * per * 64 KiB + 64 KiB < 2^31; split = splitOk && a.ptr && span <= seg && span <= pool
+    // (min(pool, ptrBlocks) + 1) * per * 64 KiB + 64 KiB < 2^31; split = splitOk && a.ptr.buf && span <= seg && span <= pool
     auto plan = [](int span, uint32_t maxCap, const DecodeKnobs &k = DecodeKnobs(), DecodeCall s = linked_call(100000, 1),
                    uint32_t count = 100, uint32_t longestStream = 0) {
         LinkStat st;

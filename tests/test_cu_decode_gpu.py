@@ -185,7 +185,7 @@ def _linked_device_call(S, engine, fr, nblk, bl, raw_len):
 def test_big_linked_blocks_by_the_workgroup_form(engine, oracle, monkeypatch):
     """A linked stream of BlockMax1MB-sized blocks (Config.hs:109-116; written with the dictionary carried from block to block,
     cbits/lz4.c:1608-1636): every dependent block by the workgroup-per-block decoder against a guess of its dictionary, pass after
-    pass until the guesses stand (api.cpp path 6, kernels.hip k_decode_cu_linked).  Bytes and results are the input's and those of
+    pass until the guesses stand (api.cpp path 6, kernels/decode_par_cu.inc k_decode_cu_linked).  Bytes and results are the input's and those of
     the pointer pass (MI355LZ4_LINKED_BIG=0); a corrupted block, and a stream whose blocks never forget their dictionary, leave the
     call to that pass with the same results."""
     S = pytest.importorskip("streamly_lz4_amd")

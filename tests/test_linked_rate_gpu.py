@@ -100,7 +100,7 @@ def test_single_linked_stream_rate(engine, slz4, oracle, kind, n_blocks, repeat,
     tolerant parallel pass + the data-parallel pointer pass (linked_ptr.hpp).  Bit-exact; the rate is recorded.
     repeat > 1: the framed stream is appended to itself (still one valid linked stream: a block written without
     a dictionary may follow any block), long enough to span several segments of the second pass (the 10 240-block case
-    is above the span from which the run-in decode is the default: kernels.hip, "RUN-IN DECODE")."""
+    is above the span from which the run-in decode is the default: kernels/runin.inc, "RUN-IN DECODE")."""
     import torch
     dev = torch.device("cuda:0")
     if kind == "text":
@@ -189,7 +189,7 @@ def test_single_linked_stream_host_api_rate(engine, slz4, oracle, linked, record
 
 def test_long_linked_stream_default_is_runin_decode(engine, slz4, oracle, monkeypatch, record):
     """ONE reference-written linked stream long enough (9 216 blocks of 64 KiB and more) that the default path is the
-    run-in decode (pieces of the stream, each decoded from 11 blocks in front of it, kernels.hip): its output must be the
+    run-in decode (pieces of the stream, each decoded from 11 blocks in front of it, kernels/runin.inc): its output must be the
     input, and the same bytes as the pointer pass's (MI355LZ4_LINKED_RUNIN=0).  Rates go to linked_rate.jsonl."""
     import torch
     dev = torch.device("cuda:0")

@@ -1,5 +1,5 @@
 """Small batches: a block compressed by several waves (segments with the table seeded from the bytes in front of them,
-csrc/kernels.hip "K2, small batches"; the reference's benchmark protocol is such a batch: 10 MiB per file,
+csrc/kernels/encode.inc "K2, small batches"; the reference's benchmark protocol is such a batch: 10 MiB per file,
 benchmark/Main.hs:80-84).  The segment count is read once per process (MI355LZ4_SEG), so every setting runs in a child:
 each block must decode through the ORACLE to exactly its input and stay within LZ4_compressBound, the GPU decoders
 agree, the output is deterministic, and the size stays close to the one-wave-per-block encoder's."""
