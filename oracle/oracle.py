@@ -12,6 +12,7 @@ import numpy as np
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 _PAD = 64  # readable slack after every buffer handed to a decoder (malformed-input probes)
+_SESSION_GAP = 4096  # between the destinations of a session's steps (ref_harness.c, SESSION_GAP)
 
 _u8p = C.POINTER(C.c_uint8)
 
@@ -19,9 +20,11 @@ _u8p = C.POINTER(C.c_uint8)
 def build(force=False):
     """Compile liboracle.so (and _ref when /root/reference is present)."""
     so = os.path.join(_HERE, "liboracle.so")
-    if force or not os.path.exists(so) or os.path.exists("/root/reference/cbits/lz4.c") and not os.path.exists(
-        os.path.join(_HERE, "_ref", "liblz4ref.so")
-    ):
+    ref = os.path.join(_HERE, "_ref", "liblz4ref.so")
+    harness = os.path.join(_HERE, "ref_harness.c")
+    # (a _ref built from an older harness lacks its newer entry points: rebuilt where the reference's sources are)
+    stale = not os.path.exists(ref) or os.path.getmtime(ref) < os.path.getmtime(harness)
+    if force or not os.path.exists(so) or os.path.exists("/root/reference/cbits/lz4.c") and stale:
         subprocess.check_call(["make", "-C", _HERE], stdout=subprocess.DEVNULL)
     return so
 
@@ -145,9 +148,85 @@ class Reference(_Lib):
         L.ref_decompress_block_dict.restype = C.c_int
         L.ref_decompress_block_dict.argtypes = [_u8p, C.c_int, _u8p, C.c_int, _u8p, C.c_int]
         L.ref_version.restype = C.c_int
+        # The session runners of ref_harness.c.  A prebuilt _ref from an older harness, where the reference's sources are not
+        # there to rebuild it, has none: the same public functions of the codec inside it are then called from here, with the
+        # same layout (_session_calls).
+        self.has_sessions = hasattr(L, "ref_decode_session") and hasattr(L, "ref_compress_session")
+        szp, ip, vp = C.POINTER(C.c_size_t), C.POINTER(C.c_int), C.c_void_p
+        if self.has_sessions:
+            L.ref_decode_session.restype = C.c_int
+            L.ref_decode_session.argtypes = [C.c_int, _u8p, szp, ip, ip, _u8p, C.c_size_t, szp, ip]
+            L.ref_compress_session.restype = C.c_int
+            L.ref_compress_session.argtypes = [C.c_int, _u8p, szp, ip, ip, ip, _u8p, C.c_size_t, szp, ip]
+        else:
+            for name, res, args in (("LZ4_createStream", vp, []), ("LZ4_freeStream", C.c_int, [vp]),
+                                    ("LZ4_createStreamDecode", vp, []), ("LZ4_freeStreamDecode", C.c_int, [vp]),
+                                    ("LZ4_compress_fast_continue", C.c_int, [vp, vp, vp, C.c_int, C.c_int, C.c_int]),
+                                    ("LZ4_decompress_safe_continue", C.c_int, [vp, vp, vp, C.c_int, C.c_int])):
+                f = getattr(L, name)
+                f.restype, f.argtypes = res, args
 
     def version(self):
         return self.lib.ref_version()
+
+    def _session_calls(self, n, src, off, lens, caps, accels, arena):
+        """ref_harness.c's session runners restated over the codec's public functions (a _ref without the runners): every
+        destination a region of its own, _SESSION_GAP bytes apart at least"""
+        L = self.lib
+        do, pos = [], _SESSION_GAP
+        for c in caps:
+            do.append(pos)
+            pos = (pos + max(c, 0) + _SESSION_GAP + 63) & ~63
+        if pos > arena.size:
+            raise RuntimeError("session arena too small")
+        sp, ap = src.ctypes.data, arena.ctypes.data
+        if accels is None:
+            ctx = L.LZ4_createStreamDecode()
+            res = [L.LZ4_decompress_safe_continue(ctx, sp + off[i], ap + do[i], lens[i], caps[i]) for i in range(n)]
+            L.LZ4_freeStreamDecode(ctx)
+        else:
+            ctx = L.LZ4_createStream()
+            res = [L.LZ4_compress_fast_continue(ctx, sp + off[i], ap + do[i], lens[i], caps[i], accels[i]) for i in range(n)]
+            L.LZ4_freeStream(ctx)
+        return res, do
+
+    def _session(self, name, srcs, lens, caps, accels=None):
+        """Runs one session of the harness: srcs laid out _PAD bytes apart in one buffer, lens as given (a length may
+        only name a size), every destination a region of its own.  Returns [(code, bytes written up to the code)]."""
+        n = len(srcs)
+        off, pos = [], _PAD
+        for s in srcs:
+            off.append(pos)
+            pos += len(s) + _PAD
+        src = np.zeros(pos, dtype=np.uint8)
+        for o, s in zip(off, srcs):
+            src[o:o + len(s)] = np.frombuffer(bytes(s), dtype=np.uint8)
+        arena = np.zeros(sum(max(c, 0) + _SESSION_GAP + 64 for c in caps) + 2 * _SESSION_GAP, dtype=np.uint8)
+        if not self.has_sessions:
+            res, do = self._session_calls(n, src, off, lens, caps, accels, arena)
+            return [(int(r), arena[o:o + max(int(r), 0)].tobytes()) for r, o in zip(res, do)]
+        ia = lambda v: np.array(v, dtype=np.int32)
+        so, ln, cp = np.array(off, dtype=np.uintp), ia(lens), ia(caps)
+        do, res = np.zeros(n, dtype=np.uintp), np.zeros(n, dtype=np.int32)
+        szp, ip = C.POINTER(C.c_size_t), C.POINTER(C.c_int)
+        args = [n, _ptr(src), so.ctypes.data_as(szp), ln.ctypes.data_as(ip), cp.ctypes.data_as(ip)]
+        if accels is not None:
+            ac = ia(accels)
+            args.append(ac.ctypes.data_as(ip))
+        args += [_ptr(arena), arena.size, do.ctypes.data_as(szp), res.ctypes.data_as(ip)]
+        if getattr(self.lib, name)(*args) != 0:
+            raise RuntimeError("session arena too small")
+        return [(int(r), arena[int(o):int(o) + max(int(r), 0)].tobytes()) for r, o in zip(res, do)]
+
+    def decode_session(self, steps):
+        """steps [(block, cap)] through ONE LZ4_streamDecode_t, LZ4_decompress_safe_continue call by call."""
+        return self._session("ref_decode_session", [b for b, _ in steps], [len(b) for b, _ in steps], [c for _, c in steps])
+
+    def compress_session(self, steps):
+        """steps [(data, srcSize, dstCapacity, accel)] through ONE LZ4_stream_t, LZ4_compress_fast_continue call by call;
+        srcSize is passed as given (it may name a size the data does not have: the forced refusals)."""
+        return self._session("ref_compress_session", [s[0] for s in steps], [s[1] for s in steps], [s[2] for s in steps],
+                             [s[3] for s in steps])
 
     def decompress_block(self, comp, cap, dict_bytes=None):
         src, n = _padded(comp)

@@ -109,6 +109,52 @@ int ref_compress_block(const uint8_t *src, uint8_t *dst, int n, int cap, int acc
     return r;
 }
 
+/* ---- sessions: the legacy calls one by one through ONE context (tests/legacy_cases.py) ----
+ * Every step's destination is a region of its own in `arena`, SESSION_GAP bytes apart at least, so that no call finds
+ * its destination where the previous output ended: every call after the first that decoded takes the "switching to
+ * another buffer" branch, which is what separately allocated blocks reach.  dstOff[i] reports where step i wrote.
+ * Returns 0, or -1 when the arena is too small (nothing is run then). */
+#define SESSION_GAP 4096
+static size_t session_layout(int n, const int *caps, size_t *dstOff)
+{
+    size_t pos = SESSION_GAP;
+    int i;
+    for (i = 0; i < n; i++) {
+        dstOff[i] = pos;
+        pos += (size_t)(caps[i] > 0 ? caps[i] : 0) + SESSION_GAP;
+        pos = (pos + 63) & ~(size_t)63;
+    }
+    return pos;
+}
+
+int ref_decode_session(int n, const uint8_t *src, const size_t *srcOff, const int *srcLen, const int *caps,
+                       uint8_t *arena, size_t arenaLen, size_t *dstOff, int *results)
+{
+    LZ4_streamDecode_t *ctx;
+    int i;
+    if (session_layout(n, caps, dstOff) > arenaLen) return -1;
+    ctx = LZ4_createStreamDecode();
+    for (i = 0; i < n; i++)
+        results[i] = LZ4_decompress_safe_continue(ctx, (const char *)src + srcOff[i], (char *)arena + dstOff[i], srcLen[i], caps[i]);
+    LZ4_freeStreamDecode(ctx);
+    return 0;
+}
+
+/* srcLen[i] is passed as it is (a negative or an oversized one is only named: the codec refuses it before it reads);
+ * the caller keeps the sources apart from each other, as separately allocated arrays are. */
+int ref_compress_session(int n, const uint8_t *src, const size_t *srcOff, const int *srcLen, const int *caps,
+                         const int *accels, uint8_t *arena, size_t arenaLen, size_t *dstOff, int *results)
+{
+    LZ4_stream_t *ctx;
+    int i;
+    if (session_layout(n, caps, dstOff) > arenaLen) return -1;
+    ctx = LZ4_createStream();
+    for (i = 0; i < n; i++)
+        results[i] = LZ4_compress_fast_continue(ctx, (const char *)src + srcOff[i], (char *)arena + dstOff[i], srcLen[i], caps[i], accels[i]);
+    LZ4_freeStream(ctx);
+    return 0;
+}
+
 /* ---- CPU baseline timers (bench.py cpu_baseline, kind "reference") ----
  * Pre-split blocks in separate allocations; time only the codec calls. */
 static double now_s(void)

@@ -10,10 +10,10 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 LIBDIR = os.path.join(ROOT, "streamly-lz4_amd", "lib")
 
 
-def _build(tmp_path):
-    exe = str(tmp_path / "roundtrip")
+def _build(tmp_path, source=os.path.join("examples", "roundtrip.c"), name="roundtrip"):
+    exe = str(tmp_path / name)
     subprocess.check_call(["gcc", "-std=c99", "-Wall", "-Wextra", "-Werror", "-pedantic", "-I", os.path.join(ROOT, "include"),
-                           os.path.join(ROOT, "examples", "roundtrip.c"), "-L", LIBDIR, "-lmi355lz4",
+                           os.path.join(ROOT, source), "-L", LIBDIR, "-lmi355lz4",
                            "-Wl,-rpath," + LIBDIR, "-o", exe])
     return exe
 
@@ -45,3 +45,12 @@ def test_example_round_trips(tmp_path, linked):
     r = subprocess.run([exe, "300", str(linked)], capture_output=True, text=True, timeout=120)
     assert r.returncode == 0 and "round trip ok" in r.stdout, (r.stdout, r.stderr)
     assert ("linked" if linked else "independent") in r.stdout
+
+
+@pytest.mark.gpu
+def test_legacy_face_from_c(tmp_path):
+    """tests/native/legacy_drop_in.c: lz4.h alone, one compression and one decompression context, 40 blocks in allocations of
+    their own at the capacities the Haskell caller passes; LZ4_COMPRESSBOUND equals LZ4_compressBound."""
+    exe = _build(tmp_path, os.path.join("tests", "native", "legacy_drop_in.c"), "legacy_drop_in")
+    r = subprocess.run([exe], capture_output=True, text=True, timeout=120)
+    assert r.returncode == 0 and "legacy round trip ok" in r.stdout, (r.stdout, r.stderr)
