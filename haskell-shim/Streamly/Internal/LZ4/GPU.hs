@@ -45,6 +45,12 @@ module Streamly.Internal.LZ4.GPU
     , resetCompressStreams
     , c_compressStreamsDevice
     , compressChunksMany
+    , c_cstreamsLoadDict
+    , c_compressDictDevice
+    , c_decompressDictDevice
+    , loadDict
+    , compressChunksWithDict
+    , decompressChunksWithDict
     , DecompressStreams
     , newDecompressStreams
     , freeDecompressStreams
@@ -145,6 +151,28 @@ foreign import ccall safe "mi355lz4.h mi355lz4_compress_streams"
     c_compressStreams
         :: Ptr C_Engine -> Ptr C_CStreams -> Ptr (Ptr Word8) -> Ptr Int32 -> CInt -> Ptr Int32 -> Ptr Int32 -> CInt
         -> CInt -> CInt -> Ptr Word8 -> CSize -> Ptr CSize -> Ptr Int32 -> Ptr Int32 -> IO CInt
+
+-- Shared-dictionary batches (include/mi355lz4.h, "shared-dictionary batches"): LZ4_loadDict on one slot of the set, a batch of
+-- independent blocks compressed from a copy of that slot each (the slot is only read), and LZ4_decompress_safe_usingDict for a
+-- batch against one dictionary.  The _device forms take device pointers and only enqueue.
+foreign import ccall safe "mi355lz4.h mi355lz4_cstreams_load_dict"
+    c_cstreamsLoadDict :: Ptr C_Engine -> Ptr C_CStreams -> CInt -> Ptr Word8 -> CInt -> IO CInt
+foreign import ccall safe "mi355lz4.h mi355lz4_compress_dict_device"
+    c_compressDictDevice
+        :: Ptr C_Engine -> Ptr C_CStreams -> CInt -> Ptr Word8 -> Ptr Word64 -> Ptr Int32 -> Word64 -> CInt -> CInt
+        -> CInt -> CInt -> Ptr Word8 -> CSize -> Ptr Int32 -> IO CInt
+foreign import ccall safe "mi355lz4.h mi355lz4_decompress_dict_device"
+    c_decompressDictDevice
+        :: Ptr C_Engine -> Ptr Word8 -> Word64 -> Ptr Word64 -> CInt -> CInt -> CInt -> Ptr Word8 -> CInt
+        -> Ptr Word8 -> Ptr Word64 -> Ptr Int32 -> Ptr Int32 -> IO CInt
+foreign import ccall safe "mi355lz4.h mi355lz4_compress_dict"
+    c_compressDict
+        :: Ptr C_Engine -> Ptr C_CStreams -> CInt -> Ptr (Ptr Word8) -> Ptr Int32 -> CInt -> CInt -> CInt
+        -> Ptr Word8 -> CSize -> Ptr CSize -> Ptr Int32 -> Ptr Int32 -> IO CInt
+foreign import ccall safe "mi355lz4.h mi355lz4_decompress_dict"
+    c_decompressDict
+        :: Ptr C_Engine -> Ptr Word8 -> CSize -> CInt -> CInt -> Ptr Word8 -> CInt
+        -> Ptr Word8 -> CSize -> Ptr CSize -> Ptr Int32 -> CInt -> Ptr CInt -> IO CInt
 
 -- Decoded sizes without decoding (device pointers in, device pointers out; only enqueues): what every block of a
 -- size-less framing (BlockMax64KB .. BlockMax4MB) decodes to, read off its token chain.  size[i] >= 0, or a negative
@@ -437,6 +465,61 @@ compressChunksMany (Engine eng) (CompressStreams cs) cfg speed pipes = do
             split [] _ = []
             split (c : rest) xs = let (h, t) = splitAt c xs in h : split rest t
         return (split counts outs)
+
+-- | @LZ4_loadDict@ on one slot of the set: the dictionary is DEVICE memory (@len@ bytes at @dict@); enqueued, the slot keeps its
+-- own copy.  The slot then serves 'compressChunksWithDict', or continues through 'compressChunksMany'.
+loadDict :: Engine -> CompressStreams -> Int -> Ptr Word8 -> Int -> IO ()
+loadDict (Engine p) (CompressStreams cs) slot dict len = do
+    rc <- c_cstreamsLoadDict p cs (fromIntegral slot) dict (fromIntegral len)
+    when (rc /= 0) $ error "mi355lz4_cstreams_load_dict failed"
+
+-- | A batch of arrays, every one compressed on its own against the loaded slot @slot@ of the set: one framed array per input
+-- array, the bytes @LZ4_loadDict@ + @LZ4_compress_fast_continue@ on a copy of the loaded stream write.  The slot is only read.
+compressChunksWithDict
+    :: Engine -> CompressStreams -> Int -> BlockConfig -> Int -> [Array.Array Word8] -> IO [Array.Array Word8]
+compressChunksWithDict (Engine eng) (CompressStreams cs) slot cfg speed arrs = do
+    let n = length arrs
+        meta = metaSizeOf cfg
+        lens = map Array.byteLength arrs
+        cap = sum (map (\l -> fromIntegral (c_bound (fromIntegral l)) + meta + 4) lens)
+    (MArray.Array cont dstBegin_ dstBegin dstMax) <- MArray.newArray (max cap 1)
+    allocaArray n $ \pSrc -> allocaArray n $ \pLen -> allocaArray n $ \pFlen ->
+      allocaArray n $ \pStatus -> alloca $ \pOutLen -> do
+        let withAll [] k = k []
+            withAll (a:as) k = Array.asPtrUnsafe (Array.unsafeCast a) $ \p -> withAll as (k . (p :))
+        withAll arrs $ \ptrs -> do
+            pokeArray pSrc ptrs
+            pokeArray pLen (map fromIntegral lens)
+            rc <- c_compressDict eng cs (fromIntegral slot) pSrc pLen (fromIntegral n) (fromIntegral speed)
+                      (fromIntegral meta) dstBegin (fromIntegral cap) pOutLen pFlen pStatus
+            when (rc /= 0) $ error "compressChunksWithDict: mi355lz4_compress_dict failed"
+        flens <- map fromIntegral <$> peekArray n pFlen
+        let offs = scanl (+) 0 flens
+        return [ Array.unsafeFreeze (MArray.Array cont dstBegin_ (dstBegin `plusPtr` (o + l)) dstMax)
+                   `seq` Array.Array cont (dstBegin `plusPtr` o) (dstBegin `plusPtr` (o + l))
+               | (o, l) <- zip offs flens ]
+
+-- | A batch of resized blocks (header + data each), every one decoded against the dictionary (host memory, may be empty) as
+-- @LZ4_decompress_safe_usingDict@ does: one decoded array per block.
+decompressChunksWithDict
+    :: Engine -> BlockConfig -> Array.Array Word8 -> [Array.Array Word8] -> IO [Array.Array Word8]
+decompressChunksWithDict (Engine eng) cfg dict blocks = do
+    let n = length blocks
+        meta = metaSizeOf cfg
+    framed <- concatArrays blocks
+    cap <- sum <$> forM blocks (\a -> Array.asPtrUnsafe (Array.unsafeCast a) $ \p ->
+               if meta == 8 then fromIntegral <$> (peek (castPtr p `plusPtr` 4) :: IO Int32)
+                            else return (fixedUncompOf cfg))
+    (MArray.Array cont _ b _) <- MArray.newArray (max cap 1)
+    allocaArray (max n 1) $ \pBlen -> alloca $ \pOutLen -> alloca $ \pN ->
+      Array.asPtrUnsafe (Array.unsafeCast framed) $ \pIn -> Array.asPtrUnsafe (Array.unsafeCast dict) $ \pDict -> do
+        rc <- c_decompressDict eng pIn (fromIntegral (Array.byteLength framed)) (fromIntegral meta)
+                  (fromIntegral (fixedUncompOf cfg)) pDict (fromIntegral (Array.byteLength dict))
+                  b (fromIntegral cap) pOutLen pBlen (fromIntegral n) pN
+        when (rc /= 0) $ error "decompressChunksWithDict: mi355lz4_decompress_dict failed"
+        lens <- map fromIntegral <$> peekArray n pBlen
+        let offs = scanl (+) 0 lens
+        return [ Array.Array cont (b `plusPtr` o) (b `plusPtr` (o + l)) | (o, l) <- zip offs lens ]
 
 -- | The next resized blocks of many @decompressChunksRaw@ pipelines in one GPU call, the counterpart of
 -- 'compressChunksMany': @(slot, blocks)@ per pipeline, every pipeline continuing its slot of the set -- what the

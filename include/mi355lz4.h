@@ -99,6 +99,12 @@ typedef struct mi355lz4_ctx mi355lz4_ctx;
  *   streamSlot[] names for a stream with blocks -- never a slot the call does not name, never framed, blockOff, outOff or
  *   outCap.  _dstreams_reset / _dstreams_set_dict write the slots they name and nothing else (never the dictionary handed
  *   in).  _decompress_dstreams is a host-buffer call as above.
+ * Shared-dictionary batches: _cstreams_load_dict writes the slot of `cs` it names and nothing else (never the dictionary
+ *   handed in).  _compress_dict_device: the slot ranges of _compress_batch_device and framedLen[0, nBlocks); never any
+ *   slot of `cs` -- the loaded slot is only read -- never src, srcOff or srcLen.  _decompress_dict_device: no byte of `out`
+ *   outside the union of [outOff[i], outOff[i] + cap_i), cap_i as for the decode calls, for a block that decodes, one that
+ *   fails and one whose header is rejected alike; result[] only in [0, nBlocks); never the dictionary, framed, blockOff,
+ *   outOff or outCap.  _compress_dict and _decompress_dict are host-buffer calls as above.
  * Scratch that a call needs is the engine's own. */
 
 /* ---- engine lifecycle ------------------------------------------------ */
@@ -548,6 +554,82 @@ int mi355lz4_compress_streams(mi355lz4_ctx *ctx, mi355lz4_cstreams *cs, const ui
                               const int32_t *srcLen, int nBlocks, const int32_t *streamFirst,
                               const int32_t *streamSlot, int nStreams, int accel, int headerKind, uint8_t *framedOut,
                               size_t cap, size_t *outLen, int32_t *blockFramedLen, int32_t *status);
+
+/* ---- shared-dictionary batches: LZ4_loadDict and LZ4_decompress_safe_usingDict ------------------------------------------
+ * Small records (rows, log lines, messages, pages of 1-16 KiB) compress poorly on their own, because every block starts with
+ * an empty window; the codec's answer is one dictionary shared by all of them.  Here a slot of a mi355lz4_cstreams is loaded
+ * once and then serves any number of batches, read-only; the decode side takes the dictionary's bytes directly.
+ *
+ * _cstreams_load_dict is LZ4_loadDict (cbits/lz4.c:1475-1515) on slot `slot`, on the device: afterwards the slot holds what
+ * LZ4_loadDict leaves in an LZ4_stream_t -- the table zeroed, currentOffset 65536 and, for len >= 8 (HASH_UNIT of the
+ * reference's 64-bit build), the last min(len, 65536) bytes of dictDevice[0, len) saved with dictSize their count and every
+ * third position p <= dictEnd - 8 of those bytes entered with index p - (dictEnd - 65536) under the byU32 hash5, the last
+ * writer of a bucket winning.  len < 8: no dictionary and an empty table, but currentOffset is 65536 all the same.  The
+ * call only enqueues on the engine's stream and reads nothing on the host; the slot keeps its own copy, so dictDevice may be
+ * freed or overwritten once the call has run on the device.  A slot loaded this way continues through
+ * mi355lz4_compress_streams_device unchanged: LZ4_loadDict followed by LZ4_compress_fast_continue over separately allocated
+ * arrays.
+ * MI355LZ4_E_ARG: a null ctx or cs, a slot out of range, len < 0, a null dictDevice with len > 0, `cs` created on another
+ * device. */
+int mi355lz4_cstreams_load_dict(mi355lz4_ctx *ctx, mi355lz4_cstreams *cs, int slot, const uint8_t *dictDevice, int len);
+/* Compress nBlocks independent blocks, every one against the state in slot dictSlot of `cs`.  The block arguments and the
+ * outputs are those of mi355lz4_compress_batch_device (slotStride as mi355lz4_slot_stride_ex says).
+ * Bytes: block i is what LZ4_compress_fast_continue(&copy, src_i, dst, n_i, LZ4_compressBound(n_i), accel) writes on a COPY
+ * of the slot's LZ4_stream_t, for any accel (clamped to 1..65537) and any length 0..maxBlockLen -- after
+ * _cstreams_load_dict, the reference's LZ4_loadDict once and a copy of the loaded stream per block.  The state is whatever
+ * the slot holds: a slot that streams have continued works the same way (its last array's tail is the dictionary).
+ * The slot is never written and blocks do not see each other: the same slot may serve any number of calls, from any
+ * engine on its device, also at the same time -- as long as no call that WRITES the slot (_load_dict, _reset,
+ * _compress_streams_device naming it) is in flight beside them.
+ * Asynchronous: the call only enqueues on the engine's stream; it does not wait and does not read srcLen on the host.  A
+ * length outside 0..maxBlockLen can therefore be no error code: that block gets framedLen[i] = 0 and its slot range is left
+ * untouched, as in the streams call; the other blocks are unaffected.
+ * Switches: block checksums apply; the compression level must be 0.  Segments, the linked switch and the engine's own exact
+ * stream (mi355lz4_set_compress_exact) play no part, on or off.
+ * MI355LZ4_E_ARG: a null ctx or cs, `cs` created on another device, a compression level other than 0, dictSlot out of
+ * range, nBlocks < 0, a headerKind other than 4 / 8, maxBlockLen outside 0..MI355LZ4_MAX_INPUT_SIZE, with nBlocks > 0 a null
+ * src (maxBlockLen > 0), slots or framedLen.  MI355LZ4_E_CAPACITY: slotStride below the bound.  nBlocks == 0 is MI355LZ4_OK.
+ * One wavefront per block, the reference's serial parse: 6.9 ms for 16384 text records of 4 KiB against a 64 KiB dictionary
+ * (ratio 1.90; mi355lz4_compress_batch_device: 0.39 ms, ratio 1.33), 28.9 ms for 2560 records of 64 KiB (scripts/dict_rate.py,
+ * profiles/dict_rate.json). */
+int mi355lz4_compress_dict_device(mi355lz4_ctx *ctx, const mi355lz4_cstreams *cs, int dictSlot, const uint8_t *src,
+                                  const uint64_t *srcOff, const int32_t *srcLen, uint64_t blockStride, int maxBlockLen,
+                                  int nBlocks, int accel, int headerKind, uint8_t *slots, size_t slotStride,
+                                  int32_t *framedLen);
+/* Decode nBlocks independent blocks, every one against the dictionary dictDevice[0, dictLen) (device memory, any length).
+ * result[i] and out[outOff[i] ..) are those of LZ4_decompress_safe_usingDict(data_i, dst_i, compLen_i, cap_i, dict, dictLen)
+ * on its external-dictionary path (LZ4_decompress_safe_forceExtDict, cbits/lz4.c:2404-2417), for well-formed and malformed
+ * blocks alike: only the last 64 KiB of the dictionary can be reached, and a dictionary under 64 KiB arms the offset check
+ * (:1764).  The prefix mode the reference takes when a destination happens to lie directly behind the dictionary is not
+ * restated, here or elsewhere in this engine: wherever the outputs lie, the dictionary is external.  dictLen == 0 is
+ * LZ4_decompress_safe: the results of mi355lz4_decompress_batch_device with linked == 0.
+ * Block arguments, cap_i, the header rejections, checksum verification and what the call may write are those of
+ * mi355lz4_decompress_batch_device with linked == 0.  The dictionary is never written.
+ * Enqueue only: every block is decoded once, with the dictionary -- no standalone first pass, no second pass, no host wait;
+ * per-block failures are in result[].  mi355lz4_set_decoder is ignored by this call: the workgroup-per-block form has no
+ * dictionary, so every block takes the lane-parallel decoder, one wavefront per block.
+ * MI355LZ4_E_ARG: null ctx, nBlocks < 0, fixedUncomp < 0, a headerKind other than 4 / 8, dictLen < 0, a null dictDevice with
+ * dictLen > 0, a null framed / blockOff / outOff / result with nBlocks > 0, a range begun with
+ * mi355lz4_decompress_linked_begin still open.  nBlocks == 0 is MI355LZ4_OK.
+ * Rates: 0.22 ms for 16384 blocks of 4 KiB, 0.47 ms for 2560 of 64 KiB, text against a 64 KiB dictionary (the same blocks
+ * without one through mi355lz4_decompress_batch_device: 0.18 and 0.40 ms; scripts/dict_rate.py, profiles/dict_rate.json). */
+int mi355lz4_decompress_dict_device(mi355lz4_ctx *ctx, const uint8_t *framed, uint64_t framedLen, const uint64_t *blockOff,
+                                    int nBlocks, int headerKind, int fixedUncomp, const uint8_t *dictDevice, int dictLen,
+                                    uint8_t *out, const uint64_t *outOff, const int32_t *outCap /* may be NULL */,
+                                    int32_t *result);
+/* Host-buffer forms, synchronous.  _compress_dict: as mi355lz4_compress_batch (one dense framed stream in block order,
+ * blockFramedLen and status per block, the same group pipeline), every block against slot dictSlot of `cs`; the lengths are
+ * checked on the host, a bad one is MI355LZ4_E_ARG and nothing is enqueued.  _decompress_dict: as mi355lz4_decompress_batch
+ * with a host dictionary (dict, dictLen; may be NULL / 0) in place of linked / dict; a single group, as
+ * mi355lz4_decompress_partial is: the whole chain and the dictionary's last 64 KiB go to the device, one decode, one copy
+ * back -- the group pipeline of the full decode is not used.  The multi-device handle and the legacy LZ4_* face have no
+ * dictionary calls. */
+int mi355lz4_compress_dict(mi355lz4_ctx *ctx, const mi355lz4_cstreams *cs, int dictSlot, const uint8_t *const *src,
+                           const int32_t *srcLen, int nBlocks, int accel, int headerKind, uint8_t *framedOut, size_t cap,
+                           size_t *outLen, int32_t *blockFramedLen, int32_t *status);
+int mi355lz4_decompress_dict(mi355lz4_ctx *ctx, const uint8_t *framedIn, size_t inLen, int headerKind, int fixedUncomp,
+                             const uint8_t *dict, int dictLen, uint8_t *out, size_t cap, size_t *outLen, int32_t *blockLen,
+                             int maxBlocks, int *nBlocks);
 
 /* ---- many linked decode streams, continued across calls ---------------------------------------------------------------
  * The decode-side counterpart of mi355lz4_cstreams, and the device-resident form of the reference's one LZ4_streamDecode_t

@@ -110,6 +110,14 @@ public:
     // output it threads through lives in the slot, on the device.  Throws Error (a failed block included).
     std::vector<std::vector<Array>> decompressStreams(const BlockConfig &cfg, const std::vector<std::vector<Array>> &streams,
                                                       class DecompressStreams &ds, const std::vector<int32_t> &slots);
+    // Shared-dictionary batches (mi355lz4_compress_dict / mi355lz4_decompress_dict).  compressWithDict: every array compressed
+    // on its own against slot `slot` of cs, which CompressStreams::loadDict has loaded -- one framed array per input array, the
+    // reference's bytes for LZ4_loadDict + LZ4_compress_fast_continue on a copy of the loaded stream; the slot is only read.
+    // decompressWithDict: resized blocks (header + data each), every one decoded against `dict` (host memory, may be empty) as
+    // LZ4_decompress_safe_usingDict does -- one decoded array per block.  Both throw Error (a failed block included).
+    std::vector<Array> compressWithDict(const BlockConfig &cfg, int speed, const std::vector<Array> &arrays,
+                                        const class CompressStreams &cs, int slot);
+    std::vector<Array> decompressWithDict(const BlockConfig &cfg, const std::vector<Array> &blocks, const Array &dict);
 private:
     mi355lz4_ctx *ctx_ = nullptr;
     size_t batch_;
@@ -128,6 +136,9 @@ public:
     int count() const;
     void reset();                                       // LZ4_resetStream, all slots
     void reset(const std::vector<int32_t> &slots);      // ... the listed ones
+    // LZ4_loadDict on a slot (mi355lz4_cstreams_load_dict): table, currentOffset 65536 and the last 64 KiB of
+    // dictDevice[0, len) (DEVICE memory; under 8 bytes: no dictionary); enqueued, the slot keeps its own copy
+    void loadDict(int slot, const uint8_t *dictDevice, int len);
 private:
     Engine &eng_;
     mi355lz4_cstreams *cs_ = nullptr;

@@ -851,6 +851,18 @@ extern "C" int mi355lz4_debug_cstream_state(mi355lz4_cstreams *cs, int slot, uin
     return MI355LZ4_OK;
 }
 
+// Diagnostic hook (not part of the public header): slot `slot` as it is after everything queued on the device has run, all
+// CSTREAM_SLOT_BYTES of it (table, scalars, saved bytes) into bytes (host memory).  The tests compare a loaded slot with
+// LZ4_loadDict's state and show that a shared slot is never written.
+extern "C" int mi355lz4_debug_cstream_slot(mi355lz4_cstreams *cs, int slot, uint8_t *bytes)
+{
+    if (!cs || !bytes || slot < 0 || slot >= cs->nSlots) return fail(MI355LZ4_E_ARG, "debug_cstream_slot: bad arguments");
+    HIP_TRY(hipSetDevice(cs->device));
+    HIP_TRY(hipDeviceSynchronize());
+    HIP_TRY(hipMemcpy(bytes, cs->state + (size_t)slot * CSTREAM_SLOT_BYTES, CSTREAM_SLOT_BYTES, hipMemcpyDeviceToHost));
+    return MI355LZ4_OK;
+}
+
 // the stream table of a call, checked: ascending over [0, nBlocks], every slot in range and named once
 static int stream_table_check(int nSlots, int nBlocks, const int32_t *streamFirst, const int32_t *streamSlot, int nStreams,
                               const char *who)
@@ -965,6 +977,50 @@ extern "C" int mi355lz4_compress_streams_device(mi355lz4_ctx *c, mi355lz4_cstrea
     HIP_TRY(hipSetDevice(c->device));
     const EncodeArgs a = make_encode_args(src, srcOff, srcLen, blockStride, maxBlockLen, nBlocks, accel, headerKind, slots, slotStride, framedLen);
     return streams_enqueue(c, cs, a, 0, nBlocks, streamFirst, streamSlot, nStreams);
+}
+
+// ---------------------------------------------------------------------------
+// Shared-dictionary batches.  mi355lz4_cstreams_load_dict is LZ4_loadDict on one slot of a set, on the device;
+// mi355lz4_compress_dict_device compresses every block of a batch from a copy of that slot (k_exact_dict: one wave per block,
+// the slot read-only), so the same loaded slot serves any number of calls.  Both only enqueue.
+// ---------------------------------------------------------------------------
+extern "C" int mi355lz4_cstreams_load_dict(mi355lz4_ctx *c, mi355lz4_cstreams *cs, int slot, const uint8_t *dictDevice, int len)
+{
+    if (int r = slots_same_device(c, cs, "cstreams_load_dict")) return r;
+    if (slot < 0 || slot >= cs->nSlots) return fail(MI355LZ4_E_ARG, "cstreams_load_dict: slot %d of %d", slot, cs->nSlots);
+    if (len < 0 || (len > 0 && !dictDevice)) return fail(MI355LZ4_E_ARG, "cstreams_load_dict: bad dictionary");
+    HIP_TRY(hipSetDevice(c->device));
+    launch_cstreams_load_dict(cs->state + (size_t)slot * CSTREAM_SLOT_BYTES, dictDevice, len, c->stream);
+    return check_launch("cstreams load_dict launch");
+}
+
+extern "C" int mi355lz4_compress_dict_device(mi355lz4_ctx *c, const mi355lz4_cstreams *cs, int dictSlot, const uint8_t *src,
+                                             const uint64_t *srcOff, const int32_t *srcLen, uint64_t blockStride,
+                                             int maxBlockLen, int nBlocks, int accel, int headerKind, uint8_t *slots,
+                                             size_t slotStride, int32_t *framedLen)
+{
+    if (int r = slots_same_device(c, cs, "compress_dict_device")) return r;
+    if (c->compLevel != 0)
+        return fail(MI355LZ4_E_ARG, "compress_dict_device: compression level %d; the dictionary batch is level 0's encoder", c->compLevel);
+    if (dictSlot < 0 || dictSlot >= cs->nSlots) return fail(MI355LZ4_E_ARG, "compress_dict_device: slot %d of %d", dictSlot, cs->nSlots);
+    if (nBlocks < 0 || (headerKind != 4 && headerKind != 8) || maxBlockLen < 0 || (unsigned)maxBlockLen > (unsigned)MI355LZ4_MAX_INPUT_SIZE)
+        return fail(MI355LZ4_E_ARG, "compress_dict_device: bad arguments");
+    if (nBlocks == 0) return MI355LZ4_OK;
+    if (!src && maxBlockLen > 0) return fail(MI355LZ4_E_ARG, "compress_dict_device: null src");
+    if (!slots || !framedLen) return fail(MI355LZ4_E_ARG, "compress_dict_device: null output");
+    if (slotStride < mi355lz4_compress_bound(maxBlockLen) + (size_t)headerKind + (c->blockChecksum ? 4u : 0u))
+        return fail(MI355LZ4_E_CAPACITY, "compress_dict_device: slotStride %zu < bound", slotStride);
+    HIP_TRY(hipSetDevice(c->device));
+    ExactDictArgs x;
+    x.e = make_encode_args(src, srcOff, srcLen, blockStride, maxBlockLen, nBlocks, accel, headerKind, slots, slotStride, framedLen);
+    x.state = cs->state + (size_t)dictSlot * CSTREAM_SLOT_BYTES;
+    launch_exact_dict(x, c->stream);
+    if (int r = check_launch("exact dict launch")) return r;
+    if (c->blockChecksum) {                               // the trailers, behind the encoder (encode_device, finish)
+        launch_xxh32_append(slots, slotStride, headerKind, framedLen, nBlocks, c->stream);
+        return check_launch("checksum launch");
+    }
+    return MI355LZ4_OK;
 }
 
 extern "C" int mi355lz4_compact_device(mi355lz4_ctx *c, const uint8_t *slots, size_t slotStride,
@@ -1435,6 +1491,27 @@ int mi355lz4_detail::dstreams_check(const mi355lz4_ctx *c, const mi355lz4_dstrea
     return stream_table_check(ds->nSlots, nBlocks, streamFirst, streamSlot, nStreams, who);
 }
 
+// Block checksums for the calls that decode every block once (dstreams, dictionary batches), as decode_device has them: ck_flags
+// enqueues k_xxh32_verify over a's blocks into the engine's ckBuf and arms a.ckFail (nothing when checksums are off); ck_done,
+// behind the launches that read the flags, marks where the next decode on another stream has to wait.
+static int ck_flags(mi355lz4_ctx *c, DecodeArgs &a)
+{
+    if (!c->blockChecksum) return MI355LZ4_OK;
+    int rc;
+    if (c->ckEvent && c->ckStream != c->stream) HIP_TRY(hipStreamWaitEvent(c->stream, c->ckEvent, 0));
+    if ((rc = dev_reserve(c->ckBuf, (size_t)a.nBlocks * 4))) return rc;
+    launch_xxh32_verify(a, (int32_t *)c->ckBuf.p, c->stream);
+    if ((rc = check_launch("checksum launch"))) return rc;
+    a.ckFail = (const int32_t *)c->ckBuf.p;
+    return MI355LZ4_OK;
+}
+static void ck_done(mi355lz4_ctx *c)
+{
+    if (!c->blockChecksum) return;
+    if (!c->ckEvent && hipEventCreateWithFlags(&c->ckEvent, hipEventDisableTiming) != hipSuccess) c->ckEvent = nullptr;
+    if (c->ckEvent && hipEventRecord(c->ckEvent, c->stream) == hipSuccess) c->ckStream = c->stream;
+}
+
 // Enqueue the streams' parts that fall into blocks [b0, b1) of the table (d.* describes exactly those blocks, as a.* does in
 // streams_enqueue): the checksum flags first, as in decode_device, then one wave per stream with blocks.
 int mi355lz4_detail::dstreams_enqueue(mi355lz4_ctx *c, mi355lz4_dstreams *ds, const DecodeCall &d, int b0, int b1,
@@ -1446,13 +1523,7 @@ int mi355lz4_detail::dstreams_enqueue(mi355lz4_ctx *c, mi355lz4_dstreams *ds, co
     x.d.headerKind = d.headerKind; x.d.fixedUncomp = d.fixedUncomp; x.d.linked = 1;
     x.d.out = d.out; x.d.outOff = d.outOff; x.d.outCap = d.outCap; x.d.result = d.result; x.d.onlyBlk = -1;
     int rc;
-    if (c->blockChecksum) {
-        if (c->ckEvent && c->ckStream != c->stream) HIP_TRY(hipStreamWaitEvent(c->stream, c->ckEvent, 0));
-        if ((rc = dev_reserve(c->ckBuf, (size_t)d.nBlocks * 4))) return rc;
-        launch_xxh32_verify(x.d, (int32_t *)c->ckBuf.p, c->stream);
-        if ((rc = check_launch("checksum launch"))) return rc;
-        x.d.ckFail = (const int32_t *)c->ckBuf.p;
-    }
+    if ((rc = ck_flags(c, x.d))) return rc;
     int nWork = 0;
     StreamTableRing::Ring *used = nullptr;
     if ((rc = stream_table_upload(c, ds->table, b0, b1, streamFirst, streamSlot, nStreams, &x.work, &nWork, &used))) return rc;
@@ -1462,10 +1533,7 @@ int mi355lz4_detail::dstreams_enqueue(mi355lz4_ctx *c, mi355lz4_dstreams *ds, co
         if ((rc = check_launch("decode streams launch"))) return rc;
         if ((rc = stream_table_launched(c, used))) return rc;
     }
-    if (c->blockChecksum) {
-        if (!c->ckEvent && hipEventCreateWithFlags(&c->ckEvent, hipEventDisableTiming) != hipSuccess) c->ckEvent = nullptr;
-        if (c->ckEvent && hipEventRecord(c->ckEvent, c->stream) == hipSuccess) c->ckStream = c->stream;
-    }
+    ck_done(c);
     return MI355LZ4_OK;
 }
 
@@ -1483,6 +1551,34 @@ extern "C" int mi355lz4_decompress_dstreams_device(mi355lz4_ctx *c, mi355lz4_dst
     HIP_TRY(hipSetDevice(c->device));
     const DecodeCall d{framed, framedLen, blockOff, nBlocks, headerKind, fixedUncomp, 1, out, outOff, outCap, result};
     return dstreams_enqueue(c, ds, d, 0, nBlocks, streamFirst, streamSlot, nStreams);
+}
+
+// Independent blocks against one external dictionary: LZ4_decompress_safe_usingDict's external-dictionary path
+// for every block, k_decode_dict.  Every block is decoded once, with the dictionary, so the call only enqueues; the checksum
+// flags go first (ck_flags).  The decoder-variant knob has no say: the workgroup form has no dictionary.
+extern "C" int mi355lz4_decompress_dict_device(mi355lz4_ctx *c, const uint8_t *framed, uint64_t framedLen,
+                                               const uint64_t *blockOff, int nBlocks, int headerKind, int fixedUncomp,
+                                               const uint8_t *dictDevice, int dictLen, uint8_t *out, const uint64_t *outOff,
+                                               const int32_t *outCap, int32_t *result)
+{
+    if (!c) return fail(MI355LZ4_E_ARG, "null ctx");
+    if (c->plan.active) return fail(MI355LZ4_E_ARG, "decompress_dict_device: a linked decode begun with mi355lz4_decompress_linked_begin is still open");
+    if (nBlocks < 0 || (headerKind != 4 && headerKind != 8) || fixedUncomp < 0)
+        return fail(MI355LZ4_E_ARG, "decompress_dict_device: bad arguments");
+    if (dictLen < 0 || (dictLen > 0 && !dictDevice)) return fail(MI355LZ4_E_ARG, "decompress_dict_device: bad dictionary");
+    if (nBlocks == 0) return MI355LZ4_OK;
+    if (!framed || !blockOff || !outOff || !result) return fail(MI355LZ4_E_ARG, "decompress_dict_device: null pointer");
+    HIP_TRY(hipSetDevice(c->device));
+    DecodeArgs a{};
+    a.framed = framed; a.framedLen = framedLen; a.blockOff = blockOff; a.nBlocks = nBlocks; a.segEnd = nBlocks;
+    a.headerKind = headerKind; a.fixedUncomp = fixedUncomp;
+    a.out = out; a.outOff = outOff; a.outCap = outCap; a.result = result; a.onlyBlk = -1;
+    a.dict0 = dictDevice; a.dict0Len = (uint32_t)dictLen;
+    if (int rc = ck_flags(c, a)) return rc;
+    launch_decode_dict(a, c->stream);
+    const int rc = check_launch("decode dict launch");
+    ck_done(c);
+    return rc;
 }
 
 extern "C" int mi355lz4_xxh32_device(mi355lz4_ctx *c, const uint8_t *base, const uint64_t *off, const int32_t *len, int n,

@@ -177,10 +177,13 @@ static inline int32_t host_le32(const uint8_t *p)
 // the streams of a mi355lz4_compress_streams / mi355lz4_decompress_dstreams call: every stream continues through its slot of the
 // set, whatever group its blocks fall into (null: mi355lz4_compress_batch / mi355lz4_decompress_batch, no set)
 template <class Set> struct HostStreams { Set *set; const int32_t *first, *slot; int n; };
+// the loaded slot of a mi355lz4_compress_dict call: every block of every group from a copy of it (null: no dictionary)
+struct HostDict { const mi355lz4_cstreams *set; int slot; };
 
 static int compress_host(mi355lz4_ctx *c, const uint8_t *const *src, const int32_t *srcLen,
                          int nBlocks, int accel, int headerKind, uint8_t *framedOut, size_t cap,
-                         size_t *outLen, int32_t *blockFramedLen, int32_t *status, const HostStreams<mi355lz4_cstreams> *hs)
+                         size_t *outLen, int32_t *blockFramedLen, int32_t *status, const HostStreams<mi355lz4_cstreams> *hs,
+                         const HostDict *hd = nullptr)
 {
     if (!c) return fail(MI355LZ4_E_ARG, "null ctx");
     if (nBlocks < 0 || (headerKind != 4 && headerKind != 8) || !outLen)
@@ -202,7 +205,7 @@ static int compress_host(mi355lz4_ctx *c, const uint8_t *const *src, const int32
         offs[(size_t)i] = total;
         if (i > 0 && src[i] != src[0] + total) contiguous = false;
         // 16-aligned block starts; back to back for a linked stream (a block's dictionary lies directly in front of it)
-        total += (c->linkedCompress && !hs) ? (size_t)srcLen[i] : (((size_t)srcLen[i] + 15) & ~(size_t)15);
+        total += (c->linkedCompress && !hs && !hd) ? (size_t)srcLen[i] : (((size_t)srcLen[i] + 15) & ~(size_t)15);
         if (srcLen[i] > maxLen) maxLen = srcLen[i];
     }
     const size_t stride = mi355lz4_slot_stride_ex(maxLen, headerKind, c->blockChecksum);
@@ -276,6 +279,10 @@ static int compress_host(mi355lz4_ctx *c, const uint8_t *const *src, const int32
                                                   0, maxLen, b1 - b0, accel, headerKind, (uint8_t *)c->slots.p + (size_t)b0 * stride,
                                                   stride, (int32_t *)c->lenB.p + b0);
             r = streams_enqueue(c, hs->set, a, b0, b1, hs->first, hs->slot, hs->n);
+        } else if (hd) {                           // (independent blocks, the slot only read: the groups may overlap)
+            r = mi355lz4_compress_dict_device(c, hd->set, hd->slot, (const uint8_t *)c->in.p, (const uint64_t *)c->offA.p + b0,
+                                              (const int32_t *)c->lenA.p + b0, 0, maxLen, b1 - b0, accel, headerKind,
+                                              (uint8_t *)c->slots.p + (size_t)b0 * stride, stride, (int32_t *)c->lenB.p + b0);
         } else {
             r = encode_device(c, (const uint8_t *)c->in.p, (const uint64_t *)c->offA.p + b0,
                               (const int32_t *)c->lenA.p + b0, 0, maxLen, b1 - b0, accel, headerKind,
@@ -357,6 +364,21 @@ extern "C" int mi355lz4_compress_streams(mi355lz4_ctx *c, mi355lz4_cstreams *cs,
     if (r) return r;
     const HostStreams<mi355lz4_cstreams> hs{cs, streamFirst, streamSlot, nStreams};
     return compress_host(c, src, srcLen, nBlocks, accel, headerKind, framedOut, cap, outLen, blockFramedLen, status, &hs);
+}
+
+// Host-buffer form of mi355lz4_compress_dict_device: the group pipeline of mi355lz4_compress_batch, every group's blocks from a
+// copy of the loaded slot.  The lengths are the caller's host array: checked before anything is queued.
+extern "C" int mi355lz4_compress_dict(mi355lz4_ctx *c, const mi355lz4_cstreams *cs, int dictSlot, const uint8_t *const *src,
+                                      const int32_t *srcLen, int nBlocks, int accel, int headerKind, uint8_t *framedOut,
+                                      size_t cap, size_t *outLen, int32_t *blockFramedLen, int32_t *status)
+{
+    if (outLen) *outLen = 0;
+    if (!c || !cs) return fail(MI355LZ4_E_ARG, "compress_dict: null argument");
+    if (mi355lz4_cstreams_count(cs) <= dictSlot || dictSlot < 0) return fail(MI355LZ4_E_ARG, "compress_dict: slot %d out of range", dictSlot);
+    if (engine_compression_level(c) != 0)
+        return fail(MI355LZ4_E_ARG, "compress_dict: compression level %d; the dictionary batch is level 0's encoder", engine_compression_level(c));
+    const HostDict hd{cs, dictSlot};
+    return compress_host(c, src, srcLen, nBlocks, accel, headerKind, framedOut, cap, outLen, blockFramedLen, status, nullptr, &hd);
 }
 
 extern "C" int mi355lz4_index_host_ex(const uint8_t *framedIn, size_t inLen, int headerKind, int fixedUncomp,
@@ -744,6 +766,42 @@ extern "C" int mi355lz4_decompress_partial(mi355lz4_ctx *c, const uint8_t *frame
                                            (int32_t *)c->res.p);
     if (r) return r;
     return host_tail(c, "decompress_partial", h, out, cap, outLen, blockLen, nBlocksOut);
+}
+
+// Independent blocks of a chain in host memory against one dictionary in host memory (mi355lz4_decompress_dict_device).  One group,
+// synchronous, as the partial form: the chain and the dictionary's last 64 KiB go up (keeping exactly 64 KiB of a longer one
+// preserves "dictSize >= 64 KB => no offset check", upload_dict), one decode lays the blocks out at their capacities, one copy back.
+extern "C" int mi355lz4_decompress_dict(mi355lz4_ctx *c, const uint8_t *framedIn, size_t inLen, int headerKind, int fixedUncomp,
+                                        const uint8_t *dict, int dictLen, uint8_t *out, size_t cap, size_t *outLen,
+                                        int32_t *blockLen, int maxBlocks, int *nBlocksOut)
+{
+    if (!c) return fail(MI355LZ4_E_ARG, "null ctx");
+    if (!outLen || !nBlocksOut || maxBlocks < 0 || fixedUncomp < 0 || (headerKind != 4 && headerKind != 8))
+        return fail(MI355LZ4_E_ARG, "decompress_dict: bad arguments");
+    if (dictLen < 0 || (dictLen > 0 && !dict)) return fail(MI355LZ4_E_ARG, "decompress_dict: bad dictionary");
+    if (c->plan.active) return fail(MI355LZ4_E_ARG, "a linked decode begun with mi355lz4_decompress_linked_begin is still open");
+    *outLen = 0;
+    *nBlocksOut = 0;
+    HostChain h;
+    int r = host_chain(h, "decompress_dict", MI355LZ4_E_STREAM, framedIn, inLen, headerKind, fixedUncomp, c->blockChecksum, maxBlocks, at_capacity);
+    if (r) return r;
+    const int n = h.n;
+    if (n == 0) return MI355LZ4_OK;
+    HIP_TRY(hipSetDevice(c->device));
+    if ((r = dev_reserve(c->in, inLen + 16)) || (r = dev_reserve(c->offA, (size_t)n * 8)) || (r = dev_reserve(c->offB, ((size_t)n + 1) * 8)) ||
+        (r = dev_reserve(c->res, (size_t)n * 4)) || (r = dev_reserve(c->out, (size_t)h.total + 16)))
+        return r;
+    uint32_t dlen = 0;
+    if ((r = upload_dict(c, 1, dict, dictLen, &dlen))) return r;
+    if ((r = h2d_staged(c, c->in.p, framedIn, inLen))) return r;
+    HIP_TRY(hipMemcpyAsync(c->offA.p, h.boff.data(), (size_t)n * 8, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipMemcpyAsync(c->offB.p, h.ooff.data(), ((size_t)n + 1) * 8, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));          // (the vectors and the dictionary are pageable memory)
+    r = mi355lz4_decompress_dict_device(c, (const uint8_t *)c->in.p, inLen, (const uint64_t *)c->offA.p, n, headerKind, fixedUncomp,
+                                        dlen ? (const uint8_t *)c->scratch.p : nullptr, (int)dlen, (uint8_t *)c->out.p,
+                                        (const uint64_t *)c->offB.p, nullptr, (int32_t *)c->res.p);
+    if (r) return r;
+    return host_tail(c, "decompress_dict", h, out, cap, outLen, blockLen, nBlocksOut);
 }
 
 // the size pass over blocks in host memory: H2D, mi355lz4_decoded_size_device, sizes back; synchronous

@@ -161,6 +161,13 @@ struct ExactStreamsArgs {
     uint8_t *state;              // the set's slots, CSTREAM_SLOT_BYTES each
 };
 
+// a batch against one loaded slot (mi355lz4_compress_dict_device; kernels/encode.inc, k_exact_dict): every block from a copy of
+// the slot's state, the slot itself read-only
+struct ExactDictArgs {
+    EncodeArgs e;                // blocks, slots, headers, framedLen, accel (clamped); e.uniformLen bounds every length
+    const uint8_t *state;        // the one slot, CSTREAM_SLOT_BYTES
+};
+
 // many linked decode streams continued across calls (mi355lz4_decompress_dstreams_device; kernels/linked_walk.inc, k_decode_dstreams).
 // One slot of a mi355lz4_dstreams is the device form of LZ4_streamDecode_t for separately allocated blocks: the last
 // min(r, 65536) bytes of the stream's last block that decoded to r > 0 bytes, at the slot's start, and that count.
@@ -223,6 +230,12 @@ void launch_exact_verify(const ExactArgs &a, int first, int count, hipStream_t s
 void launch_exact_finish(const ExactArgs &a, hipStream_t s);
 // many reference-exact streams: one wave per entry of a.work walks its blocks from its slot's state and stores the state back
 void launch_exact_streams(const ExactStreamsArgs &a, int nWork, hipStream_t s);
+// LZ4_loadDict on one slot (slotState = its CSTREAM_SLOT_BYTES): table, scalars and the last min(len, 65536) bytes of dict
+void launch_cstreams_load_dict(uint8_t *slotState, const uint8_t *dict, int len, hipStream_t s);
+// one wave per block, each from a copy of the slot's state; nothing is stored back
+void launch_exact_dict(const ExactDictArgs &a, hipStream_t s);
+// independent blocks against one external dictionary (a.dict0, a.dict0Len; a.linked is not used): one wave per block
+void launch_decode_dict(const DecodeArgs &a, hipStream_t s);
 // many linked decode streams: one wave per entry of a.work walks its blocks from its slot's dictionary and stores the tail back;
 // launch_dstreams_set: slots [first, first + count) take the keep <= 65536 bytes at src as their dictionary (0: reset)
 void launch_decode_dstreams(const DStreamsArgs &a, int nWork, hipStream_t s);

@@ -292,6 +292,100 @@ void launch_exact_streams(const ExactStreamsArgs &a, int nWork, hipStream_t s)
     hipLaunchKernelGGL(k_exact_streams, dim3((unsigned)nWork), dim3(LZ4_WAVE), 0, s, a);
 }
 
+// LZ4_loadDict (cbits/lz4.c:1475-1515) on one slot of a mi355lz4_cstreams (mi355lz4_cstreams_load_dict, DESIGN.md 7i): one
+// workgroup, the table in LDS.  The reference enters every third position p <= dictEnd - 8 of the last 64 KiB in ascending
+// order, so a bucket keeps its last writer -- and the index p - (dictEnd - 65536) rises with p, so the last writer is the
+// largest index: an LDS atomicMax over the zeroed table gives the same table whatever order the lanes run in.  (Index 0 --
+// the first position of a full 64 KiB -- reads as "empty", as it does in the reference.)  Then the table, the scalars
+// {currentOffset 65536, dictSize, saved bytes} and the slot's own copy of the bytes go out with vector stores.  Under 8 bytes
+// (HASH_UNIT) the reference returns behind the reset and the offset: no dictionary, an empty table, currentOffset 65536.
+#define LOAD_DICT_THREADS 256
+__global__ __launch_bounds__(LOAD_DICT_THREADS) void k_cstreams_load_dict(uint8_t *st, const uint8_t *dict, int len)
+{
+    __shared__ dev_v4 tab4[EXACT_TABLE / 4];
+    uint32_t *tab = (uint32_t *)tab4;
+    const uint32_t tid = threadIdx.x;
+    for (uint32_t i = tid; i < EXACT_TABLE / 4; i += LOAD_DICT_THREADS) tab4[i] = dev_v4{0u, 0u, 0u, 0u};
+    __syncthreads();
+    const uint32_t keep = len < 8 ? 0u : ((uint32_t)len > 65536u ? 65536u : (uint32_t)len);
+    const uint8_t *from = dict + ((uint32_t)len - keep);               // (not dereferenced when keep == 0)
+    if (keep)                                                           // p + 8 <= keep: the last position is dictEnd - HASH_UNIT
+        for (uint32_t p = 3u * tid; p + 8u <= keep; p += 3u * LOAD_DICT_THREADS)
+            atomicMax(&tab[ex_hash5(from + p)], p + (65536u - keep));
+    __syncthreads();
+    for (uint32_t i = tid; i < EXACT_TABLE / 4; i += LOAD_DICT_THREADS) as_global((dev_v4 *)st)[i] = tab4[i];
+    if (tid == 0) {
+        LZ4_GLOBAL uint32_t *scal = as_global((uint32_t *)(st + CSTREAM_SCALAR_OFF));
+        scal[0] = 65536u; scal[1] = keep; scal[2] = keep; scal[3] = 0u;
+    }
+    // the bytes: each wave a run of 16 KiB pieces
+    const uint32_t piece = 16384u;
+    for (uint32_t at = (tid / LZ4_WAVE) * piece; at < keep; at += (LOAD_DICT_THREADS / LZ4_WAVE) * piece)
+        wave_copy_bytes(st + CSTREAM_DICT_OFF + at, from + at, keep - at < piece ? keep - at : piece);
+}
+
+void launch_cstreams_load_dict(uint8_t *slotState, const uint8_t *dict, int len, hipStream_t s)
+{
+    hipLaunchKernelGGL(k_cstreams_load_dict, dim3(1), dim3(LOAD_DICT_THREADS), 0, s, slotState, dict, len);
+}
+
+// A batch of blocks, each compressed on its own from a COPY of one slot's state (mi355lz4_compress_dict_device, DESIGN.md 7i):
+// block blockIdx.x is what LZ4_compress_fast_continue writes on a copy of that LZ4_stream_t.  One wavefront per block; it
+// loads the table and the scalars as k_exact_streams does, runs the statements in front of the encoder (cbits/lz4.c:1577-1627,
+// the renorm included: the state is whatever the slot holds) and encodes with the slot's saved bytes as the dictionary.
+// Nothing goes back to the slot, and no block sees another: the slot is shared, read-only state.
+__global__ __launch_bounds__(LZ4_WAVE) void k_exact_dict(ExactDictArgs x)
+{
+    __shared__ dev_v4 tab4[EXACT_TABLE / 4];
+    uint32_t *tab = (uint32_t *)tab4;
+    const int lane = lane_id();
+    const int j = (int)blockIdx.x;
+    const int n = uni(x.e.srcLen ? x.e.srcLen[j] : x.e.uniformLen);
+    if (n < 0 || n > x.e.uniformLen) {
+        if (lane == 0) x.e.framedLen[j] = 0;
+        return;
+    }
+    const uint8_t *st = x.state;
+    const uint32_t *scal = (const uint32_t *)(st + CSTREAM_SCALAR_OFF);
+    for (int i = lane; i < EXACT_TABLE / 4; i += LZ4_WAVE) tab4[i] = as_global((const dev_v4 *)st)[i];
+    uint32_t cur = ex_uni(as_global(scal)[0]), dictSize = ex_uni(as_global(scal)[1]);
+    const uint32_t dictBytes = ex_uni(as_global(scal)[2]);
+    const uint8_t *dictEnd = st + CSTREAM_DICT_OFF + dictBytes;
+    __syncthreads();
+    ExactBlock m;
+    m.delta = 0;
+    if (cur + (uint32_t)n > 0x80000000u) {                              // LZ4_renormDictT, cbits/lz4.c:1545-1562
+        m.delta = cur - 65536u;
+        cur = 65536u;
+        if (dictSize > 65536u) dictSize = 65536u;
+        for (int i = lane; i < EXACT_TABLE / 4; i += LZ4_WAVE) tab4[i] = exact_canon4(tab4[i], 0u, m.delta);
+        __syncthreads();
+    }
+    if (dictSize - 1u < 4u - 1u) dictSize = 0;                          // :1581-1587
+    m.start = cur; m.dictSize = dictSize; m.n = n; m.pad = 0;
+    m.dictSmall = (dictSize < 65536u && dictSize < cur) ? 1 : 0;        // :1627
+    uint8_t *slot = x.e.slots + (size_t)j * x.e.slotStride;
+    const int cap = n + n / 255 + 16;                                   // LZ4_compressBound
+    int c;
+    if (n == 0) {                                                       // cbits/lz4.c:1263-1273
+        c = 1;
+        if (lane == 0) slot[x.e.headerKind] = 0;
+    } else {
+        c = exact_encode_block(tab, exact_src(x.e, j), n, dictEnd, m, (uint32_t)x.e.accel, slot + x.e.headerKind, cap, true);
+    }
+    if (lane == 0) {
+        store_le32(slot, c);
+        if (x.e.headerKind == 8) store_le32(slot + 4, n);
+        x.e.framedLen[j] = (c > 0) ? x.e.headerKind + c : 0;
+    }
+}
+
+void launch_exact_dict(const ExactDictArgs &a, hipStream_t s)
+{
+    if (a.e.nBlocks <= 0) return;
+    hipLaunchKernelGGL(k_exact_dict, dim3((unsigned)a.e.nBlocks), dim3(LZ4_WAVE), 0, s, a);
+}
+
 // ---------------------------------------------------------------------------
 // K2, small batches: several waves per block (encode_wave.hpp, SEG).  One wavefront per block cannot be faster than
 // one block (1.5 ms for 64 KiB), however empty the chip is: a call of 160 blocks -- the reference's own benchmark

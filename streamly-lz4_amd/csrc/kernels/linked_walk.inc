@@ -85,6 +85,31 @@ void launch_decode_dstreams(const DStreamsArgs &a, int nWork, hipStream_t s)
     hipLaunchKernelGGL(k_decode_dstreams, dim3((unsigned)nWork), dim3(64), 0, s, a);
 }
 
+// A batch of independent blocks against ONE external dictionary (mi355lz4_decompress_dict_device, DESIGN.md 7i): block
+// blockIdx.x is LZ4_decompress_safe_usingDict on its external-dictionary path (LZ4_decompress_safe_forceExtDict,
+// cbits/lz4.c:2404-2417) with (a.dict0, a.dict0Len), any length -- only the last 64 KiB can be reached, and a dictionary
+// under 64 KiB arms the offset check (:1764).  One wavefront per block, every block decoded once with the dictionary: no
+// standalone pass, no second pass, and the dictionary is only read.
+__global__ PAR_OCC void k_decode_dict(DecodeArgs a)
+{
+    __shared__ ParLds lds;
+    const int blk = (int)blockIdx.x;
+    const uint8_t *data = nullptr;
+    int compLen = 0, cap = 0;
+    int r = read_block_header(a, blk, data, compLen, cap);
+    if (r == 0)
+        r = decode_block_par<false, true>(data, compLen, a.out + a.outOff[blk], cap, a.dict0, a.dict0Len, a.framed,
+                                          a.framed + a.framedLen, lds, nullptr);
+    r = uni(r);
+    if (lane_id() == 0) a.result[blk] = r;
+}
+
+void launch_decode_dict(const DecodeArgs &a, hipStream_t s)
+{
+    if (a.nBlocks <= 0) return;
+    hipLaunchKernelGGL(k_decode_dict, dim3((unsigned)a.nBlocks), dim3(64), 0, s, a);
+}
+
 // LZ4_setStreamDecode for `count` slots from `first` on (one wave each): the slot's state becomes the keep <= 65536 bytes at
 // src (none: a reset).  dstreams_set_dict and dstreams_reset; nothing of the host is read.
 __global__ __launch_bounds__(LZ4_WAVE) void k_dstreams_set(uint8_t *state, int first, const uint8_t *src, uint32_t keep)

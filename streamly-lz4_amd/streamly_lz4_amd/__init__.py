@@ -135,6 +135,7 @@ def _load():
     sig("mi355lz4_cstreams_count", C.c_int, vp)
     sig("mi355lz4_cstreams_reset", C.c_int, vp, vp, _i32p, C.c_int)
     sig("mi355lz4_debug_cstream_state", C.c_int, vp, C.c_int, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32))
+    sig("mi355lz4_debug_cstream_slot", C.c_int, vp, C.c_int, _u8p)
     sig("mi355lz4_compress_streams_device", C.c_int, vp, vp, vp, vp, vp, C.c_uint64, C.c_int, C.c_int, _i32p, _i32p,
         C.c_int, C.c_int, C.c_int, vp, C.c_size_t, vp)
     sig("mi355lz4_compress_streams", C.c_int, vp, vp, C.POINTER(_u8p), _i32p, C.c_int, _i32p, _i32p, C.c_int, C.c_int,
@@ -150,6 +151,16 @@ def _load():
         C.c_int, vp, vp, vp, vp)
     sig("mi355lz4_decompress_dstreams", C.c_int, vp, vp, _u8p, C.c_size_t, C.c_int, C.c_int, _i32p, _i32p, C.c_int,
         _u8p, C.c_size_t, C.POINTER(C.c_size_t), _i32p, C.c_int, C.POINTER(C.c_int))
+    # shared-dictionary batches
+    sig("mi355lz4_cstreams_load_dict", C.c_int, vp, vp, C.c_int, vp, C.c_int)
+    sig("mi355lz4_compress_dict_device", C.c_int, vp, vp, C.c_int, vp, vp, vp, C.c_uint64, C.c_int, C.c_int, C.c_int, C.c_int,
+        vp, C.c_size_t, vp)
+    sig("mi355lz4_decompress_dict_device", C.c_int, vp, vp, C.c_uint64, vp, C.c_int, C.c_int, C.c_int, vp, C.c_int,
+        vp, vp, vp, vp)
+    sig("mi355lz4_compress_dict", C.c_int, vp, vp, C.c_int, C.POINTER(_u8p), _i32p, C.c_int, C.c_int, C.c_int, _u8p,
+        C.c_size_t, C.POINTER(C.c_size_t), _i32p, _i32p)
+    sig("mi355lz4_decompress_dict", C.c_int, vp, _u8p, C.c_size_t, C.c_int, C.c_int, _u8p, C.c_int, _u8p, C.c_size_t,
+        C.POINTER(C.c_size_t), _i32p, C.c_int, C.POINTER(C.c_int))
     # legacy face (include/lz4.h)
     sig("LZ4_createStream", vp)
     sig("LZ4_freeStream", C.c_int, vp)
@@ -207,6 +218,8 @@ DECLARED_SYMBOLS = [
     "mi355lz4_decompress_partial_device", "mi355lz4_decompress_partial",
     "mi355lz4_dstreams_create", "mi355lz4_dstreams_destroy", "mi355lz4_dstreams_count", "mi355lz4_dstreams_reset",
     "mi355lz4_dstreams_set_dict", "mi355lz4_decompress_dstreams_device", "mi355lz4_decompress_dstreams",
+    "mi355lz4_cstreams_load_dict", "mi355lz4_compress_dict_device", "mi355lz4_decompress_dict_device",
+    "mi355lz4_compress_dict", "mi355lz4_decompress_dict",
     "LZ4_createStream", "LZ4_freeStream", "LZ4_createStreamDecode", "LZ4_freeStreamDecode", "LZ4_compressBound",
     "LZ4_compress_fast_continue", "LZ4_decompress_safe_continue",
 ]
@@ -852,6 +865,71 @@ class Engine:
             _check(rc, "decompress_dstreams")
         return out[: out_len.value].tobytes(), blen[: got.value].tolist()
 
+    def compress_dict_device(self, cs, dict_slot, src, n_blocks, max_block_len, slots, slot_stride_, framed_len, accel=1,
+                             header_kind=8, src_off=None, src_len=None, block_stride=None):
+        """A batch of independent blocks, every one compressed from a copy of slot dict_slot of cs (a slot that
+        CompressStreams.load_dict has loaded): the reference's bytes for LZ4_loadDict + LZ4_compress_fast_continue on a copy
+        of the loaded stream.  The block arguments are those of compress_batch_device; the slot is only read.  Only
+        enqueues (include/mi355lz4.h, mi355lz4_compress_dict_device)."""
+        self._follow_torch()
+        _check(lib.mi355lz4_compress_dict_device(
+            self.ctx, cs._h if cs is not None else None, int(dict_slot), _dptr(src), _dptr(src_off), _dptr(src_len),
+            int(max_block_len if block_stride is None else block_stride), int(max_block_len), int(n_blocks),
+            int(accel), int(header_kind), _dptr(slots), int(slot_stride_), _dptr(framed_len)), "compress_dict_device")
+
+    def decompress_dict_device(self, framed, framed_len, block_off, n_blocks, dict_device, dict_len, out, out_off, result,
+                               header_kind=8, fixed_uncomp=0, out_cap=None):
+        """A batch of independent blocks, every one decoded against dict_device[:dict_len] (a uint8 device tensor, any
+        length; 0: none): result[i] and the bytes are those of LZ4_decompress_safe_usingDict on its external-dictionary
+        path.  The block arguments are those of decompress_batch_device.  Only enqueues; set_decoder is ignored
+        (include/mi355lz4.h, mi355lz4_decompress_dict_device)."""
+        self._follow_torch()
+        _check(lib.mi355lz4_decompress_dict_device(
+            self.ctx, _dptr(framed), int(framed_len), _dptr(block_off), int(n_blocks), int(header_kind), int(fixed_uncomp),
+            _dptr(dict_device), int(dict_len), _dptr(out), _dptr(out_off), _dptr(out_cap), _dptr(result)),
+            "decompress_dict_device")
+
+    def compress_dict(self, blocks, cs, dict_slot=0, accel=1, header_kind=8):
+        """blocks: list of bytes-like, every one compressed against slot dict_slot of cs.  Returns (framed bytes, [framed
+        length per block]); mi355lz4_compress_dict."""
+        n = len(blocks)
+        arrs = [np.frombuffer(bytes(b), dtype=np.uint8) if not isinstance(b, np.ndarray) else b for b in blocks]
+        ptrs = (_u8p * max(n, 1))(*[a.ctypes.data_as(_u8p) for a in arrs])
+        lens = np.array([a.size for a in arrs] + [0], dtype=np.int32)
+        cap = int(sum(compress_bound(int(x)) + header_kind + 4 for x in lens[:n])) + 16
+        out = np.empty(cap, dtype=np.uint8)
+        out_len = C.c_size_t()
+        flen = np.zeros(max(n, 1), dtype=np.int32)
+        status = np.zeros(max(n, 1), dtype=np.int32)
+        _check(lib.mi355lz4_compress_dict(self.ctx, cs._h, int(dict_slot), ptrs, lens.ctypes.data_as(_i32p), n, int(accel),
+                                          int(header_kind), out.ctypes.data_as(_u8p), cap, C.byref(out_len),
+                                          flen.ctypes.data_as(_i32p), status.ctypes.data_as(_i32p)), "compress_dict")
+        return out[: out_len.value].tobytes(), flen[:n].tolist()
+
+    def decompress_dict(self, framed, dict_bytes, header_kind=8, fixed_uncomp=0, max_blocks=None, raise_on_block_error=True,
+                        cap=None):
+        """A framed chain in host memory, every block decoded against dict_bytes (may be empty).  Returns (decoded bytes,
+        [decoded length or negative code per block]); mi355lz4_decompress_dict."""
+        src = np.frombuffer(bytes(framed), dtype=np.uint8)
+        if max_blocks is None:
+            max_blocks = src.size // (header_kind + 1) + 1
+        if cap is None:
+            _, ulen = index_host(framed, header_kind, fixed_uncomp, self._block_checksum)
+            cap = int(np.asarray(ulen, dtype=np.int64).clip(min=0).sum()) + 16
+        cap = int(cap)
+        out = np.empty(max(cap, 1), dtype=np.uint8)
+        out_len = C.c_size_t()
+        blen = np.zeros(max(max_blocks, 1), dtype=np.int32)
+        got = C.c_int()
+        d = np.frombuffer(bytes(dict_bytes), dtype=np.uint8) if dict_bytes else None
+        rc = lib.mi355lz4_decompress_dict(self.ctx, src.ctypes.data_as(_u8p) if src.size else None, src.size, int(header_kind),
+                                          int(fixed_uncomp), d.ctypes.data_as(_u8p) if d is not None else None,
+                                          d.size if d is not None else 0, out.ctypes.data_as(_u8p), cap, C.byref(out_len),
+                                          blen.ctypes.data_as(_i32p), int(max_blocks), C.byref(got))
+        if rc != 0 and (raise_on_block_error or rc != -5):
+            _check(rc, "decompress_dict")
+        return out[: out_len.value].tobytes(), blen[: got.value].tolist()
+
 
 class CompressStreams:
     """A set of n_slots device-resident reference-exact compress streams (mi355lz4_cstreams, about 80 KiB a slot), for
@@ -876,6 +954,15 @@ class CompressStreams:
             _check(lib.mi355lz4_cstreams_reset(self._engine.ctx, self._h, a.ctypes.data_as(_i32p), int(a.size)),
                    "cstreams_reset")
 
+    def load_dict(self, slot, dict_device, length=None):
+        """LZ4_loadDict on a slot: table, currentOffset 65536 and the last 64 KiB of dict_device[:length] (a uint8 device
+        tensor; length defaults to all of it; under 8 bytes: no dictionary).  Enqueued; the slot keeps its own copy.  The
+        slot then serves Engine.compress_dict_device / compress_dict, or continues through compress_streams_device."""
+        self._engine._follow_torch()
+        n = int(dict_device.numel() if length is None else length) if dict_device is not None else 0
+        _check(lib.mi355lz4_cstreams_load_dict(self._engine.ctx, self._h, int(slot), _dptr(dict_device) if n else None, n),
+               "cstreams_load_dict")
+
     def state(self, slot, set_current_offset=None):
         """Diagnostics: (currentOffset, dictSize, saved dictionary bytes) of a slot, after the device is idle; with
         set_current_offset the slot's currentOffset is then overwritten."""
@@ -883,6 +970,14 @@ class CompressStreams:
         new = None if set_current_offset is None else C.byref(C.c_uint32(int(set_current_offset)))
         _check(lib.mi355lz4_debug_cstream_state(self._h, int(slot), got, new), "debug_cstream_state")
         return tuple(int(v) for v in got)
+
+    SLOT_BYTES = 81984          # kernels.h, CSTREAM_SLOT_BYTES: uint32 table[4096], 64 bytes of scalars, 65536 saved bytes
+
+    def slot_bytes(self, slot):
+        """Diagnostics: all SLOT_BYTES of a slot (table, scalars, saved dictionary bytes), after the device is idle."""
+        buf = np.empty(self.SLOT_BYTES, dtype=np.uint8)
+        _check(lib.mi355lz4_debug_cstream_slot(self._h, int(slot), buf.ctypes.data_as(_u8p)), "debug_cstream_slot")
+        return buf.tobytes()
 
     def close(self):
         if self._h:
