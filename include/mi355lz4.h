@@ -183,7 +183,22 @@ int mi355lz4_compress_bound(int n);
 size_t mi355lz4_slot_stride(int blockLen, int headerKind);
 
 /* ---- device-resident batched API (all data pointers are DEVICE pointers;
- *      asynchronous on the engine's stream) ----------------------------- */
+ *      asynchronous on the engine's stream) -----------------------------
+ * Where a call's regions may lie.  Every block of a call is a region of its own: block i of a decode call is read at
+ * framed + blockOff[i] and written at out + outOff[i]; block i of a compress call is read at src + srcOff[i] (or at
+ * src + i * blockStride) and written at slots + i * slotStride; a dictionary, a local block of _interleave_device and a
+ * range of _xxh32_device are regions too.
+ *   - Regions may lie in any order and at any distance from each other: no array of offsets has to ascend, a block may lie
+ *     below its predecessor or below the call's first block, and two blocks may be more than 2^32 bytes apart.  A linked
+ *     decode's blocks are given in stream order in the ARRAYS; where their bytes lie is free ("separately allocated
+ *     blocks").  Only the linked compressor looks at placement: block i - 1 is block i's dictionary when it lies directly
+ *     in front of it.
+ *   - Output regions (cap_i bytes at outOff[i], a slot, a range of dense / global) must not overlap each other or any
+ *     input region of the same call.
+ *   - Offsets, strides and a decode call's uint64_t framedLen are full 64-bit quantities, and so is every product the
+ *     engine forms from them (i * slotStride, i * blockStride, a slot's place in a cstreams / dstreams set): buffers,
+ *     strides and state sets beyond 4 GiB are ordinary arguments.
+ * tests/test_placement_gpu.py runs every call below with its regions permuted, straddling and beyond 2^31 and 2^32. */
 
 /* Compress nBlocks blocks.  Block i is src[srcOff[i] .. srcOff[i]+srcLen[i]);
  * srcOff == NULL means srcOff[i] = i * blockStride; srcLen == NULL means every
