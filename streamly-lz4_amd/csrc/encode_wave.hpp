@@ -503,6 +503,14 @@ __device__ int encode_block_wave(const uint8_t *src, int n, uint8_t *dst, int ac
 
     if (blockLen >= 13) {                               // LZ4_minLength, :221,:921
         const int mfl = n - LZ4_MFLIMIT + 1;            // match start must be < mfl (:883)
+        // A window finds the repeats of the windows in front of it, never its own: its 64 positions are probed before any of
+        // them is entered, and the first window of a block meets an empty table.  A block of one window (up to 75 bytes) so
+        // came out as literals whatever it held -- a period of 3 bytes as much as noise -- and one of two windows had most of
+        // its repeats out of sight.  Such a short block enters ENC_SHORT_STEP positions per fruitless dense window and probes the
+        // rest again, no miss charged; every other block enters the window and charges it, as before.
+#ifndef ENC_SHORT_STEP
+#define ENC_SHORT_STEP 8
+#endif
         // match end must be <= matchlimit (:884): the BLOCK's last 5 bytes are literals; a segment with a few bytes
         // of the block behind it stops short of its seam by what is missing
         const int matchlimit = SEG ? n - max(0, LZ4_LASTLITERALS - seg->tail) : n - LZ4_LASTLITERALS;
@@ -1197,10 +1205,17 @@ __device__ int encode_block_wave(const uint8_t *src, int n, uint8_t *dst, int ac
                 // ---- greedy left-to-right selection of non-overlapping matches ----
                 uint64_t hitm = __ballot(hit);
                 if (!hitm) {
-                    if (valid) { table[h] = (TabT)myPos; ENC_TAG_SET(h, tg); }
+                    // a short block (ENC_SHORT_STEP above).  Worked out here, on the rare path, and hidden from the
+                    // optimiser's hoisting: the scalar registers are all taken, and a value more that lives across the
+                    // windows is a register more that spills in them
+                    int len = blockLen;
+                    asm volatile("" : "+s"(len));
+                    const bool shortBlock = len - LZ4_MFLIMIT + 1 <= 2 * LZ4_WAVE;
+                    const int adv = shortBlock ? ENC_SHORT_STEP : LZ4_WAVE;
+                    if (valid && lane < adv) { table[h] = (TabT)myPos; ENC_TAG_SET(h, tg); }
                     __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-                    missAcc += LZ4_WAVE;
-                    p += LZ4_WAVE;
+                    missAcc += shortBlock ? 0u : (uint32_t)LZ4_WAVE;
+                    p += adv;
                     pfPos = -1;
                     continue;
                 }

@@ -19,6 +19,7 @@ for p in (ROOT, os.path.join(ROOT, "streamly-lz4_amd"), os.path.join(ROOT, "test
 
 from conftest import DECODERS  # noqa: E402
 import lz4f  # noqa: E402
+from lz4_check import check_block  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
@@ -105,6 +106,8 @@ def _walk(block, n, dict_len=0):
     assert pos == n
     if n < 13:
         assert seqs == 0
+    strict = check_block(block, n, dict_len)       # the strict validator too: bounds, the last token, compressBound
+    assert (strict[0], strict[3]) == (seqs, into_dict)
     return seqs, into_dict
 
 
