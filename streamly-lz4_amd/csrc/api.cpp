@@ -432,6 +432,21 @@ extern "C" int mi355lz4_debug_runin_state(mi355lz4_ctx *c, int *get, const int *
     return MI355LZ4_OK;
 }
 
+// Diagnostic hook (not part of the public header): what the HIP runtime says about a kernel of the lane-parallel decode family on
+// this context's device.  which: 0 k_decode_par<false>, 1 k_decode_par_redo, 2 k_decode_dict, 3 k_decode_par_partial<false>,
+// 4 k_decode_par_partial<true>, 5 k_decode_dstreams, 6 k_decode_fixup_linked, 7 k_decode_fixup_runs, 8 k_runin_decode, 9 k_runin_fix,
+// 10 k_decode_tolerant.  out (4 ints) = {resident workgroups per CU (hipOccupancyMaxActiveBlocksPerMultiprocessor; a workgroup is
+// one wave), static LDS bytes and registers (hipFuncGetAttributes), sizeof(ParLds)}.
+extern "C" int mi355lz4_debug_kernel_info(mi355lz4_ctx *c, int which, int *out)
+{
+    if (!c || !out) return fail(MI355LZ4_E_ARG, "debug_kernel_info: null argument");
+    HIP_TRY(hipSetDevice(c->device));
+    const int r = decode_kernel_info(which, out);
+    if (r == -1) return fail(MI355LZ4_E_ARG, "debug_kernel_info: unknown kernel");
+    if (r != 0) HIP_TRY((hipError_t)r);
+    return MI355LZ4_OK;
+}
+
 // Diagnostic hook (not part of the public header): the workgroup-per-block decoder writes 16 words per block of the
 // next calls to devBuf (caller-owned device memory, 64 bytes per block; null switches it off): decode_cu.hpp, `dbg`.
 extern "C" int mi355lz4_debug_cu(mi355lz4_ctx *c, uint32_t *devBuf)

@@ -8,7 +8,7 @@
 // ends) at ~30-50 issue slots and two dependent memory round trips per ~27-byte
 // sequence.  Here one iteration handles a BATCH of sequences:
 //
-//   1. window     1 KiB of the compressed stream is staged in LDS (16 B / lane;
+//   1. window     832 bytes of the compressed stream are staged in LDS (16 B / lane of 52 lanes;
 //                 the next window is prefetched into registers while this one is used).
 //   2. speculate  every lane parses 8 candidate token positions (512 candidates)
 //                 from registers: where would the next token be if one started here?
@@ -59,15 +59,21 @@ namespace lz4dev {
 #ifndef PAR_SQ
 #define PAR_SQ 3            // squaring rounds: the chain is then followed in groups of 2^PAR_SQ lanes
 #endif
-#define PAR_WIN 1024        // bytes of compressed stream staged per window (16 per lane)
+#ifndef PAR_WIN
+#define PAR_WIN 832         // bytes of compressed stream staged per window (16 per lane of the first PAR_WIN / 16 lanes).  A token starts below
+                            // byte 512 (8 nodes per lane) and a plain sequence has at most one extension byte each way: it ends by byte
+                            // 511 + 2 + 269 + 3 = 785, and the last field read behind it (12 bytes from the literals' start) stays under 800.
+                            // So 832 accepts exactly the sequences 1024 accepted; the 12 lanes behind the window repeat its last lane's request (win_lane)
+#endif
 #ifndef PAR_RING
-#define PAR_RING 6144       // LDS output staging (8.3 KiB of LDS per wave in all: 19 waves per CU)
+#define PAR_RING 5728       // LDS output staging.  With the window and the jump table ParLds is 7664 bytes: see the static_assert below
 #endif
 #ifndef PAR_HIST
 #define PAR_HIST 2000       // bytes of history kept in the ring across a slide: two 16-byte chunks per lane (2048 needed a third pass for one or two chunks)
 #endif
 #ifndef PAR_BATCH_OUT
-#define PAR_BATCH_OUT 2560  // max output bytes of one batch
+#define PAR_BATCH_OUT 2048  // max output bytes of one batch: the ring slides when fewer are free.  Measured with this ring at 20 waves per CU
+                            // (lzsynth / text, GB/s, all with the window stored under a lane mask, docs/MEASUREMENT_LOG.md 15): 1792: 1075-1079 / 677-678, 2048: 1072-1079 / 675-677, 2560 (more slides): 1051-1052 / 669-672
 #endif
 #ifndef PAR_FAR_WIDE
 #define PAR_FAR_WIDE 0      // far matches: 1 = one 16-byte request per lane instead of two requests per length class.  Measured
@@ -79,9 +85,10 @@ namespace lz4dev {
 #endif
 #ifndef PAR_PRIO
 #define PAR_PRIO 0x33     // s_setprio per phase, two bits each: chain (bits 0-1), decode + literals + need (2-3), match rounds (4-5), flush +
-                          // window + speculation (6-7).  The phases that are chains of dependent LDS round trips go first among the 19
-                          // waves of a CU.  Measured (lzsynth / text, GB/s; 0: 996-1000 / 634-638): 0x03 998 / 633, 0x30 1009 / 639,
-                          // 0x33 1015 / 642-643, 0x3b 1010 / 642, 0x3f 1010 / 640, 0x27 1003 / 640, 0x36 1011 / 640
+                          // window + speculation (6-7).  The phases that are chains of dependent LDS round trips go first among the
+                          // waves of a CU.  Measured at 18 waves per CU (lzsynth / text, GB/s; 0: 996-1000 / 634-638): 0x03 998 / 633, 0x30 1009 / 639,
+                          // 0x33 1015 / 642-643, 0x3b 1010 / 642, 0x3f 1010 / 640, 0x27 1003 / 640, 0x36 1011 / 640; again at 20 waves
+                          // (65 536 blocks, the same three builds as PAR_BATCH_OUT's): 0: 1060-1065 / 667-670, 0x30: 1075-1082 / 674-676, 0x33: 1072-1079 / 675-677
 #endif
 #ifndef PAR_WAVES
 #define PAR_WAVES 5         // occupancy target (waves per SIMD) the register allocator is held to (<= 102 VGPRs)
@@ -96,6 +103,18 @@ struct __attribute__((aligned(16))) ParLds {
     uint8_t ring[PAR_RING + 32];
 };
 #define PAR_END (2 * PAR_NODES)
+// The decoder is bound by the waves that carry its chains of LDS round trips, and the LDS decides how many a CU holds: the registers
+// (95) allow 5 per SIMD = 20.  gfx950 hands its 160 KiB out in granules of 1280 bytes (measured, docs/MEASUREMENT_LOG.md 15: footprints
+// of 8272 and 8192 bytes both keep SQ_WAVE_CYCLES / SQ_BUSY_CYCLES at 33.59 = 18 waves per CU -- seven granules --, 7664 bytes
+// gives 37.47 = 20; the runtime's occupancy query divides 160 KiB by the bytes and says 19 / 20 / 20).  Six granules are 7680 bytes.
+#ifndef PAR_LDS_LIMIT
+#define PAR_LDS_LIMIT 7680  // (experiments with a larger footprint raise it)
+#endif
+static_assert(sizeof(ParLds) <= PAR_LDS_LIMIT, "ParLds above six 1280-byte LDS granules: 18 waves per CU instead of 20");
+#define PAR_WIN_LANES (PAR_WIN / 16)     // lanes whose 16 bytes make up the window
+static_assert(PAR_WIN % 16 == 0 && PAR_WIN_LANES <= LZ4_WAVE, "the window is 16 bytes per lane");
+static_assert(PAR_MAXNODES + 288 <= PAR_WIN + 32, "a plain sequence that starts at the last node, and the reads behind it, stay in win[]");
+static_assert(PAR_HIST + 30 + PAR_BATCH_OUT + 32 <= PAR_RING, "a batch fits the ring right after a slide");
 
 typedef uint64_t par_u64u __attribute__((aligned(1)));
 typedef uint32_t par_u32u __attribute__((aligned(1)));
@@ -208,9 +227,14 @@ __device__ int decode_block_par(const uint8_t *src, int srcLen, uint8_t *dst, in
     int flushed = 0;        // output positions < flushed are in global memory
     SeqState st;
 
+    // The window is 16 bytes per lane of the first PAR_WIN_LANES lanes.  The lanes behind them do what the last of those does --
+    // the same address, so no further request to memory, and the same 16 bytes stored to the same place -- instead of sitting out
+    // behind a branch: a window store under a lane mask cost a wave 5 % of a text block's latency (0.330 against 0.316 ms for 160
+    // blocks), the flush phase that waits for the prefetch twice its cycles (docs/MEASUREMENT_LOG.md 15).
+    auto win_lane = [&]() -> int { return (PAR_WIN_LANES < LZ4_WAVE) ? min(lane, PAR_WIN_LANES - 1) : lane; };
     // 16 bytes of the compressed stream for this lane's slot of the window that starts at `base`
     auto fetch_window = [&](uintptr_t base) -> uint4 {
-        const uint8_t *q = (const uint8_t *)(base + 16u * (uint32_t)lane);
+        const uint8_t *q = (const uint8_t *)(base + 16u * (uint32_t)win_lane());
         if (q >= bufLo && q + 16 <= bufHi) {
             const par_v4 v = *as_global((const par_v4 *)q);
             return make_uint4(v.x, v.y, v.z, v.w);
@@ -281,7 +305,7 @@ __device__ int decode_block_par(const uint8_t *src, int srcLen, uint8_t *dst, in
             // the first batch or the one after a handover
             if (abase != wbase) { wbase = abase; wnext = fetch_window(abase); winStale = true; }
             if (winStale) {
-                *(uint4 *)&L.win[16 * lane] = wnext;
+                *(uint4 *)&L.win[16 * win_lane()] = wnext;
                 winStale = false;
                 wave_fence();
             }
@@ -846,7 +870,7 @@ __device__ int decode_block_par(const uint8_t *src, int srcLen, uint8_t *dst, in
             // the next window goes to LDS now (nobody reads the old one any more): this is where the wave
             // waits for the prefetch, BEFORE the flush issues its stores, so that no later wait for a load
             // also has to wait for those stores to be acknowledged
-            *(uint4 *)&L.win[16 * lane] = wnext;
+            *(uint4 *)&L.win[16 * win_lane()] = wnext;
             wave_fence();
             flush(op, false);
             if (op - ringBase + (int)A + PAR_BATCH_OUT + 32 > PAR_RING) {

@@ -203,6 +203,9 @@ void launch_decode_partial(const DecodeArgs &a, int form, hipStream_t s);
 void launch_decode_tok(const DecodeArgs &a, hipStream_t s);      // token lists (a.tok.list / a.tok.cnt), then the list-driven decoder
 #endif
 #define PAR_STATS_COUNT 32
+// What the runtime says about kernel `which` of the lane-parallel family (kernels/kernel_info.inc lists them): out[0] = resident
+// workgroups per CU, out[1] = static LDS bytes, out[2] = registers, out[3] = sizeof(ParLds).  0, -1 for an unknown kernel, or a hipError_t.
+int decode_kernel_info(int which, int *out);
 void launch_linked_tolerant(const DecodeArgs &a, hipStream_t s);   // both cover blocks [a.segFirst, a.segEnd)
 void launch_linked_resolve(const DecodeArgs &a, hipStream_t s);
 void launch_linked_resolve_a(const DecodeArgs &a, hipStream_t s);   // pointers only (no output byte is read)

@@ -25,6 +25,7 @@
 //   linked_tolerant.inc    k_decode_tolerant: deferred lists; k_decode_fixup_regions: their replay      linked_replay.hpp
 //   linked_ptr.inc         k_ptr_expand / _jump / _fetch<CHASE> / _finish: the pointer passes           linked_ptr.hpp
 //                          k_longest_stream, k_dict_share; launch_linked_resolve_a / _b / _fetch_block
+//   kernel_info.inc        (no kernel) decode_kernel_info: resident workgroups per CU and static LDS of the decode_par.hpp kernels
 //
 // Everything is HBM/LDS byte work; there is deliberately no MFMA anywhere.
 #include "kernels.h"
@@ -57,3 +58,4 @@ using namespace lz4dev;
 #include "kernels/runin.inc"
 #include "kernels/linked_tolerant.inc"
 #include "kernels/linked_ptr.inc"
+#include "kernels/kernel_info.inc"

@@ -80,7 +80,7 @@ struct LinkStat {
 // Asynchronous form: one stream only (the streams call keeps the wait: its choice between walk and pointer pass needs the counts)
 inline bool async_gate(const DecodeCall &d, const EngineMode &m) { return m.asyncCap > 0 && !d.streamFirst; }
 // Whether a call of decoder variant 0 takes the workgroup-per-block decoder (decode_cu.hpp): a CU decodes a 64 KiB block in 0.09-0.11 ms
-// where a wavefront takes 0.2-0.3, but 19 wavefronts share a CU.  Measured (device-resident, ms, workgroup / wavefront form; lzsynth):
+// where a wavefront takes 0.2-0.3, but 18 wavefronts shared a CU when this was measured (20 now, decode_par.hpp).  Measured (device-resident, ms, workgroup / wavefront form; lzsynth):
 // 64 KiB blocks: 256: 0.10 / 0.20, 512: 0.20 / 0.21, 768: 0.29 / 0.21; 16 KiB: 256: 0.045 / 0.074, 512: 0.083 / 0.075; 4 KiB: 160: 0.042 /
 // 0.037 (a workgroup's fixed costs are 28 us a block).  So: up to one block per CU when blocks are not tiny, up to two when they are big --
 // judged by the compressed bytes per block, which is all the host knows.

@@ -129,6 +129,7 @@ def _load():
     sig("mi355lz4_get_compress_exact", C.c_int, vp)
     sig("mi355lz4_compress_exact_reset", C.c_int, vp)
     sig("mi355lz4_debug_exact_state", C.c_int, vp, C.POINTER(C.c_int))
+    sig("mi355lz4_debug_kernel_info", C.c_int, vp, C.c_int, C.POINTER(C.c_int))
     # many exact streams in one call
     sig("mi355lz4_cstreams_create", C.c_int, vp, C.c_int, C.POINTER(vp))
     sig("mi355lz4_cstreams_destroy", None, vp)
@@ -483,6 +484,18 @@ class Engine:
             return False
         f.restype = C.c_int
         return bool(f())
+
+    # kernels of the lane-parallel decode family that kernel_info() knows (mi355lz4_debug_kernel_info)
+    DECODE_KERNELS = ("k_decode_par", "k_decode_par_redo", "k_decode_dict", "k_decode_par_partial", "k_decode_par_partial_redo",
+                      "k_decode_dstreams", "k_decode_fixup_linked", "k_decode_fixup_runs", "k_runin_decode", "k_runin_fix",
+                      "k_decode_tolerant")
+
+    def kernel_info(self, kernel="k_decode_par"):
+        """What the HIP runtime says about a decode kernel on this device: resident workgroups (= waves) per CU, static LDS
+        bytes, registers, and sizeof(ParLds) of the build."""
+        out = (C.c_int * 4)()
+        _check(lib.mi355lz4_debug_kernel_info(self.ctx, self.DECODE_KERNELS.index(kernel), out), "debug_kernel_info")
+        return {"resident_per_cu": int(out[0]), "lds_bytes": int(out[1]), "regs": int(out[2]), "par_lds_bytes": int(out[3])}
 
     def set_decoder(self, variant):
         _check(lib.mi355lz4_set_decoder(self.ctx, int(variant)), "set_decoder")
