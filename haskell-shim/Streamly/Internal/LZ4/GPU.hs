@@ -51,6 +51,13 @@ module Streamly.Internal.LZ4.GPU
     , loadDict
     , compressChunksWithDict
     , decompressChunksWithDict
+    , HcDict
+    , newHcDict
+    , freeHcDict
+    , loadHcDict
+    , hcDictSize
+    , c_compressHcDictDevice
+    , compressChunksWithDictHC
     , DecompressStreams
     , newDecompressStreams
     , freeDecompressStreams
@@ -173,6 +180,29 @@ foreign import ccall safe "mi355lz4.h mi355lz4_decompress_dict"
     c_decompressDict
         :: Ptr C_Engine -> Ptr Word8 -> CSize -> CInt -> CInt -> Ptr Word8 -> CInt
         -> Ptr Word8 -> CSize -> Ptr CSize -> Ptr Int32 -> CInt -> Ptr CInt -> IO CInt
+
+-- High-compression levels against a shared dictionary (include/mi355lz4.h, "high-compression levels against a shared
+-- dictionary"): a prepared dictionary on the device -- its last 64 KiB and the image of the hash-chain encoder's tables -- and a
+-- batch of independent blocks compressed at the engine's level 1..12 with it in front of each (the object is only read).
+data C_HcDict
+newtype HcDict = HcDict (Ptr C_HcDict)
+
+foreign import ccall safe "mi355lz4.h mi355lz4_hcdict_create"
+    c_hcdictCreate :: Ptr C_Engine -> Ptr (Ptr C_HcDict) -> IO CInt
+foreign import ccall safe "mi355lz4.h mi355lz4_hcdict_destroy"
+    c_hcdictDestroy :: Ptr C_HcDict -> IO ()
+foreign import ccall safe "mi355lz4.h mi355lz4_hcdict_load"
+    c_hcdictLoad :: Ptr C_Engine -> Ptr C_HcDict -> Ptr Word8 -> CInt -> IO CInt
+foreign import ccall unsafe "mi355lz4.h mi355lz4_hcdict_size"
+    c_hcdictSize :: Ptr C_HcDict -> IO CInt
+foreign import ccall safe "mi355lz4.h mi355lz4_compress_hcdict_device"
+    c_compressHcDictDevice
+        :: Ptr C_Engine -> Ptr C_HcDict -> Ptr Word8 -> Ptr Word64 -> Ptr Int32 -> Word64 -> CInt -> CInt
+        -> CInt -> Ptr Word8 -> CSize -> Ptr Int32 -> IO CInt
+foreign import ccall safe "mi355lz4.h mi355lz4_compress_hcdict"
+    c_compressHcDict
+        :: Ptr C_Engine -> Ptr C_HcDict -> Ptr (Ptr Word8) -> Ptr Int32 -> CInt -> CInt
+        -> Ptr Word8 -> CSize -> Ptr CSize -> Ptr Int32 -> Ptr Int32 -> IO CInt
 
 -- Decoded sizes without decoding (device pointers in, device pointers out; only enqueues): what every block of a
 -- size-less framing (BlockMax64KB .. BlockMax4MB) decodes to, read off its token chain.  size[i] >= 0, or a negative
@@ -493,6 +523,54 @@ compressChunksWithDict (Engine eng) (CompressStreams cs) slot cfg speed arrs = d
             rc <- c_compressDict eng cs (fromIntegral slot) pSrc pLen (fromIntegral n) (fromIntegral speed)
                       (fromIntegral meta) dstBegin (fromIntegral cap) pOutLen pFlen pStatus
             when (rc /= 0) $ error "compressChunksWithDict: mi355lz4_compress_dict failed"
+        flens <- map fromIntegral <$> peekArray n pFlen
+        let offs = scanl (+) 0 flens
+        return [ Array.unsafeFreeze (MArray.Array cont dstBegin_ (dstBegin `plusPtr` (o + l)) dstMax)
+                   `seq` Array.Array cont (dstBegin `plusPtr` o) (dstBegin `plusPtr` (o + l))
+               | (o, l) <- zip offs flens ]
+
+-- | A prepared high-compression dictionary on the engine's device, holding the empty dictionary until 'loadHcDict'.
+newHcDict :: Engine -> IO HcDict
+newHcDict (Engine p) = alloca $ \pp -> do
+    rc <- c_hcdictCreate p pp
+    when (rc /= 0) $ error "mi355lz4_hcdict_create failed"
+    HcDict <$> peek pp
+
+freeHcDict :: HcDict -> IO ()
+freeHcDict (HcDict hd) = c_hcdictDestroy hd
+
+-- | Build the object's image from a dictionary in DEVICE memory (@len@ bytes at @dict@, the last 64 KiB count); enqueued, the
+-- object keeps its own copy.  It then serves 'compressChunksWithDictHC'.
+loadHcDict :: Engine -> HcDict -> Ptr Word8 -> Int -> IO ()
+loadHcDict (Engine p) (HcDict hd) dict len = do
+    rc <- c_hcdictLoad p hd dict (fromIntegral len)
+    when (rc /= 0) $ error "mi355lz4_hcdict_load failed"
+
+-- | The bytes the last 'loadHcDict' kept.
+hcDictSize :: HcDict -> IO Int
+hcDictSize (HcDict hd) = fromIntegral <$> c_hcdictSize hd
+
+-- | 'compressChunksWithDict' at the engine's compression level 1..12 ('setCompressionLevel'): one framed array per input array,
+-- compressed by the hash-chain encoder with the prepared dictionary in front of it.  'decompressChunksWithDict' reads them with
+-- the dictionary's bytes.  The object is only read.
+compressChunksWithDictHC
+    :: Engine -> HcDict -> BlockConfig -> [Array.Array Word8] -> IO [Array.Array Word8]
+compressChunksWithDictHC (Engine eng) (HcDict hd) cfg arrs = do
+    let n = length arrs
+        meta = metaSizeOf cfg
+        lens = map Array.byteLength arrs
+        cap = sum (map (\l -> fromIntegral (c_bound (fromIntegral l)) + meta + 4) lens)
+    (MArray.Array cont dstBegin_ dstBegin dstMax) <- MArray.newArray (max cap 1)
+    allocaArray n $ \pSrc -> allocaArray n $ \pLen -> allocaArray n $ \pFlen ->
+      allocaArray n $ \pStatus -> alloca $ \pOutLen -> do
+        let withAll [] k = k []
+            withAll (a:as) k = Array.asPtrUnsafe (Array.unsafeCast a) $ \p -> withAll as (k . (p :))
+        withAll arrs $ \ptrs -> do
+            pokeArray pSrc ptrs
+            pokeArray pLen (map fromIntegral lens)
+            rc <- c_compressHcDict eng hd pSrc pLen (fromIntegral n) (fromIntegral meta) dstBegin (fromIntegral cap)
+                      pOutLen pFlen pStatus
+            when (rc /= 0) $ error "compressChunksWithDictHC: mi355lz4_compress_hcdict failed"
         flens <- map fromIntegral <$> peekArray n pFlen
         let offs = scanl (+) 0 flens
         return [ Array.unsafeFreeze (MArray.Array cont dstBegin_ (dstBegin `plusPtr` (o + l)) dstMax)

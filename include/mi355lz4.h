@@ -105,6 +105,10 @@ typedef struct mi355lz4_ctx mi355lz4_ctx;
  *   outside the union of [outOff[i], outOff[i] + cap_i), cap_i as for the decode calls, for a block that decodes, one that
  *   fails and one whose header is rejected alike; result[] only in [0, nBlocks); never the dictionary, framed, blockOff,
  *   outOff or outCap.  _compress_dict and _decompress_dict are host-buffer calls as above.
+ * High-compression dictionary batches: _hcdict_load writes the object it is handed and nothing else (never the dictionary handed
+ *   in).  _compress_hcdict_device: the slot ranges of _compress_batch_device and framedLen[0, nBlocks) (a length outside
+ *   0..maxBlockLen: framedLen[i] = 0, the slot untouched); never the mi355lz4_hcdict -- it is only read -- never src, srcOff or
+ *   srcLen.  _compress_hcdict is a host-buffer call as above.
  * Scratch that a call needs is the engine's own. */
 
 /* ---- engine lifecycle ------------------------------------------------ */
@@ -599,7 +603,7 @@ int mi355lz4_cstreams_load_dict(mi355lz4_ctx *ctx, mi355lz4_cstreams *cs, int sl
  * Asynchronous: the call only enqueues on the engine's stream; it does not wait and does not read srcLen on the host.  A
  * length outside 0..maxBlockLen can therefore be no error code: that block gets framedLen[i] = 0 and its slot range is left
  * untouched, as in the streams call; the other blocks are unaffected.
- * Switches: block checksums apply; the compression level must be 0.  Segments, the linked switch and the engine's own exact
+ * Switches: block checksums apply; the compression level must be 0 (levels 1..12: mi355lz4_compress_hcdict_device).  Segments, the linked switch and the engine's own exact
  * stream (mi355lz4_set_compress_exact) play no part, on or off.
  * MI355LZ4_E_ARG: a null ctx or cs, `cs` created on another device, a compression level other than 0, dictSlot out of
  * range, nBlocks < 0, a headerKind other than 4 / 8, maxBlockLen outside 0..MI355LZ4_MAX_INPUT_SIZE, with nBlocks > 0 a null
@@ -645,6 +649,65 @@ int mi355lz4_compress_dict(mi355lz4_ctx *ctx, const mi355lz4_cstreams *cs, int d
 int mi355lz4_decompress_dict(mi355lz4_ctx *ctx, const uint8_t *framedIn, size_t inLen, int headerKind, int fixedUncomp,
                              const uint8_t *dict, int dictLen, uint8_t *out, size_t cap, size_t *outLen, int32_t *blockLen,
                              int maxBlocks, int *nBlocks);
+
+/* ---- high-compression levels against a shared dictionary: lz4 -9 -D dict ----------------------------------------------------
+ * mi355lz4_compress_dict_device is level 0's encoder.  These calls are the hash-chain encoder of levels 1..12
+ * (mi355lz4_set_compression_level) with one dictionary in front of every block of a batch: LZ4_loadDictHC once, then
+ * LZ4_compress_HC_continue on a copy of the loaded stream per block, in this engine's own parse -- the blocks are plain LZ4
+ * (mi355lz4_decompress_dict_device and LZ4_decompress_safe_usingDict read them with the dictionary) but not liblz4's bytes.
+ *
+ * A mi355lz4_hcdict is an opaque prepared dictionary on the device of the engine it was created with, about 216 KiB: its own
+ * copy of the dictionary's last keep = min(len, 65536) bytes and the image of the encoder's tables (the chain ring, 65536 x
+ * u16, and the head table) as they are after the inserts of window positions [0, keep - 3) of those bytes alone -- the
+ * positions whose four bytes lie inside the dictionary; window position 0 is the first kept byte.  The encoder reloads the
+ * image for every block instead of inserting up to 64 KiB of dictionary again.
+ * _hcdict_create allocates an object that holds the empty dictionary (no kernel).  _hcdict_load builds the image from
+ * dictDevice[0, len) (device memory; len == 0 is legal, under 4 bytes no position is inserted): one workgroup, enqueued on the
+ * engine's stream, nothing read on the host; the object keeps its own copy, so dictDevice may be freed or overwritten once the
+ * call has run on the device.  Loading again replaces the image.  _hcdict_size: the bytes the last _load kept (0 before the
+ * first).  _hcdict_destroy waits for the device first.  Compress calls only read the object: it may serve any number of
+ * calls, from any engine on its device, also at the same time -- as long as no _hcdict_load is in flight beside them (the
+ * sharing rule of a loaded mi355lz4_cstreams slot).
+ * MI355LZ4_E_ARG: _create: a null ctx or out; _load: a null ctx or hd, `hd` created on another device, len < 0, a null
+ * dictDevice with len > 0; _size: a null hd. */
+typedef struct mi355lz4_hcdict mi355lz4_hcdict;
+int mi355lz4_hcdict_create(mi355lz4_ctx *ctx, mi355lz4_hcdict **out);
+void mi355lz4_hcdict_destroy(mi355lz4_hcdict *hd);
+int mi355lz4_hcdict_load(mi355lz4_ctx *ctx, mi355lz4_hcdict *hd, const uint8_t *dictDevice, int len);
+int mi355lz4_hcdict_size(const mi355lz4_hcdict *hd);
+/* Compress nBlocks independent blocks at the engine's compression level (1..12; depth 2^(min(level, 9) - 1), as every HC call),
+ * every one with the dictionary of `hd` in front of it.  Block arguments, outputs, headers (4 / 8), trailers
+ * (mi355lz4_set_block_checksum) and slotStride (mi355lz4_slot_stride_ex) are those of mi355lz4_compress_dict_device; there is
+ * no accel (the HC levels ignore it).
+ * Bytes: block i is exactly what this engine writes for it when the dictionary's kept bytes lie directly in front of the block
+ * in memory -- the second block of the two-block linked call [D[-65536:], B] through mi355lz4_compress_batch_device at the same
+ * level; with an empty dictionary, mi355lz4_compress_batch_device's block at that level.  A match may start in the dictionary
+ * and run on into the block's own bytes.
+ * Asynchronous: the call only enqueues on the engine's stream and does not read srcLen on the host.  A length outside
+ * 0..maxBlockLen gives framedLen[i] = 0 and an untouched slot range; the other blocks are unaffected.
+ * Switches: the level must be 1..12 -- level 0 against a dictionary is mi355lz4_compress_dict_device.  Segments, the linked
+ * switch and the engine's exact stream play no part, on or off.
+ * maxBlockLen is at most 4 MiB (the largest block size of the reference's BlockSize): a shared dictionary is for small records,
+ * and every workgroup of the launch stages the dictionary and its current block contiguously in engine-owned scratch
+ * (65536 + maxBlockLen bytes a workgroup, one workgroup per CU).
+ * MI355LZ4_E_ARG: a null ctx or hd, `hd` created on another device, compression level 0, nBlocks < 0, a headerKind other than
+ * 4 / 8, maxBlockLen outside 0..4 MiB, with nBlocks > 0 a null src (maxBlockLen > 0), slots or framedLen.
+ * MI355LZ4_E_CAPACITY: slotStride below the bound.  nBlocks == 0 is MI355LZ4_OK.
+ * One workgroup of 1024 threads per block, as the HC levels without a dictionary: a poor fit for 4 KiB records.  Measured once
+ * (scripts/hcdict_rate.py, profiles/hcdict_rate.json; medians of 5 event-timed calls): 16384 text records of 4 KiB against a
+ * 64 KiB dictionary at level 9 in 28.3 ms, ratio 2.44 (level 3: 12.4 ms, 2.16; mi355lz4_compress_dict_device: 6.9 ms, 1.90;
+ * level 9 without a dictionary: 8.6 ms, 1.37); 2560 records of 64 KiB at level 9 in 69.8 ms, ratio 2.44 (level 0 with the
+ * dictionary: 28.8 ms, 1.88; level 9 without: 52.3 ms, 2.12).  _hcdict_load of 64 KiB: 0.8 ms. */
+int mi355lz4_compress_hcdict_device(mi355lz4_ctx *ctx, const mi355lz4_hcdict *hd, const uint8_t *src,
+                                    const uint64_t *srcOff, const int32_t *srcLen, uint64_t blockStride, int maxBlockLen,
+                                    int nBlocks, int headerKind, uint8_t *slots, size_t slotStride, int32_t *framedLen);
+/* Host-buffer form, synchronous: as mi355lz4_compress_dict (one dense framed stream in block order, blockFramedLen and status per
+ * block, the same group pipeline) with the device call above per group.  The lengths are checked on the host: one outside
+ * 0..4 MiB is MI355LZ4_E_ARG and nothing is enqueued or written.  The multi-device handle and the legacy LZ4_* face have no
+ * such call. */
+int mi355lz4_compress_hcdict(mi355lz4_ctx *ctx, const mi355lz4_hcdict *hd, const uint8_t *const *src,
+                             const int32_t *srcLen, int nBlocks, int headerKind, uint8_t *framedOut, size_t cap,
+                             size_t *outLen, int32_t *blockFramedLen, int32_t *status);
 
 /* ---- many linked decode streams, continued across calls ---------------------------------------------------------------
  * The decode-side counterpart of mi355lz4_cstreams, and the device-resident form of the reference's one LZ4_streamDecode_t

@@ -24,6 +24,7 @@
 
 struct mi355lz4_ctx;
 struct mi355lz4_cstreams;
+struct mi355lz4_hcdict;
 struct mi355lz4_dstreams;
 
 namespace streamly_lz4 {
@@ -118,6 +119,10 @@ public:
     std::vector<Array> compressWithDict(const BlockConfig &cfg, int speed, const std::vector<Array> &arrays,
                                         const class CompressStreams &cs, int slot);
     std::vector<Array> decompressWithDict(const BlockConfig &cfg, const std::vector<Array> &blocks, const Array &dict);
+    // The same batch at the engine's compression level 1..12 (mi355lz4_compress_hcdict): every array compressed on its own by
+    // the hash-chain encoder with the dictionary of `hd` (HcDict::load) in front of it -- lz4 -9 -D dict; decompressWithDict
+    // reads the result with the dictionary's bytes.  The object is only read.  Throws Error (level 0 included).
+    std::vector<Array> compressWithDictHC(const BlockConfig &cfg, const std::vector<Array> &arrays, const class HcDict &hd);
 private:
     mi355lz4_ctx *ctx_ = nullptr;
     size_t batch_;
@@ -142,6 +147,23 @@ public:
 private:
     Engine &eng_;
     mi355lz4_cstreams *cs_ = nullptr;
+};
+
+// A prepared high-compression dictionary on the engine's device (mi355lz4_hcdict: about 216 KiB -- the dictionary's last 64 KiB
+// and the image of the hash-chain encoder's tables after its inserts), for Engine::compressWithDictHC.
+class HcDict {
+public:
+    explicit HcDict(Engine &eng);                       // the empty dictionary; throws Error
+    ~HcDict();
+    HcDict(const HcDict &) = delete;
+    HcDict &operator=(const HcDict &) = delete;
+    mi355lz4_hcdict *handle() const { return hd_; }
+    int size() const;                                   // bytes the last load kept: min(len, 65536)
+    // builds the image from dictDevice[0, len) (DEVICE memory); enqueued, the object keeps its own copy; replaces the last load
+    void load(const uint8_t *dictDevice, int len);
+private:
+    Engine &eng_;
+    mi355lz4_hcdict *hd_ = nullptr;
 };
 
 // A set of nSlots device-resident linked decode streams (mi355lz4_dstreams: about 64 KiB a slot -- the last block's last

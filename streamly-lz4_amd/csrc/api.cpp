@@ -263,6 +263,7 @@ extern "C" void mi355lz4_destroy(mi355lz4_ctx *c)
     if (c->stream) hipStreamSynchronize(c->stream);
     for (DevBuf *b : {&c->in, &c->slots, &c->dense, &c->out, &c->offA, &c->offB, &c->lenA, &c->lenB, &c->res, &c->scratch,
                       &c->tolPool, &c->tolMeta, &c->linkBuf, &c->ptrBuf, &c->seg[0].b, &c->seg[1].b, &c->seg[2].b, &c->seg[3].b, &c->tokBuf,
+                      &c->hcStage[0].b, &c->hcStage[1].b, &c->hcStage[2].b, &c->hcStage[3].b,
                       &c->ckBuf, &c->exState, &c->exMeta, &c->exTabs, &c->exFlags})
         dev_release(*b);
     if (c->linkEvent) hipEventDestroy(c->linkEvent);
@@ -1031,6 +1032,127 @@ extern "C" int mi355lz4_compress_dict_device(mi355lz4_ctx *c, const mi355lz4_cst
     x.state = cs->state + (size_t)dictSlot * CSTREAM_SLOT_BYTES;
     launch_exact_dict(x, c->stream);
     if (int r = check_launch("exact dict launch")) return r;
+    if (c->blockChecksum) {                               // the trailers, behind the encoder (encode_device, finish)
+        launch_xxh32_append(slots, slotStride, headerKind, framedLen, nBlocks, c->stream);
+        return check_launch("checksum launch");
+    }
+    return MI355LZ4_OK;
+}
+
+// ---------------------------------------------------------------------------
+// High-compression levels against a shared dictionary.  A mi355lz4_hcdict is the device image of encode_hc.hpp's
+// tables after the dictionary's inserts (k_hcdict_build, once per load); mi355lz4_compress_hcdict_device reloads it for every
+// block (k_encode_hc_dict) and only reads it, so one object serves any number of calls.  Both only enqueue.
+// ---------------------------------------------------------------------------
+extern "C" int mi355lz4_hcdict_create(mi355lz4_ctx *c, mi355lz4_hcdict **out)
+{
+    if (out) *out = nullptr;
+    if (!c || !out) return fail(MI355LZ4_E_ARG, "hcdict_create: bad arguments");
+    HIP_TRY(hipSetDevice(c->device));
+    mi355lz4_hcdict *hd = new (std::nothrow) mi355lz4_hcdict();
+    if (!hd) return fail(MI355LZ4_E_ARG, "out of host memory");
+    hd->device = c->device;
+    hipError_t e = hipMalloc((void **)&hd->image, HCDICT_IMAGE_BYTES);
+    // an empty dictionary until the first load: empty heads, keep 0 (no kernel: two memsets, and the wait slots_create has)
+    if (e == hipSuccess) e = hipMemsetAsync(hd->image, 0, HCDICT_IMAGE_BYTES, c->stream);
+    if (e == hipSuccess) e = hipMemsetAsync(hd->image + HCDICT_CHAIN_BYTES, 0xFF, (size_t)HCDICT_HEAD_ENTRIES * 4, c->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+    if (e != hipSuccess) {
+        if (hd->image) hipFree(hd->image);
+        delete hd;
+        return fail(MI355LZ4_E_HIP, "hcdict_create: %zu bytes: %s", (size_t)HCDICT_IMAGE_BYTES, hipGetErrorString(e));
+    }
+    *out = hd;
+    return MI355LZ4_OK;
+}
+
+extern "C" void mi355lz4_hcdict_destroy(mi355lz4_hcdict *hd)
+{
+    if (!hd) return;
+    hipSetDevice(hd->device);
+    hipDeviceSynchronize();                 // calls that still read the image
+    if (hd->image) hipFree(hd->image);
+    delete hd;
+}
+
+extern "C" int mi355lz4_hcdict_size(const mi355lz4_hcdict *hd) { return hd ? hd->keep : fail(MI355LZ4_E_ARG, "hcdict_size: null object"); }
+
+static int hcdict_same_device(const mi355lz4_ctx *c, const mi355lz4_hcdict *hd, const char *who)
+{
+    if (!c || !hd) return fail(MI355LZ4_E_ARG, "%s: null argument", who);
+    if (hd->device != c->device) return fail(MI355LZ4_E_ARG, "%s: the dictionary lives on device %d, the engine on %d", who, hd->device, c->device);
+    return MI355LZ4_OK;
+}
+
+extern "C" int mi355lz4_hcdict_load(mi355lz4_ctx *c, mi355lz4_hcdict *hd, const uint8_t *dictDevice, int len)
+{
+    if (int r = hcdict_same_device(c, hd, "hcdict_load")) return r;
+    if (len < 0 || (len > 0 && !dictDevice)) return fail(MI355LZ4_E_ARG, "hcdict_load: bad dictionary");
+    HIP_TRY(hipSetDevice(c->device));
+    launch_hcdict_build(hd->image, dictDevice, len, c->stream);
+    if (int r = check_launch("hcdict build launch")) return r;
+    hd->keep = len < 65536 ? len : 65536;
+    return MI355LZ4_OK;
+}
+
+// Diagnostic hook (not part of the public header): the object's whole device image (HCDICT_IMAGE_BYTES: chain, head, count,
+// bytes) into bytes (host memory), after everything queued on the device has run.  The tests show with it that compress calls
+// never write the image.
+extern "C" int mi355lz4_debug_hcdict_image(mi355lz4_hcdict *hd, uint8_t *bytes)
+{
+    if (!hd || !bytes) return fail(MI355LZ4_E_ARG, "debug_hcdict_image: bad arguments");
+    HIP_TRY(hipSetDevice(hd->device));
+    HIP_TRY(hipDeviceSynchronize());
+    HIP_TRY(hipMemcpy(bytes, hd->image, HCDICT_IMAGE_BYTES, hipMemcpyDeviceToHost));
+    return MI355LZ4_OK;
+}
+
+// the staging windows of a call on the engine's current stream: one scratch per stream the engine has been used on, four at the
+// most, the one used longest ago taken over once its stream is done with it (the rule of the segment scratch, encode_device)
+static int hcdict_stage(mi355lz4_ctx *c, size_t bytes, uint8_t **out)
+{
+    mi355lz4_ctx::SegScratch *slot = nullptr;
+    for (int i = 0; i < c->nHcStage; i++) if (c->hcStage[i].s == c->stream) slot = &c->hcStage[i];
+    if (!slot && c->nHcStage < 4) { slot = &c->hcStage[c->nHcStage++]; slot->s = c->stream; }
+    if (!slot) {
+        slot = &c->hcStage[0];
+        for (int i = 1; i < c->nHcStage; i++) if (c->hcStage[i].tick < slot->tick) slot = &c->hcStage[i];
+        HIP_TRY(hipStreamSynchronize(slot->s));
+        slot->s = c->stream;
+    }
+    slot->tick = ++c->segTick;
+    if (bytes > slot->b.cap) HIP_TRY(hipStreamSynchronize(slot->s));   // (dev_reserve frees what queued work may still use)
+    if (int r = dev_reserve(slot->b, bytes)) return r;
+    *out = (uint8_t *)slot->b.p;
+    return MI355LZ4_OK;
+}
+
+extern "C" int mi355lz4_compress_hcdict_device(mi355lz4_ctx *c, const mi355lz4_hcdict *hd, const uint8_t *src,
+                                               const uint64_t *srcOff, const int32_t *srcLen, uint64_t blockStride,
+                                               int maxBlockLen, int nBlocks, int headerKind, uint8_t *slots,
+                                               size_t slotStride, int32_t *framedLen)
+{
+    if (int r = hcdict_same_device(c, hd, "compress_hcdict_device")) return r;
+    if (c->compLevel < 1)
+        return fail(MI355LZ4_E_ARG, "compress_hcdict_device: compression level %d; level 0 against a dictionary is mi355lz4_compress_dict_device",
+                    c->compLevel);
+    if (nBlocks < 0 || (headerKind != 4 && headerKind != 8) || maxBlockLen < 0)
+        return fail(MI355LZ4_E_ARG, "compress_hcdict_device: bad arguments");
+    if (maxBlockLen > HCDICT_MAX_BLOCK)
+        return fail(MI355LZ4_E_ARG, "compress_hcdict_device: maxBlockLen %d above the %d bytes a dictionary batch takes", maxBlockLen, HCDICT_MAX_BLOCK);
+    if (nBlocks == 0) return MI355LZ4_OK;
+    if (!src && maxBlockLen > 0) return fail(MI355LZ4_E_ARG, "compress_hcdict_device: null src");
+    if (!slots || !framedLen) return fail(MI355LZ4_E_ARG, "compress_hcdict_device: null output");
+    if (slotStride < mi355lz4_compress_bound(maxBlockLen) + (size_t)headerKind + (c->blockChecksum ? 4u : 0u))
+        return fail(MI355LZ4_E_CAPACITY, "compress_hcdict_device: slotStride %zu < bound", slotStride);
+    HIP_TRY(hipSetDevice(c->device));
+    HcDictArgs x;
+    x.e = make_encode_args(src, srcOff, srcLen, blockStride, maxBlockLen, nBlocks, 1, headerKind, slots, slotStride, framedLen);
+    x.image = hd->image;
+    x.stageStride = 65536 + (((size_t)maxBlockLen + 255) & ~(size_t)255) + 256;
+    if (int r = hcdict_stage(c, (size_t)encode_hc_dict_grid(nBlocks) * x.stageStride, &x.stage)) return r;
+    launch_encode_hc_dict(x, c->compLevel, c->stream);
+    if (int r = check_launch("hc dict launch")) return r;
     if (c->blockChecksum) {                               // the trailers, behind the encoder (encode_device, finish)
         launch_xxh32_append(slots, slotStride, headerKind, framedLen, nBlocks, c->stream);
         return check_launch("checksum launch");

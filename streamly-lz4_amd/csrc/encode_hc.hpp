@@ -126,6 +126,10 @@ __device__ __forceinline__ uint32_t hc_search(const HcLds &L, const uint8_t *src
 
 // One block: n bytes at src, dictLen bytes of dictionary in front of them; writes the LZ4 block to dst, returns its length.
 // Every thread of the workgroup calls it with the same arguments; the return value is meaningful in wave 0.
+// PREPARED (k_encode_hc_dict, a mi355lz4_hcdict): the caller has loaded chain[] and head[] as they are after the inserts of
+// the dictionary's positions [0, dictLen - 3) -- those whose four bytes lie inside the dictionary -- so only the last three
+// positions, which hash across the seam into the block, are inserted here; the rounds, the parse and the bytes are the same.
+template <bool PREPARED = false>
 __device__ int encode_block_hc(HcLds &L, const uint8_t *blockSrc, int n, int dictLen, uint8_t *dst, int depth)
 {
     const int t = (int)threadIdx.x, lane = lane_id(), wave = t >> 6;
@@ -138,10 +142,15 @@ __device__ int encode_block_hc(HcLds &L, const uint8_t *blockSrc, int n, int dic
     }
     const uint8_t *src = blockSrc - dictLen;          // window position 0 = the dictionary's first byte
     const int end = dictLen + n;
-    for (int i = t; i < HC_HEAD; i += HC_THREADS) L.head[i] = HC_NONE;
+    if (!PREPARED)
+        for (int i = t; i < HC_HEAD; i += HC_THREADS) L.head[i] = HC_NONE;
     if (t == 0) { L.cur = dictLen; L.best[0] = 0u; }
     __syncthreads();
-    for (int r = 0; r < dictLen; r += HC_THREADS) hc_insert(L, src, r, min(r + HC_THREADS, dictLen), end);
+    if (PREPARED) {
+        if (dictLen > 0) hc_insert(L, src, max(dictLen - 3, 0), dictLen, end);
+    } else {
+        for (int r = 0; r < dictLen; r += HC_THREADS) hc_insert(L, src, r, min(r + HC_THREADS, dictLen), end);
+    }
 
     // wave 0's parse state (uniform)
     uint8_t *op = dst;

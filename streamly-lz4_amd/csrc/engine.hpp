@@ -81,6 +81,9 @@ struct mi355lz4_ctx {
     struct SegScratch { hipStream_t s = nullptr; DevBuf b; unsigned long long tick = 0; } seg[4];
     int nSeg = 0;
     unsigned long long segTick = 0;
+    // mi355lz4_compress_hcdict_device: the workgroups' staging windows (dictionary + block), one scratch per stream as above
+    SegScratch hcStage[4];
+    int nHcStage = 0;
     int linkedAsyncCap = 0;                // > 0: linked device decodes do not wait on the host (mi355lz4_set_linked_async)
     RuninState runin;                      // the run-in decode's adaptive state (linked_plan.hpp)
     int linkedPath = -1;                   // diagnostics: how the last linked call was finished (LinkedPath; mi355lz4_debug_runin_state)
@@ -91,6 +94,14 @@ struct mi355lz4_ctx {
     bool linkBusy = false;
     unsigned long long *stats = nullptr;   // diagnostics: device counters of the lane-parallel decoder (off by default)
     uint32_t *cuDbg = nullptr;             // diagnostics: 16 words per block from the workgroup-per-block decoder (mi355lz4_debug_cu)
+};
+
+// A prepared high-compression dictionary (api.cpp, "high-compression levels against a shared dictionary"): the device image
+// k_hcdict_build wrote (kernels.h, HCDICT_*).  keep is what the last _load enqueued; the kernels read the image's own count.
+struct mi355lz4_hcdict {
+    int device = 0;
+    int keep = 0;
+    uint8_t *image = nullptr;
 };
 
 namespace mi355lz4_detail {

@@ -244,6 +244,50 @@ std::vector<Array> Engine::compressWithDict(const BlockConfig &cfg, int speed, c
     return out;
 }
 
+HcDict::HcDict(Engine &eng) : eng_(eng)
+{
+    if (mi355lz4_hcdict_create(eng.ctx(), &hd_) != MI355LZ4_OK) throw Error(std::string("streamly_lz4::HcDict: ") + mi355lz4_last_error());
+}
+HcDict::~HcDict() { mi355lz4_hcdict_destroy(hd_); }
+int HcDict::size() const { return mi355lz4_hcdict_size(hd_); }
+void HcDict::load(const uint8_t *dictDevice, int len)
+{
+    if (mi355lz4_hcdict_load(eng_.ctx(), hd_, dictDevice, len) != MI355LZ4_OK)
+        throw Error(std::string("streamly_lz4::HcDict::load: ") + mi355lz4_last_error());
+}
+
+std::vector<Array> Engine::compressWithDictHC(const BlockConfig &cfg, const std::vector<Array> &arrays, const HcDict &hd)
+{
+    const int meta = metaSize(cfg);
+    std::vector<const uint8_t *> ptrs;
+    std::vector<int32_t> lens;
+    size_t cap = 16;
+    for (const Array &a : arrays) {
+        if (a.size() > (size_t)maxBlockSize(cfg))                               // compressChunk, Internal/LZ4.hs:237-241
+            throw Error("compressChunk: Source array length " + std::to_string(a.size()) +
+                        " exceeds the maximum block size of " + std::to_string(maxBlockSize(cfg)));
+        ptrs.push_back(a.data());
+        lens.push_back((int32_t)a.size());
+        cap += (size_t)mi355lz4_compress_bound((int)a.size()) + (size_t)meta + 4;
+    }
+    const int n = (int)lens.size();
+    std::vector<uint8_t> framed(cap);
+    std::vector<int32_t> flen((size_t)n + 1), status((size_t)n + 1);
+    ptrs.push_back(nullptr);
+    lens.push_back(0);
+    size_t outLen = 0;
+    if (mi355lz4_compress_hcdict(ctx_, hd.handle(), ptrs.data(), lens.data(), n, meta, framed.data(), cap, &outLen, flen.data(),
+                                 status.data()) != MI355LZ4_OK)
+        throw Error(std::string("compressWithDictHC: ") + mi355lz4_last_error());
+    std::vector<Array> out;
+    size_t pos = 0;
+    for (int k = 0; k < n; k++) {
+        out.emplace_back(framed.begin() + (long)pos, framed.begin() + (long)(pos + (size_t)flen[(size_t)k]));
+        pos += (size_t)flen[(size_t)k];
+    }
+    return out;
+}
+
 std::vector<Array> Engine::decompressWithDict(const BlockConfig &cfg, const std::vector<Array> &blocks, const Array &dict)
 {
     const int meta = metaSize(cfg);

@@ -168,6 +168,26 @@ struct ExactDictArgs {
     const uint8_t *state;        // the one slot, CSTREAM_SLOT_BYTES
 };
 
+// a prepared high-compression dictionary (mi355lz4_hcdict; kernels/encode.inc, k_hcdict_build): the image of encode_hc.hpp's chain[]
+// and head[] after the inserts of the kept bytes' positions [0, keep - 3), the count, and the object's own copy of the bytes
+#define HCDICT_CHAIN_BYTES ((size_t)65536 * 2)
+#define HCDICT_HEAD_ENTRIES 6144                                  // HC_HEAD (encode_hc.hpp; checked where the kernels are compiled)
+#define HCDICT_TABLE_BYTES (HCDICT_CHAIN_BYTES + (size_t)HCDICT_HEAD_ENTRIES * 4)    // 155648: chain, then head, as HcLds starts
+#define HCDICT_KEEP_OFF    HCDICT_TABLE_BYTES                     // uint32 keep = min(len, 65536) (the rest of the 64 bytes is unused)
+#define HCDICT_DICT_OFF    (HCDICT_KEEP_OFF + 64)                 // the kept bytes, the first one first
+#define HCDICT_IMAGE_BYTES (HCDICT_DICT_OFF + 65536)              // 221248: about 216 KiB an object
+#define HCDICT_MAX_BLOCK   (4 << 20)                              // the largest block of a mi355lz4_compress_hcdict_device call
+
+// a batch against one prepared dictionary (mi355lz4_compress_hcdict_device; kernels/encode.inc, k_encode_hc_dict): workgroup w
+// lays the kept bytes and, behind them, one block at a time into its window at stage + w * stageStride -- the dictionary ends
+// and the block starts at byte 65536 of the window -- so that encode_block_hc sees what a linked call sees
+struct HcDictArgs {
+    EncodeArgs e;                // blocks, slots, headers, framedLen; e.uniformLen bounds every length; accel, linked, lookBack unused
+    const uint8_t *image;        // HCDICT_IMAGE_BYTES, read-only
+    uint8_t *stage;              // encode_hc_dict_grid(nBlocks) windows
+    size_t stageStride;          // >= 65536 + e.uniformLen
+};
+
 // many linked decode streams continued across calls (mi355lz4_decompress_dstreams_device; kernels/linked_walk.inc, k_decode_dstreams).
 // One slot of a mi355lz4_dstreams is the device form of LZ4_streamDecode_t for separately allocated blocks: the last
 // min(r, 65536) bytes of the stream's last block that decoded to r > 0 bytes, at the slot's start, and that count.
@@ -237,6 +257,11 @@ void launch_exact_streams(const ExactStreamsArgs &a, int nWork, hipStream_t s);
 void launch_cstreams_load_dict(uint8_t *slotState, const uint8_t *dict, int len, hipStream_t s);
 // one wave per block, each from a copy of the slot's state; nothing is stored back
 void launch_exact_dict(const ExactDictArgs &a, hipStream_t s);
+// a prepared high-compression dictionary: one workgroup builds the image (HCDICT_IMAGE_BYTES) from the last min(len, 65536) bytes of dict
+void launch_hcdict_build(uint8_t *image, const uint8_t *dict, int len, hipStream_t s);
+// compression levels 1..12 against that image: a persistent grid of encode_hc_dict_grid(nBlocks) workgroups, one window of a.stage each
+int encode_hc_dict_grid(int nBlocks);
+void launch_encode_hc_dict(const HcDictArgs &a, int level, hipStream_t s);
 // independent blocks against one external dictionary (a.dict0, a.dict0Len; a.linked is not used): one wave per block
 void launch_decode_dict(const DecodeArgs &a, hipStream_t s);
 // many linked decode streams: one wave per entry of a.work walks its blocks from its slot's dictionary and stores the tail back;

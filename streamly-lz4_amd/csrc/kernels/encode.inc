@@ -94,6 +94,103 @@ void launch_encode_hc(const EncodeArgs &a, int level, hipStream_t s)
 }
 
 // ---------------------------------------------------------------------------
+// K2, high-compression levels against a shared dictionary (mi355lz4_hcdict, DESIGN.md 7j).  k_hcdict_build runs the dictionary's
+// insert rounds once and stores the tables; k_encode_hc_dict reloads them for every block instead of inserting 64 KiB again.
+// ---------------------------------------------------------------------------
+static_assert(HCDICT_HEAD_ENTRIES == HC_HEAD && HCDICT_TABLE_BYTES == offsetof(HcLds, best) && HCDICT_TABLE_BYTES % 16 == 0,
+              "the image is the front of HcLds: chain[], then head[]");
+
+// The image of a dictionary of `len` bytes at `dict` (its last keep = min(len, 65536) count): chain[] and head[] after hc_insert
+// over the window positions [0, keep - 3) of the kept bytes alone -- the positions whose four bytes lie inside them -- from
+// zeroed chains and empty heads, then keep and the bytes.  One workgroup.  Under 4 bytes no position is inserted.
+__global__ __launch_bounds__(HC_THREADS) void k_hcdict_build(uint8_t *image, const uint8_t *dict, int len)
+{
+    __shared__ HcLds L;
+    const int t = (int)threadIdx.x;
+    const int keep = min(max(len, 0), 65536);
+    const uint8_t *from = dict + (len - keep);                          // (not dereferenced when keep == 0)
+    dev_v4 *tab4 = (dev_v4 *)&L;
+    for (int i = t; i < (int)(HCDICT_CHAIN_BYTES / 16); i += HC_THREADS) tab4[i] = dev_v4{0u, 0u, 0u, 0u};
+    for (int i = t; i < HC_HEAD; i += HC_THREADS) L.head[i] = HC_NONE;
+    __syncthreads();
+    for (int r = 0; r + 4 <= keep; r += HC_THREADS) hc_insert(L, from, r, min(r + HC_THREADS, keep), keep);
+    for (int i = t; i < (int)(HCDICT_TABLE_BYTES / 16); i += HC_THREADS) as_global((dev_v4 *)image)[i] = tab4[i];
+    if (t == 0) as_global((uint32_t *)(image + HCDICT_KEEP_OFF))[0] = (uint32_t)keep;
+    // the bytes: each wave a run of 4 KiB pieces
+    const uint32_t piece = 4096u;
+    for (uint32_t at = (uint32_t)(t / LZ4_WAVE) * piece; at < (uint32_t)keep; at += HC_WAVES * piece)
+        wave_copy_bytes(image + HCDICT_DICT_OFF + at, from + at, min((uint32_t)keep - at, piece));
+}
+
+void launch_hcdict_build(uint8_t *image, const uint8_t *dict, int len, hipStream_t s)
+{
+    hipLaunchKernelGGL(k_hcdict_build, dim3(1), dim3(HC_THREADS), 0, s, image, dict, len);
+}
+
+// k_encode_hc with the dictionary of a mi355lz4_hcdict in front of every block: the same persistent grid, one window of x.stage per
+// workgroup.  The kept bytes go into the window once; for every block the workgroup copies the block behind them, reloads the
+// whole table image (the block before has overwritten heads and ring entries) and runs encode_block_hc<PREPARED>, which inserts
+// the three seam positions and then does what it does for the second block of a linked call.  A length outside
+// 0..uniformLen gives framedLen 0 and leaves the slot alone.  Nothing of the image is written.
+__global__ __launch_bounds__(HC_THREADS) void k_encode_hc_dict(HcDictArgs x, int depth)
+{
+    __shared__ HcLds L;
+    const int t = (int)threadIdx.x, wave = t >> 6;
+    const EncodeArgs &a = x.e;
+    const int keep = (int)min(ex_uni(as_global((const uint32_t *)(x.image + HCDICT_KEEP_OFF))[0]), 65536u);
+    uint8_t *blockAt = x.stage + (size_t)blockIdx.x * x.stageStride + 65536;
+    {
+        const uint32_t piece = 4096u;
+        for (uint32_t at = (uint32_t)wave * piece; at < (uint32_t)keep; at += HC_WAVES * piece)
+            wave_copy_bytes(blockAt - keep + at, x.image + HCDICT_DICT_OFF + at, min((uint32_t)keep - at, piece));
+    }
+    for (int blk = (int)blockIdx.x; blk < a.nBlocks; blk += (int)gridDim.x) {
+        const uint64_t off = a.srcOff ? a.srcOff[blk] : (uint64_t)blk * a.blockStride;
+        const int n = a.srcLen ? a.srcLen[blk] : a.uniformLen;
+        if (n < 0 || n > a.uniformLen) {
+            if (t == 0) a.framedLen[blk] = 0;
+            continue;
+        }
+        uint8_t *slot = a.slots + (size_t)blk * a.slotStride;
+        int c;
+        if (n < LZ4_MFLIMIT + 1) {                                      // all literals: no window, no table
+            c = encode_block_hc<true>(L, a.src + off, n, 0, slot + a.headerKind, depth);
+        } else {
+            __syncthreads();                                            // wave 0 may still be reading the block before from the window
+            const uint32_t piece = 1024u;
+            for (uint32_t at = (uint32_t)wave * piece; at < (uint32_t)n; at += HC_WAVES * piece)
+                wave_copy_bytes(blockAt + at, a.src + off + at, min((uint32_t)n - at, piece));
+            for (int i = t; i < (int)(HCDICT_TABLE_BYTES / 16); i += HC_THREADS) ((dev_v4 *)&L)[i] = as_global((const dev_v4 *)x.image)[i];
+            c = encode_block_hc<true>(L, blockAt, n, keep, slot + a.headerKind, depth);   // (its first barrier is behind both copies)
+        }
+        if (t == 0) {
+            store_le32(slot, c);
+            if (a.headerKind == 8) store_le32(slot + 4, n);
+            a.framedLen[blk] = (c > 0) ? a.headerKind + c : 0;
+        }
+    }
+}
+
+static int hc_cu_count()
+{
+    static int cus[64];
+    int dev = 0;
+    (void)hipGetDevice(&dev);
+    int &nc = cus[dev & 63];
+    if (nc <= 0 && hipDeviceGetAttribute(&nc, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) nc = 256;
+    return max(nc, 1);
+}
+
+int encode_hc_dict_grid(int nBlocks) { return min(nBlocks, hc_cu_count()); }
+
+void launch_encode_hc_dict(const HcDictArgs &a, int level, hipStream_t s)
+{
+    if (a.e.nBlocks <= 0) return;
+    const int depth = 1 << (min(level, 9) - 1);
+    hipLaunchKernelGGL(k_encode_hc_dict, dim3((unsigned)encode_hc_dict_grid(a.e.nBlocks)), dim3(HC_THREADS), 0, s, a, depth);
+}
+
+// ---------------------------------------------------------------------------
 // K2, reference-exact compression (encode_exact.hpp, DESIGN.md 7d).  One wave per piece of a call, its hash table in LDS.
 // ---------------------------------------------------------------------------
 // canonical form of table entry v for a block (DESIGN 7d): the block's renorm applied, entries that no position of the

@@ -162,6 +162,16 @@ def _load():
         C.c_size_t, C.POINTER(C.c_size_t), _i32p, _i32p)
     sig("mi355lz4_decompress_dict", C.c_int, vp, _u8p, C.c_size_t, C.c_int, C.c_int, _u8p, C.c_int, _u8p, C.c_size_t,
         C.POINTER(C.c_size_t), _i32p, C.c_int, C.POINTER(C.c_int))
+    # high-compression levels against a shared dictionary
+    sig("mi355lz4_hcdict_create", C.c_int, vp, C.POINTER(vp))
+    sig("mi355lz4_hcdict_destroy", None, vp)
+    sig("mi355lz4_hcdict_load", C.c_int, vp, vp, vp, C.c_int)
+    sig("mi355lz4_hcdict_size", C.c_int, vp)
+    sig("mi355lz4_debug_hcdict_image", C.c_int, vp, _u8p)
+    sig("mi355lz4_compress_hcdict_device", C.c_int, vp, vp, vp, vp, vp, C.c_uint64, C.c_int, C.c_int, C.c_int, vp, C.c_size_t,
+        vp)
+    sig("mi355lz4_compress_hcdict", C.c_int, vp, vp, C.POINTER(_u8p), _i32p, C.c_int, C.c_int, _u8p, C.c_size_t,
+        C.POINTER(C.c_size_t), _i32p, _i32p)
     # legacy face (include/lz4.h)
     sig("LZ4_createStream", vp)
     sig("LZ4_freeStream", C.c_int, vp)
@@ -221,6 +231,8 @@ DECLARED_SYMBOLS = [
     "mi355lz4_dstreams_set_dict", "mi355lz4_decompress_dstreams_device", "mi355lz4_decompress_dstreams",
     "mi355lz4_cstreams_load_dict", "mi355lz4_compress_dict_device", "mi355lz4_decompress_dict_device",
     "mi355lz4_compress_dict", "mi355lz4_decompress_dict",
+    "mi355lz4_hcdict_create", "mi355lz4_hcdict_destroy", "mi355lz4_hcdict_load", "mi355lz4_hcdict_size",
+    "mi355lz4_compress_hcdict_device", "mi355lz4_compress_hcdict",
     "LZ4_createStream", "LZ4_freeStream", "LZ4_createStreamDecode", "LZ4_freeStreamDecode", "LZ4_compressBound",
     "LZ4_compress_fast_continue", "LZ4_decompress_safe_continue",
 ]
@@ -919,6 +931,35 @@ class Engine:
                                           flen.ctypes.data_as(_i32p), status.ctypes.data_as(_i32p)), "compress_dict")
         return out[: out_len.value].tobytes(), flen[:n].tolist()
 
+    def compress_hcdict_device(self, hd, src, n_blocks, max_block_len, slots, slot_stride_, framed_len, header_kind=8,
+                               src_off=None, src_len=None, block_stride=None):
+        """A batch of independent blocks at the engine's compression level (1..12), every one with the dictionary of the
+        HcDict hd in front of it: the bytes of block 1 of the linked call [dictionary, block] at that level.  The block
+        arguments are those of compress_batch_device; hd is only read.  Only enqueues (include/mi355lz4.h,
+        mi355lz4_compress_hcdict_device)."""
+        self._follow_torch()
+        _check(lib.mi355lz4_compress_hcdict_device(
+            self.ctx, hd._h if hd is not None else None, _dptr(src), _dptr(src_off), _dptr(src_len),
+            int(max_block_len if block_stride is None else block_stride), int(max_block_len), int(n_blocks),
+            int(header_kind), _dptr(slots), int(slot_stride_), _dptr(framed_len)), "compress_hcdict_device")
+
+    def compress_hcdict(self, blocks, hd, header_kind=8):
+        """blocks: list of bytes-like, every one compressed at the engine's level against the HcDict hd.  Returns (framed
+        bytes, [framed length per block]); mi355lz4_compress_hcdict."""
+        n = len(blocks)
+        arrs = [np.frombuffer(bytes(b), dtype=np.uint8) if not isinstance(b, np.ndarray) else b for b in blocks]
+        ptrs = (_u8p * max(n, 1))(*[a.ctypes.data_as(_u8p) for a in arrs])
+        lens = np.array([a.size for a in arrs] + [0], dtype=np.int32)
+        cap = int(sum(compress_bound(int(x)) + header_kind + 4 for x in lens[:n])) + 16
+        out = np.empty(cap, dtype=np.uint8)
+        out_len = C.c_size_t()
+        flen = np.zeros(max(n, 1), dtype=np.int32)
+        status = np.zeros(max(n, 1), dtype=np.int32)
+        _check(lib.mi355lz4_compress_hcdict(self.ctx, hd._h if hd is not None else None, ptrs, lens.ctypes.data_as(_i32p), n,
+                                            int(header_kind), out.ctypes.data_as(_u8p), cap, C.byref(out_len),
+                                            flen.ctypes.data_as(_i32p), status.ctypes.data_as(_i32p)), "compress_hcdict")
+        return out[: out_len.value].tobytes(), flen[:n].tolist()
+
     def decompress_dict(self, framed, dict_bytes, header_kind=8, fixed_uncomp=0, max_blocks=None, raise_on_block_error=True,
                         cap=None):
         """A framed chain in host memory, every block decoded against dict_bytes (may be empty).  Returns (decoded bytes,
@@ -942,6 +983,47 @@ class Engine:
         if rc != 0 and (raise_on_block_error or rc != -5):
             _check(rc, "decompress_dict")
         return out[: out_len.value].tobytes(), blen[: got.value].tolist()
+
+
+class HcDict:
+    """A prepared high-compression dictionary on the engine's device (mi355lz4_hcdict, about 216 KiB): the dictionary's last
+    64 KiB and the image of the hash-chain encoder's tables after its inserts, for Engine.compress_hcdict_device /
+    compress_hcdict.  Holds the empty dictionary until load()."""
+
+    IMAGE_BYTES = 221248        # kernels.h, HCDICT_IMAGE_BYTES: u16 chain[65536], u32 head[6144], 64 bytes of count, 65536 bytes
+
+    def __init__(self, engine):
+        self._h = C.c_void_p()
+        self._engine = engine
+        engine._follow_torch()
+        _check(lib.mi355lz4_hcdict_create(engine.ctx, C.byref(self._h)), "hcdict_create")
+
+    def __len__(self):
+        return int(lib.mi355lz4_hcdict_size(self._h))
+
+    def load(self, dict_device, length=None):
+        """Build the image from dict_device[:length] (a uint8 device tensor; length defaults to all of it; the last 64 KiB
+        count, 0 is legal).  Enqueued; the object keeps its own copy.  Replaces what was loaded before."""
+        self._engine._follow_torch()
+        n = int(dict_device.numel() if length is None else length) if dict_device is not None else 0
+        _check(lib.mi355lz4_hcdict_load(self._engine.ctx, self._h, _dptr(dict_device) if n else None, n), "hcdict_load")
+
+    def image(self):
+        """Diagnostics: all IMAGE_BYTES of the device image (chain, head, count, bytes), after the device is idle."""
+        buf = np.empty(self.IMAGE_BYTES, dtype=np.uint8)
+        _check(lib.mi355lz4_debug_hcdict_image(self._h, buf.ctypes.data_as(_u8p)), "debug_hcdict_image")
+        return buf.tobytes()
+
+    def close(self):
+        if self._h:
+            lib.mi355lz4_hcdict_destroy(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
 
 
 class CompressStreams:
