@@ -66,10 +66,11 @@ namespace lz4dev {
                             // So 832 accepts exactly the sequences 1024 accepted; the 12 lanes behind the window repeat its last lane's request (win_lane)
 #endif
 #ifndef PAR_RING
-#define PAR_RING 5728       // LDS output staging.  With the window and the jump table ParLds is 7664 bytes: see the static_assert below
+#define PAR_RING 5504       // LDS output staging.  With the window ParLds is 6400 bytes, the jump table an overlay on the ring's top: see ParLds below
 #endif
 #ifndef PAR_HIST
-#define PAR_HIST 2000       // bytes of history kept in the ring across a slide: two 16-byte chunks per lane (2048 needed a third pass for one or two chunks)
+#define PAR_HIST 1776       // bytes of history kept in the ring across a slide: two 16-byte chunks per lane (2048 needed a third pass for one or two chunks).
+                            // With the 5504-byte ring 1776 keeps the slides at 22.5 per lzsynth block (2000: 34.9; scripts/par_ring_model.py)
 #endif
 #ifndef PAR_BATCH_OUT
 #define PAR_BATCH_OUT 2048  // max output bytes of one batch: the ring slides when fewer are free.  Measured with this ring at 20 waves per CU
@@ -93,24 +94,48 @@ namespace lz4dev {
 #ifndef PAR_WAVES
 #define PAR_WAVES 5         // occupancy target (waves per SIMD) the register allocator is held to (<= 102 VGPRs)
 #endif
+#ifndef PAR_WAVES_MAIN
+#define PAR_WAVES_MAIN (PAR_WAVES > 6 ? PAR_WAVES : 6)    // ... of k_decode_par<STATS> and k_decode_par_redo alone (<= 80 VGPRs): 24 waves per CU, which five LDS granules allow
+#endif
 
 // jump[] is the successor table of step 3.  Entries are BYTE offsets into jump[] itself (2 x node
 // index), so a gather is one ds_read_u16 with no address arithmetic.  The absorbing state of a batch is the node behind
 // the last one that may hold a token (`absorb` in the speculative parse), at most 2*PAR_NODES: the entry behind the table.
+//
+// The table (and the rank records of the dependency masks, which reuse its bytes) has no LDS of its own: it is a fixed OVERLAY on the
+// last PAR_JUMP_BYTES of ring[].  Its lifetime is from a batch's speculative parse to its dependency masks, and both ends lie where
+// the ring's top is free:
+//   - every batch is parsed with the ring's content -- output positions [ringBase, op), ring bytes [A, op - ringBase + A) -- ending
+//     at or below PAR_RING - PAR_BATCH_OUT - 32: that is the condition under which the batch before did NOT slide; after a slide, and
+//     after the reload that follows a hand-over, the content ends below PAR_HIST + 31, which is lower still (static_assert below).
+//     So the ring's top PAR_BATCH_OUT + 32 bytes hold nothing at a parse, and the table is smaller than that;
+//   - the batch's first store to the ring (literals, then far matches, near matches) comes after the last read of the rank records.
+//     LDS operations of one wave execute in order, the table and the ring are one array to the compiler, and wave_fence() stands
+//     between the phases as before.
+// Nothing of this depends on the template parameters of decode_block_par: the list-driven form skips the table and uses the rank
+// records only, the tolerant form's taint bits live in TolCtx, the partial form only ends the loop sooner, and with PAR_RANK 0 the
+// table's life ends with the chain.  A batch's output may then run over the dead table up to the ring's last byte.
+#define PAR_JUMP_BYTES (2 * (PAR_MAXNODES + 8))
+#define PAR_JUMP_OFS ((PAR_RING + 32 - PAR_JUMP_BYTES) & ~15)       // first byte of the table in ring[]
 struct __attribute__((aligned(16))) ParLds {
     uint8_t win[PAR_WIN + 32];
-    uint16_t jump[PAR_MAXNODES + 8];
     uint8_t ring[PAR_RING + 32];
+    __device__ __forceinline__ uint16_t *jump() { return (uint16_t *)&ring[PAR_JUMP_OFS]; }
 };
 #define PAR_END (2 * PAR_NODES)
 // The decoder is bound by the waves that carry its chains of LDS round trips, and the LDS decides how many a CU holds: the registers
 // (95) allow 5 per SIMD = 20.  gfx950 hands its 160 KiB out in granules of 1280 bytes (measured, docs/MEASUREMENT_LOG.md 15: footprints
 // of 8272 and 8192 bytes both keep SQ_WAVE_CYCLES / SQ_BUSY_CYCLES at 33.59 = 18 waves per CU -- seven granules --, 7664 bytes
-// gives 37.47 = 20; the runtime's occupancy query divides 160 KiB by the bytes and says 19 / 20 / 20).  Six granules are 7680 bytes.
+// gives 37.47 = 20; the runtime's occupancy query divides 160 KiB by the bytes and says 19 / 20 / 20).  Six granules are 7680 bytes,
+// FIVE are 6400: what 24 waves per CU (six per SIMD: k_decode_par and k_decode_par_redo, PAR_WAVES_MAIN) may use.
 #ifndef PAR_LDS_LIMIT
-#define PAR_LDS_LIMIT 7680  // (experiments with a larger footprint raise it)
+#define PAR_LDS_LIMIT 6400  // (experiments with a larger footprint raise it)
 #endif
-static_assert(sizeof(ParLds) <= PAR_LDS_LIMIT, "ParLds above six 1280-byte LDS granules: 18 waves per CU instead of 20");
+static_assert(sizeof(ParLds) <= PAR_LDS_LIMIT, "ParLds above five 1280-byte LDS granules: 20 waves per CU or fewer instead of 24");
+static_assert((PAR_WIN + 32) % 16 == 0 && PAR_JUMP_OFS % 16 == 0, "the table and its 16-byte rank records are aligned");
+static_assert(PAR_JUMP_OFS + PAR_JUMP_BYTES <= PAR_RING + 32, "the table lies inside ring[]");
+static_assert(PAR_JUMP_BYTES <= PAR_BATCH_OUT + 32 && PAR_JUMP_OFS >= ((PAR_RING - PAR_BATCH_OUT - 32 + 15) & ~15),
+              "the table overlays ring bytes that hold no output when a batch is parsed (the no-slide bound)");
 #define PAR_WIN_LANES (PAR_WIN / 16)     // lanes whose 16 bytes make up the window
 static_assert(PAR_WIN % 16 == 0 && PAR_WIN_LANES <= LZ4_WAVE, "the window is 16 bytes per lane");
 static_assert(PAR_MAXNODES + 288 <= PAR_WIN + 32, "a plain sequence that starts at the last node, and the reads behind it, stay in win[]");
@@ -162,6 +187,33 @@ __device__ __forceinline__ int par_scan_incl(int x)
     x += __builtin_amdgcn_update_dpp(0, x, 0x142, 0xa, 0xf, false);   // row_bcast:15 -> rows 1,3
     x += __builtin_amdgcn_update_dpp(0, x, 0x143, 0xc, 0xf, false);   // row_bcast:31 -> rows 2,3
     return x;
+}
+
+// A window slot [q, q + 16) that is not wholly inside the framed buffer [bufLo, bufHi): the buffer's bytes, zeros outside.  Only the
+// first window of the buffer's first block and the last windows of its last block come here.  ONE 16-byte load from the nearest place
+// inside the buffer (which holds a block of 64 bytes or more: decode_block_par's first test), moved into place in registers: 32 bytes
+// E = {low, high} shifted down by m bytes.  (This was 16 conditional byte loads, inlined once per fetch_window -- four times in
+// decode_block_par -- whose registers the batch loop paid for; as a function out of line, every value of the batch would have had
+// to survive a call in the loop.)
+__device__ __forceinline__ uint4 par_fetch_window_edge(const uint8_t *q, const uint8_t *bufLo, const uint8_t *bufHi)
+{
+    uint32_t E[8] = {0u, 0u, 0u, 0u, 0u, 0u, 0u, 0u};
+    uint32_t m = 0;
+    if (q + 16 > bufLo && q < bufHi) {
+        const uint8_t *qc = (q < bufLo) ? bufLo : bufHi - 16;
+        par_v4 v;
+        __builtin_memcpy(&v, as_global(qc), 16);
+        const bool below = q < bufLo;                    // the slot starts d bytes in front of the buffer: byte k is v's byte k - d
+        const uint32_t d = (uint32_t)(below ? bufLo - q : q - qc);                       // 1..15
+        m = below ? 16u - d : d;                         // ... else it ends behind the buffer: byte k is v's byte k + d
+        E[0] = below ? 0u : v.x; E[1] = below ? 0u : v.y; E[2] = below ? 0u : v.z; E[3] = below ? 0u : v.w;
+        E[4] = below ? v.x : 0u; E[5] = below ? v.y : 0u; E[6] = below ? v.z : 0u; E[7] = below ? v.w : 0u;
+    }
+    if (m & 8u) { for (int i = 0; i < 6; i++) E[i] = E[i + 2]; }       // (m <= 15: bytes up to 15 + 15 of the 32 are read)
+    if (m & 4u) { for (int i = 0; i < 5; i++) E[i] = E[i + 1]; }
+    uint32_t w[4];
+    for (int i = 0; i < 4; i++) w[i] = __builtin_amdgcn_alignbyte(E[i + 1], E[i], m & 3u);
+    return make_uint4(w[0], w[1], w[2], w[3]);
 }
 
 // Diagnostic counters (STATS build only; never part of a timed run)
@@ -219,7 +271,10 @@ __device__ int decode_block_par(const uint8_t *src, int srcLen, uint8_t *dst, in
     const uint8_t *dictEnd = DICT ? dict + dictLen : dst;
     const int dictLo = DICT ? -(int)min(dictLen, 65535u) : 0;
 
-    int lane = lane_id();
+    // (an opaque definition, like the one behind the call below: lane_id() itself is merged with the kernel's own lane_id() behind this
+    // function, and the one value then lives across the call -- where, at six waves per SIMD, no register is left for it)
+    int lane;
+    asm volatile("v_mbcnt_lo_u32_b32 %0, -1, 0\n\tv_mbcnt_hi_u32_b32 %0, -1, %0" : "=v"(lane));
     const int iend = srcLen;
     const uint32_t A = (uint32_t)((uintptr_t)dst & 15);   // ring index of output position p is p - ringBase + A
     int ip = 0, op = 0;
@@ -235,14 +290,11 @@ __device__ int decode_block_par(const uint8_t *src, int srcLen, uint8_t *dst, in
     // 16 bytes of the compressed stream for this lane's slot of the window that starts at `base`
     auto fetch_window = [&](uintptr_t base) -> uint4 {
         const uint8_t *q = (const uint8_t *)(base + 16u * (uint32_t)win_lane());
-        if (q >= bufLo && q + 16 <= bufHi) {
+        if (__builtin_expect(q >= bufLo && q + 16 <= bufHi, 1)) {
             const par_v4 v = *as_global((const par_v4 *)q);
             return make_uint4(v.x, v.y, v.z, v.w);
         }
-        uint32_t w[4] = {0, 0, 0, 0};
-        for (int k = 0; k < 16; k++)
-            if (q + k >= bufLo && q + k < bufHi) w[k >> 2] |= (uint32_t)as_global(q)[k] << (8 * (k & 3));
-        return make_uint4(w[0], w[1], w[2], w[3]);
+        return par_fetch_window_edge(q, bufLo, bufHi);
     };
 
     // ring -> global for positions [flushed, upto); 16-byte aligned stores in the body.
@@ -286,7 +338,7 @@ __device__ int decode_block_par(const uint8_t *src, int srcLen, uint8_t *dst, in
     uintptr_t wbase = (uintptr_t)src & ~(uintptr_t)15;     // window base whose data is in `wnext`
     uint4 wnext = fetch_window(wbase);
     bool winStale = true;                                  // L.win does not hold the window at wbase yet
-    const uint8_t *jumpB = (const uint8_t *)L.jump;
+    const uint8_t *jumpB = (const uint8_t *)L.jump();
     // (the absorbing state behind the table is written with every batch's table: its place depends on the nodes per lane)
 
     for (;;) {
@@ -373,10 +425,10 @@ __device__ int decode_block_par(const uint8_t *src, int srcLen, uint8_t *dst, in
                         const par_h2 nxt = term + mlx + h2(base3 + 0x00020002u * (uint32_t)p);
                         P[p] = u32(__builtin_elementwise_min(nxt, lim) << 1);
                     }
-                    uint32_t *tw = (uint32_t *)&L.jump[NL * lane];
+                    uint32_t *tw = (uint32_t *)&L.jump()[NL * lane];
 #pragma unroll
                     for (int p = 0; p < NL / 2; p++) tw[p] = P[p];
-                    if (lane == 0) L.jump[NL * LZ4_WAVE] = (uint16_t)(2 * NL * LZ4_WAVE);   // absorbing state behind the table
+                    if (lane == 0) L.jump()[NL * LZ4_WAVE] = (uint16_t)(2 * NL * LZ4_WAVE);   // absorbing state behind the table
 #pragma unroll
                     for (int p = 0; p < NL / 2; p++) { J[2 * p] = P[p] & 0xffffu; J[2 * p + 1] = P[p] >> 16; }
                 }
@@ -404,7 +456,7 @@ __device__ int decode_block_par(const uint8_t *src, int srcLen, uint8_t *dst, in
                     else sh = par_row_shr<8>(cj);
                     if (lane >= d && lane < 2 * d) c2 = (uint32_t)sh;
                     wave_fence();
-                    uint32_t *tw = (uint32_t *)&L.jump[NL * lane];
+                    uint32_t *tw = (uint32_t *)&L.jump()[NL * lane];
 #pragma unroll
                     for (int p = 0; p < NL / 2; p++) tw[p] = J[2 * p] | (J[2 * p + 1] << 16);
                     wave_fence();
@@ -591,7 +643,7 @@ __device__ int decode_block_par(const uint8_t *src, int srcLen, uint8_t *dst, in
                 // bits in the records before}, so a query is ONE aligned 16-byte gather and two popcounts -- instead of a
                 // six-step binary search over the lanes (12 ds_bpermute and their address arithmetic per batch).
                 static_assert(16 * (PAR_BATCH_OUT / 64 + 1) <= 2 * PAR_NODES, "rank records fit the jump table");
-                uint8_t *rk = (uint8_t *)L.jump;
+                uint8_t *rk = (uint8_t *)L.jump();
                 constexpr int NREC = PAR_BATCH_OUT / 64 + 1;
                 {
                     uint32_t z = 0;
@@ -908,8 +960,13 @@ __device__ int decode_block_par(const uint8_t *src, int srcLen, uint8_t *dst, in
         const bool tail = (iend - ip < 64 || cap - op < 128);
         if (STATS && !tail) sc[PS_HANDOVERS]++;
         lap(PS_T_FLUSH);
+        // The lane id and the window registers are dead from here to their new values behind the call; said so that the register
+        // allocator does not take them to live across it (the callee clobbers v0-v79: at six waves per SIMD such a value has no
+        // register at all and is spilled for the whole function).  Only the forms that run at six waves need it.
+        if (!DICT && !TOL && !PARTIAL) asm volatile("" : "=v"(lane), "=v"(wnext.x), "=v"(wnext.y), "=v"(wnext.z), "=v"(wnext.w));
         int r = decode_seq_dispatch<TOL, PARTIAL>(st, tail ? 0 : 1, src, srcLen, dst, cap, dict, dictLen, bufLo, bufHi, tol);
-        if (r == SEQ_CONTINUE && (!st.fast || iend - st.ip < 64 || cap - st.op < 128))
+        r = uni(r);                                       // (wave-uniform, like all of st: the second call then stands in uniform control flow)
+        if (r == SEQ_CONTINUE && (!uni((int)st.fast) || iend - uni(st.ip) < 64 || cap - uni(st.op) < 128))
             r = decode_seq_dispatch<TOL, PARTIAL>(st, 0, src, srcLen, dst, cap, dict, dictLen, bufLo, bufHi, tol);
         lap(PS_T_SEQ);
         r = uni(r);

@@ -6,8 +6,14 @@
 #else
 #define PAR_OCC __launch_bounds__(64, PAR_WAVES)
 #endif
+// The two kernels of this file that decode whole independent blocks run at six waves per SIMD; every other user of ParLds keeps PAR_OCC.
+#ifdef PAR_WAVES_MAX
+#define PAR_OCC_MAIN __attribute__((amdgpu_flat_work_group_size(64, 64), amdgpu_waves_per_eu(PAR_WAVES_MAIN, (PAR_WAVES_MAX > PAR_WAVES_MAIN ? PAR_WAVES_MAX : PAR_WAVES_MAIN))))
+#else
+#define PAR_OCC_MAIN __launch_bounds__(64, PAR_WAVES_MAIN)
+#endif
 template <bool STATS>
-__global__ PAR_OCC void k_decode_par(DecodeArgs a, unsigned long long *stats)
+__global__ PAR_OCC_MAIN void k_decode_par(DecodeArgs a, unsigned long long *stats)
 {
     __shared__ ParLds lds;
     const int blk = (int)blockIdx.x;
@@ -32,7 +38,7 @@ void launch_decode_par(const DecodeArgs &a, unsigned long long *stats, hipStream
 
 // The blocks the workgroup-per-block decoder left behind (result CU_REDO), by the lane-parallel decoder.  (A kernel of its
 // own, not a template parameter of k_decode_par: that changed the headline kernel's register allocation.)
-__global__ PAR_OCC void k_decode_par_redo(DecodeArgs a)
+__global__ PAR_OCC_MAIN void k_decode_par_redo(DecodeArgs a)
 {
     __shared__ ParLds lds;
     const int blk = (int)blockIdx.x;
