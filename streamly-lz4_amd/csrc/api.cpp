@@ -6,6 +6,7 @@
 #include "engine.hpp"
 
 #include <algorithm>
+#include <climits>
 #include <cstdarg>
 #include <cstdio>
 #include <cstdlib>
@@ -538,24 +539,10 @@ static int exact_encode(mi355lz4_ctx *c, EncodeArgs a, const int32_t *hostLen)
     for (int j = 0; j < n; j++)
         if (lens[(size_t)j] < 0 || lens[(size_t)j] > a.uniformLen)
             return fail(MI355LZ4_E_ARG, "compress_exact: block %d length %d outside 0..maxBlockLen", j, lens[(size_t)j]);
-    // cbits/lz4.c:1565-1637 with the lengths alone: renorm (:1545-1562), dictionaries under 4 bytes (:1581-1587), dictSmall
+    // cbits/lz4.c:1565-1637 with the lengths alone (kernels.h, exact_step)
     std::vector<ExactBlock> meta((size_t)n + 1);
     uint32_t cur = c->ex.cur, dictSize = c->ex.dictSize;
-    for (int j = 0; j < n; j++) {
-        const uint32_t len = (uint32_t)lens[(size_t)j];
-        ExactBlock &m = meta[(size_t)j];
-        m.delta = 0;
-        if (cur + len > 0x80000000u) {
-            m.delta = cur - 65536u;
-            cur = 65536u;
-            if (dictSize > 65536u) dictSize = 65536u;
-        }
-        if (dictSize - 1u < 4u - 1u) dictSize = 0;
-        m.start = cur; m.dictSize = dictSize; m.n = (int32_t)len; m.pad = 0;
-        m.dictSmall = (dictSize < 65536u && dictSize < cur) ? 1 : 0;
-        cur += len;
-        dictSize = len;
-    }
+    for (int j = 0; j < n; j++) meta[(size_t)j] = exact_step(cur, dictSize, (uint32_t)lens[(size_t)j]);
     meta[(size_t)n] = ExactBlock{cur, dictSize, 0u, 0, 0, 0};
 
     // R = 0: no speculation, one serial chain
@@ -641,30 +628,66 @@ EncodeArgs mi355lz4_detail::make_encode_args(const uint8_t *src, const uint64_t 
                       nullptr, 0, 0};
 }
 
+// The argument contract of a device batch, written once for the four entry points; `who` names the caller in the messages.  In two
+// halves, because the empty call returns between them (and the HC dictionary call's own limit comes in front of that):
+// batch_shape_check the counts, the header kind and the block length against the call's limit, batch_buffers_check the pointers
+// and the slot stride against bound + header + trailer.
+static int batch_shape_check(const char *who, int nBlocks, int headerKind, int maxBlockLen, int limit)
+{
+    if (nBlocks < 0 || (headerKind != 4 && headerKind != 8) || maxBlockLen < 0 || (unsigned)maxBlockLen > (unsigned)limit)
+        return fail(MI355LZ4_E_ARG, "%s: bad arguments", who);
+    return MI355LZ4_OK;
+}
+static int batch_buffers_check(const mi355lz4_ctx *c, const char *who, const uint8_t *src, int maxBlockLen, int headerKind,
+                               const uint8_t *slots, size_t slotStride, const int32_t *framedLen)
+{
+    if (!src && maxBlockLen > 0) return fail(MI355LZ4_E_ARG, "%s: null src", who);
+    if (!slots || !framedLen) return fail(MI355LZ4_E_ARG, "%s: null output", who);
+    if (slotStride < (size_t)mi355lz4_compress_bound(maxBlockLen) + (size_t)headerKind + (c->blockChecksum ? 4u : 0u))
+        return fail(MI355LZ4_E_CAPACITY, "%s: slotStride %zu < bound", who, slotStride);
+    return MI355LZ4_OK;
+}
+
+// Behind an encoder's launch.  encode_trailers: with block checksums on, the trailers go behind the encoder's output, on the same
+// stream, before anything reads framedLen.  encode_launched: the launch checked first (`what` names it for check_launch).
+static int encode_trailers(mi355lz4_ctx *c, const EncodeArgs &a)
+{
+    if (!c->blockChecksum) return MI355LZ4_OK;
+    launch_xxh32_append(a.slots, a.slotStride, a.headerKind, a.framedLen, a.nBlocks, c->stream);
+    return check_launch("checksum launch");
+}
+static int encode_launched(mi355lz4_ctx *c, const EncodeArgs &a, const char *what)
+{
+    if (int r = check_launch(what)) return r;
+    return encode_trailers(c, a);
+}
+
+// One scratch per stream the engine has been used on, `count` of the four slots so far: the slot of the engine's current stream,
+// else a free one, else the one used longest ago -- *takeOver then says that it is still another stream's, and the caller waits
+// for slot->s by its own rule before the slot changes hands.
+static mi355lz4_ctx::SegScratch *scratch_slot(mi355lz4_ctx *c, mi355lz4_ctx::SegScratch *slots, int &count, bool *takeOver)
+{
+    *takeOver = false;
+    for (int i = 0; i < count; i++) if (slots[i].s == c->stream) return &slots[i];
+    if (count < 4) return &slots[count++];
+    mi355lz4_ctx::SegScratch *slot = &slots[0];
+    for (int i = 1; i < count; i++) if (slots[i].tick < slot->tick) slot = &slots[i];
+    *takeOver = true;
+    return slot;
+}
+
 int mi355lz4_detail::encode_device(mi355lz4_ctx *c, const uint8_t *src, const uint64_t *srcOff, const int32_t *srcLen,
                                    uint64_t blockStride, int maxBlockLen, int nBlocks, int accel, int headerKind, uint8_t *slots,
                                    size_t slotStride, int32_t *framedLen, int lookBack, const int32_t *hostLen)
 {
     if (!c) return fail(MI355LZ4_E_ARG, "null ctx");
-    if (nBlocks < 0 || (headerKind != 4 && headerKind != 8) || maxBlockLen < 0 ||
-        (unsigned)maxBlockLen > (unsigned)MI355LZ4_MAX_INPUT_SIZE)
-        return fail(MI355LZ4_E_ARG, "compress_batch_device: bad arguments");
+    if (int r = batch_shape_check("compress_batch_device", nBlocks, headerKind, maxBlockLen, MI355LZ4_MAX_INPUT_SIZE)) return r;
     if (nBlocks == 0) return MI355LZ4_OK;
-    if (!src && maxBlockLen > 0) return fail(MI355LZ4_E_ARG, "compress_batch_device: null src");
-    if (!slots || !framedLen) return fail(MI355LZ4_E_ARG, "compress_batch_device: null output");
-    const size_t trailer = c->blockChecksum ? 4u : 0u;
-    if (slotStride < (size_t)mi355lz4_compress_bound(maxBlockLen) + (size_t)headerKind + trailer)
-        return fail(MI355LZ4_E_CAPACITY, "compress_batch_device: slotStride %zu < bound", slotStride);
+    if (int r = batch_buffers_check(c, "compress_batch_device", src, maxBlockLen, headerKind, slots, slotStride, framedLen)) return r;
     HIP_TRY(hipSetDevice(c->device));
     EncodeArgs a = make_encode_args(src, srcOff, srcLen, blockStride, maxBlockLen, nBlocks, accel, headerKind, slots, slotStride, framedLen);
     a.stats = c->stats; a.linked = c->linkedCompress; a.lookBack = lookBack;
-    // block checksums: the trailers go behind the encoder's output, on the same stream, before anything reads framedLen
-    auto finish = [&]() -> int {
-        int r = check_launch("encode launch");
-        if (r || !c->blockChecksum) return r;
-        launch_xxh32_append(slots, slotStride, headerKind, framedLen, nBlocks, c->stream);
-        return check_launch("checksum launch");
-    };
+    auto finish = [&]() -> int { return encode_launched(c, a, "encode launch"); };
     // the reference-exact stream: its own chain of kernels, whatever the linked switch says
     if (c->compExact) {
         if (c->compLevel != 0)
@@ -711,14 +734,10 @@ int mi355lz4_detail::encode_device(mi355lz4_ctx *c, const uint8_t *src, const ui
             // that was used longest ago, once the work queued on that slot's stream is done with it.
             mi355lz4_ctx::SegScratch *slot = nullptr;
             if (fits) {
-                for (int i = 0; i < c->nSeg; i++) if (c->seg[i].s == c->stream) slot = &c->seg[i];
-                if (!slot && c->nSeg < 4) { slot = &c->seg[c->nSeg++]; slot->s = c->stream; }
-                if (!slot) {
-                    slot = &c->seg[0];
-                    for (int i = 1; i < c->nSeg; i++) if (c->seg[i].tick < slot->tick) slot = &c->seg[i];
-                    (void)hipStreamSynchronize(slot->s);
-                    slot->s = c->stream;
-                }
+                bool takeOver;
+                slot = scratch_slot(c, c->seg, c->nSeg, &takeOver);
+                if (takeOver) (void)hipStreamSynchronize(slot->s);
+                slot->s = c->stream;
                 slot->tick = ++c->segTick;
                 // a scratch that a big forced call left behind is given back when a call needs less than a quarter of it
                 if (slot->b.cap > SEG_SCRATCH_MAX && (listBytes + 3 * cntBytes + 256) * 4 < slot->b.cap) {
@@ -967,12 +986,8 @@ int mi355lz4_detail::streams_enqueue(mi355lz4_ctx *c, mi355lz4_cstreams *cs, con
     x.state = cs->state;
     launch_exact_streams(x, nWork, c->stream);
     if ((rc = check_launch("exact streams launch"))) return rc;
-    if ((rc = stream_table_launched(c, used))) return rc;
-    if (c->blockChecksum) {                               // the trailers, behind the encoder (encode_device, finish)
-        launch_xxh32_append(a.slots, a.slotStride, a.headerKind, a.framedLen, a.nBlocks, c->stream);
-        return check_launch("checksum launch");
-    }
-    return MI355LZ4_OK;
+    if ((rc = stream_table_launched(c, used))) return rc;       // (the ring entry is busy from here on, whatever the trailers do)
+    return encode_trailers(c, a);
 }
 
 extern "C" int mi355lz4_compress_streams_device(mi355lz4_ctx *c, mi355lz4_cstreams *cs, const uint8_t *src,
@@ -983,13 +998,10 @@ extern "C" int mi355lz4_compress_streams_device(mi355lz4_ctx *c, mi355lz4_cstrea
 {
     int r = streams_check(c, cs, nBlocks, streamFirst, streamSlot, nStreams, "compress_streams_device");
     if (r) return r;
-    if ((headerKind != 4 && headerKind != 8) || maxBlockLen < 0 || (unsigned)maxBlockLen > (unsigned)MI355LZ4_MAX_INPUT_SIZE)
-        return fail(MI355LZ4_E_ARG, "compress_streams_device: bad arguments");
+    // (nBlocks < 0 has gone to the stream-table check above)
+    if ((r = batch_shape_check("compress_streams_device", nBlocks, headerKind, maxBlockLen, MI355LZ4_MAX_INPUT_SIZE))) return r;
     if (nBlocks == 0) return MI355LZ4_OK;
-    if (!src && maxBlockLen > 0) return fail(MI355LZ4_E_ARG, "compress_streams_device: null src");
-    if (!slots || !framedLen) return fail(MI355LZ4_E_ARG, "compress_streams_device: null output");
-    if (slotStride < mi355lz4_compress_bound(maxBlockLen) + (size_t)headerKind + (c->blockChecksum ? 4u : 0u))
-        return fail(MI355LZ4_E_CAPACITY, "compress_streams_device: slotStride %zu < bound", slotStride);
+    if ((r = batch_buffers_check(c, "compress_streams_device", src, maxBlockLen, headerKind, slots, slotStride, framedLen))) return r;
     HIP_TRY(hipSetDevice(c->device));
     const EncodeArgs a = make_encode_args(src, srcOff, srcLen, blockStride, maxBlockLen, nBlocks, accel, headerKind, slots, slotStride, framedLen);
     return streams_enqueue(c, cs, a, 0, nBlocks, streamFirst, streamSlot, nStreams);
@@ -1019,24 +1031,15 @@ extern "C" int mi355lz4_compress_dict_device(mi355lz4_ctx *c, const mi355lz4_cst
     if (c->compLevel != 0)
         return fail(MI355LZ4_E_ARG, "compress_dict_device: compression level %d; the dictionary batch is level 0's encoder", c->compLevel);
     if (dictSlot < 0 || dictSlot >= cs->nSlots) return fail(MI355LZ4_E_ARG, "compress_dict_device: slot %d of %d", dictSlot, cs->nSlots);
-    if (nBlocks < 0 || (headerKind != 4 && headerKind != 8) || maxBlockLen < 0 || (unsigned)maxBlockLen > (unsigned)MI355LZ4_MAX_INPUT_SIZE)
-        return fail(MI355LZ4_E_ARG, "compress_dict_device: bad arguments");
+    if (int r = batch_shape_check("compress_dict_device", nBlocks, headerKind, maxBlockLen, MI355LZ4_MAX_INPUT_SIZE)) return r;
     if (nBlocks == 0) return MI355LZ4_OK;
-    if (!src && maxBlockLen > 0) return fail(MI355LZ4_E_ARG, "compress_dict_device: null src");
-    if (!slots || !framedLen) return fail(MI355LZ4_E_ARG, "compress_dict_device: null output");
-    if (slotStride < mi355lz4_compress_bound(maxBlockLen) + (size_t)headerKind + (c->blockChecksum ? 4u : 0u))
-        return fail(MI355LZ4_E_CAPACITY, "compress_dict_device: slotStride %zu < bound", slotStride);
+    if (int r = batch_buffers_check(c, "compress_dict_device", src, maxBlockLen, headerKind, slots, slotStride, framedLen)) return r;
     HIP_TRY(hipSetDevice(c->device));
     ExactDictArgs x;
     x.e = make_encode_args(src, srcOff, srcLen, blockStride, maxBlockLen, nBlocks, accel, headerKind, slots, slotStride, framedLen);
     x.state = cs->state + (size_t)dictSlot * CSTREAM_SLOT_BYTES;
     launch_exact_dict(x, c->stream);
-    if (int r = check_launch("exact dict launch")) return r;
-    if (c->blockChecksum) {                               // the trailers, behind the encoder (encode_device, finish)
-        launch_xxh32_append(slots, slotStride, headerKind, framedLen, nBlocks, c->stream);
-        return check_launch("checksum launch");
-    }
-    return MI355LZ4_OK;
+    return encode_launched(c, x.e, "exact dict launch");
 }
 
 // ---------------------------------------------------------------------------
@@ -1111,15 +1114,10 @@ extern "C" int mi355lz4_debug_hcdict_image(mi355lz4_hcdict *hd, uint8_t *bytes)
 // most, the one used longest ago taken over once its stream is done with it (the rule of the segment scratch, encode_device)
 static int hcdict_stage(mi355lz4_ctx *c, size_t bytes, uint8_t **out)
 {
-    mi355lz4_ctx::SegScratch *slot = nullptr;
-    for (int i = 0; i < c->nHcStage; i++) if (c->hcStage[i].s == c->stream) slot = &c->hcStage[i];
-    if (!slot && c->nHcStage < 4) { slot = &c->hcStage[c->nHcStage++]; slot->s = c->stream; }
-    if (!slot) {
-        slot = &c->hcStage[0];
-        for (int i = 1; i < c->nHcStage; i++) if (c->hcStage[i].tick < slot->tick) slot = &c->hcStage[i];
-        HIP_TRY(hipStreamSynchronize(slot->s));
-        slot->s = c->stream;
-    }
+    bool takeOver;
+    mi355lz4_ctx::SegScratch *slot = scratch_slot(c, c->hcStage, c->nHcStage, &takeOver);
+    if (takeOver) HIP_TRY(hipStreamSynchronize(slot->s));
+    slot->s = c->stream;
     slot->tick = ++c->segTick;
     if (bytes > slot->b.cap) HIP_TRY(hipStreamSynchronize(slot->s));   // (dev_reserve frees what queued work may still use)
     if (int r = dev_reserve(slot->b, bytes)) return r;
@@ -1136,15 +1134,12 @@ extern "C" int mi355lz4_compress_hcdict_device(mi355lz4_ctx *c, const mi355lz4_h
     if (c->compLevel < 1)
         return fail(MI355LZ4_E_ARG, "compress_hcdict_device: compression level %d; level 0 against a dictionary is mi355lz4_compress_dict_device",
                     c->compLevel);
-    if (nBlocks < 0 || (headerKind != 4 && headerKind != 8) || maxBlockLen < 0)
-        return fail(MI355LZ4_E_ARG, "compress_hcdict_device: bad arguments");
+    // (no block length is "bad" here but a negative one: this call's own limit has its own message, in front of the empty call)
+    if (int r = batch_shape_check("compress_hcdict_device", nBlocks, headerKind, maxBlockLen, INT_MAX)) return r;
     if (maxBlockLen > HCDICT_MAX_BLOCK)
         return fail(MI355LZ4_E_ARG, "compress_hcdict_device: maxBlockLen %d above the %d bytes a dictionary batch takes", maxBlockLen, HCDICT_MAX_BLOCK);
     if (nBlocks == 0) return MI355LZ4_OK;
-    if (!src && maxBlockLen > 0) return fail(MI355LZ4_E_ARG, "compress_hcdict_device: null src");
-    if (!slots || !framedLen) return fail(MI355LZ4_E_ARG, "compress_hcdict_device: null output");
-    if (slotStride < mi355lz4_compress_bound(maxBlockLen) + (size_t)headerKind + (c->blockChecksum ? 4u : 0u))
-        return fail(MI355LZ4_E_CAPACITY, "compress_hcdict_device: slotStride %zu < bound", slotStride);
+    if (int r = batch_buffers_check(c, "compress_hcdict_device", src, maxBlockLen, headerKind, slots, slotStride, framedLen)) return r;
     HIP_TRY(hipSetDevice(c->device));
     HcDictArgs x;
     x.e = make_encode_args(src, srcOff, srcLen, blockStride, maxBlockLen, nBlocks, 1, headerKind, slots, slotStride, framedLen);
@@ -1152,12 +1147,7 @@ extern "C" int mi355lz4_compress_hcdict_device(mi355lz4_ctx *c, const mi355lz4_h
     x.stageStride = 65536 + (((size_t)maxBlockLen + 255) & ~(size_t)255) + 256;
     if (int r = hcdict_stage(c, (size_t)encode_hc_dict_grid(nBlocks) * x.stageStride, &x.stage)) return r;
     launch_encode_hc_dict(x, c->compLevel, c->stream);
-    if (int r = check_launch("hc dict launch")) return r;
-    if (c->blockChecksum) {                               // the trailers, behind the encoder (encode_device, finish)
-        launch_xxh32_append(slots, slotStride, headerKind, framedLen, nBlocks, c->stream);
-        return check_launch("checksum launch");
-    }
-    return MI355LZ4_OK;
+    return encode_launched(c, x.e, "hc dict launch");
 }
 
 extern "C" int mi355lz4_compact_device(mi355lz4_ctx *c, const uint8_t *slots, size_t slotStride,

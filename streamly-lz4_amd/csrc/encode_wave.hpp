@@ -99,6 +99,16 @@ __device__ __forceinline__ uint8_t *emit_ext_len(uint8_t *op, uint32_t rest)
     return op + nff + 1;
 }
 
+// A block's last literals (cbits/lz4.c:1204-1231), by the whole wave: the token, the length's extra bytes, the run's bytes.
+__device__ __forceinline__ uint8_t *emit_last_literals(uint8_t *op, const uint8_t *from, uint32_t run)
+{
+    uint8_t *tok = op++;
+    if (lane_id() == 0) *tok = (uint8_t)(min(run, 15u) << 4);
+    if (run >= 15) op = emit_ext_len(op, run - 15);
+    wave_copy_bytes(op, from, run);
+    return op + run;
+}
+
 // number of leading equal bytes (0..16) of two 16-byte groups
 __device__ __forceinline__ uint32_t common16(const uint4 &a, const uint4 &b)
 {
@@ -1378,14 +1388,7 @@ __device__ int encode_block_wave(const uint8_t *src, int n, uint8_t *dst, int ac
     flush_queue();
     if (SEG) return anchor + seg->base;
     // ---- last literals (:1204-1231) ----
-    {
-        const uint32_t lastRun = (uint32_t)(n - anchor);
-        uint8_t *tok = op++;
-        if (lane == 0) *tok = (uint8_t)(min(lastRun, 15u) << 4);
-        if (lastRun >= 15) op = emit_ext_len(op, lastRun - 15);
-        wave_copy_bytes(op, src + anchor, lastRun);
-        op += lastRun;
-    }
+    op = emit_last_literals(op, src + anchor, (uint32_t)(n - anchor));
     return (int)(op - dst);
 }
 

@@ -134,6 +134,27 @@ struct ExactBlock {
 };
 #define EXACT_TABLE 4096     // LZ4_HASHLOG 12, byU32
 
+// One array of n bytes through LZ4_compress_fast_continue's statements around the encoder (cbits/lz4.c:1565-1634), from the
+// scalars and the length alone: the block's state, and cur (currentOffset) and dictSize advanced behind it.  The host plans the
+// single stream with it (api.cpp, exact_encode); k_exact_streams and k_exact_dict run it per wave.  Whoever holds the table
+// applies the renorm that a non-zero delta asks for.
+__host__ __device__ inline ExactBlock exact_step(uint32_t &cur, uint32_t &dictSize, uint32_t n)
+{
+    ExactBlock m;
+    m.delta = 0;
+    if (cur + n > 0x80000000u) {                                        // LZ4_renormDictT, :1545-1562
+        m.delta = cur - 65536u;
+        cur = 65536u;
+        if (dictSize > 65536u) dictSize = 65536u;
+    }
+    if (dictSize - 1u < 4u - 1u) dictSize = 0;                          // :1581-1587
+    m.start = cur; m.dictSize = dictSize; m.n = (int32_t)n; m.pad = 0;
+    m.dictSmall = (dictSize < 65536u && dictSize < cur) ? 1 : 0;        // :1627
+    cur += n;                                                           // :1633-1634
+    dictSize = n;
+    return m;
+}
+
 struct ExactArgs {
     EncodeArgs e;                // blocks, slots, headers, framedLen, accel (clamped); e.linked is not used
     const ExactBlock *meta;      // nBlocks + 1 entries (the last: the state after the call)

@@ -1,6 +1,53 @@
 // kernels/encode.inc -- the encoders: k_encode, k_encode_hc, the reference-exact chain and streams, the segment encoder of small batches.
 // A part of kernels.hip, the one device translation unit: included there, in this order, and not compiled on its own.
 // ---------------------------------------------------------------------------
+// What every encoder kernel knows about a call's blocks and slots, once.
+// ---------------------------------------------------------------------------
+// (The helpers take EncodeArgs by value, and enc_linked_dict has one return: with the kernel's argument handed on by reference,
+// or with a second return, k_encode<true, false> and k_encode_seg came out with other scalar spill counts than the written-out
+// code they replace -- docs/MEASUREMENT_LOG.md section 17.  Inlined, a copy costs nothing.  k_seg_sizes alone keeps its length
+// written out: through the by-value helper it takes 36 scalar registers, not 32.)
+// where block blk of a call lies and how long it is (a caller that needs one of the two leaves the other unread)
+struct EncBlock { uint64_t off; int n; };
+__device__ __forceinline__ EncBlock enc_block(const EncodeArgs a, int blk)
+{
+    return EncBlock{a.srcOff ? a.srcOff[blk] : (uint64_t)blk * a.blockStride, a.srcLen ? a.srcLen[blk] : a.uniformLen};
+}
+
+// linked stream: the block before is the dictionary when it lies directly in front of this one (at off), its last 64 KiB at the most
+__device__ __forceinline__ int enc_linked_dict(const EncodeArgs a, int blk, uint64_t off)
+{
+    int dictLen = 0;
+    if (a.linked && (blk > 0 || a.lookBack > 0)) {
+        const EncBlock p = enc_block(a, blk - 1);
+        if (p.n > 0 && p.off + (uint64_t)p.n == off) dictLen = min(p.n, 65536);
+    }
+    return dictLen;
+}
+
+// cbits/lz4.c:1263-1273: empty input -> single 0 token
+__device__ __forceinline__ int enc_empty_block(uint8_t *dst, bool writer)
+{
+    if (writer) dst[0] = 0;
+    return 1;
+}
+
+// the end of every block: c compressed bytes of n, the slot's header and the block's framedLen, by the one lane or thread that writes
+__device__ __forceinline__ void enc_finish_slot(const EncodeArgs a, int blk, uint8_t *slot, int c, int n, bool writer)
+{
+    if (!writer) return;
+    store_le32(slot, c);                                   // Internal/LZ4.hs:262
+    if (a.headerKind == 8) store_le32(slot + 4, n);        // Internal/LZ4.hs:261
+    a.framedLen[blk] = (c > 0) ? a.headerKind + c : 0;
+}
+
+// n bytes by a workgroup of nWaves waves, this one being `wave`: each wave copies a run of pieces of `piece` bytes
+__device__ __forceinline__ void wg_copy_pieces(uint8_t *dst, const uint8_t *src, uint32_t n, uint32_t piece, uint32_t wave, uint32_t nWaves)
+{
+    for (uint32_t at = wave * piece; at < n; at += nWaves * piece) wave_copy_bytes(dst + at, src + at, min(n - at, piece));
+}
+
+// ---------------------------------------------------------------------------
 // K2: encode
 // ---------------------------------------------------------------------------
 // MOD: table entries are positions modulo 64 Ki (encode_wave.hpp, tab_candidate): needed when positions run beyond
@@ -20,24 +67,13 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(ENC_WAVES_PE
     // positions + tags (encode_wave.hpp): 10 KiB, 16 waves per CU (the ENC_STAGE experiment's 256 bytes behind them make it 15)
     __shared__ __attribute__((aligned(16))) uint16_t table[ENC_TABLE_ENTRIES + ENC_LDS_PAD + ((PAIR && ENC_STAGE) ? 128 : 0)];
     const int blk = (int)blockIdx.x;
-    const uint64_t off = a.srcOff ? a.srcOff[blk] : (uint64_t)blk * a.blockStride;
-    const int n = a.srcLen ? a.srcLen[blk] : a.uniformLen;
+    const EncBlock b = enc_block(a, blk);
     uint8_t *slot = a.slots + (size_t)blk * a.slotStride;
-    int dictLen = 0;
-    if (MOD && a.linked && (blk > 0 || a.lookBack > 0)) {
-        // linked stream: the block before is the dictionary when it lies directly in front of this one
-        const uint64_t poff = a.srcOff ? a.srcOff[blk - 1] : (uint64_t)(blk - 1) * a.blockStride;
-        const int pn = a.srcLen ? a.srcLen[blk - 1] : a.uniformLen;
-        if (pn > 0 && poff + (uint64_t)pn == off) dictLen = min(pn, 65536);
-    }
+    const int dictLen = MOD ? enc_linked_dict(a, blk, b.off) : 0;
     int c = 0;
-    if (n >= 0 && (MOD || n <= 65536))
-        c = encode_block_wave<uint16_t, MOD, false, PAIR>(a.src + off, n, slot + a.headerKind, a.accel, table, a.stats, dictLen);
-    if (lane_id() == 0) {
-        store_le32(slot, c);                                   // Internal/LZ4.hs:262
-        if (a.headerKind == 8) store_le32(slot + 4, n);        // Internal/LZ4.hs:261
-        a.framedLen[blk] = (c > 0) ? a.headerKind + c : 0;
-    }
+    if (b.n >= 0 && (MOD || b.n <= 65536))
+        c = encode_block_wave<uint16_t, MOD, false, PAIR>(a.src + b.off, b.n, slot + a.headerKind, a.accel, table, a.stats, dictLen);
+    enc_finish_slot(a, blk, slot, c, b.n, lane_id() == 0);
 }
 
 void launch_encode(const EncodeArgs &a, bool bigBlocks, hipStream_t s)
@@ -61,35 +97,31 @@ __global__ __launch_bounds__(HC_THREADS) void k_encode_hc(EncodeArgs a, int dept
 {
     __shared__ HcLds L;
     for (int blk = (int)blockIdx.x; blk < a.nBlocks; blk += (int)gridDim.x) {
-        const uint64_t off = a.srcOff ? a.srcOff[blk] : (uint64_t)blk * a.blockStride;
-        const int n = a.srcLen ? a.srcLen[blk] : a.uniformLen;
+        const EncBlock b = enc_block(a, blk);
         uint8_t *slot = a.slots + (size_t)blk * a.slotStride;
-        int dictLen = 0;
-        if (a.linked && (blk > 0 || a.lookBack > 0)) {           // k_encode's dictionary: the block directly in front
-            const uint64_t poff = a.srcOff ? a.srcOff[blk - 1] : (uint64_t)(blk - 1) * a.blockStride;
-            const int pn = a.srcLen ? a.srcLen[blk - 1] : a.uniformLen;
-            if (pn > 0 && poff + (uint64_t)pn == off) dictLen = min(pn, 65536);
-        }
+        const int dictLen = enc_linked_dict(a, blk, b.off);
         int c = 0;
-        if (n >= 0) c = encode_block_hc(L, a.src + off, n, dictLen, slot + a.headerKind, depth);
-        if (threadIdx.x == 0) {
-            store_le32(slot, c);
-            if (a.headerKind == 8) store_le32(slot + 4, n);
-            a.framedLen[blk] = (c > 0) ? a.headerKind + c : 0;
-        }
+        if (b.n >= 0) c = encode_block_hc(L, a.src + b.off, b.n, dictLen, slot + a.headerKind, depth);
+        enc_finish_slot(a, blk, slot, c, b.n, threadIdx.x == 0);
     }
 }
 
-void launch_encode_hc(const EncodeArgs &a, int level, hipStream_t s)
+// the current device's CU count (the persistent grids' size), asked for once per device
+static int hc_cu_count()
 {
-    if (a.nBlocks <= 0) return;
     static int cus[64];
     int dev = 0;
     (void)hipGetDevice(&dev);
     int &nc = cus[dev & 63];
     if (nc <= 0 && hipDeviceGetAttribute(&nc, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) nc = 256;
+    return max(nc, 1);
+}
+
+void launch_encode_hc(const EncodeArgs &a, int level, hipStream_t s)
+{
+    if (a.nBlocks <= 0) return;
     const int depth = 1 << (min(level, 9) - 1);
-    const unsigned grid = (unsigned)min(a.nBlocks, max(nc, 1));
+    const unsigned grid = (unsigned)min(a.nBlocks, hc_cu_count());
     hipLaunchKernelGGL(k_encode_hc, dim3(grid), dim3(HC_THREADS), 0, s, a, depth);
 }
 
@@ -116,10 +148,7 @@ __global__ __launch_bounds__(HC_THREADS) void k_hcdict_build(uint8_t *image, con
     for (int r = 0; r + 4 <= keep; r += HC_THREADS) hc_insert(L, from, r, min(r + HC_THREADS, keep), keep);
     for (int i = t; i < (int)(HCDICT_TABLE_BYTES / 16); i += HC_THREADS) as_global((dev_v4 *)image)[i] = tab4[i];
     if (t == 0) as_global((uint32_t *)(image + HCDICT_KEEP_OFF))[0] = (uint32_t)keep;
-    // the bytes: each wave a run of 4 KiB pieces
-    const uint32_t piece = 4096u;
-    for (uint32_t at = (uint32_t)(t / LZ4_WAVE) * piece; at < (uint32_t)keep; at += HC_WAVES * piece)
-        wave_copy_bytes(image + HCDICT_DICT_OFF + at, from + at, min((uint32_t)keep - at, piece));
+    wg_copy_pieces(image + HCDICT_DICT_OFF, from, (uint32_t)keep, 4096u, (uint32_t)(t / LZ4_WAVE), HC_WAVES);     // the bytes
 }
 
 void launch_hcdict_build(uint8_t *image, const uint8_t *dict, int len, hipStream_t s)
@@ -139,14 +168,10 @@ __global__ __launch_bounds__(HC_THREADS) void k_encode_hc_dict(HcDictArgs x, int
     const EncodeArgs &a = x.e;
     const int keep = (int)min(ex_uni(as_global((const uint32_t *)(x.image + HCDICT_KEEP_OFF))[0]), 65536u);
     uint8_t *blockAt = x.stage + (size_t)blockIdx.x * x.stageStride + 65536;
-    {
-        const uint32_t piece = 4096u;
-        for (uint32_t at = (uint32_t)wave * piece; at < (uint32_t)keep; at += HC_WAVES * piece)
-            wave_copy_bytes(blockAt - keep + at, x.image + HCDICT_DICT_OFF + at, min((uint32_t)keep - at, piece));
-    }
+    wg_copy_pieces(blockAt - keep, x.image + HCDICT_DICT_OFF, (uint32_t)keep, 4096u, (uint32_t)wave, HC_WAVES);
     for (int blk = (int)blockIdx.x; blk < a.nBlocks; blk += (int)gridDim.x) {
-        const uint64_t off = a.srcOff ? a.srcOff[blk] : (uint64_t)blk * a.blockStride;
-        const int n = a.srcLen ? a.srcLen[blk] : a.uniformLen;
+        const EncBlock b = enc_block(a, blk);
+        const int n = b.n;
         if (n < 0 || n > a.uniformLen) {
             if (t == 0) a.framedLen[blk] = 0;
             continue;
@@ -154,31 +179,15 @@ __global__ __launch_bounds__(HC_THREADS) void k_encode_hc_dict(HcDictArgs x, int
         uint8_t *slot = a.slots + (size_t)blk * a.slotStride;
         int c;
         if (n < LZ4_MFLIMIT + 1) {                                      // all literals: no window, no table
-            c = encode_block_hc<true>(L, a.src + off, n, 0, slot + a.headerKind, depth);
+            c = encode_block_hc<true>(L, a.src + b.off, n, 0, slot + a.headerKind, depth);
         } else {
             __syncthreads();                                            // wave 0 may still be reading the block before from the window
-            const uint32_t piece = 1024u;
-            for (uint32_t at = (uint32_t)wave * piece; at < (uint32_t)n; at += HC_WAVES * piece)
-                wave_copy_bytes(blockAt + at, a.src + off + at, min((uint32_t)n - at, piece));
+            wg_copy_pieces(blockAt, a.src + b.off, (uint32_t)n, 1024u, (uint32_t)wave, HC_WAVES);
             for (int i = t; i < (int)(HCDICT_TABLE_BYTES / 16); i += HC_THREADS) ((dev_v4 *)&L)[i] = as_global((const dev_v4 *)x.image)[i];
             c = encode_block_hc<true>(L, blockAt, n, keep, slot + a.headerKind, depth);   // (its first barrier is behind both copies)
         }
-        if (t == 0) {
-            store_le32(slot, c);
-            if (a.headerKind == 8) store_le32(slot + 4, n);
-            a.framedLen[blk] = (c > 0) ? a.headerKind + c : 0;
-        }
+        enc_finish_slot(a, blk, slot, c, n, t == 0);
     }
-}
-
-static int hc_cu_count()
-{
-    static int cus[64];
-    int dev = 0;
-    (void)hipGetDevice(&dev);
-    int &nc = cus[dev & 63];
-    if (nc <= 0 && hipDeviceGetAttribute(&nc, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) nc = 256;
-    return max(nc, 1);
 }
 
 int encode_hc_dict_grid(int nBlocks) { return min(nBlocks, hc_cu_count()); }
@@ -210,7 +219,17 @@ __device__ __forceinline__ dev_v4 exact_canon4(dev_v4 v, uint32_t start, uint32_
 // the byte range of block j of a call
 __device__ __forceinline__ const uint8_t *exact_src(const EncodeArgs &e, int j)
 {
-    return e.src + (e.srcOff ? e.srcOff[j] : (uint64_t)j * e.blockStride);
+    return e.src + enc_block(e, j).off;
+}
+
+// A slot's state (kernels.h, CSTREAM_*) into the wave: the table into LDS -- the caller's barrier comes behind it -- and the
+// scalars; returns the end of the saved dictionary bytes.
+__device__ __forceinline__ const uint8_t *exact_load_slot(dev_v4 *tab4, const uint8_t *st, uint32_t &cur, uint32_t &dictSize)
+{
+    const uint32_t *scal = (const uint32_t *)(st + CSTREAM_SCALAR_OFF);
+    for (int i = lane_id(); i < EXACT_TABLE / 4; i += LZ4_WAVE) tab4[i] = as_global((const dev_v4 *)st)[i];
+    cur = ex_uni(as_global(scal)[0]); dictSize = ex_uni(as_global(scal)[1]);
+    return st + CSTREAM_DICT_OFF + ex_uni(as_global(scal)[2]);
 }
 
 // piece p = first + blockIdx.x owns blocks [p*P, min(p*P + P, n)).  Speculating (redo = 0), it starts R blocks early
@@ -251,17 +270,9 @@ __global__ __launch_bounds__(LZ4_WAVE) void k_exact_chain(ExactArgs x, int first
         uint8_t *slot = x.e.slots + (size_t)j * x.e.slotStride;
         const int cap = m.n + m.n / 255 + 16;                           // LZ4_compressBound
         int c;
-        if (m.n == 0) {                                                 // cbits/lz4.c:1263-1273
-            c = 1;
-            if (write && lane == 0) slot[x.e.headerKind] = 0;
-        } else {
-            c = exact_encode_block(tab, src, m.n, dictEnd, m, (uint32_t)x.e.accel, slot + x.e.headerKind, cap, write);
-        }
-        if (write && lane == 0) {
-            store_le32(slot, c);
-            if (x.e.headerKind == 8) store_le32(slot + 4, m.n);
-            x.e.framedLen[j] = (c > 0) ? x.e.headerKind + c : 0;
-        }
+        if (m.n == 0) c = enc_empty_block(slot + x.e.headerKind, write && lane == 0);
+        else c = exact_encode_block(tab, src, m.n, dictEnd, m, (uint32_t)x.e.accel, slot + x.e.headerKind, cap, write);
+        enc_finish_slot(x.e, j, slot, c, m.n, write && lane == 0);
         __syncthreads();
     }
     const ExactBlock next = x.meta[own1];
@@ -330,48 +341,29 @@ __global__ __launch_bounds__(LZ4_WAVE) void k_exact_streams(ExactStreamsArgs x)
     uint8_t *st = x.state + (size_t)uni(w[2]) * CSTREAM_SLOT_BYTES;
     uint8_t *dictSave = st + CSTREAM_DICT_OFF;
     uint32_t *scal = (uint32_t *)(st + CSTREAM_SCALAR_OFF);
-    for (int i = lane; i < EXACT_TABLE / 4; i += LZ4_WAVE) tab4[i] = as_global((const dev_v4 *)st)[i];
-    uint32_t cur = ex_uni(as_global(scal)[0]), dictSize = ex_uni(as_global(scal)[1]);
-    uint32_t dictBytes = ex_uni(as_global(scal)[2]);
-    const uint8_t *dictEnd = dictSave + dictBytes;
+    uint32_t cur, dictSize;
+    const uint8_t *dictEnd = exact_load_slot(tab4, st, cur, dictSize);
     const uint8_t *lastSrc = nullptr;                                   // the last good array of the call: the next dictionary
     uint32_t lastN = 0;
     __syncthreads();
     for (int j = b0; j < b1; j++) {
-        const int n = uni(x.e.srcLen ? x.e.srcLen[j] : x.e.uniformLen);
+        const int n = uni(enc_block(x.e, j).n);
         if (n < 0 || n > x.e.uniformLen) {
             for (int k = j + lane; k < b1; k += LZ4_WAVE) x.e.framedLen[k] = 0;
             break;
         }
-        ExactBlock m;
-        m.delta = 0;
-        if (cur + (uint32_t)n > 0x80000000u) {                          // LZ4_renormDictT, cbits/lz4.c:1545-1562
-            m.delta = cur - 65536u;
-            cur = 65536u;
-            if (dictSize > 65536u) dictSize = 65536u;
+        const ExactBlock m = exact_step(cur, dictSize, (uint32_t)n);
+        if (m.delta) {                                                  // LZ4_renormDictT, cbits/lz4.c:1545-1562
             for (int i = lane; i < EXACT_TABLE / 4; i += LZ4_WAVE) tab4[i] = exact_canon4(tab4[i], 0u, m.delta);
             __syncthreads();
         }
-        if (dictSize - 1u < 4u - 1u) dictSize = 0;                      // :1581-1587
-        m.start = cur; m.dictSize = dictSize; m.n = n; m.pad = 0;
-        m.dictSmall = (dictSize < 65536u && dictSize < cur) ? 1 : 0;    // :1627
         const uint8_t *src = exact_src(x.e, j);
         uint8_t *slot = x.e.slots + (size_t)j * x.e.slotStride;
         const int cap = n + n / 255 + 16;                               // LZ4_compressBound
         int c;
-        if (n == 0) {                                                   // cbits/lz4.c:1263-1273
-            c = 1;
-            if (lane == 0) slot[x.e.headerKind] = 0;
-        } else {
-            c = exact_encode_block(tab, src, n, dictEnd, m, (uint32_t)x.e.accel, slot + x.e.headerKind, cap, true);
-        }
-        if (lane == 0) {
-            store_le32(slot, c);
-            if (x.e.headerKind == 8) store_le32(slot + 4, n);
-            x.e.framedLen[j] = (c > 0) ? x.e.headerKind + c : 0;
-        }
-        cur += (uint32_t)n;                                             // :1633-1634
-        dictSize = (uint32_t)n;
+        if (n == 0) c = enc_empty_block(slot + x.e.headerKind, lane == 0);
+        else c = exact_encode_block(tab, src, n, dictEnd, m, (uint32_t)x.e.accel, slot + x.e.headerKind, cap, true);
+        enc_finish_slot(x.e, j, slot, c, n, lane == 0);
         dictEnd = src + n;
         lastSrc = src; lastN = (uint32_t)n;
         __syncthreads();
@@ -415,10 +407,7 @@ __global__ __launch_bounds__(LOAD_DICT_THREADS) void k_cstreams_load_dict(uint8_
         LZ4_GLOBAL uint32_t *scal = as_global((uint32_t *)(st + CSTREAM_SCALAR_OFF));
         scal[0] = 65536u; scal[1] = keep; scal[2] = keep; scal[3] = 0u;
     }
-    // the bytes: each wave a run of 16 KiB pieces
-    const uint32_t piece = 16384u;
-    for (uint32_t at = (tid / LZ4_WAVE) * piece; at < keep; at += (LOAD_DICT_THREADS / LZ4_WAVE) * piece)
-        wave_copy_bytes(st + CSTREAM_DICT_OFF + at, from + at, keep - at < piece ? keep - at : piece);
+    wg_copy_pieces(st + CSTREAM_DICT_OFF, from, keep, 16384u, tid / LZ4_WAVE, LOAD_DICT_THREADS / LZ4_WAVE);      // the bytes
 }
 
 void launch_cstreams_load_dict(uint8_t *slotState, const uint8_t *dict, int len, hipStream_t s)
@@ -437,44 +426,25 @@ __global__ __launch_bounds__(LZ4_WAVE) void k_exact_dict(ExactDictArgs x)
     uint32_t *tab = (uint32_t *)tab4;
     const int lane = lane_id();
     const int j = (int)blockIdx.x;
-    const int n = uni(x.e.srcLen ? x.e.srcLen[j] : x.e.uniformLen);
+    const int n = uni(enc_block(x.e, j).n);
     if (n < 0 || n > x.e.uniformLen) {
         if (lane == 0) x.e.framedLen[j] = 0;
         return;
     }
-    const uint8_t *st = x.state;
-    const uint32_t *scal = (const uint32_t *)(st + CSTREAM_SCALAR_OFF);
-    for (int i = lane; i < EXACT_TABLE / 4; i += LZ4_WAVE) tab4[i] = as_global((const dev_v4 *)st)[i];
-    uint32_t cur = ex_uni(as_global(scal)[0]), dictSize = ex_uni(as_global(scal)[1]);
-    const uint32_t dictBytes = ex_uni(as_global(scal)[2]);
-    const uint8_t *dictEnd = st + CSTREAM_DICT_OFF + dictBytes;
+    uint32_t cur, dictSize;                                             // (the copy's: what exact_step advances them to goes nowhere)
+    const uint8_t *dictEnd = exact_load_slot(tab4, x.state, cur, dictSize);
     __syncthreads();
-    ExactBlock m;
-    m.delta = 0;
-    if (cur + (uint32_t)n > 0x80000000u) {                              // LZ4_renormDictT, cbits/lz4.c:1545-1562
-        m.delta = cur - 65536u;
-        cur = 65536u;
-        if (dictSize > 65536u) dictSize = 65536u;
+    const ExactBlock m = exact_step(cur, dictSize, (uint32_t)n);
+    if (m.delta) {                                                      // LZ4_renormDictT, cbits/lz4.c:1545-1562
         for (int i = lane; i < EXACT_TABLE / 4; i += LZ4_WAVE) tab4[i] = exact_canon4(tab4[i], 0u, m.delta);
         __syncthreads();
     }
-    if (dictSize - 1u < 4u - 1u) dictSize = 0;                          // :1581-1587
-    m.start = cur; m.dictSize = dictSize; m.n = n; m.pad = 0;
-    m.dictSmall = (dictSize < 65536u && dictSize < cur) ? 1 : 0;        // :1627
     uint8_t *slot = x.e.slots + (size_t)j * x.e.slotStride;
     const int cap = n + n / 255 + 16;                                   // LZ4_compressBound
     int c;
-    if (n == 0) {                                                       // cbits/lz4.c:1263-1273
-        c = 1;
-        if (lane == 0) slot[x.e.headerKind] = 0;
-    } else {
-        c = exact_encode_block(tab, exact_src(x.e, j), n, dictEnd, m, (uint32_t)x.e.accel, slot + x.e.headerKind, cap, true);
-    }
-    if (lane == 0) {
-        store_le32(slot, c);
-        if (x.e.headerKind == 8) store_le32(slot + 4, n);
-        x.e.framedLen[j] = (c > 0) ? x.e.headerKind + c : 0;
-    }
+    if (n == 0) c = enc_empty_block(slot + x.e.headerKind, lane == 0);
+    else c = exact_encode_block(tab, exact_src(x.e, j), n, dictEnd, m, (uint32_t)x.e.accel, slot + x.e.headerKind, cap, true);
+    enc_finish_slot(x.e, j, slot, c, n, lane == 0);
 }
 
 void launch_exact_dict(const ExactDictArgs &a, hipStream_t s)
@@ -495,8 +465,8 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(ENC_WAVES_PE
 {
     __shared__ uint16_t table[ENC_TABLE_ENTRIES + ENC_LDS_PAD];
     const int blk = (int)(blockIdx.x / (unsigned)a.segs), j = (int)(blockIdx.x % (unsigned)a.segs);
-    const uint64_t off = a.e.srcOff ? a.e.srcOff[blk] : (uint64_t)blk * a.e.blockStride;
-    const int n = a.e.srcLen ? a.e.srcLen[blk] : a.e.uniformLen;
+    const EncBlock b = enc_block(a.e, blk);
+    const int n = b.n;
     uint32_t count = 0;
     if (n > 0) {
         const int s0 = min(n, j * a.segLen), s1 = (j == a.segs - 1) ? n : min(n, (j + 1) * a.segLen);
@@ -508,7 +478,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(ENC_WAVES_PE
             so.base = s0 - dictLen;
             so.last = s1 >= n;
             so.tail = n - s1;
-            (void)encode_block_wave<uint16_t, true, true>(a.e.src + off + s0, s1 - s0, nullptr, a.e.accel, table, a.e.stats, dictLen, &so);
+            (void)encode_block_wave<uint16_t, true, true>(a.e.src + b.off + s0, s1 - s0, nullptr, a.e.accel, table, a.e.stats, dictLen, &so);
             count = so.count;
         }
     }
@@ -538,6 +508,7 @@ __global__ __launch_bounds__(64) void k_seg_sizes(EncodeSegArgs a)
 {
     const int blk = (int)(blockIdx.x / (unsigned)a.segs), j = (int)(blockIdx.x % (unsigned)a.segs);
     const int lane = lane_id();
+    // (the length written out, not enc_block(a.e, blk).n: with the helper this kernel takes 36 scalar registers where the parent's took 32)
     const int n = a.e.srcLen ? a.e.srcLen[blk] : a.e.uniformLen;
     const int cnt = (n > 0) ? (int)a.segCount[(size_t)blk * a.segs + j] : 0;
     const int s0 = min(max(n, 0), j * a.segLen);
@@ -567,20 +538,15 @@ __global__ __launch_bounds__(64) void k_emit_seg(EncodeSegArgs a)
 {
     const int blk = (int)(blockIdx.x / (unsigned)a.segs), j = (int)(blockIdx.x % (unsigned)a.segs);
     const int lane = lane_id();
-    const uint64_t off = a.e.srcOff ? a.e.srcOff[blk] : (uint64_t)blk * a.e.blockStride;
-    const int n = a.e.srcLen ? a.e.srcLen[blk] : a.e.uniformLen;
+    const EncBlock b = enc_block(a.e, blk);
+    const int n = b.n;
     uint8_t *slot = a.e.slots + (size_t)blk * a.e.slotStride;
     uint8_t *op0 = slot + a.e.headerKind;
-    const uint8_t *src = a.e.src + off;
+    const uint8_t *src = a.e.src + b.off;
     const bool lastSeg = j == a.segs - 1;
     if (n <= 0) {
-        if (lastSeg && lane == 0) {
-            int c = 0;
-            if (n == 0) { op0[0] = 0; c = 1; }                 // cbits/lz4.c:1263-1273: empty input -> single 0 token
-            store_le32(slot, c);
-            if (a.e.headerKind == 8) store_le32(slot + 4, n);
-            a.e.framedLen[blk] = (c > 0) ? a.e.headerKind + c : 0;
-        }
+        const int c = (n == 0) ? enc_empty_block(op0, lastSeg && lane == 0) : 0;
+        enc_finish_slot(a.e, blk, slot, c, n, lastSeg && lane == 0);
         return;
     }
     // where this segment's bytes go: behind the segments in front of it (at most 64: one per lane)
@@ -604,18 +570,8 @@ __global__ __launch_bounds__(64) void k_emit_seg(EncodeSegArgs a)
     }
     if (!lastSeg) return;
     // ---- the block's last segment: last literals (:1204-1231), header ----
-    const uint32_t lastRun = (uint32_t)(n - prevEnd);
-    uint8_t *tok = op++;
-    if (lane == 0) *tok = (uint8_t)(min(lastRun, 15u) << 4);
-    if (lastRun >= 15) op = emit_ext_len(op, lastRun - 15);
-    wave_copy_bytes(op, src + prevEnd, lastRun);
-    op += lastRun;
-    const int c = (int)(op - op0);
-    if (lane == 0) {
-        store_le32(slot, c);                                   // Internal/LZ4.hs:262
-        if (a.e.headerKind == 8) store_le32(slot + 4, n);      // Internal/LZ4.hs:261
-        a.e.framedLen[blk] = (c > 0) ? a.e.headerKind + c : 0;
-    }
+    op = emit_last_literals(op, src + prevEnd, (uint32_t)(n - prevEnd));
+    enc_finish_slot(a.e, blk, slot, (int)(op - op0), n, lane == 0);
 }
 
 void launch_encode_seg(const EncodeSegArgs &a, hipStream_t s)
