@@ -66,15 +66,17 @@ namespace lz4dev {
                             // So 832 accepts exactly the sequences 1024 accepted; the 12 lanes behind the window repeat its last lane's request (win_lane)
 #endif
 #ifndef PAR_RING
-#define PAR_RING 5504       // LDS output staging.  With the window ParLds is 6400 bytes, the jump table an overlay on the ring's top: see ParLds below
+#define PAR_RING 5088       // LDS output staging.  ParLds is ring[PAR_RING + 32] alone, 5120 bytes: the jump table and the window are overlays on
+                            // the ring's top, see ParLds below
 #endif
 #ifndef PAR_HIST
-#define PAR_HIST 1776       // bytes of history kept in the ring across a slide: two 16-byte chunks per lane (2048 needed a third pass for one or two chunks).
-                            // With the 5504-byte ring 1776 keeps the slides at 22.5 per lzsynth block (2000: 34.9; scripts/par_ring_model.py)
+#define PAR_HIST 1500       // bytes of history kept in the ring across a slide: two 16-byte chunks per lane (2048 needed a third pass for one or two chunks).
+                            // With the 5088-byte ring 1500 keeps the slides at 21.4 per lzsynth block (1600: 24.3; scripts/par_ring_model.py)
 #endif
 #ifndef PAR_BATCH_OUT
-#define PAR_BATCH_OUT 2048  // max output bytes of one batch: the ring slides when fewer are free.  Measured with this ring at 20 waves per CU
-                            // (lzsynth / text, GB/s, all with the window stored under a lane mask, docs/MEASUREMENT_LOG.md 15): 1792: 1075-1079 / 677-678, 2048: 1072-1079 / 675-677, 2560 (more slides): 1051-1052 / 669-672
+#define PAR_BATCH_OUT 1856  // max output bytes of one batch: the ring slides when fewer are free, and the overlays (1904 bytes) must fit the
+                            // PAR_BATCH_OUT + 64 bytes this keeps free.  Measured with this ring at 28 waves per CU (lzsynth / text, GB/s,
+                            // profiles/par_28w_retune.txt): 1856: 1187-1193 / 751-752, 1920 (more slides): 1186-1191 / 748-751
 #endif
 #ifndef PAR_FAR_WIDE
 #define PAR_FAR_WIDE 0      // far matches: 1 = one 16-byte request per lane instead of two requests per length class.  Measured
@@ -95,50 +97,63 @@ namespace lz4dev {
 #define PAR_WAVES 5         // occupancy target (waves per SIMD) the register allocator is held to (<= 102 VGPRs)
 #endif
 #ifndef PAR_WAVES_MAIN
-#define PAR_WAVES_MAIN (PAR_WAVES > 6 ? PAR_WAVES : 6)    // ... of k_decode_par<STATS> and k_decode_par_redo alone (<= 80 VGPRs): 24 waves per CU, which five LDS granules allow
+#define PAR_WAVES_MAIN (PAR_WAVES > 7 ? PAR_WAVES : 7)    // ... of k_decode_par<STATS> and k_decode_par_redo alone (<= 72 VGPRs): 28 waves per CU, which four LDS granules allow
 #endif
 
 // jump[] is the successor table of step 3.  Entries are BYTE offsets into jump[] itself (2 x node
 // index), so a gather is one ds_read_u16 with no address arithmetic.  The absorbing state of a batch is the node behind
 // the last one that may hold a token (`absorb` in the speculative parse), at most 2*PAR_NODES: the entry behind the table.
 //
-// The table (and the rank records of the dependency masks, which reuse its bytes) has no LDS of its own: it is a fixed OVERLAY on the
-// last PAR_JUMP_BYTES of ring[].  Its lifetime is from a batch's speculative parse to its dependency masks, and both ends lie where
-// the ring's top is free:
-//   - every batch is parsed with the ring's content -- output positions [ringBase, op), ring bytes [A, op - ringBase + A) -- ending
-//     at or below PAR_RING - PAR_BATCH_OUT - 32: that is the condition under which the batch before did NOT slide; after a slide, and
-//     after the reload that follows a hand-over, the content ends below PAR_HIST + 31, which is lower still (static_assert below).
-//     So the ring's top PAR_BATCH_OUT + 32 bytes hold nothing at a parse, and the table is smaller than that;
-//   - the batch's first store to the ring (literals, then far matches, near matches) comes after the last read of the rank records.
-//     LDS operations of one wave execute in order, the table and the ring are one array to the compiler, and wave_fence() stands
-//     between the phases as before.
+// Neither the table (and the rank records of the dependency masks, which reuse its bytes) nor the window of compressed bytes has LDS
+// of its own: both are fixed OVERLAYS on the top of ring[], the table on its last PAR_JUMP_BYTES, the window (PAR_WIN + 32 bytes)
+// right below the table.  Both live only while the ring's top holds no output:
+//   - a batch ends -- its flush and its slide decided, the slide done -- with the ring's content (output positions [ringBase, op),
+//     ring bytes [A, op - ringBase + A)) ending at or below PAR_RING - PAR_BATCH_OUT - 32: that is the condition under which it did
+//     NOT slide; after a slide, and after the reload that follows a hand-over, the content ends below PAR_HIST + 31, which is lower
+//     still (static_assert below).  So from there to the next batch's first store to the ring, the ring's top PAR_BATCH_OUT + 64
+//     bytes hold nothing, and the two overlays together are smaller than that;
+//   - the WINDOW of batch k + 1 is stored right there: behind batch k's flush and slide (or, first batch and batch behind a
+//     hand-over, in front of the parse: `winStale`), never in front of them, where batch k's output may still cover its bytes.  It
+//     is read by the parse, by the decode of the sequences' fields (step 4) and by the literal copy (step 5), the only phase that
+//     both reads the window and writes the ring: every lane loads its literals' first and last 16 bytes from the window into
+//     registers before any lane stores to the ring, and the middle of a run longer than 32 bytes comes from the compressed
+//     stream in global memory.  The far and the near matches read no window; by then it is dead, and output may run over it;
+//   - the TABLE lives from a batch's speculative parse to its dependency masks: the batch's first store to the ring (literals, then
+//     far matches, near matches) comes after the last read of the rank records.
+//   LDS operations of one wave execute in order, the overlays and the ring are one array to the compiler, and wave_fence() stands
+//   between the phases.
 // Nothing of this depends on the template parameters of decode_block_par: the list-driven form skips the table and uses the rank
 // records only, the tolerant form's taint bits live in TolCtx, the partial form only ends the loop sooner, and with PAR_RANK 0 the
-// table's life ends with the chain.  A batch's output may then run over the dead table up to the ring's last byte.
+// table's life ends with the chain.  A batch's output may run over the dead overlays up to the ring's last byte.
 #define PAR_JUMP_BYTES (2 * (PAR_MAXNODES + 8))
 #define PAR_JUMP_OFS ((PAR_RING + 32 - PAR_JUMP_BYTES) & ~15)       // first byte of the table in ring[]
+#define PAR_WIN_BYTES (PAR_WIN + 32)                                // (the 32: field reads behind a sequence that ends at the window's end)
+#define PAR_WIN_OFS (PAR_JUMP_OFS - PAR_WIN_BYTES)                  // first byte of the window in ring[]
+#define PAR_FREE_OFS ((PAR_RING - PAR_BATCH_OUT - 32 + 15) & ~15)   // no content at or above this ring byte when a batch ends
 struct __attribute__((aligned(16))) ParLds {
-    uint8_t win[PAR_WIN + 32];
     uint8_t ring[PAR_RING + 32];
     __device__ __forceinline__ uint16_t *jump() { return (uint16_t *)&ring[PAR_JUMP_OFS]; }
+    __device__ __forceinline__ uint8_t *win() { return &ring[PAR_WIN_OFS]; }
 };
 #define PAR_END (2 * PAR_NODES)
-// The decoder is bound by the waves that carry its chains of LDS round trips, and the LDS decides how many a CU holds: the registers
-// (95) allow 5 per SIMD = 20.  gfx950 hands its 160 KiB out in granules of 1280 bytes (measured, docs/MEASUREMENT_LOG.md 15: footprints
-// of 8272 and 8192 bytes both keep SQ_WAVE_CYCLES / SQ_BUSY_CYCLES at 33.59 = 18 waves per CU -- seven granules --, 7664 bytes
-// gives 37.47 = 20; the runtime's occupancy query divides 160 KiB by the bytes and says 19 / 20 / 20).  Six granules are 7680 bytes,
-// FIVE are 6400: what 24 waves per CU (six per SIMD: k_decode_par and k_decode_par_redo, PAR_WAVES_MAIN) may use.
+// The decoder is bound by the waves that carry its chains of LDS round trips, and the LDS decides how many a CU holds.  gfx950 hands
+// its 160 KiB out in granules of 1280 bytes (measured, docs/MEASUREMENT_LOG.md 15: footprints of 8272 and 8192 bytes both keep
+// SQ_WAVE_CYCLES / SQ_BUSY_CYCLES at 33.59 = 18 waves per CU -- seven granules --, 7664 bytes gives 37.47 = 20; the runtime's occupancy
+// query divides 160 KiB by the bytes and says 19 / 20 / 20).  Five granules, 6400 bytes, allowed 24 (docs/MEASUREMENT_LOG.md 16);
+// FOUR are 5120: what 28 waves per CU (seven per SIMD: k_decode_par and k_decode_par_redo, PAR_WAVES_MAIN) may use.
 #ifndef PAR_LDS_LIMIT
-#define PAR_LDS_LIMIT 6400  // (experiments with a larger footprint raise it)
+#define PAR_LDS_LIMIT 5120  // (experiments with a larger footprint raise it)
 #endif
-static_assert(sizeof(ParLds) <= PAR_LDS_LIMIT, "ParLds above five 1280-byte LDS granules: 20 waves per CU or fewer instead of 24");
-static_assert((PAR_WIN + 32) % 16 == 0 && PAR_JUMP_OFS % 16 == 0, "the table and its 16-byte rank records are aligned");
-static_assert(PAR_JUMP_OFS + PAR_JUMP_BYTES <= PAR_RING + 32, "the table lies inside ring[]");
-static_assert(PAR_JUMP_BYTES <= PAR_BATCH_OUT + 32 && PAR_JUMP_OFS >= ((PAR_RING - PAR_BATCH_OUT - 32 + 15) & ~15),
-              "the table overlays ring bytes that hold no output when a batch is parsed (the no-slide bound)");
+static_assert(sizeof(ParLds) <= PAR_LDS_LIMIT, "ParLds above four 1280-byte LDS granules: 24 waves per CU or fewer instead of 28");
+static_assert(PAR_WIN_BYTES % 16 == 0 && PAR_JUMP_OFS % 16 == 0 && PAR_WIN_OFS % 16 == 0,
+              "the table, its 16-byte rank records and the window's 16-byte slots are aligned");
+static_assert(PAR_WIN_OFS >= 0 && PAR_WIN_OFS + PAR_WIN_BYTES <= PAR_JUMP_OFS && PAR_JUMP_OFS + PAR_JUMP_BYTES <= PAR_RING + 32,
+              "the window and the table lie inside ring[], one behind the other");
+static_assert(PAR_JUMP_BYTES + PAR_WIN_BYTES <= PAR_BATCH_OUT + 64 && PAR_WIN_OFS >= PAR_FREE_OFS && PAR_JUMP_OFS >= PAR_FREE_OFS,
+              "the overlays lie on ring bytes that hold no output from a batch's end to the next batch's first store (the no-slide bound)");
 #define PAR_WIN_LANES (PAR_WIN / 16)     // lanes whose 16 bytes make up the window
 static_assert(PAR_WIN % 16 == 0 && PAR_WIN_LANES <= LZ4_WAVE, "the window is 16 bytes per lane");
-static_assert(PAR_MAXNODES + 288 <= PAR_WIN + 32, "a plain sequence that starts at the last node, and the reads behind it, stay in win[]");
+static_assert(PAR_MAXNODES + 288 <= PAR_WIN + 32, "a plain sequence that starts at the last node, and the reads behind it, stay in the window");
 static_assert(PAR_HIST + 30 + PAR_BATCH_OUT + 32 <= PAR_RING, "a batch fits the ring right after a slide");
 
 typedef uint64_t par_u64u __attribute__((aligned(1)));
@@ -263,6 +278,17 @@ __device__ int decode_block_par(const uint8_t *src, int srcLen, uint8_t *dst, in
         }
     };
     static_assert(!PARTIAL || (!DICT && !TOL), "the partial mode has no dictionary");
+    if (DICT) {
+        // The dictionary form is called, not inlined into its kernels, and a called function gets its arguments in vector registers:
+        // the block's pointers and sizes, the same in every lane, took some fourteen of them for the whole batch loop, and the
+        // allocator spilled them -- each reload a wait for every load in flight, the prefetched window's trip to HBM included (linked
+        // text decoded a fifth slower when the window's longer life took four more registers).  Said to be uniform, they live in
+        // scalar registers.  The check to run again: no scratch_load in the batch loop of decode_block_par<false, true>
+        // (profiles/par_28w_kernel_resources.txt).
+        auto up = [](const uint8_t *p) -> const uint8_t * { return (const uint8_t *)(uintptr_t)uni64((int64_t)(uintptr_t)p); };
+        src = up(src); dst = (uint8_t *)up(dst); dict = up(dict); bufLo = up(bufLo); bufHi = up(bufHi); list = up(list);
+        srcLen = uni(srcLen); cap = uni(cap); dictLen = (uint32_t)uni((int)dictLen); listLen = uni(listLen);
+    }
     if (cap < 128 || srcLen < 64) return decode_block_seq<TOL, PARTIAL>(src, srcLen, dst, cap, dict, dictLen, bufLo, bufHi, tol);
     // external dictionary (linked streams, cbits/lz4.c:2347-2355): a match that lies ENTIRELY in the
     // previous block's output is a far match with another base pointer; one that straddles the seam
@@ -272,7 +298,7 @@ __device__ int decode_block_par(const uint8_t *src, int srcLen, uint8_t *dst, in
     const int dictLo = DICT ? -(int)min(dictLen, 65535u) : 0;
 
     // (an opaque definition, like the one behind the call below: lane_id() itself is merged with the kernel's own lane_id() behind this
-    // function, and the one value then lives across the call -- where, at six waves per SIMD, no register is left for it)
+    // function, and the one value then lives across the call -- where, at six or seven waves per SIMD, no register is left for it)
     int lane;
     asm volatile("v_mbcnt_lo_u32_b32 %0, -1, 0\n\tv_mbcnt_hi_u32_b32 %0, -1, %0" : "=v"(lane));
     const int iend = srcLen;
@@ -286,6 +312,13 @@ __device__ int decode_block_par(const uint8_t *src, int srcLen, uint8_t *dst, in
     // the same address, so no further request to memory, and the same 16 bytes stored to the same place -- instead of sitting out
     // behind a branch: a window store under a lane mask cost a wave 5 % of a text block's latency (0.330 against 0.316 ms for 160
     // blocks), the flush phase that waits for the prefetch twice its cycles (docs/MEASUREMENT_LOG.md 15).
+    // A value the compiler takes for new where it stands: what is computed from it inside the batch loop is computed there, in an
+    // instruction or two, instead of being hoisted out of the loop into a register of its own, which at seven waves per SIMD is a
+    // spill slot (the window's store address, the mask of my own lane, a zero, the flush's first ring address).  This steers the
+    // register allocator and nothing fails when a compiler decides otherwise: the check to run again is the listing of
+    // profiles/par_28w_kernel_resources.txt (scripts/kernel_resources.sh and a disassembly of k_decode_par<false>: no scratch
+    // instruction between the batch loop's head and its back edge).
+    auto fresh = [](int v) -> int { asm volatile("" : "+v"(v)); return v; };
     auto win_lane = [&]() -> int { return (PAR_WIN_LANES < LZ4_WAVE) ? min(lane, PAR_WIN_LANES - 1) : lane; };
     // 16 bytes of the compressed stream for this lane's slot of the window that starts at `base`
     auto fetch_window = [&](uintptr_t base) -> uint4 {
@@ -321,7 +354,7 @@ __device__ int decode_block_par(const uint8_t *src, int srcLen, uint8_t *dst, in
         }
         if (((AF + (uint32_t)f) & (PAR_FLUSH - 1)) == 0) {
             const int n16 = final ? (upto - f) >> 4 : ((upto - f) / PAR_FLUSH) * (PAR_FLUSH / 16);
-            for (int c = lane; c < n16; c += LZ4_WAVE) {
+            for (int c = fresh(lane); c < n16; c += LZ4_WAVE) {      // (fresh: the ring address of my first chunk is not worth a register across the loop)
                 const uint4 v = *(const uint4 *)&L.ring[f - ringBase + (int)A + 16 * c];
                 *(uint4 *)(dst + f + 16 * c) = v;
             }
@@ -357,7 +390,7 @@ __device__ int decode_block_par(const uint8_t *src, int srcLen, uint8_t *dst, in
             // the first batch or the one after a handover
             if (abase != wbase) { wbase = abase; wnext = fetch_window(abase); winStale = true; }
             if (winStale) {
-                *(uint4 *)&L.win[16 * win_lane()] = wnext;
+                *(uint4 *)&L.win()[16 * win_lane()] = wnext;
                 winStale = false;
                 wave_fence();
             }
@@ -395,12 +428,12 @@ __device__ int decode_block_par(const uint8_t *src, int srcLen, uint8_t *dst, in
                     typedef unsigned short par_h2 __attribute__((ext_vector_type(2)));
                     uint32_t w0, w1, w2;                      // my NL bytes and the one behind them, from byte 0 of w0 on
                     if (NL == 8) {
-                        const uint64_t lo = *(const uint64_t *)&L.win[8 * lane];
+                        const uint64_t lo = *(const uint64_t *)&L.win()[8 * lane];
                         w0 = (uint32_t)lo; w1 = (uint32_t)(lo >> 32);
                         w2 = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)w0, 0x130, 0xf, 0xf, false);   // next lane's first bytes
                     } else {
                         const uint32_t a = (uint32_t)(NL * lane);
-                        const uint32_t *q = (const uint32_t *)&L.win[a & ~3u];
+                        const uint32_t *q = (const uint32_t *)&L.win()[a & ~3u];
                         const uint32_t d0 = q[0], d1 = q[1], d2 = q[2], d3 = q[3];
                         const uint32_t sh = a & 3u;
                         w0 = __builtin_amdgcn_alignbyte(d1, d0, sh);
@@ -428,7 +461,7 @@ __device__ int decode_block_par(const uint8_t *src, int srcLen, uint8_t *dst, in
                     uint32_t *tw = (uint32_t *)&L.jump()[NL * lane];
 #pragma unroll
                     for (int p = 0; p < NL / 2; p++) tw[p] = P[p];
-                    if (lane == 0) L.jump()[NL * LZ4_WAVE] = (uint16_t)(2 * NL * LZ4_WAVE);   // absorbing state behind the table
+                    if (lane == 0) L.jump()[NL * LZ4_WAVE + lane] = (uint16_t)(2 * NL * LZ4_WAVE);   // absorbing state behind the table (the address from the lane id: no register held at zero for it; see `fresh`)
 #pragma unroll
                     for (int p = 0; p < NL / 2; p++) { J[2 * p] = P[p] & 0xffffu; J[2 * p + 1] = P[p] >> 16; }
                 }
@@ -513,13 +546,13 @@ __device__ int decode_block_par(const uint8_t *src, int srcLen, uint8_t *dst, in
             // ---------------- 4. decode own sequence, place it ----------------
             const bool has = c2 < absorb;
             const uint32_t cc = has ? (c2 >> 1) : 0u;
-            const uint32_t tb = lds_u32_any(L.win, cc);                          // token, next byte
+            const uint32_t tb = lds_u32_any(L.win(), cc);                        // token, next byte
             const uint32_t t = tb & 0xffu, b1 = (tb >> 8) & 0xffu;
             const bool is15 = (t >> 4) == 15u;
             const uint32_t lit = is15 ? 15u + b1 : (t >> 4);
             const uint32_t litStart = cc + 1u + (is15 ? 1u : 0u);
             const uint32_t offPos = litStart + lit;                             // <= 511 + 272: inside the window
-            const uint32_t ob = lds_u32_any(L.win, offPos);                      // offset (2 bytes), match-length byte
+            const uint32_t ob = lds_u32_any(L.win(), offPos);                    // offset (2 bytes), match-length byte
             const uint32_t off16 = ob & 0xffffu, b2 = (ob >> 16) & 0xffu;
             const bool mlx = (t & 15u) == 15u;
             const uint32_t ml = (t & 15u) + LZ4_MINMATCH + (mlx ? b2 : 0u);
@@ -589,7 +622,9 @@ __device__ int decode_block_par(const uint8_t *src, int srcLen, uint8_t *dst, in
                 }
                 wave_fence();
             }
-            const uint8_t *gsrc = (DICT && spos < 0) ? dictEnd + spos : dst + spos;
+            // (without a dictionary the source is dst + a 32-bit offset: a uniform base, no 64-bit address per lane)
+            const uint8_t *gsrcD = (DICT && spos < 0) ? dictEnd + spos : dst + spos;
+            auto gsrc_at = [&](uint32_t k) -> const uint8_t * { return DICT ? gsrcD + k : dst + (size_t)((uint32_t)spos + k); };
             const bool farMine = act && !nearSrc && !deferred;
             // chunks of 16, 8 or 4 bytes; the last chunk is re-anchored at the end so that nothing past the match is
             // written.  Far sources never overlap their destination.
@@ -607,20 +642,20 @@ __device__ int decode_block_par(const uint8_t *src, int srcLen, uint8_t *dst, in
                 // the short classes' second chunk is cut out of it in registers like the near matches' below.  The request
                 // never leaves the output buffer (cap - op >= 128), and a dictionary match shorter than 16 bytes is only
                 // taken when 16 bytes are left in the dictionary (`ok` above).
-                if (farMine) __builtin_memcpy(&f0, gsrc, 16);
-                if (farMine && fstep == 16 && ml > 16u) __builtin_memcpy(&f1, gsrc + min(16u, flast), 16);
+                if (farMine) __builtin_memcpy(&f0, gsrc_at(0u), 16);
+                if (farMine && fstep == 16 && ml > 16u) __builtin_memcpy(&f1, gsrc_at(min(16u, flast)), 16);
 #else
                 if (farMine && fstep == 16) {
-                    __builtin_memcpy(&f0, gsrc, 16);
-                    __builtin_memcpy(&f1, gsrc + min(16u, flast), 16);
+                    __builtin_memcpy(&f0, gsrc_at(0u), 16);
+                    __builtin_memcpy(&f1, gsrc_at(min(16u, flast)), 16);
                 }
                 if (farMine && fstep == 8) {
-                    fa = *(const par_u64u *)(gsrc);
-                    fb = *(const par_u64u *)(gsrc + flast);
+                    fa = *(const par_u64u *)gsrc_at(0u);
+                    fb = *(const par_u64u *)gsrc_at(flast);
                 }
                 if (farMine && fstep == 4) {
-                    fw0 = *(const par_u32u *)(gsrc);
-                    fw1 = *(const par_u32u *)(gsrc + flast);
+                    fw0 = *(const par_u32u *)gsrc_at(0u);
+                    fw1 = *(const par_u32u *)gsrc_at(flast);
                 }
 #endif
             }
@@ -676,7 +711,7 @@ __device__ int decode_block_par(const uint8_t *src, int srcLen, uint8_t *dst, in
                     const int jlo = rank(xlo), jhi = rank(xhi);
                     const uint64_t upto = (jhi >= 63) ? ~0ull : ((1ull << (jhi + 1)) - 1ull);
                     need = upto & ~((1ull << jlo) - 1ull);
-                    need &= ~(1ull << lane);
+                    need &= ~(1ull << fresh(lane));
                 }
                 wave_fence();
             }
@@ -701,29 +736,50 @@ __device__ int decode_block_par(const uint8_t *src, int srcLen, uint8_t *dst, in
             }
 #endif
             // ---------------- 5. literals: window -> ring ----------------
+            // The window is an overlay on ring bytes this batch's output may reach (ParLds), and a literal store of one lane may land on
+            // the window bytes another lane's literals come from.  So every lane's window reads -- at most 32 bytes, two registers of
+            // 16 -- are issued before the first store of any lane, the three length classes' loads side by side; the middle of a run
+            // longer than 32 bytes (rare) comes from the compressed stream in global memory.
             {
                 const uint32_t sA = litStart;
                 const uint32_t dA = (uint32_t)(outStart - ringBase) + A;
                 const uint32_t n = act ? lit : 0u;
-                if (n > 16) {                                   // rare (token nibble 15 with an extension byte)
-                    const uint32_t last = n - 16;
-                    for (uint32_t o = 0;; o += 16) {
-                        const uint32_t oo = min(o, last);
-                        *(par_v4u *)&L.ring[dA + oo] = *(const par_v4u *)&L.win[sA + oo];
-                        if (o >= last) break;
-                    }
-                } else if (n > 8) {
-                    // 9..16 literals in ONE round trip: a 16-byte chunk when its tail may fall into my own match
-                    // area (written afterwards), else two 8-byte chunks, the second re-anchored at the end
+                const uint8_t *W = L.win();
+                par_v4 r0 = {0u, 0u, 0u, 0u}, r1 = {0u, 0u, 0u, 0u};
+                if (n > 8) {
                     if (n + ml >= 16) {
-                        *(par_v4u *)&L.ring[dA] = *(const par_v4u *)&L.win[sA];
+                        // 9..16 literals as one 16-byte chunk: its tail falls into my own match area, written afterwards.  More than
+                        // 16 (rare: token nibble 15 with an extension byte): the run's first and last 16 bytes
+                        r0 = *(const par_v4u *)&W[sA];
+                        if (n > 16) r1 = *(const par_v4u *)&W[sA + n - 16];
                     } else {
-                        const uint64_t a = *(const par_u64u *)&L.win[sA], b = *(const par_u64u *)&L.win[sA + n - 8];
-                        *(par_u64u *)&L.ring[dA] = a;
-                        *(par_u64u *)&L.ring[dA + n - 8] = b;
+                        // ... else two 8-byte chunks, the second re-anchored at the end
+                        const uint64_t a = *(const par_u64u *)&W[sA], b = *(const par_u64u *)&W[sA + n - 8];
+                        r0.x = (uint32_t)a; r0.y = (uint32_t)(a >> 32); r0.z = (uint32_t)b; r0.w = (uint32_t)(b >> 32);
                     }
                 } else if (n > 0) {
-                    const uint64_t v = lds_u64_any(L.win, sA);  // aligned reads + funnel
+                    const uint64_t v = lds_u64_any(W, sA);      // aligned reads + funnel
+                    r0.x = (uint32_t)v; r0.y = (uint32_t)(v >> 32);
+                }
+                wave_fence();                                   // the window is dead from here on
+                if (n > 8) {
+                    if (n + ml >= 16) {
+                        *(par_v4u *)&L.ring[dA] = r0;
+                        if (n > 16) {
+                            *(par_v4u *)&L.ring[dA + n - 16] = r1;
+                            const uint8_t *g = src + ipW0;                      // window byte 0 in the block (uniform): bytes [16, n - 16) of my run
+                            for (uint32_t o = 16; o < n - 16; o += 16) {
+                                par_v4 v;
+                                __builtin_memcpy(&v, g + (size_t)(sA + o), 16);
+                                *(par_v4u *)&L.ring[dA + o] = v;
+                            }
+                        }
+                    } else {
+                        *(par_u64u *)&L.ring[dA] = (uint64_t)r0.x | ((uint64_t)r0.y << 32);
+                        *(par_u64u *)&L.ring[dA + n - 8] = (uint64_t)r0.z | ((uint64_t)r0.w << 32);
+                    }
+                } else if (n > 0) {
+                    const uint64_t v = (uint64_t)r0.x | ((uint64_t)r0.y << 32);
                     if (n + ml >= 8) {
                         // one 8-byte store; the bytes past the literals fall into my own match area, which is
                         // written afterwards (steps 6 and 7)
@@ -769,8 +825,8 @@ __device__ int decode_block_par(const uint8_t *src, int srcLen, uint8_t *dst, in
                     const bool on = farMine && base < ml;
                     const uint32_t o0 = min(base, flast), o1 = min(base + 16u, flast);
                     if (on) {
-                        __builtin_memcpy(&v0, gsrc + o0, 16);
-                        __builtin_memcpy(&v1, gsrc + o1, 16);
+                        __builtin_memcpy(&v0, gsrc_at(o0), 16);
+                        __builtin_memcpy(&v1, gsrc_at(o1), 16);
                     }
                     if (on) {
                         *(par_v4u *)&L.ring[mdA + o0] = v0;
@@ -919,11 +975,15 @@ __device__ int decode_block_par(const uint8_t *src, int srcLen, uint8_t *dst, in
             // ---------------- advance, 8. flush, slide ----------------
             op = opNext;
             ip = ipNext;
-            // the next window goes to LDS now (nobody reads the old one any more): this is where the wave
-            // waits for the prefetch, BEFORE the flush issues its stores, so that no later wait for a load
-            // also has to wait for those stores to be acknowledged
-            *(uint4 *)&L.win[16 * win_lane()] = wnext;
-            wave_fence();
+            // this is where the wave waits for the prefetched window, BEFORE the flush issues its stores, so that no later wait
+            // for a load also has to wait for those stores to be acknowledged.  Its store to LDS comes behind the flush and the
+            // slide: until then this batch's output may lie on the window's bytes (ParLds)
+            // (a use of the four registers as they stand, not a new definition of them: as in/out operands of their own the window
+            // left the load's register tuple, and the copies out of it stood right behind the prefetch -- a wait for HBM in mid-batch)
+            {
+                const par_v4 w = {wnext.x, wnext.y, wnext.z, wnext.w};
+                asm volatile("" : : "v"(w));
+            }
             flush(op, false);
             if (op - ringBase + (int)A + PAR_BATCH_OUT + 32 > PAR_RING) {
                 if (STATS) sc[PS_SLIDES]++;
@@ -950,6 +1010,10 @@ __device__ int decode_block_par(const uint8_t *src, int srcLen, uint8_t *dst, in
                 ringBase = newBase;
                 wave_fence();
             }
+            // the next window goes to LDS now: the ring's content ends at or below the no-slide bound (it did not slide) or below
+            // PAR_HIST + 31 (it did), and the window's bytes lie above both
+            *(uint4 *)&L.win()[16 * min(fresh(lane), PAR_WIN_LANES - 1)] = wnext;
+            wave_fence();
         }
 
         // ================= slow path: the sequential decoder =================
@@ -961,8 +1025,8 @@ __device__ int decode_block_par(const uint8_t *src, int srcLen, uint8_t *dst, in
         if (STATS && !tail) sc[PS_HANDOVERS]++;
         lap(PS_T_FLUSH);
         // The lane id and the window registers are dead from here to their new values behind the call; said so that the register
-        // allocator does not take them to live across it (the callee clobbers v0-v79: at six waves per SIMD such a value has no
-        // register at all and is spilled for the whole function).  Only the forms that run at six waves need it.
+        // allocator does not take them to live across it (the callee clobbers v0-v79: at seven waves per SIMD such a value has no
+        // register at all and is spilled for the whole function).  Only the forms that run at seven waves need it.
         if (!DICT && !TOL && !PARTIAL) asm volatile("" : "=v"(lane), "=v"(wnext.x), "=v"(wnext.y), "=v"(wnext.z), "=v"(wnext.w));
         int r = decode_seq_dispatch<TOL, PARTIAL>(st, tail ? 0 : 1, src, srcLen, dst, cap, dict, dictLen, bufLo, bufHi, tol);
         r = uni(r);                                       // (wave-uniform, like all of st: the second call then stands in uniform control flow)
