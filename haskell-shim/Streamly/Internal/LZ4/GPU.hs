@@ -58,6 +58,8 @@ module Streamly.Internal.LZ4.GPU
     , hcDictSize
     , c_compressHcDictDevice
     , compressChunksWithDictHC
+    , c_compressPagesDevice
+    , compressChunksPaged
     , DecompressStreams
     , newDecompressStreams
     , freeDecompressStreams
@@ -203,6 +205,18 @@ foreign import ccall safe "mi355lz4.h mi355lz4_compress_hcdict"
     c_compressHcDict
         :: Ptr C_Engine -> Ptr C_HcDict -> Ptr (Ptr Word8) -> Ptr Int32 -> CInt -> CInt
         -> Ptr Word8 -> CSize -> Ptr CSize -> Ptr Int32 -> Ptr Int32 -> IO CInt
+
+-- Fixed-size output pages (LZ4_compress_destSize, N inputs per call): input i is cut into at most maxPages pages of
+-- pageSize[i] compressed bytes, page (i, k) at pages + (i * maxPages + k) * pageStride behind a header of headerKind (0, 4, 8)
+-- bytes.  The device form takes device pointers and only enqueues; the host form is synchronous.
+foreign import ccall safe "mi355lz4.h mi355lz4_compress_pages_device"
+    c_compressPagesDevice
+        :: Ptr C_Engine -> Ptr Word8 -> Ptr Word64 -> Ptr Int32 -> CInt -> Ptr Int32 -> CInt -> CInt
+        -> Ptr Word8 -> CSize -> Ptr Int32 -> Ptr Int32 -> Ptr Int32 -> Ptr Int32 -> IO CInt
+foreign import ccall safe "mi355lz4.h mi355lz4_compress_pages"
+    c_compressPages
+        :: Ptr C_Engine -> Ptr (Ptr Word8) -> Ptr Int32 -> CInt -> CInt -> CInt -> CInt
+        -> Ptr Word8 -> CSize -> Ptr Int32 -> Ptr Int32 -> Ptr Int32 -> Ptr Int32 -> IO CInt
 
 -- Decoded sizes without decoding (device pointers in, device pointers out; only enqueues): what every block of a
 -- size-less framing (BlockMax64KB .. BlockMax4MB) decodes to, read off its token chain.  size[i] >= 0, or a negative
@@ -576,6 +590,40 @@ compressChunksWithDictHC (Engine eng) (HcDict hd) cfg arrs = do
         return [ Array.unsafeFreeze (MArray.Array cont dstBegin_ (dstBegin `plusPtr` (o + l)) dstMax)
                    `seq` Array.Array cont (dstBegin `plusPtr` o) (dstBegin `plusPtr` (o + l))
                | (o, l) <- zip offs flens ]
+
+-- | Fixed-size output pages: every array cut into a chain of at most @maxPages@ pages whose blocks are at most @pageSize@
+-- bytes; page k is what @LZ4_compress_destSize@ makes of the bytes behind pages 0..k-1.  Per input: its pages in order, each with
+-- the configuration's header in front of its block, and the bytes of the input they hold (less than its length when
+-- @maxPages@ was too few).  Block checksums must be off.
+compressChunksPaged
+    :: Engine -> BlockConfig -> Int -> Int -> [Array.Array Word8] -> IO [([Array.Array Word8], Int)]
+compressChunksPaged (Engine eng) cfg pageSize maxPages arrs = do
+    let n = length arrs
+        meta = metaSizeOf cfg
+        stride = meta + max pageSize 1
+        np = n * max maxPages 1
+        lens = map Array.byteLength arrs
+    (MArray.Array cont dstBegin_ dstBegin dstMax) <- MArray.newArray (max (np * stride) 1)
+    allocaArray (max n 1) $ \pSrc -> allocaArray (max n 1) $ \pLen -> allocaArray (max np 1) $ \pSrcLen ->
+      allocaArray (max np 1) $ \pCompLen -> allocaArray (max n 1) $ \pCount -> allocaArray (max n 1) $ \pCons -> do
+        let withAll [] k = k []
+            withAll (a:as) k = Array.asPtrUnsafe (Array.unsafeCast a) $ \p -> withAll as (k . (p :))
+        withAll arrs $ \ptrs -> do
+            pokeArray pSrc ptrs
+            pokeArray pLen (map fromIntegral lens)
+            rc <- c_compressPages eng pSrc pLen (fromIntegral n) (fromIntegral pageSize) (fromIntegral maxPages)
+                      (fromIntegral meta) dstBegin (fromIntegral stride) pSrcLen pCompLen pCount pCons
+            when (rc /= 0) $ error "compressChunksPaged: mi355lz4_compress_pages failed"
+        counts <- map fromIntegral <$> peekArray n pCount
+        cons <- map fromIntegral <$> peekArray n pCons
+        comp <- map fromIntegral <$> peekArray np (pCompLen :: Ptr Int32)
+        return [ ( [ let o = (i * maxPages + k) * stride
+                         l = meta + comp !! (i * maxPages + k)
+                     in Array.unsafeFreeze (MArray.Array cont dstBegin_ (dstBegin `plusPtr` (o + l)) dstMax)
+                          `seq` Array.Array cont (dstBegin `plusPtr` o) (dstBegin `plusPtr` (o + l))
+                   | k <- [0 .. c - 1] ]
+                 , used )
+               | (i, c, used) <- zip3 [0 ..] counts cons ]
 
 -- | A batch of resized blocks (header + data each), every one decoded against the dictionary (host memory, may be empty) as
 -- @LZ4_decompress_safe_usingDict@ does: one decoded array per block.

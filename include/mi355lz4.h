@@ -109,6 +109,12 @@ typedef struct mi355lz4_ctx mi355lz4_ctx;
  *   in).  _compress_hcdict_device: the slot ranges of _compress_batch_device and framedLen[0, nBlocks) (a length outside
  *   0..maxBlockLen: framedLen[i] = 0, the slot untouched); never the mi355lz4_hcdict -- it is only read -- never src, srcOff or
  *   srcLen.  _compress_hcdict is a host-buffer call as above.
+ * Fixed-size pages (_compress_pages_device): of page (i, k) -- the pageStride bytes at pages + (i*maxPages + k)*pageStride --
+ *   the bytes [0, headerKind + pageCompLen[i*maxPages + k]) and nothing behind them (stricter than the reference, whose wide
+ *   copies write past what it returns); pages that are not written -- behind nPages[i], of a skipped input -- not at all.
+ *   pageSrcLen[] and pageCompLen[] only at the entries of pages written; nPages[i]; consumed[i] unless the input is skipped
+ *   (nPages[i] = 0 is then all that is written for it).  Never src, srcOff, srcLen or pageSize.  _compress_pages writes the same
+ *   ranges of the caller's host arrays and nothing else.
  * Scratch that a call needs is the engine's own. */
 
 /* ---- engine lifecycle ------------------------------------------------ */
@@ -708,6 +714,59 @@ int mi355lz4_compress_hcdict_device(mi355lz4_ctx *ctx, const mi355lz4_hcdict *hd
 int mi355lz4_compress_hcdict(mi355lz4_ctx *ctx, const mi355lz4_hcdict *hd, const uint8_t *const *src,
                              const int32_t *srcLen, int nBlocks, int headerKind, uint8_t *framedOut, size_t cap,
                              size_t *outLen, int32_t *blockFramedLen, int32_t *status);
+
+/* ---- fixed-size output pages: LZ4_compress_destSize for batches ---------------------------------------------------------
+ * Every other compress call takes a block of a given size and writes what that needs.  This one takes a destination of a given
+ * size and puts as much of the input into it as fits: LZ4_compress_destSize (cbits/lz4.h:205-228, cbits/lz4.c:1382-1414), for
+ * callers whose storage is made of fixed-size units -- pages of a table store, sectors, fixed-size clusters, network frames --
+ * and who would otherwise compress to slots of compressBound bytes and repack, or guess block sizes and retry.  DESIGN.md 7k.
+ *
+ * Input i is src[srcOff[i], srcOff[i] + srcLen[i]) (device memory, any alignment).  Page k of input i is exactly what
+ *     LZ4_compress_destSize(src_i + pos, dst, &remaining, pageSize[i])
+ * returns and writes, where pos is the sum of what pages 0..k-1 of the input consumed and remaining = srcLen[i] - pos: the
+ * reference's bytes, its return value in pageCompLen[i*maxPages + k], and the count it stores through srcSizePtr in
+ * pageSrcLen[i*maxPages + k].  The page lies at pages + (i*maxPages + k) * pageStride (a 64-bit product).  headerKind 0 writes
+ * the raw block there; 4 or 8 writes [compLen] or [compLen][uncompLen] in front of it (little-endian, as every framed block of
+ * this engine has).  pageSize counts the block's bytes only: it is the reference's targetDstSize.  A headerKind 8 page is an
+ * ordinary block for mi355lz4_decompress_batch_device, with its address as blockOff.  maxPages == 1 is LZ4_compress_destSize
+ * for a batch.
+ * An input's chain stops when the input is consumed (an empty input is one page with the reference's one-byte empty block,
+ * cbits/lz4.c:1263-1273); when maxPages pages are written; at a page that returns 0 -- pageSize < 1: that page is not written
+ * and not counted --; and behind a page that consumes nothing while input remains -- pageSize == 1: the reference writes a
+ * zero token and consumes 0; that page is written and counted.  nPages[i] counts the pages written, consumed[i] the bytes
+ * they hold; an unfinished input shows as consumed[i] < srcLen[i].
+ * The table type is chosen per page from what remains, as cbits/lz4.c:1390 does (byU16 with the 4-byte hash under 65547 bytes,
+ * byU32 with the 5-byte hash from there on), so a long input changes type in the middle of its chain; a page whose pageSize
+ * reaches LZ4_compressBound(remaining) is LZ4_compress_fast_extState's at acceleration 1 (cbits/lz4.c:1387) and takes all that
+ * remains.  Every page starts from a fresh table.
+ * Progress, what a caller sizes maxPages by: a page of pageSize T >= 1 that leaves input behind consumes at least
+ * (T - 1) - (T + 240) / 256 bytes (integer division) -- the all-literals page; tests/test_pages_gpu.py holds every page to it.
+ * Asynchronous: the call only enqueues on the engine's stream and reads neither srcLen nor pageSize on the host.  An input
+ * whose length lies outside 0..MI355LZ4_MAX_INPUT_SIZE, or whose headerKind + pageSize[i] exceeds pageStride, gets
+ * nPages[i] = 0 and nothing else written for it; the other inputs are unaffected.
+ * Switches: the compression level, accel, the linked switch, segments and the engine's exact stream play no part.  Block
+ * checksums must be off: a checksummed page format is out of scope.
+ * MI355LZ4_E_ARG: a null ctx, nInputs < 0, maxPages < 1, a headerKind other than 0 / 4 / 8, pageStride < headerKind + 1, block
+ * checksums switched on, with nInputs > 0 a null src, srcOff, srcLen, pageSize, pages or result array.  nInputs == 0 is
+ * MI355LZ4_OK.  What the call may write: see the top of this header.
+ * One wavefront walks one input's chain (k_exact_pages; 16 KiB of LDS for either table, zeroed once per page), and a chain is
+ * serial: a call's parallelism is its number of inputs.  Measured once (scripts/pages_rate.py, profiles/pages_rate.json; medians of
+ * 5 event-timed calls): 16384 text records of 4 KiB into 1 KiB pages in 6.1 ms (65536 pages, 87 % full, ratio 1.14;
+ * mi355lz4_compress_batch_device on the same records: 0.39 ms, ratio 1.33); 2560 records of 64 KiB into 4 KiB pages in 23.9 ms
+ * (30720 pages, 93 % full, ratio 1.43; the batch call: 1.60 ms, ratio 1.82).  No rate is part of the contract. */
+int mi355lz4_compress_pages_device(mi355lz4_ctx *ctx, const uint8_t *src, const uint64_t *srcOff, const int32_t *srcLen,
+                                   int nInputs, const int32_t *pageSize, int maxPages, int headerKind,
+                                   uint8_t *pages, size_t pageStride,
+                                   int32_t *pageSrcLen, int32_t *pageCompLen, int32_t *nPages, int32_t *consumed);
+/* Host-buffer form, synchronous: input i is src[i][0, srcLen[i]) in host memory, one pageSize for all; pages, pageSrcLen,
+ * pageCompLen, nPages and consumed are host arrays laid out as above.  One group, as mi355lz4_decompress_partial is: one upload,
+ * the device call, then the four arrays and every written page's bytes [0, headerKind + compLen) copied back.  The lengths and
+ * pageSize are checked on the host: a length outside 0..MI355LZ4_MAX_INPUT_SIZE, a null src[i] with srcLen[i] > 0, pageSize < 1
+ * or pageStride < headerKind + pageSize is MI355LZ4_E_ARG, besides the device call's, and nothing is enqueued or written.  The
+ * multi-device handle and the legacy LZ4_* face have no such call. */
+int mi355lz4_compress_pages(mi355lz4_ctx *ctx, const uint8_t *const *src, const int32_t *srcLen, int nInputs, int pageSize,
+                            int maxPages, int headerKind, uint8_t *pages, size_t pageStride,
+                            int32_t *pageSrcLen, int32_t *pageCompLen, int32_t *nPages, int32_t *consumed);
 
 /* ---- many linked decode streams, continued across calls ---------------------------------------------------------------
  * The decode-side counterpart of mi355lz4_cstreams, and the device-resident form of the reference's one LZ4_streamDecode_t

@@ -123,6 +123,13 @@ public:
     // the hash-chain encoder with the dictionary of `hd` (HcDict::load) in front of it -- lz4 -9 -D dict; decompressWithDict
     // reads the result with the dictionary's bytes.  The object is only read.  Throws Error (level 0 included).
     std::vector<Array> compressWithDictHC(const BlockConfig &cfg, const std::vector<Array> &arrays, const class HcDict &hd);
+    // Fixed-size output pages (mi355lz4_compress_pages): every array cut into a chain of at most maxPages pages whose blocks are
+    // at most pageSize bytes -- page k is what LZ4_compress_destSize makes of the bytes behind pages 0..k-1.  Per input the pages in
+    // order, each with cfg's header in front of its block (an ordinary block for decompressChunks when the header carries both
+    // sizes), and in `consumed` (when given) the bytes of every input its pages hold: less than its length when maxPages was too
+    // few.  Throws Error (block checksums in cfg included: pages carry no trailer).
+    std::vector<std::vector<Array>> compressPages(const BlockConfig &cfg, const std::vector<Array> &arrays, int pageSize, int maxPages,
+                                                  std::vector<int32_t> *consumed = nullptr);
 private:
     mi355lz4_ctx *ctx_ = nullptr;
     size_t batch_;

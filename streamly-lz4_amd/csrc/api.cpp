@@ -1043,6 +1043,29 @@ extern "C" int mi355lz4_compress_dict_device(mi355lz4_ctx *c, const mi355lz4_cst
 }
 
 // ---------------------------------------------------------------------------
+// Fixed-size output pages: LZ4_compress_destSize for a batch, and chains of such pages per input (k_exact_pages:
+// one wave per input, every page from a zeroed table).  Enqueues only; srcLen and pageSize stay unread on the host.
+// ---------------------------------------------------------------------------
+extern "C" int mi355lz4_compress_pages_device(mi355lz4_ctx *c, const uint8_t *src, const uint64_t *srcOff, const int32_t *srcLen,
+                                              int nInputs, const int32_t *pageSize, int maxPages, int headerKind,
+                                              uint8_t *pages, size_t pageStride, int32_t *pageSrcLen, int32_t *pageCompLen,
+                                              int32_t *nPages, int32_t *consumed)
+{
+    if (!c) return fail(MI355LZ4_E_ARG, "null ctx");
+    if (nInputs < 0 || maxPages < 1 || (headerKind != 0 && headerKind != 4 && headerKind != 8) || pageStride < (size_t)headerKind + 1)
+        return fail(MI355LZ4_E_ARG, "compress_pages_device: bad arguments");
+    if (c->blockChecksum) return fail(MI355LZ4_E_ARG, "compress_pages_device: block checksums are on; pages carry no trailer");
+    if (nInputs == 0) return MI355LZ4_OK;
+    if (!src || !srcOff || !srcLen || !pageSize || !pages || !pageSrcLen || !pageCompLen || !nPages || !consumed)
+        return fail(MI355LZ4_E_ARG, "compress_pages_device: null pointer");
+    HIP_TRY(hipSetDevice(c->device));
+    const PagesArgs x{src, srcOff, srcLen, nInputs, pageSize, maxPages, headerKind, pages, pageStride, pageSrcLen, pageCompLen,
+                      nPages, consumed};
+    launch_exact_pages(x, c->stream);
+    return check_launch("exact pages launch");
+}
+
+// ---------------------------------------------------------------------------
 // High-compression levels against a shared dictionary.  A mi355lz4_hcdict is the device image of encode_hc.hpp's
 // tables after the dictionary's inserts (k_hcdict_build, once per load); mi355lz4_compress_hcdict_device reloads it for every
 // block (k_encode_hc_dict) and only reads it, so one object serves any number of calls.  Both only enqueue.

@@ -828,6 +828,72 @@ extern "C" int mi355lz4_decompress_dict(mi355lz4_ctx *c, const uint8_t *framedIn
     return host_tail(c, "decompress_dict", h, out, cap, outLen, blockLen, nBlocksOut);
 }
 
+// Host-buffer form of mi355lz4_compress_pages_device: inputs in host memory, one pageSize for all.  One group, synchronous, as the
+// partial form: the inputs go up packed back to back, the device call fills engine-owned pages, the four arrays come back, and of
+// every page that was written its bytes [0, headerKind + compLen) -- the rest of the caller's `pages` stays as it was.
+extern "C" int mi355lz4_compress_pages(mi355lz4_ctx *c, const uint8_t *const *src, const int32_t *srcLen, int nInputs, int pageSize,
+                                       int maxPages, int headerKind, uint8_t *pages, size_t pageStride, int32_t *pageSrcLen,
+                                       int32_t *pageCompLen, int32_t *nPages, int32_t *consumed)
+{
+    if (!c) return fail(MI355LZ4_E_ARG, "null ctx");
+    if (nInputs < 0 || maxPages < 1 || pageSize < 1 || (headerKind != 0 && headerKind != 4 && headerKind != 8) ||
+        pageStride < (size_t)headerKind + (size_t)pageSize)
+        return fail(MI355LZ4_E_ARG, "compress_pages: bad arguments");
+    if (c->blockChecksum) return fail(MI355LZ4_E_ARG, "compress_pages: block checksums are on; pages carry no trailer");
+    if (nInputs == 0) return MI355LZ4_OK;
+    if (!src || !srcLen || !pages || !pageSrcLen || !pageCompLen || !nPages || !consumed)
+        return fail(MI355LZ4_E_ARG, "compress_pages: null pointer");
+    const size_t n = (size_t)nInputs, np = n * (size_t)maxPages;
+    std::vector<uint64_t> off(n);
+    uint64_t total = 0;
+    for (size_t i = 0; i < n; i++) {
+        if (srcLen[i] < 0 || srcLen[i] > MI355LZ4_MAX_INPUT_SIZE || (srcLen[i] > 0 && !src[i]))
+            return fail(MI355LZ4_E_ARG, "compress_pages: input %zu: bad length or null pointer", i);
+        off[i] = total;
+        total += (uint64_t)srcLen[i];
+    }
+    HIP_TRY(hipSetDevice(c->device));
+    int r;
+    // c->res: pageSrcLen[np], pageCompLen[np], nPages[n], consumed[n]; c->lenB: pageSize[n]
+    if ((r = dev_reserve(c->in, (size_t)total + 16)) || (r = dev_reserve(c->offA, n * 8)) || (r = dev_reserve(c->lenA, n * 4)) ||
+        (r = dev_reserve(c->lenB, n * 4)) || (r = dev_reserve(c->res, (2 * np + 2 * n) * 4)) || (r = dev_reserve(c->out, np * pageStride + 16)))
+        return r;
+    // the inputs packed into the pinned staging buffer, then one copy
+    if ((r = pin_reserve(c->pinIn, (size_t)total + 16))) return r;
+    std::vector<CopyTask> tasks;
+    for (size_t i = 0; i < n; i++)
+        if (srcLen[i] > 0) tasks.push_back(CopyTask{(uint8_t *)c->pinIn.p + off[i], src[i], (size_t)srcLen[i]});
+    pool_run(tasks);
+    if (total) HIP_TRY(hipMemcpyAsync(c->in.p, c->pinIn.p, (size_t)total, hipMemcpyHostToDevice, c->stream));
+    const std::vector<int32_t> ps(n, pageSize);
+    HIP_TRY(hipMemcpyAsync(c->offA.p, off.data(), n * 8, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipMemcpyAsync(c->lenA.p, srcLen, n * 4, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipMemcpyAsync(c->lenB.p, ps.data(), n * 4, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));          // (the vectors are pageable memory)
+    int32_t *dSrcLen = (int32_t *)c->res.p, *dCompLen = dSrcLen + np, *dPages = dCompLen + np, *dCons = dPages + n;
+    r = mi355lz4_compress_pages_device(c, (const uint8_t *)c->in.p, (const uint64_t *)c->offA.p, (const int32_t *)c->lenA.p, nInputs,
+                                       (const int32_t *)c->lenB.p, maxPages, headerKind, (uint8_t *)c->out.p, pageStride, dSrcLen,
+                                       dCompLen, dPages, dCons);
+    if (r) return r;
+    std::vector<int32_t> back(2 * np + 2 * n);
+    HIP_TRY(hipMemcpyAsync(back.data(), c->res.p, back.size() * 4, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    const int32_t *hSrcLen = back.data(), *hCompLen = hSrcLen + np, *hPages = hCompLen + np, *hCons = hPages + n;
+    for (size_t i = 0; i < n; i++) {
+        nPages[i] = hPages[i];
+        consumed[i] = hCons[i];
+        for (size_t k = 0; k < (size_t)hPages[i]; k++) {
+            const size_t at = i * (size_t)maxPages + k;
+            pageSrcLen[at] = hSrcLen[at];
+            pageCompLen[at] = hCompLen[at];
+            HIP_TRY(hipMemcpyAsync(pages + at * pageStride, (const uint8_t *)c->out.p + at * pageStride,
+                                   (size_t)headerKind + (size_t)hCompLen[at], hipMemcpyDeviceToHost, c->stream));
+        }
+    }
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    return MI355LZ4_OK;
+}
+
 // the size pass over blocks in host memory: H2D, mi355lz4_decoded_size_device, sizes back; synchronous
 extern "C" int mi355lz4_decoded_sizes_host(mi355lz4_ctx *c, const uint8_t *framed, size_t len, const uint64_t *blockOff,
                                            int nBlocks, int headerKind, int maxUncomp, int32_t *size)

@@ -288,6 +288,38 @@ std::vector<Array> Engine::compressWithDictHC(const BlockConfig &cfg, const std:
     return out;
 }
 
+// host arrays -> device, one chain of pages per array, the written pages back (mi355lz4_compress_pages)
+std::vector<std::vector<Array>> Engine::compressPages(const BlockConfig &cfg, const std::vector<Array> &arrays, int pageSize, int maxPages,
+                                                      std::vector<int32_t> *consumed)
+{
+    if (cfg.blockChecksum) throw Error("compressPages: pages carry no block checksum");
+    if (pageSize < 1 || maxPages < 1) throw Error("compressPages: pageSize and maxPages must be at least 1");
+    const int meta = metaSize(cfg);
+    const size_t n = arrays.size(), stride = (size_t)meta + (size_t)pageSize;
+    std::vector<const uint8_t *> ptrs;
+    std::vector<int32_t> lens;
+    for (const Array &a : arrays) {
+        if (a.size() > (size_t)MI355LZ4_MAX_INPUT_SIZE) throw Error("compressPages: array of " + std::to_string(a.size()) + " bytes");
+        ptrs.push_back(a.data());
+        lens.push_back((int32_t)a.size());
+    }
+    ptrs.push_back(nullptr);
+    lens.push_back(0);
+    std::vector<uint8_t> pages(n * (size_t)maxPages * stride + 1);
+    std::vector<int32_t> srcLen(n * (size_t)maxPages + 1), compLen(n * (size_t)maxPages + 1), count(n + 1), cons(n + 1);
+    if (mi355lz4_compress_pages(ctx_, ptrs.data(), lens.data(), (int)n, pageSize, maxPages, meta, pages.data(), stride, srcLen.data(),
+                                compLen.data(), count.data(), cons.data()) != MI355LZ4_OK)
+        throw Error(std::string("compressPages: ") + mi355lz4_last_error());
+    std::vector<std::vector<Array>> out(n);
+    for (size_t i = 0; i < n; i++)
+        for (size_t k = 0; k < (size_t)count[i]; k++) {
+            const size_t at = i * (size_t)maxPages + k;
+            out[i].emplace_back(pages.begin() + (long)(at * stride), pages.begin() + (long)(at * stride + (size_t)meta + (size_t)compLen[at]));
+        }
+    if (consumed) consumed->assign(cons.begin(), cons.begin() + (long)n);
+    return out;
+}
+
 std::vector<Array> Engine::decompressWithDict(const BlockConfig &cfg, const std::vector<Array> &blocks, const Array &dict)
 {
     const int meta = metaSize(cfg);

@@ -189,6 +189,25 @@ struct ExactDictArgs {
     const uint8_t *state;        // the one slot, CSTREAM_SLOT_BYTES
 };
 
+// fixed-size output pages (mi355lz4_compress_pages_device; encode_fill.hpp; kernels/encode.inc, k_exact_pages): input i is cut into
+// pages of pageSize[i] compressed bytes, page (i, k) at pages + (i * maxPages + k) * pageStride, each LZ4_compress_destSize's
+struct PagesArgs {
+    const uint8_t *src;
+    const uint64_t *srcOff;
+    const int32_t *srcLen;
+    int nInputs;
+    const int32_t *pageSize;     // per input: the reference's targetDstSize (the block's bytes, without the header)
+    int maxPages;
+    int headerKind;              // 0, 4 or 8
+    uint8_t *pages;
+    size_t pageStride;
+    int32_t *pageSrcLen;         // [nInputs * maxPages]: what the page consumed
+    int32_t *pageCompLen;        // [nInputs * maxPages]: the reference's return value
+    int32_t *nPages;             // [nInputs]
+    int32_t *consumed;           // [nInputs]
+};
+#define PAGES_MAX_INPUT 0x7E000000   // LZ4_MAX_INPUT_SIZE (MI355LZ4_MAX_INPUT_SIZE in include/mi355lz4.h)
+
 // a prepared high-compression dictionary (mi355lz4_hcdict; kernels/encode.inc, k_hcdict_build): the image of encode_hc.hpp's chain[]
 // and head[] after the inserts of the kept bytes' positions [0, keep - 3), the count, and the object's own copy of the bytes
 #define HCDICT_CHAIN_BYTES ((size_t)65536 * 2)
@@ -278,6 +297,8 @@ void launch_exact_streams(const ExactStreamsArgs &a, int nWork, hipStream_t s);
 void launch_cstreams_load_dict(uint8_t *slotState, const uint8_t *dict, int len, hipStream_t s);
 // one wave per block, each from a copy of the slot's state; nothing is stored back
 void launch_exact_dict(const ExactDictArgs &a, hipStream_t s);
+// fixed-size output pages: one wave per input walks its chain of pages, each from a zeroed table
+void launch_exact_pages(const PagesArgs &a, hipStream_t s);
 // a prepared high-compression dictionary: one workgroup builds the image (HCDICT_IMAGE_BYTES) from the last min(len, 65536) bytes of dict
 void launch_hcdict_build(uint8_t *image, const uint8_t *dict, int len, hipStream_t s);
 // compression levels 1..12 against that image: a persistent grid of encode_hc_dict_grid(nBlocks) workgroups, one window of a.stage each

@@ -11,6 +11,7 @@
 //                          k_encode_hc: hash chains + lazy parse                             encode_hc.hpp
 //                          k_exact_chain / _verify / _finish, k_exact_streams: the reference's bytes   encode_exact.hpp
 //                          k_encode_seg, k_seg_sizes, k_emit_seg: small batches, waves per block       encode_wave.hpp
+//                          k_exact_pages: fixed-size output pages, LZ4_compress_destSize      encode_fill.hpp
 //   compact.inc            k_scan_u64, k_copy_slots, k_interleave, k_header_sizes, k_decoded_size       size_walk.hpp
 //   checksum.inc           k_xxh32_ranges / _append / _verify: four lanes per range          checksum.hpp
 //   generate.inc           k_generate: synthetic inputs (bench and test support)
@@ -43,6 +44,7 @@
 #include "encode_exact.hpp"
 #include "checksum.hpp"
 #include "size_walk.hpp"
+#include "encode_fill.hpp"
 
 using namespace lz4dev;
 

@@ -582,3 +582,61 @@ void launch_encode_seg(const EncodeSegArgs &a, hipStream_t s)
     hipLaunchKernelGGL(k_seg_sizes, grid, dim3(64), 0, s, a);
     hipLaunchKernelGGL(k_emit_seg, grid, dim3(64), 0, s, a);
 }
+
+// ---------------------------------------------------------------------------
+// K2, fixed-size output pages (mi355lz4_compress_pages_device, encode_fill.hpp, DESIGN.md 7k).  One wavefront per input walks the
+// input's chain: page k is what LZ4_compress_destSize (cbits/lz4.c:1382-1414) makes of the bytes behind what pages 0..k-1 took.
+// Every page starts from a zeroed table, as the reference's LZ4_initStream gives it; the table's type and the mode are chosen per
+// page from what remains (:1387-1394), so a long input's chain changes from byU32 to byU16 on its way.  The chain stops when the
+// input is consumed, at maxPages pages, at a page that returns 0 (pageSize < 1: it is not written and not counted) and behind a
+// page that took nothing (pageSize 1: a zero token).  A chain is serial: a call's parallelism is its number of inputs.
+// A length outside 0..LZ4_MAX_INPUT_SIZE or a page that does not fit its stride: nPages[i] = 0 and nothing else.
+// ---------------------------------------------------------------------------
+__global__ __launch_bounds__(LZ4_WAVE) void k_exact_pages(PagesArgs x)
+{
+    __shared__ dev_v4 tab4[EXACT_TABLE / 4];
+    uint32_t *tab = (uint32_t *)tab4;
+    const int lane = lane_id();
+    const int i = (int)blockIdx.x;
+    const int n = uni(x.srcLen[i]);
+    const int T = uni(x.pageSize[i]);
+    if (n < 0 || n > PAGES_MAX_INPUT || (T > 0 && (uint64_t)x.headerKind + (uint64_t)T > (uint64_t)x.pageStride)) {
+        if (lane == 0) x.nPages[i] = 0;
+        return;
+    }
+    const uint8_t *src = x.src + uni64((int64_t)x.srcOff[i]);
+    const uint64_t first = (uint64_t)i * (uint64_t)x.maxPages;
+    int pos = 0, k = 0;
+    while (k < x.maxPages && T >= 1) {                                  // T < 1: the page returns 0, cbits/lz4.c:902, :1264
+        const int rem = n - pos;
+        uint8_t *page = x.pages + (first + (uint64_t)k) * (uint64_t)x.pageStride;
+        uint8_t *dst = page + x.headerKind;
+        int c, used = 0;
+        if (rem == 0) {
+            c = enc_empty_block(dst, lane == 0);                        // :1263-1273 (only an empty input gets here)
+        } else {
+            for (int j = lane; j < EXACT_TABLE / 4; j += LZ4_WAVE) tab4[j] = dev_v4{0u, 0u, 0u, 0u};
+            __syncthreads();
+            const bool fill = T < rem + rem / 255 + 16;                 // :1387, LZ4_compressBound
+            if (rem < FILL_64K_LIMIT) c = fill_encode_page<byU16>(tab, src + pos, rem, dst, T, fill, used);    // :1390
+            else c = fill_encode_page<byU32>(tab, src + pos, rem, dst, T, fill, used);
+            __syncthreads();
+        }
+        if (lane == 0) {
+            if (x.headerKind >= 4) store_le32(page, c);
+            if (x.headerKind == 8) store_le32(page + 4, used);
+            x.pageCompLen[first + (uint64_t)k] = c;
+            x.pageSrcLen[first + (uint64_t)k] = used;
+        }
+        k++;
+        pos += used;
+        if (pos >= n || used == 0) break;
+    }
+    if (lane == 0) { x.nPages[i] = k; x.consumed[i] = pos; }
+}
+
+void launch_exact_pages(const PagesArgs &a, hipStream_t s)
+{
+    if (a.nInputs <= 0) return;
+    hipLaunchKernelGGL(k_exact_pages, dim3((unsigned)a.nInputs), dim3(LZ4_WAVE), 0, s, a);
+}

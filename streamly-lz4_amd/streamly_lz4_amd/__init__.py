@@ -172,6 +172,10 @@ def _load():
         vp)
     sig("mi355lz4_compress_hcdict", C.c_int, vp, vp, C.POINTER(_u8p), _i32p, C.c_int, C.c_int, _u8p, C.c_size_t,
         C.POINTER(C.c_size_t), _i32p, _i32p)
+    # fixed-size output pages
+    sig("mi355lz4_compress_pages_device", C.c_int, vp, vp, vp, vp, C.c_int, vp, C.c_int, C.c_int, vp, C.c_size_t, vp, vp, vp, vp)
+    sig("mi355lz4_compress_pages", C.c_int, vp, C.POINTER(_u8p), _i32p, C.c_int, C.c_int, C.c_int, C.c_int, _u8p, C.c_size_t,
+        _i32p, _i32p, _i32p, _i32p)
     # legacy face (include/lz4.h)
     sig("LZ4_createStream", vp)
     sig("LZ4_freeStream", C.c_int, vp)
@@ -233,6 +237,7 @@ DECLARED_SYMBOLS = [
     "mi355lz4_compress_dict", "mi355lz4_decompress_dict",
     "mi355lz4_hcdict_create", "mi355lz4_hcdict_destroy", "mi355lz4_hcdict_load", "mi355lz4_hcdict_size",
     "mi355lz4_compress_hcdict_device", "mi355lz4_compress_hcdict",
+    "mi355lz4_compress_pages_device", "mi355lz4_compress_pages",
     "LZ4_createStream", "LZ4_freeStream", "LZ4_createStreamDecode", "LZ4_freeStreamDecode", "LZ4_compressBound",
     "LZ4_compress_fast_continue", "LZ4_decompress_safe_continue",
 ]
@@ -959,6 +964,48 @@ class Engine:
                                             int(header_kind), out.ctypes.data_as(_u8p), cap, C.byref(out_len),
                                             flen.ctypes.data_as(_i32p), status.ctypes.data_as(_i32p)), "compress_hcdict")
         return out[: out_len.value].tobytes(), flen[:n].tolist()
+
+    def compress_pages_device(self, src, src_off, src_len, n_inputs, page_size, max_pages, pages, page_stride, page_src_len,
+                              page_comp_len, n_pages, consumed, header_kind=8):
+        """Fixed-size output pages: input i (src[src_off[i] : src_off[i] + src_len[i]], device tensors) is cut into a chain of
+        at most max_pages pages, page k being what LZ4_compress_destSize makes of the bytes behind pages 0..k-1 with
+        page_size[i] as its targetDstSize: the reference's bytes at pages + (i * max_pages + k) * page_stride behind a header of
+        header_kind (0, 4, 8) bytes, its return value in page_comp_len and its consumed count in page_src_len; n_pages[i] pages,
+        consumed[i] bytes.  Only enqueues (include/mi355lz4.h, mi355lz4_compress_pages_device)."""
+        self._follow_torch()
+        _check(lib.mi355lz4_compress_pages_device(
+            self.ctx, _dptr(src), _dptr(src_off), _dptr(src_len), int(n_inputs), _dptr(page_size), int(max_pages),
+            int(header_kind), _dptr(pages), int(page_stride), _dptr(page_src_len), _dptr(page_comp_len), _dptr(n_pages),
+            _dptr(consumed)), "compress_pages_device")
+
+    def compress_pages(self, inputs, page_size, max_pages, header_kind=8, page_stride=None):
+        """inputs: list of bytes-like, every one cut into pages of page_size compressed bytes.  Returns a list, per input, of
+        (pages, consumed): pages a list of (page bytes with its header, bytes of the input it holds); mi355lz4_compress_pages."""
+        n = len(inputs)
+        if page_stride is None:
+            page_stride = int(header_kind) + max(int(page_size), 1)
+        arrs = [np.frombuffer(bytes(b), dtype=np.uint8) if not isinstance(b, np.ndarray) else b for b in inputs]
+        ptrs = (_u8p * max(n, 1))(*[a.ctypes.data_as(_u8p) for a in arrs])
+        lens = np.array([a.size for a in arrs] + [0], dtype=np.int32)
+        np_ = max(n * max(int(max_pages), 0), 1)
+        pages = np.zeros(np_ * int(page_stride), dtype=np.uint8)
+        psrc = np.zeros(np_, dtype=np.int32)
+        pcomp = np.zeros(np_, dtype=np.int32)
+        cnt = np.zeros(max(n, 1), dtype=np.int32)
+        cons = np.zeros(max(n, 1), dtype=np.int32)
+        _check(lib.mi355lz4_compress_pages(self.ctx, ptrs, lens.ctypes.data_as(_i32p), n, int(page_size), int(max_pages),
+                                           int(header_kind), pages.ctypes.data_as(_u8p), int(page_stride),
+                                           psrc.ctypes.data_as(_i32p), pcomp.ctypes.data_as(_i32p), cnt.ctypes.data_as(_i32p),
+                                           cons.ctypes.data_as(_i32p)), "compress_pages")
+        res = []
+        for i in range(n):
+            pl = []
+            for k in range(int(cnt[i])):
+                at = i * int(max_pages) + k
+                lo = at * int(page_stride)
+                pl.append((pages[lo: lo + int(header_kind) + int(pcomp[at])].tobytes(), int(psrc[at])))
+            res.append((pl, int(cons[i])))
+        return res
 
     def decompress_dict(self, framed, dict_bytes, header_kind=8, fixed_uncomp=0, max_blocks=None, raise_on_block_error=True,
                         cap=None):
