@@ -58,6 +58,8 @@ module Streamly.Internal.LZ4.GPU
     , hcDictSize
     , c_compressHcDictDevice
     , compressChunksWithDictHC
+    , c_compressFastDictDevice
+    , compressChunksWithDictFast
     , c_compressPagesDevice
     , compressChunksPaged
     , DecompressStreams
@@ -204,6 +206,15 @@ foreign import ccall safe "mi355lz4.h mi355lz4_compress_hcdict_device"
 foreign import ccall safe "mi355lz4.h mi355lz4_compress_hcdict"
     c_compressHcDict
         :: Ptr C_Engine -> Ptr C_HcDict -> Ptr (Ptr Word8) -> Ptr Int32 -> CInt -> CInt
+        -> Ptr Word8 -> CSize -> Ptr CSize -> Ptr Int32 -> Ptr Int32 -> IO CInt
+-- ... and level 0 against the same object, by the wave encoder (accel in front of headerKind)
+foreign import ccall safe "mi355lz4.h mi355lz4_compress_fastdict_device"
+    c_compressFastDictDevice
+        :: Ptr C_Engine -> Ptr C_HcDict -> Ptr Word8 -> Ptr Word64 -> Ptr Int32 -> Word64 -> CInt -> CInt
+        -> CInt -> CInt -> Ptr Word8 -> CSize -> Ptr Int32 -> IO CInt
+foreign import ccall safe "mi355lz4.h mi355lz4_compress_fastdict"
+    c_compressFastDict
+        :: Ptr C_Engine -> Ptr C_HcDict -> Ptr (Ptr Word8) -> Ptr Int32 -> CInt -> CInt -> CInt
         -> Ptr Word8 -> CSize -> Ptr CSize -> Ptr Int32 -> Ptr Int32 -> IO CInt
 
 -- Fixed-size output pages (LZ4_compress_destSize, N inputs per call): input i is cut into at most maxPages pages of
@@ -585,6 +596,32 @@ compressChunksWithDictHC (Engine eng) (HcDict hd) cfg arrs = do
             rc <- c_compressHcDict eng hd pSrc pLen (fromIntegral n) (fromIntegral meta) dstBegin (fromIntegral cap)
                       pOutLen pFlen pStatus
             when (rc /= 0) $ error "compressChunksWithDictHC: mi355lz4_compress_hcdict failed"
+        flens <- map fromIntegral <$> peekArray n pFlen
+        let offs = scanl (+) 0 flens
+        return [ Array.unsafeFreeze (MArray.Array cont dstBegin_ (dstBegin `plusPtr` (o + l)) dstMax)
+                   `seq` Array.Array cont (dstBegin `plusPtr` o) (dstBegin `plusPtr` (o + l))
+               | (o, l) <- zip offs flens ]
+
+-- | The same at level 0 by the wave encoder, with acceleration @accel@: the engine's own fast parse against the prepared
+-- dictionary, not the reference's bytes ('compressChunksWithDict' has those).  'decompressChunksWithDict' reads the result.
+compressChunksWithDictFast
+    :: Engine -> HcDict -> Int -> BlockConfig -> [Array.Array Word8] -> IO [Array.Array Word8]
+compressChunksWithDictFast (Engine eng) (HcDict hd) accel cfg arrs = do
+    let n = length arrs
+        meta = metaSizeOf cfg
+        lens = map Array.byteLength arrs
+        cap = sum (map (\l -> fromIntegral (c_bound (fromIntegral l)) + meta + 4) lens)
+    (MArray.Array cont dstBegin_ dstBegin dstMax) <- MArray.newArray (max cap 1)
+    allocaArray n $ \pSrc -> allocaArray n $ \pLen -> allocaArray n $ \pFlen ->
+      allocaArray n $ \pStatus -> alloca $ \pOutLen -> do
+        let withAll [] k = k []
+            withAll (a:as) k = Array.asPtrUnsafe (Array.unsafeCast a) $ \p -> withAll as (k . (p :))
+        withAll arrs $ \ptrs -> do
+            pokeArray pSrc ptrs
+            pokeArray pLen (map fromIntegral lens)
+            rc <- c_compressFastDict eng hd pSrc pLen (fromIntegral n) (fromIntegral accel) (fromIntegral meta) dstBegin (fromIntegral cap)
+                      pOutLen pFlen pStatus
+            when (rc /= 0) $ error "compressChunksWithDictFast: mi355lz4_compress_fastdict failed"
         flens <- map fromIntegral <$> peekArray n pFlen
         let offs = scanl (+) 0 flens
         return [ Array.unsafeFreeze (MArray.Array cont dstBegin_ (dstBegin `plusPtr` (o + l)) dstMax)

@@ -108,7 +108,8 @@ typedef struct mi355lz4_ctx mi355lz4_ctx;
  * High-compression dictionary batches: _hcdict_load writes the object it is handed and nothing else (never the dictionary handed
  *   in).  _compress_hcdict_device: the slot ranges of _compress_batch_device and framedLen[0, nBlocks) (a length outside
  *   0..maxBlockLen: framedLen[i] = 0, the slot untouched); never the mi355lz4_hcdict -- it is only read -- never src, srcOff or
- *   srcLen.  _compress_hcdict is a host-buffer call as above.
+ *   srcLen.  _compress_hcdict is a host-buffer call as above.  _compress_fastdict_device and _compress_fastdict: the same
+ *   ranges and the same rules, at level 0.
  * Fixed-size pages (_compress_pages_device): of page (i, k) -- the pageStride bytes at pages + (i*maxPages + k)*pageStride --
  *   the bytes [0, headerKind + pageCompLen[i*maxPages + k]) and nothing behind them (stricter than the reference, whose wide
  *   copies write past what it returns); pages that are not written -- behind nPages[i], of a skipped input -- not at all.
@@ -703,7 +704,8 @@ int mi355lz4_hcdict_size(const mi355lz4_hcdict *hd);
  * (scripts/hcdict_rate.py, profiles/hcdict_rate.json; medians of 5 event-timed calls): 16384 text records of 4 KiB against a
  * 64 KiB dictionary at level 9 in 28.3 ms, ratio 2.44 (level 3: 12.4 ms, 2.16; mi355lz4_compress_dict_device: 6.9 ms, 1.90;
  * level 9 without a dictionary: 8.6 ms, 1.37); 2560 records of 64 KiB at level 9 in 69.8 ms, ratio 2.44 (level 0 with the
- * dictionary: 28.8 ms, 1.88; level 9 without: 52.3 ms, 2.12).  _hcdict_load of 64 KiB: 0.8 ms. */
+ * dictionary: 28.8 ms, 1.88; level 9 without: 52.3 ms, 2.12).  _hcdict_load of 64 KiB: 0.8 ms (0.91 ms since it also builds the wave
+ * encoder's image, profiles/fastdict_rate.json). */
 int mi355lz4_compress_hcdict_device(mi355lz4_ctx *ctx, const mi355lz4_hcdict *hd, const uint8_t *src,
                                     const uint64_t *srcOff, const int32_t *srcLen, uint64_t blockStride, int maxBlockLen,
                                     int nBlocks, int headerKind, uint8_t *slots, size_t slotStride, int32_t *framedLen);
@@ -714,6 +716,50 @@ int mi355lz4_compress_hcdict_device(mi355lz4_ctx *ctx, const mi355lz4_hcdict *hd
 int mi355lz4_compress_hcdict(mi355lz4_ctx *ctx, const mi355lz4_hcdict *hd, const uint8_t *const *src,
                              const int32_t *srcLen, int nBlocks, int headerKind, uint8_t *framedOut, size_t cap,
                              size_t *outLen, int32_t *blockFramedLen, int32_t *status);
+
+/* ---- level 0 against the same prepared dictionary, fast: the wave encoder -------------------------------------------------------
+ * mi355lz4_compress_dict_device gives the reference's bytes and pays for them with the reference's serial parse.  These calls
+ * give the engine's own level-0 parse instead -- the encoder of mi355lz4_compress_batch_device, 64 positions a step -- against the
+ * dictionary of a mi355lz4_hcdict: one object, loaded once, serves every level.  Beside the image above the object holds the wave
+ * encoder's table (4096 16-bit positions and their tags, 10240 bytes, and a 16-byte header) as it is after the dictionary's seed
+ * steps; _hcdict_load builds it with a second kernel of one wavefront, and the encoder reloads it for every block instead of
+ * seeding up to 64 KiB again.  DESIGN.md 7l.
+ *
+ * Block arguments, outputs, headers (4 / 8), trailers (mi355lz4_set_block_checksum), the slotStride bound
+ * (mi355lz4_slot_stride_ex), framedLen, the error codes and the 4 MiB limit on maxBlockLen are those of
+ * mi355lz4_compress_hcdict_device; accel is added, clamped to 1..65537 as in mi355lz4_compress_batch_device.
+ * Bytes: with keep = min(len, 65536) the bytes the last _hcdict_load kept, block i is exactly what this engine writes for it as
+ * the second block of the two-block linked call [D[-keep:], B_i] -- mi355lz4_compress_batch_device at level 0 with
+ * mi355lz4_set_linked_compress(1), the same accel, and max(keep, maxBlockLen) as its maxBlockLen (so the encoder's form for blocks
+ * above 64 KiB is taken exactly when this call's maxBlockLen is above 65536).  With keep == 0, block i is the block of the one-block
+ * call with the linked switch on.  Blocks under 13 bytes are literals only; an empty block is the single zero token.  The output
+ * is a plain LZ4 block: mi355lz4_decompress_dict_device and LZ4_decompress_safe_usingDict read it with the dictionary.  These are
+ * not liblz4's bytes.
+ * Asynchronous: the call only enqueues on the engine's stream and does not read srcLen on the host.  A length outside
+ * 0..maxBlockLen gives framedLen[i] = 0 and an untouched slot range; the other blocks are unaffected.
+ * Switches: the level must be 0 (levels 1..12 against a dictionary are mi355lz4_compress_hcdict_device).  Segments, the linked switch
+ * and the engine's exact stream play no part, on or off.
+ * A persistent grid of single wavefronts, 16 a CU as mi355lz4_compress_batch_device has them; every wave stages the dictionary and
+ * its current block contiguously in engine-owned scratch (65536 + maxBlockLen bytes a wave, at most 1 GiB a call: the grid shrinks
+ * to fit).  MI355LZ4_FASTDICT_WAVES (read per call; tests and measurements): n > 0 waves per CU, n < 0 a grid of -n waves in all.
+ * MI355LZ4_E_ARG: a null ctx or hd, `hd` created on another device, a compression level other than 0, nBlocks < 0, a headerKind
+ * other than 4 / 8, maxBlockLen outside 0..4 MiB, with nBlocks > 0 a null src (maxBlockLen > 0), slots or framedLen.
+ * MI355LZ4_E_CAPACITY: slotStride below the bound.  nBlocks == 0 is MI355LZ4_OK.
+ * Measured once (scripts/fastdict_rate.py, profiles/fastdict_rate.json; one session, medians of 5 event-timed calls): 16384 text
+ * records of 4 KiB against a 64 KiB dictionary in 0.60 ms, ratio 1.92 (mi355lz4_compress_dict_device: 6.84 ms, 1.90, its fastest call
+ * 6.82 ms; mi355lz4_compress_hcdict_device level 3: 12.18 ms, 2.16; mi355lz4_compress_batch_device without a dictionary: 0.39 ms, 1.33);
+ * 2560 records of 64 KiB in 1.47 ms, ratio 1.93 (28.53 ms, 1.88; level 3: 29.58 ms, 2.16; without a dictionary: 1.62 ms, 1.82).  4 / 8 / 16
+ * waves a CU: 1.42 / 0.82 / 0.61 ms on the 4 KiB shape, so 16 is the default.  _hcdict_load of 64 KiB, both images: 0.91 ms. */
+int mi355lz4_compress_fastdict_device(mi355lz4_ctx *ctx, const mi355lz4_hcdict *hd, const uint8_t *src,
+                                      const uint64_t *srcOff, const int32_t *srcLen, uint64_t blockStride, int maxBlockLen,
+                                      int nBlocks, int accel, int headerKind, uint8_t *slots, size_t slotStride,
+                                      int32_t *framedLen);
+/* Host-buffer form, synchronous: as mi355lz4_compress_hcdict (the same group pipeline) with the device call above per group.  The
+ * lengths are checked on the host: one outside 0..4 MiB is MI355LZ4_E_ARG and nothing is enqueued or written.  The multi-device
+ * handle and the legacy LZ4_* face have no such call. */
+int mi355lz4_compress_fastdict(mi355lz4_ctx *ctx, const mi355lz4_hcdict *hd, const uint8_t *const *src,
+                               const int32_t *srcLen, int nBlocks, int accel, int headerKind, uint8_t *framedOut, size_t cap,
+                               size_t *outLen, int32_t *blockFramedLen, int32_t *status);
 
 /* ---- fixed-size output pages: LZ4_compress_destSize for batches ---------------------------------------------------------
  * Every other compress call takes a block of a given size and writes what that needs.  This one takes a destination of a given

@@ -123,6 +123,9 @@ public:
     // the hash-chain encoder with the dictionary of `hd` (HcDict::load) in front of it -- lz4 -9 -D dict; decompressWithDict
     // reads the result with the dictionary's bytes.  The object is only read.  Throws Error (level 0 included).
     std::vector<Array> compressWithDictHC(const BlockConfig &cfg, const std::vector<Array> &arrays, const class HcDict &hd);
+    // The same batch at level 0 by the wave encoder (mi355lz4_compress_fastdict): the engine's own fast parse against the
+    // dictionary of `hd`, not the reference's bytes (compressWithDict has those); decompressWithDict reads the result.
+    std::vector<Array> compressWithDictFast(const BlockConfig &cfg, const std::vector<Array> &arrays, const class HcDict &hd, int accel = 1);
     // Fixed-size output pages (mi355lz4_compress_pages): every array cut into a chain of at most maxPages pages whose blocks are
     // at most pageSize bytes -- page k is what LZ4_compress_destSize makes of the bytes behind pages 0..k-1.  Per input the pages in
     // order, each with cfg's header in front of its block (an ordinary block for decompressChunks when the header carries both

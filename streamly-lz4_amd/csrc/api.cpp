@@ -1079,12 +1079,16 @@ extern "C" int mi355lz4_hcdict_create(mi355lz4_ctx *c, mi355lz4_hcdict **out)
     if (!hd) return fail(MI355LZ4_E_ARG, "out of host memory");
     hd->device = c->device;
     hipError_t e = hipMalloc((void **)&hd->image, HCDICT_IMAGE_BYTES);
-    // an empty dictionary until the first load: empty heads, keep 0 (no kernel: two memsets, and the wait slots_create has)
+    if (e == hipSuccess) e = hipMalloc((void **)&hd->fastImage, FASTDICT_IMAGE_BYTES);
+    // an empty dictionary until the first load: empty heads, keep 0 (no kernel: two memsets, and the wait slots_create has);
+    // the wave encoder's image of it is an empty table, keep 0
     if (e == hipSuccess) e = hipMemsetAsync(hd->image, 0, HCDICT_IMAGE_BYTES, c->stream);
     if (e == hipSuccess) e = hipMemsetAsync(hd->image + HCDICT_CHAIN_BYTES, 0xFF, (size_t)HCDICT_HEAD_ENTRIES * 4, c->stream);
+    if (e == hipSuccess) e = hipMemsetAsync(hd->fastImage, 0, FASTDICT_IMAGE_BYTES, c->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
     if (e != hipSuccess) {
         if (hd->image) hipFree(hd->image);
+        if (hd->fastImage) hipFree(hd->fastImage);
         delete hd;
         return fail(MI355LZ4_E_HIP, "hcdict_create: %zu bytes: %s", (size_t)HCDICT_IMAGE_BYTES, hipGetErrorString(e));
     }
@@ -1098,6 +1102,7 @@ extern "C" void mi355lz4_hcdict_destroy(mi355lz4_hcdict *hd)
     hipSetDevice(hd->device);
     hipDeviceSynchronize();                 // calls that still read the image
     if (hd->image) hipFree(hd->image);
+    if (hd->fastImage) hipFree(hd->fastImage);
     delete hd;
 }
 
@@ -1117,6 +1122,8 @@ extern "C" int mi355lz4_hcdict_load(mi355lz4_ctx *c, mi355lz4_hcdict *hd, const 
     HIP_TRY(hipSetDevice(c->device));
     launch_hcdict_build(hd->image, dictDevice, len, c->stream);
     if (int r = check_launch("hcdict build launch")) return r;
+    launch_hcdict_build_fast(hd->fastImage, dictDevice, len, c->stream);
+    if (int r = check_launch("hcdict fast build launch")) return r;
     hd->keep = len < 65536 ? len : 65536;
     return MI355LZ4_OK;
 }
@@ -1130,6 +1137,16 @@ extern "C" int mi355lz4_debug_hcdict_image(mi355lz4_hcdict *hd, uint8_t *bytes)
     HIP_TRY(hipSetDevice(hd->device));
     HIP_TRY(hipDeviceSynchronize());
     HIP_TRY(hipMemcpy(bytes, hd->image, HCDICT_IMAGE_BYTES, hipMemcpyDeviceToHost));
+    return MI355LZ4_OK;
+}
+
+// ... and the wave encoder's image (FASTDICT_IMAGE_BYTES: the table, then keep and the first seam step) the same way
+extern "C" int mi355lz4_debug_hcdict_fast_image(mi355lz4_hcdict *hd, uint8_t *bytes)
+{
+    if (!hd || !bytes) return fail(MI355LZ4_E_ARG, "debug_hcdict_fast_image: bad arguments");
+    HIP_TRY(hipSetDevice(hd->device));
+    HIP_TRY(hipDeviceSynchronize());
+    HIP_TRY(hipMemcpy(bytes, hd->fastImage, FASTDICT_IMAGE_BYTES, hipMemcpyDeviceToHost));
     return MI355LZ4_OK;
 }
 
@@ -1171,6 +1188,38 @@ extern "C" int mi355lz4_compress_hcdict_device(mi355lz4_ctx *c, const mi355lz4_h
     if (int r = hcdict_stage(c, (size_t)encode_hc_dict_grid(nBlocks) * x.stageStride, &x.stage)) return r;
     launch_encode_hc_dict(x, c->compLevel, c->stream);
     return encode_launched(c, x.e, "hc dict launch");
+}
+
+// Level 0 against the same object: the wave encoder, block i as the second block of the linked call [kept bytes,
+// block i].  k_encode_fastdict reloads the table image per block and stages the block behind its own copy of the dictionary; the
+// windows come from the pool above (a call's windows are its stream's).  Enqueues only.  MI355LZ4_FASTDICT_WAVES is read per call.
+extern "C" int mi355lz4_compress_fastdict_device(mi355lz4_ctx *c, const mi355lz4_hcdict *hd, const uint8_t *src,
+                                                 const uint64_t *srcOff, const int32_t *srcLen, uint64_t blockStride,
+                                                 int maxBlockLen, int nBlocks, int accel, int headerKind, uint8_t *slots,
+                                                 size_t slotStride, int32_t *framedLen)
+{
+    if (int r = hcdict_same_device(c, hd, "compress_fastdict_device")) return r;
+    if (c->compLevel != 0)
+        return fail(MI355LZ4_E_ARG, "compress_fastdict_device: compression level %d; levels 1..12 against a dictionary are mi355lz4_compress_hcdict_device",
+                    c->compLevel);
+    if (int r = batch_shape_check("compress_fastdict_device", nBlocks, headerKind, maxBlockLen, INT_MAX)) return r;
+    if (maxBlockLen > HCDICT_MAX_BLOCK)
+        return fail(MI355LZ4_E_ARG, "compress_fastdict_device: maxBlockLen %d above the %d bytes a dictionary batch takes", maxBlockLen, HCDICT_MAX_BLOCK);
+    if (nBlocks == 0) return MI355LZ4_OK;
+    if (int r = batch_buffers_check(c, "compress_fastdict_device", src, maxBlockLen, headerKind, slots, slotStride, framedLen)) return r;
+    HIP_TRY(hipSetDevice(c->device));
+    FastDictArgs x;
+    x.e = make_encode_args(src, srcOff, srcLen, blockStride, maxBlockLen, nBlocks, accel, headerKind, slots, slotStride, framedLen);
+    x.e.stats = c->stats;
+    x.image = hd->image;
+    x.fast = hd->fastImage;
+    // the dictionary, the block, and what the encoder may ask for around a position near the block's end (the 56 bytes behind a
+    // candidate, the 8 in front of the next one), in whole 256-byte lines
+    x.stageStride = 65536 + (((size_t)maxBlockLen + 64 + 255) & ~(size_t)255);
+    const int grid = encode_fastdict_grid(nBlocks, env_int("MI355LZ4_FASTDICT_WAVES", 0), x.stageStride);
+    if (int r = hcdict_stage(c, (size_t)grid * x.stageStride, &x.stage)) return r;
+    launch_encode_fastdict(x, grid, c->stream);
+    return encode_launched(c, x.e, "fast dict launch");
 }
 
 extern "C" int mi355lz4_compact_device(mi355lz4_ctx *c, const uint8_t *slots, size_t slotStride,

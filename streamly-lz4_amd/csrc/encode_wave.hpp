@@ -409,7 +409,10 @@ __device__ __forceinline__ bool tab_candidate(TabT e, int myPos, uint32_t &cand)
 // segment (a match may END at the seam; only the block's last segment keeps the last 5 bytes as literals) and leaves
 // its trailing literals to the segment behind it: the return value is the position (block-relative) where they start.
 // PAIR: the dense windows go two to a step (see "Two windows per step" below); false: one window per step.
-template <typename TabT, bool DICT = false, bool SEG = false, bool PAIR = false>
+// PREP (k_encode_fastdict, a mi355lz4_hcdict): the caller has made the table -- zeroed it, or loaded the image of the
+// dictionary's seed steps and replayed the seam's (kernels/encode.inc, enc_seed_step) -- so neither the zeroing nor the
+// seed loop runs here.  Everything behind them is the same code.
+template <typename TabT, bool DICT = false, bool SEG = false, bool PAIR = false, bool PREP = false>
 __device__ int encode_block_wave(const uint8_t *src, int n, uint8_t *dst, int accel, TabT *table,
                                  unsigned long long *stats = nullptr, int dictLen = 0, SegOut *seg = nullptr)
 {
@@ -480,14 +483,14 @@ __device__ int encode_block_wave(const uint8_t *src, int n, uint8_t *dst, int ac
     }
 
     // zero the table (positions are block-relative; 0 is a real position, as in the reference)
-    {
+    if (!PREP) {
         uint32_t *t32 = (uint32_t *)table;
         const int nd = (int)(ENC_TAB_N * sizeof(TabT) / 4) + ENC_TAB_N / 8;    // positions, then the tags
         for (int i = lane; i < nd; i += LZ4_WAVE) t32[i] = 0;
     }
     __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
     ENC_TAG_DECL
-    if (DICT && blockLen >= 13) {
+    if (DICT && !PREP && blockLen >= 13) {
         // seed: positions of the dictionary, in order (a later position replaces an earlier one); the
         // 8 bytes behind a position near its end run into the block itself
         // (the LDS executes one wave's stores in order: no fence between them)

@@ -97,11 +97,13 @@ struct mi355lz4_ctx {
 };
 
 // A prepared high-compression dictionary (api.cpp, "high-compression levels against a shared dictionary"): the device image
-// k_hcdict_build wrote (kernels.h, HCDICT_*).  keep is what the last _load enqueued; the kernels read the image's own count.
+// k_hcdict_build wrote (kernels.h, HCDICT_*), and beside it the wave encoder's table image from k_hcdict_build_fast (FASTDICT_*)
+// for level 0.  keep is what the last _load enqueued; the kernels read the images' own counts.
 struct mi355lz4_hcdict {
     int device = 0;
     int keep = 0;
     uint8_t *image = nullptr;
+    uint8_t *fastImage = nullptr;
 };
 
 namespace mi355lz4_detail {

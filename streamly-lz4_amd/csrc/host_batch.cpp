@@ -179,7 +179,8 @@ static inline int32_t host_le32(const uint8_t *p)
 template <class Set> struct HostStreams { Set *set; const int32_t *first, *slot; int n; };
 // the loaded slot of a mi355lz4_compress_dict call: every block of every group from a copy of it (null: no dictionary)
 // (hc: a mi355lz4_compress_hcdict call instead, every block against that prepared dictionary at the engine's level)
-struct HostDict { const mi355lz4_cstreams *set; int slot; const mi355lz4_hcdict *hc = nullptr; };
+// (fast: a mi355lz4_compress_fastdict call, the same object at level 0 with the call's accel)
+struct HostDict { const mi355lz4_cstreams *set; int slot; const mi355lz4_hcdict *hc = nullptr; bool fast = false; };
 
 static int compress_host(mi355lz4_ctx *c, const uint8_t *const *src, const int32_t *srcLen,
                          int nBlocks, int accel, int headerKind, uint8_t *framedOut, size_t cap,
@@ -280,6 +281,10 @@ static int compress_host(mi355lz4_ctx *c, const uint8_t *const *src, const int32
                                                   0, maxLen, b1 - b0, accel, headerKind, (uint8_t *)c->slots.p + (size_t)b0 * stride,
                                                   stride, (int32_t *)c->lenB.p + b0);
             r = streams_enqueue(c, hs->set, a, b0, b1, hs->first, hs->slot, hs->n);
+        } else if (hd && hd->hc && hd->fast) {     // (the same, by the wave encoder)
+            r = mi355lz4_compress_fastdict_device(c, hd->hc, (const uint8_t *)c->in.p, (const uint64_t *)c->offA.p + b0,
+                                                  (const int32_t *)c->lenA.p + b0, 0, maxLen, b1 - b0, accel, headerKind,
+                                                  (uint8_t *)c->slots.p + (size_t)b0 * stride, stride, (int32_t *)c->lenB.p + b0);
         } else if (hd && hd->hc) {                 // (independent blocks, the image only read, a staging scratch per compute stream)
             r = mi355lz4_compress_hcdict_device(c, hd->hc, (const uint8_t *)c->in.p, (const uint64_t *)c->offA.p + b0,
                                                 (const int32_t *)c->lenA.p + b0, 0, maxLen, b1 - b0, headerKind,
@@ -403,6 +408,26 @@ extern "C" int mi355lz4_compress_hcdict(mi355lz4_ctx *c, const mi355lz4_hcdict *
     HostDict hd{nullptr, 0};
     hd.hc = hcd;
     return compress_host(c, src, srcLen, nBlocks, 0, headerKind, framedOut, cap, outLen, blockFramedLen, status, nullptr, &hd);
+}
+
+// Host-buffer form of mi355lz4_compress_fastdict_device: the same pipeline, every group's blocks against the prepared dictionary by
+// the wave encoder (level 0).  The lengths are the caller's host array: checked before anything is queued.
+extern "C" int mi355lz4_compress_fastdict(mi355lz4_ctx *c, const mi355lz4_hcdict *hcd, const uint8_t *const *src,
+                                          const int32_t *srcLen, int nBlocks, int accel, int headerKind, uint8_t *framedOut,
+                                          size_t cap, size_t *outLen, int32_t *blockFramedLen, int32_t *status)
+{
+    if (outLen) *outLen = 0;
+    if (!c || !hcd) return fail(MI355LZ4_E_ARG, "compress_fastdict: null argument");
+    if (engine_compression_level(c) != 0)
+        return fail(MI355LZ4_E_ARG, "compress_fastdict: compression level %d; levels 1..12 against a dictionary are mi355lz4_compress_hcdict",
+                    engine_compression_level(c));
+    for (int i = 0; srcLen && i < nBlocks; i++)
+        if (srcLen[i] < 0 || srcLen[i] > HCDICT_MAX_BLOCK)
+            return fail(MI355LZ4_E_ARG, "compress_fastdict: block %d length %d outside 0..%d", i, srcLen[i], HCDICT_MAX_BLOCK);
+    HostDict hd{nullptr, 0};
+    hd.hc = hcd;
+    hd.fast = true;
+    return compress_host(c, src, srcLen, nBlocks, accel, headerKind, framedOut, cap, outLen, blockFramedLen, status, nullptr, &hd);
 }
 
 extern "C" int mi355lz4_index_host_ex(const uint8_t *framedIn, size_t inLen, int headerKind, int fixedUncomp,

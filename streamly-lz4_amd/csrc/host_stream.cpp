@@ -288,6 +288,38 @@ std::vector<Array> Engine::compressWithDictHC(const BlockConfig &cfg, const std:
     return out;
 }
 
+std::vector<Array> Engine::compressWithDictFast(const BlockConfig &cfg, const std::vector<Array> &arrays, const HcDict &hd, int accel)
+{
+    const int meta = metaSize(cfg);
+    std::vector<const uint8_t *> ptrs;
+    std::vector<int32_t> lens;
+    size_t cap = 16;
+    for (const Array &a : arrays) {
+        if (a.size() > (size_t)maxBlockSize(cfg))                               // compressChunk, Internal/LZ4.hs:237-241
+            throw Error("compressChunk: Source array length " + std::to_string(a.size()) +
+                        " exceeds the maximum block size of " + std::to_string(maxBlockSize(cfg)));
+        ptrs.push_back(a.data());
+        lens.push_back((int32_t)a.size());
+        cap += (size_t)mi355lz4_compress_bound((int)a.size()) + (size_t)meta + 4;
+    }
+    const int n = (int)lens.size();
+    std::vector<uint8_t> framed(cap);
+    std::vector<int32_t> flen((size_t)n + 1), status((size_t)n + 1);
+    ptrs.push_back(nullptr);
+    lens.push_back(0);
+    size_t outLen = 0;
+    if (mi355lz4_compress_fastdict(ctx_, hd.handle(), ptrs.data(), lens.data(), n, accel, meta, framed.data(), cap, &outLen, flen.data(),
+                                 status.data()) != MI355LZ4_OK)
+        throw Error(std::string("compressWithDictFast: ") + mi355lz4_last_error());
+    std::vector<Array> out;
+    size_t pos = 0;
+    for (int k = 0; k < n; k++) {
+        out.emplace_back(framed.begin() + (long)pos, framed.begin() + (long)(pos + (size_t)flen[(size_t)k]));
+        pos += (size_t)flen[(size_t)k];
+    }
+    return out;
+}
+
 // host arrays -> device, one chain of pages per array, the written pages back (mi355lz4_compress_pages)
 std::vector<std::vector<Array>> Engine::compressPages(const BlockConfig &cfg, const std::vector<Array> &arrays, int pageSize, int maxPages,
                                                       std::vector<int32_t> *consumed)

@@ -228,6 +228,25 @@ struct HcDictArgs {
     size_t stageStride;          // >= 65536 + e.uniformLen
 };
 
+// the wave encoder's side of a mi355lz4_hcdict (kernels/encode.inc, k_hcdict_build_fast): a second allocation beside
+// the image above -- encode_wave.hpp's table (positions, then tags) after the seed steps of the kept bytes that hold no seam
+// position, then uint32 {keep, first position of the first seam step, -, -}.  The kept bytes themselves are the image's.
+#define FASTDICT_TABLE_BYTES 10240                                // ENC_TABLE_ENTRIES 16-bit units (checked where the kernels are compiled)
+#define FASTDICT_KEEP_OFF    FASTDICT_TABLE_BYTES
+#define FASTDICT_IMAGE_BYTES (FASTDICT_KEEP_OFF + 16)
+#define FASTDICT_SCRATCH_MAX ((size_t)1 << 30)                    // the staging windows of one call (the bound of SEG_SCRATCH_MAX)
+#define FASTDICT_WAVES_DEFAULT 16                                 // waves per CU of k_encode_fastdict's grid (MI355LZ4_FASTDICT_WAVES)
+
+// a level-0 batch against one prepared dictionary (mi355lz4_compress_fastdict_device; kernels/encode.inc, k_encode_fastdict): wave w
+// lays the kept bytes and, behind them, one block at a time into its window at stage + w * stageStride, as HcDictArgs' workgroups do
+struct FastDictArgs {
+    EncodeArgs e;                // blocks, slots, headers, framedLen, accel (clamped); e.uniformLen bounds every length; linked, lookBack unused
+    const uint8_t *image;        // HCDICT_IMAGE_BYTES, read-only: the kept bytes
+    const uint8_t *fast;         // FASTDICT_IMAGE_BYTES, read-only
+    uint8_t *stage;              // one window per wave of the grid
+    size_t stageStride;          // >= 65536 + e.uniformLen + 64
+};
+
 // many linked decode streams continued across calls (mi355lz4_decompress_dstreams_device; kernels/linked_walk.inc, k_decode_dstreams).
 // One slot of a mi355lz4_dstreams is the device form of LZ4_streamDecode_t for separately allocated blocks: the last
 // min(r, 65536) bytes of the stream's last block that decoded to r > 0 bytes, at the slot's start, and that count.
@@ -304,6 +323,12 @@ void launch_hcdict_build(uint8_t *image, const uint8_t *dict, int len, hipStream
 // compression levels 1..12 against that image: a persistent grid of encode_hc_dict_grid(nBlocks) workgroups, one window of a.stage each
 int encode_hc_dict_grid(int nBlocks);
 void launch_encode_hc_dict(const HcDictArgs &a, int level, hipStream_t s);
+// the wave encoder's table image of the same dictionary (FASTDICT_IMAGE_BYTES): one wavefront
+void launch_hcdict_build_fast(uint8_t *fast, const uint8_t *dict, int len, hipStream_t s);
+// level 0 against both images: a persistent grid of encode_fastdict_grid(..) single waves, one window of a.stage each.  knob:
+// MI355LZ4_FASTDICT_WAVES (> 0 waves per CU, < 0 waves in all, 0 the default); the grid shrinks to FASTDICT_SCRATCH_MAX of windows
+int encode_fastdict_grid(int nBlocks, int knob, size_t stageStride);
+void launch_encode_fastdict(const FastDictArgs &a, int grid, hipStream_t s);
 // independent blocks against one external dictionary (a.dict0, a.dict0Len; a.linked is not used): one wave per block
 void launch_decode_dict(const DecodeArgs &a, hipStream_t s);
 // many linked decode streams: one wave per entry of a.work walks its blocks from its slot's dictionary and stores the tail back;

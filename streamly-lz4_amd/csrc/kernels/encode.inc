@@ -200,6 +200,125 @@ void launch_encode_hc_dict(const HcDictArgs &a, int level, hipStream_t s)
 }
 
 // ---------------------------------------------------------------------------
+// K2, the wave encoder against a shared dictionary (mi355lz4_hcdict at level 0, DESIGN.md 7l).  Block i comes out as the second
+// block of the linked call [kept bytes, block i] through k_encode<true, PAIR>.  That kernel zeroes its table and enters every
+// ENC_SEED_STEP-th position of the dictionary for every block: 64 KiB of seeding for a record of 4 KiB.  Here the table after the
+// seeding is an image made once per load, and a block reloads it.
+//
+// The seed loop (encode_wave.hpp) is a sequence of STEPS: step s enters the 64 positions s * span + lane * ENC_SEED_STEP
+// (span = 64 * ENC_SEED_STEP) with one LDS store and the tag's two atomics.  Lanes of one step that meet in a bucket settle it
+// inside those instructions, so a step is replayed whole or not at all.  The last positions (q > keep - 5) hash bytes of the block
+// and cannot be in the image: the image is the table after every step in front of the first one that holds such a position
+// (header word 1: that step's first position), and every block replays the remaining one or two steps against its staged bytes.
+// ---------------------------------------------------------------------------
+static_assert(FASTDICT_TABLE_BYTES == ENC_TABLE_ENTRIES * sizeof(uint16_t) && FASTDICT_TABLE_BYTES % 16 == 0,
+              "the fast image is the wave encoder's table: positions, then tags");
+#define ENC_SEED_SPAN (LZ4_WAVE * ENC_SEED_STEP)
+
+// One step of the seed loop, with its lane-to-position mapping and its instructions: positions q0 + lane * ENC_SEED_STEP below
+// dictLen.  EXACT_END (the builder, which has no block behind the kept bytes): a position whose 8-byte load would pass src +
+// dictLen reads its five hashed bytes one by one; such a position must have all five inside (it does in every step the builder runs).
+template <bool EXACT_END>
+__device__ __forceinline__ void enc_seed_step(uint16_t *table, const uint8_t *src, int q0, int dictLen)
+{
+    ENC_TAG_DECL
+    const int q = q0 + lane_id() * ENC_SEED_STEP;
+    uint64_t v = 0ull;
+    if (q < dictLen) {
+        if (!EXACT_END || q + 8 <= dictLen) v = *(const LZ4_GLOBAL u64_unaligned *)as_global(src + q);
+        else for (int i = 0; i < 5; i++) v |= (uint64_t)as_global(src)[q + i] << (8 * i);
+    }
+    if (q < dictLen) { uint32_t h_, t_; ENC_HT(v, h_, t_); table[h_] = (uint16_t)q; ENC_TAG_SET(h_, t_); }
+}
+
+// The table image of the last keep = min(len, 65536) bytes of dict: the seed steps without a seam position, from a zeroed table;
+// then {keep, first position of the first seam step} as the header.  One wavefront.  Reads nothing behind the kept bytes.
+__global__ __launch_bounds__(LZ4_WAVE) void k_hcdict_build_fast(uint8_t *fast, const uint8_t *dict, int len)
+{
+    __shared__ __attribute__((aligned(16))) uint16_t table[ENC_TABLE_ENTRIES];
+    const int lane = lane_id();
+    const int keep = min(max(len, 0), 65536);
+    const uint8_t *from = dict + (len - keep);                          // (not dereferenced when keep == 0)
+    dev_v4 *tab4 = (dev_v4 *)table;
+    for (int i = lane; i < (int)(FASTDICT_TABLE_BYTES / 16); i += LZ4_WAVE) tab4[i] = dev_v4{0u, 0u, 0u, 0u};
+    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+    // the first seam position: the first entered position above keep - 5; its step and the ones behind it are the blocks' to replay
+    const int qSeam = (max(keep - 4, 0) + ENC_SEED_STEP - 1) / ENC_SEED_STEP * ENC_SEED_STEP;
+    const int seam0 = qSeam / ENC_SEED_SPAN * ENC_SEED_SPAN;
+    for (int q0 = 0; q0 < seam0; q0 += ENC_SEED_SPAN) enc_seed_step<true>(table, from, q0, keep);
+    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+    for (int i = lane; i < (int)(FASTDICT_TABLE_BYTES / 16); i += LZ4_WAVE) as_global((dev_v4 *)fast)[i] = tab4[i];
+    if (lane == 0) as_global((dev_v4 *)(fast + FASTDICT_KEEP_OFF))[0] = dev_v4{(uint32_t)keep, (uint32_t)seam0, 0u, 0u};
+}
+
+void launch_hcdict_build_fast(uint8_t *fast, const uint8_t *dict, int len, hipStream_t s)
+{
+    hipLaunchKernelGGL(k_hcdict_build_fast, dim3(1), dim3(LZ4_WAVE), 0, s, fast, dict, len);
+}
+
+// A persistent grid of single waves, k_encode's occupancy, one window of x.stage per wave.  The kept bytes go into the window once,
+// ending at byte 65536 of it.  For every block of 13 bytes and more the wave copies the block behind them, loads the image into its
+// table, replays the seam steps and runs encode_block_wave<.., PREP> on the staged bytes as the linked call would on its own; the
+// output goes straight to the slot.  Shorter blocks, and every block of an empty dictionary, are encoded where they lie.  A length
+// outside 0..uniformLen gives framedLen 0 and leaves the slot alone.  Nothing of the object is written.
+template <bool PAIR>
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(ENC_WAVES_PER_EU, ENC_WAVES_PER_EU))) void k_encode_fastdict(FastDictArgs x)
+{
+    __shared__ __attribute__((aligned(16))) uint16_t table[ENC_TABLE_ENTRIES + ENC_LDS_PAD + ((PAIR && ENC_STAGE) ? 128 : 0)];
+    const int lane = lane_id();
+    const EncodeArgs a = x.e;
+    const LZ4_GLOBAL uint32_t *hdr = as_global((const uint32_t *)(x.fast + FASTDICT_KEEP_OFF));
+    const int keep = (int)min(ex_uni(hdr[0]), 65536u);
+    const int seam0 = (int)min(ex_uni(hdr[1]), 65536u);
+    uint8_t *blockAt = x.stage + (uint64_t)blockIdx.x * (uint64_t)x.stageStride + 65536;
+    if (keep > 0) wave_copy_bytes(blockAt - keep, x.image + HCDICT_DICT_OFF, (uint32_t)keep);
+    dev_v4 *tab4 = (dev_v4 *)table;
+    for (int blk = (int)blockIdx.x; blk < a.nBlocks; blk += (int)gridDim.x) {
+        const EncBlock b = enc_block(a, blk);
+        const int n = uni(b.n);
+        if (n < 0 || n > a.uniformLen) {
+            if (lane == 0) a.framedLen[blk] = 0;
+            continue;
+        }
+        const uint8_t *src = a.src + uni64((int64_t)b.off);
+        uint8_t *slot = a.slots + (size_t)blk * a.slotStride;
+        int dictLen = 0;
+        if (n >= LZ4_MFLIMIT + 1 && keep > 0) {
+            wave_copy_bytes(blockAt, src, (uint32_t)n);
+            for (int i = lane; i < (int)(FASTDICT_TABLE_BYTES / 16); i += LZ4_WAVE) tab4[i] = as_global((const dev_v4 *)x.fast)[i];
+            // the block's bytes are read back by other lanes than wrote them, and the steps below enter into the loaded table
+            wave_fence();
+            for (int q0 = seam0; q0 < keep; q0 += ENC_SEED_SPAN) enc_seed_step<false>(table, blockAt - keep, q0, keep);
+            src = blockAt;
+            dictLen = keep;
+        } else if (n >= LZ4_MFLIMIT + 1) {                              // no dictionary: the block of a one-block linked call, where it lies
+            for (int i = lane; i < (int)(FASTDICT_TABLE_BYTES / 16); i += LZ4_WAVE) tab4[i] = dev_v4{0u, 0u, 0u, 0u};
+        }                                                               // (shorter blocks are literals: no window, no table)
+        // (one call site: the encoder is inlined, and its scalar operands stay scalar)
+        const int c = encode_block_wave<uint16_t, true, false, PAIR, true>(src, n, slot + a.headerKind, a.accel, table, a.stats, dictLen);
+        enc_finish_slot(a, blk, slot, c, n, lane == 0);
+    }
+}
+
+// the grid of a call: waves per CU (knob > 0; 0: FASTDICT_WAVES_DEFAULT) or waves in all (knob < 0), no more than blocks, and no
+// more windows of stageStride bytes than FASTDICT_SCRATCH_MAX holds
+int encode_fastdict_grid(int nBlocks, int knob, size_t stageStride)
+{
+    long long waves = knob < 0 ? -(long long)knob : (long long)(knob > 0 ? knob : FASTDICT_WAVES_DEFAULT) * hc_cu_count();
+    const long long fit = (long long)(FASTDICT_SCRATCH_MAX / (stageStride ? stageStride : 1));
+    if (waves > fit) waves = fit;
+    if (waves > nBlocks) waves = nBlocks;
+    return waves < 1 ? 1 : (int)waves;
+}
+
+void launch_encode_fastdict(const FastDictArgs &a, int grid, hipStream_t s)
+{
+    if (a.e.nBlocks <= 0 || grid <= 0) return;
+    if (a.e.uniformLen > 65536) hipLaunchKernelGGL((k_encode_fastdict<false>), dim3((unsigned)grid), dim3(64), 0, s, a);
+    else hipLaunchKernelGGL((k_encode_fastdict<true>), dim3((unsigned)grid), dim3(64), 0, s, a);
+}
+
+// ---------------------------------------------------------------------------
 // K2, reference-exact compression (encode_exact.hpp, DESIGN.md 7d).  One wave per piece of a call, its hash table in LDS.
 // ---------------------------------------------------------------------------
 // canonical form of table entry v for a block (DESIGN 7d): the block's renorm applied, entries that no position of the

@@ -172,6 +172,12 @@ def _load():
         vp)
     sig("mi355lz4_compress_hcdict", C.c_int, vp, vp, C.POINTER(_u8p), _i32p, C.c_int, C.c_int, _u8p, C.c_size_t,
         C.POINTER(C.c_size_t), _i32p, _i32p)
+    # level 0 against the same prepared dictionary: the wave encoder
+    sig("mi355lz4_debug_hcdict_fast_image", C.c_int, vp, _u8p)
+    sig("mi355lz4_compress_fastdict_device", C.c_int, vp, vp, vp, vp, vp, C.c_uint64, C.c_int, C.c_int, C.c_int, C.c_int, vp,
+        C.c_size_t, vp)
+    sig("mi355lz4_compress_fastdict", C.c_int, vp, vp, C.POINTER(_u8p), _i32p, C.c_int, C.c_int, C.c_int, _u8p, C.c_size_t,
+        C.POINTER(C.c_size_t), _i32p, _i32p)
     # fixed-size output pages
     sig("mi355lz4_compress_pages_device", C.c_int, vp, vp, vp, vp, C.c_int, vp, C.c_int, C.c_int, vp, C.c_size_t, vp, vp, vp, vp)
     sig("mi355lz4_compress_pages", C.c_int, vp, C.POINTER(_u8p), _i32p, C.c_int, C.c_int, C.c_int, C.c_int, _u8p, C.c_size_t,
@@ -237,6 +243,7 @@ DECLARED_SYMBOLS = [
     "mi355lz4_compress_dict", "mi355lz4_decompress_dict",
     "mi355lz4_hcdict_create", "mi355lz4_hcdict_destroy", "mi355lz4_hcdict_load", "mi355lz4_hcdict_size",
     "mi355lz4_compress_hcdict_device", "mi355lz4_compress_hcdict",
+    "mi355lz4_compress_fastdict_device", "mi355lz4_compress_fastdict",
     "mi355lz4_compress_pages_device", "mi355lz4_compress_pages",
     "LZ4_createStream", "LZ4_freeStream", "LZ4_createStreamDecode", "LZ4_freeStreamDecode", "LZ4_compressBound",
     "LZ4_compress_fast_continue", "LZ4_decompress_safe_continue",
@@ -965,6 +972,35 @@ class Engine:
                                             flen.ctypes.data_as(_i32p), status.ctypes.data_as(_i32p)), "compress_hcdict")
         return out[: out_len.value].tobytes(), flen[:n].tolist()
 
+    def compress_fastdict_device(self, hd, src, n_blocks, max_block_len, slots, slot_stride_, framed_len, accel=1, header_kind=8,
+                                 src_off=None, src_len=None, block_stride=None):
+        """A batch of independent blocks at level 0 by the wave encoder, every one with the dictionary of the HcDict hd in
+        front of it: the bytes of block 1 of the linked call [dictionary, block] with the same accel.  The block arguments
+        are those of compress_batch_device; hd is only read.  Only enqueues (include/mi355lz4.h,
+        mi355lz4_compress_fastdict_device)."""
+        self._follow_torch()
+        _check(lib.mi355lz4_compress_fastdict_device(
+            self.ctx, hd._h if hd is not None else None, _dptr(src), _dptr(src_off), _dptr(src_len),
+            int(max_block_len if block_stride is None else block_stride), int(max_block_len), int(n_blocks), int(accel),
+            int(header_kind), _dptr(slots), int(slot_stride_), _dptr(framed_len)), "compress_fastdict_device")
+
+    def compress_fastdict(self, blocks, hd, accel=1, header_kind=8):
+        """blocks: list of bytes-like, every one compressed at level 0 by the wave encoder against the HcDict hd.  Returns
+        (framed bytes, [framed length per block]); mi355lz4_compress_fastdict."""
+        n = len(blocks)
+        arrs = [np.frombuffer(bytes(b), dtype=np.uint8) if not isinstance(b, np.ndarray) else b for b in blocks]
+        ptrs = (_u8p * max(n, 1))(*[a.ctypes.data_as(_u8p) for a in arrs])
+        lens = np.array([a.size for a in arrs] + [0], dtype=np.int32)
+        cap = int(sum(compress_bound(max(int(x), 0)) + header_kind + 4 for x in lens[:n])) + 16
+        out = np.empty(cap, dtype=np.uint8)
+        out_len = C.c_size_t()
+        flen = np.zeros(max(n, 1), dtype=np.int32)
+        status = np.zeros(max(n, 1), dtype=np.int32)
+        _check(lib.mi355lz4_compress_fastdict(self.ctx, hd._h if hd is not None else None, ptrs, lens.ctypes.data_as(_i32p), n,
+                                              int(accel), int(header_kind), out.ctypes.data_as(_u8p), cap, C.byref(out_len),
+                                              flen.ctypes.data_as(_i32p), status.ctypes.data_as(_i32p)), "compress_fastdict")
+        return out[: out_len.value].tobytes(), flen[:n].tolist()
+
     def compress_pages_device(self, src, src_off, src_len, n_inputs, page_size, max_pages, pages, page_stride, page_src_len,
                               page_comp_len, n_pages, consumed, header_kind=8):
         """Fixed-size output pages: input i (src[src_off[i] : src_off[i] + src_len[i]], device tensors) is cut into a chain of
@@ -1035,9 +1071,11 @@ class Engine:
 class HcDict:
     """A prepared high-compression dictionary on the engine's device (mi355lz4_hcdict, about 216 KiB): the dictionary's last
     64 KiB and the image of the hash-chain encoder's tables after its inserts, for Engine.compress_hcdict_device /
-    compress_hcdict.  Holds the empty dictionary until load()."""
+    compress_hcdict -- and, beside it, the wave encoder's table after the dictionary's seed steps, for level 0
+    (Engine.compress_fastdict_device / compress_fastdict).  Holds the empty dictionary until load()."""
 
     IMAGE_BYTES = 221248        # kernels.h, HCDICT_IMAGE_BYTES: u16 chain[65536], u32 head[6144], 64 bytes of count, 65536 bytes
+    FAST_IMAGE_BYTES = 10256    # kernels.h, FASTDICT_IMAGE_BYTES: u16 positions[4096], 2048 bytes of tags, u32 {keep, first seam step, -, -}
 
     def __init__(self, engine):
         self._h = C.c_void_p()
@@ -1059,6 +1097,12 @@ class HcDict:
         """Diagnostics: all IMAGE_BYTES of the device image (chain, head, count, bytes), after the device is idle."""
         buf = np.empty(self.IMAGE_BYTES, dtype=np.uint8)
         _check(lib.mi355lz4_debug_hcdict_image(self._h, buf.ctypes.data_as(_u8p)), "debug_hcdict_image")
+        return buf.tobytes()
+
+    def fast_image(self):
+        """Diagnostics: all FAST_IMAGE_BYTES of the wave encoder's image (positions, tags, header), after the device is idle."""
+        buf = np.empty(self.FAST_IMAGE_BYTES, dtype=np.uint8)
+        _check(lib.mi355lz4_debug_hcdict_fast_image(self._h, buf.ctypes.data_as(_u8p)), "debug_hcdict_fast_image")
         return buf.tobytes()
 
     def close(self):
