@@ -62,6 +62,8 @@ module Streamly.Internal.LZ4.GPU
     , compressChunksWithDictFast
     , c_compressPagesDevice
     , compressChunksPaged
+    , c_compressPagesFastDevice
+    , compressChunksPagedFast
     , DecompressStreams
     , newDecompressStreams
     , freeDecompressStreams
@@ -227,6 +229,16 @@ foreign import ccall safe "mi355lz4.h mi355lz4_compress_pages_device"
 foreign import ccall safe "mi355lz4.h mi355lz4_compress_pages"
     c_compressPages
         :: Ptr C_Engine -> Ptr (Ptr Word8) -> Ptr Int32 -> CInt -> CInt -> CInt -> CInt
+        -> Ptr Word8 -> CSize -> Ptr Int32 -> Ptr Int32 -> Ptr Int32 -> Ptr Int32 -> IO CInt
+-- The same chains by the engine's own level-0 encoder with an output budget: accel in front of headerKind.  Valid, independently
+-- decodable pages at the engine's speed, not LZ4_compress_destSize's bytes.
+foreign import ccall safe "mi355lz4.h mi355lz4_compress_pages_fast_device"
+    c_compressPagesFastDevice
+        :: Ptr C_Engine -> Ptr Word8 -> Ptr Word64 -> Ptr Int32 -> CInt -> Ptr Int32 -> CInt -> CInt -> CInt
+        -> Ptr Word8 -> CSize -> Ptr Int32 -> Ptr Int32 -> Ptr Int32 -> Ptr Int32 -> IO CInt
+foreign import ccall safe "mi355lz4.h mi355lz4_compress_pages_fast"
+    c_compressPagesFast
+        :: Ptr C_Engine -> Ptr (Ptr Word8) -> Ptr Int32 -> CInt -> CInt -> CInt -> CInt -> CInt
         -> Ptr Word8 -> CSize -> Ptr Int32 -> Ptr Int32 -> Ptr Int32 -> Ptr Int32 -> IO CInt
 
 -- Decoded sizes without decoding (device pointers in, device pointers out; only enqueues): what every block of a
@@ -634,7 +646,23 @@ compressChunksWithDictFast (Engine eng) (HcDict hd) accel cfg arrs = do
 -- @maxPages@ was too few).  Block checksums must be off.
 compressChunksPaged
     :: Engine -> BlockConfig -> Int -> Int -> [Array.Array Word8] -> IO [([Array.Array Word8], Int)]
-compressChunksPaged (Engine eng) cfg pageSize maxPages arrs = do
+compressChunksPaged (Engine eng) = pagedWith "compressChunksPaged" (c_compressPages eng)
+
+-- | 'compressChunksPaged' at the engine's speed (@mi355lz4_compress_pages_fast@, acceleration @accel@): every page is a prefix
+-- of the sequences the level-0 encoder finds in the next 64 KiB at the most, closed by the literal run that fills the page.  The
+-- pages are valid LZ4 blocks that decode on their own, not @LZ4_compress_destSize@'s bytes; highly compressible input gives pages
+-- that are not full.  The engine must be at level 0, block checksums off.
+compressChunksPagedFast
+    :: Engine -> Int -> BlockConfig -> Int -> Int -> [Array.Array Word8] -> IO [([Array.Array Word8], Int)]
+compressChunksPagedFast (Engine eng) accel =
+    pagedWith "compressChunksPagedFast" (\pSrc pLen n ps mp -> c_compressPagesFast eng pSrc pLen n ps mp (fromIntegral accel))
+
+pagedWith
+    :: String
+    -> (Ptr (Ptr Word8) -> Ptr Int32 -> CInt -> CInt -> CInt -> CInt -> Ptr Word8 -> CSize -> Ptr Int32 -> Ptr Int32 -> Ptr Int32
+        -> Ptr Int32 -> IO CInt)
+    -> BlockConfig -> Int -> Int -> [Array.Array Word8] -> IO [([Array.Array Word8], Int)]
+pagedWith who call cfg pageSize maxPages arrs = do
     let n = length arrs
         meta = metaSizeOf cfg
         stride = meta + max pageSize 1
@@ -648,9 +676,9 @@ compressChunksPaged (Engine eng) cfg pageSize maxPages arrs = do
         withAll arrs $ \ptrs -> do
             pokeArray pSrc ptrs
             pokeArray pLen (map fromIntegral lens)
-            rc <- c_compressPages eng pSrc pLen (fromIntegral n) (fromIntegral pageSize) (fromIntegral maxPages)
+            rc <- call pSrc pLen (fromIntegral n) (fromIntegral pageSize) (fromIntegral maxPages)
                       (fromIntegral meta) dstBegin (fromIntegral stride) pSrcLen pCompLen pCount pCons
-            when (rc /= 0) $ error "compressChunksPaged: mi355lz4_compress_pages failed"
+            when (rc /= 0) $ error (who ++ ": the call failed")
         counts <- map fromIntegral <$> peekArray n pCount
         cons <- map fromIntegral <$> peekArray n pCons
         comp <- map fromIntegral <$> peekArray np (pCompLen :: Ptr Int32)

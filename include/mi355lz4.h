@@ -115,7 +115,8 @@ typedef struct mi355lz4_ctx mi355lz4_ctx;
  *   copies write past what it returns); pages that are not written -- behind nPages[i], of a skipped input -- not at all.
  *   pageSrcLen[] and pageCompLen[] only at the entries of pages written; nPages[i]; consumed[i] unless the input is skipped
  *   (nPages[i] = 0 is then all that is written for it).  Never src, srcOff, srcLen or pageSize.  _compress_pages writes the same
- *   ranges of the caller's host arrays and nothing else.
+ *   ranges of the caller's host arrays and nothing else.  _compress_pages_fast_device and _compress_pages_fast: the same ranges
+ *   and the same rules.
  * Scratch that a call needs is the engine's own. */
 
 /* ---- engine lifecycle ------------------------------------------------ */
@@ -813,6 +814,44 @@ int mi355lz4_compress_pages_device(mi355lz4_ctx *ctx, const uint8_t *src, const 
 int mi355lz4_compress_pages(mi355lz4_ctx *ctx, const uint8_t *const *src, const int32_t *srcLen, int nInputs, int pageSize,
                             int maxPages, int headerKind, uint8_t *pages, size_t pageStride,
                             int32_t *pageSrcLen, int32_t *pageCompLen, int32_t *nPages, int32_t *consumed);
+
+/* ---- fast fixed-size output pages: the engine's own encoder with an output budget ----------------------------------------
+ * The calls above write LZ4_compress_destSize's bytes and pay for them with its serial parse.  A caller who needs valid,
+ * independently decodable, full pages and not those exact bytes takes these: the same arguments plus accel (clamped to 1..65537
+ * as in mi355lz4_compress_batch_device), the same layout pages + (i*maxPages + k) * pageStride, headerKind 0 / 4 / 8, pageSrcLen,
+ * pageCompLen, nPages and consumed, the same chain stops (input consumed; maxPages reached; pageSize < 1: the page is not written
+ * and not counted; pageSize == 1: a zero token that consumes 0, counted, the chain ends), the same per-input skips (a length
+ * outside 0..MI355LZ4_MAX_INPUT_SIZE or headerKind + pageSize[i] > pageStride: nPages[i] = 0 and nothing else), the same
+ * enqueue-only behaviour with srcLen and pageSize unread on the host, and the same argument errors.  The compression level must
+ * be 0 (MI355LZ4_E_ARG otherwise) and block checksums off; the linked switch, segments and the exact stream play no part.
+ * DESIGN.md 7m.  What differs is what a page holds:
+ * Let pos be what pages 0..k-1 consumed, rem = srcLen[i] - pos, n = min(rem, 65536), T = pageSize[i], and E the block that
+ * mi355lz4_compress_batch_device writes for src_i[pos, pos + n) at level 0 with this accel, unlinked, maxBlockLen 65536: sequences
+ * s_0 .. s_{m-1} and a last literal run.  If E is at most T bytes, the page is E and consumes n.  A page never holds more than
+ * 65536 input bytes: highly compressible input gives pages that are NOT full, and maxPages is sized with that in mind
+ * (srcLen / 65536 pages at the least).  Otherwise the page is s_0 .. s_j of E, byte for byte, and one literal run of
+ * r_j = min(n - inEnd_j, lit(T - outEnd_j)) bytes behind them, where outEnd_j / inEnd_j are the output / input positions behind
+ * s_j (0 / 0 for j = -1, no sequence) and lit(s) is the longest run whose token, length bytes and bytes fit in s.  It consumes
+ * inEnd_j + r_j.  j is the last sequence with outEnd_j + 1 <= T, r_j >= 5 and matchStart_j + 12 <= inEnd_j + r_j -- the
+ * end-of-block rules of cbits/lz4.c:214-221 --, or -1, the all-literals page.  The reference's shortened last match is not
+ * taken over.  Every page is a valid LZ4 block on its own, and the decoded pages of an input concatenate to its consumed prefix.
+ * A page that leaves input behind and was cut by T (not by the 64 KiB bound) has compLen >= T - 1 and consumes at least the
+ * progress bound above, (T - 1) - (T + 240) / 256.
+ * One wavefront walks one input's chain (k_pages_fast: the batch encoder's 10 KiB table, zeroed per page; its parse runs up to a
+ * queue of sequences past the page's end).  Measured once (scripts/fastpages_rate.py, profiles/fastpages_rate.json; medians of 5
+ * event-timed calls, the exact call timed in the same session): 16384 text records of 4 KiB into 1 KiB pages in 0.66 ms against 6.12 ms
+ * (fastest call 6.11) for mi355lz4_compress_pages_device, 65536 pages from either call, 88.6 % against 87.4 % full, ratio 1.129 against
+ * 1.144; 2560 records of 64 KiB into 4 KiB pages in 1.45 ms against 23.96 ms (fastest 23.86), 30720 pages from either, 95.6 % against
+ * 93.4 % full, ratio 1.395 against 1.427; page count ratio 1.000 on both.  No rate is part of the contract. */
+int mi355lz4_compress_pages_fast_device(mi355lz4_ctx *ctx, const uint8_t *src, const uint64_t *srcOff, const int32_t *srcLen,
+                                        int nInputs, const int32_t *pageSize, int maxPages, int accel, int headerKind,
+                                        uint8_t *pages, size_t pageStride,
+                                        int32_t *pageSrcLen, int32_t *pageCompLen, int32_t *nPages, int32_t *consumed);
+/* Host-buffer form, synchronous: mi355lz4_compress_pages with accel in front of headerKind, the device call above in its one
+ * group, and its host-side checks; a compression level other than 0 is MI355LZ4_E_ARG before anything is enqueued. */
+int mi355lz4_compress_pages_fast(mi355lz4_ctx *ctx, const uint8_t *const *src, const int32_t *srcLen, int nInputs, int pageSize,
+                                 int maxPages, int accel, int headerKind, uint8_t *pages, size_t pageStride,
+                                 int32_t *pageSrcLen, int32_t *pageCompLen, int32_t *nPages, int32_t *consumed);
 
 /* ---- many linked decode streams, continued across calls ---------------------------------------------------------------
  * The decode-side counterpart of mi355lz4_cstreams, and the device-resident form of the reference's one LZ4_streamDecode_t

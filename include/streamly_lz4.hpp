@@ -133,6 +133,11 @@ public:
     // few.  Throws Error (block checksums in cfg included: pages carry no trailer).
     std::vector<std::vector<Array>> compressPages(const BlockConfig &cfg, const std::vector<Array> &arrays, int pageSize, int maxPages,
                                                   std::vector<int32_t> *consumed = nullptr);
+    // The same chains at the engine's speed (mi355lz4_compress_pages_fast): every page is a prefix of the sequences this engine's
+    // level-0 encoder finds in the next 64 KiB at the most, closed by the literal run that fills the page -- valid, independently
+    // decodable pages, not LZ4_compress_destSize's bytes; highly compressible input gives pages that are not full.  Level 0 only.
+    std::vector<std::vector<Array>> compressPagesFast(const BlockConfig &cfg, const std::vector<Array> &arrays, int pageSize, int maxPages,
+                                                      std::vector<int32_t> *consumed = nullptr, int accel = 1);
 private:
     mi355lz4_ctx *ctx_ = nullptr;
     size_t batch_;

@@ -1065,6 +1065,32 @@ extern "C" int mi355lz4_compress_pages_device(mi355lz4_ctx *c, const uint8_t *sr
     return check_launch("exact pages launch");
 }
 
+// The same chains at the engine's speed: every page by the wave encoder with an output budget (k_pages_fast), this
+// engine's bytes and not LZ4_compress_destSize's.  Level 0 only; the arguments and their checks are the call's above, plus accel.
+extern "C" int mi355lz4_compress_pages_fast_device(mi355lz4_ctx *c, const uint8_t *src, const uint64_t *srcOff, const int32_t *srcLen,
+                                                   int nInputs, const int32_t *pageSize, int maxPages, int accel, int headerKind,
+                                                   uint8_t *pages, size_t pageStride, int32_t *pageSrcLen, int32_t *pageCompLen,
+                                                   int32_t *nPages, int32_t *consumed)
+{
+    if (!c) return fail(MI355LZ4_E_ARG, "null ctx");
+    if (nInputs < 0 || maxPages < 1 || (headerKind != 0 && headerKind != 4 && headerKind != 8) || pageStride < (size_t)headerKind + 1)
+        return fail(MI355LZ4_E_ARG, "compress_pages_fast_device: bad arguments");
+    if (c->blockChecksum) return fail(MI355LZ4_E_ARG, "compress_pages_fast_device: block checksums are on; pages carry no trailer");
+    if (c->compLevel != 0)
+        return fail(MI355LZ4_E_ARG, "compress_pages_fast_device: compression level %d; fast pages are level 0's encoder", c->compLevel);
+    if (nInputs == 0) return MI355LZ4_OK;
+    if (!src || !srcOff || !srcLen || !pageSize || !pages || !pageSrcLen || !pageCompLen || !nPages || !consumed)
+        return fail(MI355LZ4_E_ARG, "compress_pages_fast_device: null pointer");
+    HIP_TRY(hipSetDevice(c->device));
+    if (accel < 1) accel = 1;                 // cbits/lz4.c:1577
+    if (accel > 65537) accel = 65537;         // cbits/lz4.c:1578
+    const PagesFastArgs x{PagesArgs{src, srcOff, srcLen, nInputs, pageSize, maxPages, headerKind, pages, pageStride, pageSrcLen,
+                                    pageCompLen, nPages, consumed},
+                          accel};
+    launch_pages_fast(x, c->stream);
+    return check_launch("fast pages launch");
+}
+
 // ---------------------------------------------------------------------------
 // High-compression levels against a shared dictionary.  A mi355lz4_hcdict is the device image of encode_hc.hpp's
 // tables after the dictionary's inserts (k_hcdict_build, once per load); mi355lz4_compress_hcdict_device reloads it for every

@@ -399,6 +399,33 @@ __device__ __forceinline__ bool tab_candidate(TabT e, int myPos, uint32_t &cand)
     return cand < (uint32_t)myPos && (uint32_t)myPos - cand <= LZ4_MAXDIST;   // :1003-1006
 }
 
+// The longest literal run whose token, length bytes and bytes fit in s bytes of output: the largest r with
+// 1 + ext_len_bytes(r) + r <= s; -1 when not even the token fits.
+__device__ __forceinline__ int page_lit_fit(int s)
+{
+    if (s <= 16) return min(s - 1, 14);
+    const int w = s - 17;                          // r = 15 + x with x + x / 255 <= w
+    return 15 + w - (w + 1) / 256;
+}
+
+// BUDGET (a fixed-size output page, below): the state of the page being written
+struct EncPage {
+    bool done;       // the page is closed: nothing more is parsed or written
+    int in;          // the input position behind the last sequence written
+    int qMax;        // the queue length at which the next flush comes
+};
+// How early to write the queue out is a tuning choice, not a correctness matter: the parse does not depend on it.  A sequence is
+// three bytes at the least; at sixteen the lookahead past the page's end stays a fraction of the page.
+__device__ __forceinline__ int enc_page_queue_max(int room) { return min(LZ4_WAVE, max(8, room >> 4)); }
+// the page's end: the longest literal run that fits behind what is written, from pg.in on
+__device__ __forceinline__ uint8_t *enc_page_close(EncPage &pg, uint8_t *op, const uint8_t *dst, const uint8_t *src, int n, int budget, int *consumed)
+{
+    const int r = max(0, min(n - pg.in, page_lit_fit(budget - (int)(op - dst))));     // (never below 1: the cut behind pg.in left room)
+    *consumed = pg.in + r;
+    pg.done = true;
+    return emit_last_literals(op, src + pg.in, (uint32_t)r);
+}
+
 // DICT: the block is compressed with the dictLen bytes in front of it as its dictionary -- the previous block of
 // the stream, which LZ4_compress_fast_continue keeps as the window (cbits/lz4.c:1608-1636, kept alive by
 // Internal/LZ4.hs:376,389).  All positions are then relative to src - dictLen; the table is seeded with the
@@ -412,10 +439,16 @@ __device__ __forceinline__ bool tab_candidate(TabT e, int myPos, uint32_t &cand)
 // PREP (k_encode_fastdict, a mi355lz4_hcdict): the caller has made the table -- zeroed it, or loaded the image of the
 // dictionary's seed steps and replayed the seam's (kernels/encode.inc, enc_seed_step) -- so neither the zeroing nor the
 // seed loop runs here.  Everything behind them is the same code.
-template <typename TabT, bool DICT = false, bool SEG = false, bool PAIR = false, bool PREP = false>
+// BUDGET (k_pages_fast, a fixed-size output page; independent blocks only): the block's parse is the same, and what is written is
+// the longest prefix of its sequences that leaves room in `budget` bytes for a valid last literal run (page_lit_fit and flush_queue
+// below), closed by that run.  The whole block when it fits.  *consumed is the input the output stands for; nothing
+// behind the returned length is written.  budget >= 1.
+template <typename TabT, bool DICT = false, bool SEG = false, bool PAIR = false, bool PREP = false, bool BUDGET = false>
 __device__ int encode_block_wave(const uint8_t *src, int n, uint8_t *dst, int accel, TabT *table,
-                                 unsigned long long *stats = nullptr, int dictLen = 0, SegOut *seg = nullptr)
+                                 unsigned long long *stats = nullptr, int dictLen = 0, SegOut *seg = nullptr,
+                                 int budget = 0, int *consumed = nullptr)
 {
+    static_assert(!BUDGET || (!DICT && !SEG && PAIR), "BUDGET: independent blocks of up to 64 KiB");
     const int lane = lane_id();
     if (!DICT) dictLen = 0;
     const int blockLen = n;
@@ -444,12 +477,44 @@ __device__ int encode_block_wave(const uint8_t *src, int n, uint8_t *dst, int ac
         if (__builtin_amdgcn_inverse_ballot_w64(pendM1)) { q0 = pendR[1][0]; q1 = pendR[1][1]; if (!SMALLQ) { q2 = pendR[1][2]; q3 = pendR[1][3]; } }
         pendM0 = 0; pendM1 = 0;
     };
+    // BUDGET: the page is closed (done) behind the last sequence that left room for a valid end; in = the input position behind the
+    // last sequence written; qMax = the queue length at which the next flush comes.  (Every use sits in an `if constexpr`: the
+    // other instantiations do not even capture it.)
+    EncPage pg{false, 0, LZ4_WAVE};
+    if constexpr (BUDGET) pg.qMax = enc_page_queue_max(budget);
     auto flush_queue = [&]() {
         commit_pending();
+        if constexpr (BUDGET) { if (pg.done) qCnt = 0; }   // (parked behind the page's end by the window that closed it)
         if (qCnt == 0) return;
         int qPrev, qStart, qLen, qOff;
         if (SMALLQ) { qPrev = q0 & 0xffff; qStart = (int)((uint32_t)q0 >> 16); qLen = q1 & 0xffff; qOff = (int)((uint32_t)q1 >> 16); }
         else { qPrev = q0; qStart = q1; qLen = q2; qOff = q3; }
+        if constexpr (BUDGET) {
+            // A cut behind lane j's sequence is valid when the bytes left hold a token and a literal run of at least 5 bytes that
+            // ends 12 bytes or more behind the match's start (cbits/lz4.c:214-221).  The run is what fits or what the block has
+            // left.  A sequence without a valid cut has none behind it either: the page ends behind the last lane
+            // that has one, or, where no lane has, behind what the flush before this one wrote, which ended at such a lane.
+            const bool act = lane < qCnt;
+            const uint32_t lit = act ? (uint32_t)(qStart - qPrev) : 0u;
+            const uint32_t mc = act ? (uint32_t)(qLen - LZ4_MINMATCH) : 0u;
+            const uint32_t esz = act ? 1u + lit + ext_len_bytes(lit) + 2u + ext_len_bytes(mc) : 0u;
+            const int room = budget - (int)(op - dst) - enc_scan_incl((int)esz);
+            const int inEnd = qStart + qLen;
+            const int r = min(n - inEnd, page_lit_fit(room));
+            const uint64_t vm = enc_ballot(act && room >= 1 && r >= LZ4_LASTLITERALS && qLen + r >= LZ4_MFLIMIT);
+            const uint64_t all = (qCnt >= LZ4_WAVE) ? ~0ull : ((1ull << qCnt) - 1ull);
+            if (vm != all) {
+                if (vm) {
+                    const int j = 63 - (int)__builtin_clzll(vm);
+                    op = emit_sequences(src, op, qPrev, qStart, qLen, qOff, j + 1);
+                    pg.in = __builtin_amdgcn_readlane(inEnd, j);
+                }
+                op = enc_page_close(pg, op, dst, src, n, budget, consumed);
+                qCnt = 0;
+                return;
+            }
+            pg.in = __builtin_amdgcn_readlane(inEnd, qCnt - 1);
+        }
         if (SEG) {
             // segment mode: the sequences go to the segment's list; a second kernel stitches the lists into the block
             if (lane < qCnt) seg->list[seg->count + (uint32_t)lane] = seg_pack(qStart + seg->base, qLen, qOff);
@@ -463,6 +528,7 @@ __device__ int encode_block_wave(const uint8_t *src, int n, uint8_t *dst, int ac
         if (lane == 0) *(volatile int *)op = qPrev + qStart + qLen + qOff;      // (experiment: what the emission costs)
 #endif
         qCnt = 0;
+        if constexpr (BUDGET) pg.qMax = enc_page_queue_max(budget - (int)(op - dst));
     };
     // one sequence whose fields are wave-uniform, into slot qCnt (the caller has made room)
     auto park_uniform = [&](const int prev, const int start, const int len, const int off) {
@@ -1065,6 +1131,10 @@ __device__ int encode_block_wave(const uint8_t *src, int n, uint8_t *dst, int ac
                 }
             }
             ENC_LAP(2);
+            if constexpr (BUDGET) {
+                if (qCnt + (int)__builtin_popcountll(sel0) + (int)__builtin_popcountll(sel1) > pg.qMax) flush_queue();
+                if (pg.done) go = false;                       // (what this pair still parks is dropped with the queue)
+            } else
             if (qCnt + (int)__builtin_popcountll(sel0) + (int)__builtin_popcountll(sel1) > LZ4_WAVE) flush_queue();
             const bool cov0 = lw_finish(W0, pos0, pos0 - 8u, (uint32_t)lane + 1u, sel0, anchor, 0);
             const bool cov1 = lw_finish(W1, pos1, pos1 - 8u, (uint32_t)lane + 65u, sel1, pMid, 1);
@@ -1085,6 +1155,7 @@ __device__ int encode_block_wave(const uint8_t *src, int n, uint8_t *dst, int ac
 #endif  // ENC_NO_PIPE
         (void)group_window; (void)pair_window; (void)pipe_can_issue; (void)pair_can_issue;   // (one form per instantiation)
         while (p < mfl) {
+            if constexpr (BUDGET) { if (pg.done) break; }
             const int64_t step = (int64_t)(missAcc >> 6);
             if (step == 1) {
 #ifndef ENC_NO_PIPE
@@ -1292,6 +1363,7 @@ __device__ int encode_block_wave(const uint8_t *src, int n, uint8_t *dst, int ac
                 // per field: selected lanes go to [qCnt, qCnt+k), the others fill the remaining lanes) ----
                 {
                     const int k = (int)__builtin_popcountll(selm);
+                    if constexpr (BUDGET) { if (qCnt + k > pg.qMax) flush_queue(); } else
                     if (qCnt + k > LZ4_WAVE) flush_queue();
                     const int rank = (int)__builtin_amdgcn_mbcnt_hi((uint32_t)(selm >> 32),
                                           __builtin_amdgcn_mbcnt_lo((uint32_t)selm, 0u));
@@ -1374,6 +1446,7 @@ __device__ int encode_block_wave(const uint8_t *src, int n, uint8_t *dst, int ac
             }
 #endif
             // ---- queue the sequence (written out by flush_queue) ----
+            if constexpr (BUDGET) { if (qCnt >= pg.qMax) flush_queue(); } else
             if (qCnt == LZ4_WAVE) flush_queue();
             park_uniform(anchor, mpos, ml, mpos - cpos);
             anchor = mpos + ml;
@@ -1388,6 +1461,18 @@ __device__ int encode_block_wave(const uint8_t *src, int n, uint8_t *dst, int ac
 #ifdef ENC_STATS
     if (stats && lane == 0) for (int i = 0; i < 8; i++) atomicAdd(&stats[i], est[i]);
 #endif
+    if constexpr (BUDGET) {
+        if (!pg.done) flush_queue();
+        if (!pg.done) {
+            // every sequence is out, with a valid cut behind the last (pageIn == anchor): the block's own end if it fits
+            const int run = n - anchor;
+            if (run + 1 + (int)ext_len_bytes((uint32_t)run) <= budget - (int)(op - dst)) {
+                op = emit_last_literals(op, src + anchor, (uint32_t)run);
+                *consumed = n;
+            } else op = enc_page_close(pg, op, dst, src, n, budget, consumed);
+        }
+        return (int)(op - dst);
+    }
     flush_queue();
     if (SEG) return anchor + seg->base;
     // ---- last literals (:1204-1231) ----

@@ -856,24 +856,26 @@ extern "C" int mi355lz4_decompress_dict(mi355lz4_ctx *c, const uint8_t *framedIn
 // Host-buffer form of mi355lz4_compress_pages_device: inputs in host memory, one pageSize for all.  One group, synchronous, as the
 // partial form: the inputs go up packed back to back, the device call fills engine-owned pages, the four arrays come back, and of
 // every page that was written its bytes [0, headerKind + compLen) -- the rest of the caller's `pages` stays as it was.
-extern "C" int mi355lz4_compress_pages(mi355lz4_ctx *c, const uint8_t *const *src, const int32_t *srcLen, int nInputs, int pageSize,
-                                       int maxPages, int headerKind, uint8_t *pages, size_t pageStride, int32_t *pageSrcLen,
-                                       int32_t *pageCompLen, int32_t *nPages, int32_t *consumed)
+// (fast: mi355lz4_compress_pages_fast_device with `accel` makes the pages; `who` names the caller in the messages)
+static int pages_host(mi355lz4_ctx *c, const char *who, bool fast, int accel, const uint8_t *const *src, const int32_t *srcLen,
+                      int nInputs, int pageSize, int maxPages, int headerKind, uint8_t *pages, size_t pageStride, int32_t *pageSrcLen,
+                      int32_t *pageCompLen, int32_t *nPages, int32_t *consumed)
 {
     if (!c) return fail(MI355LZ4_E_ARG, "null ctx");
     if (nInputs < 0 || maxPages < 1 || pageSize < 1 || (headerKind != 0 && headerKind != 4 && headerKind != 8) ||
         pageStride < (size_t)headerKind + (size_t)pageSize)
-        return fail(MI355LZ4_E_ARG, "compress_pages: bad arguments");
-    if (c->blockChecksum) return fail(MI355LZ4_E_ARG, "compress_pages: block checksums are on; pages carry no trailer");
+        return fail(MI355LZ4_E_ARG, "%s: bad arguments", who);
+    if (c->blockChecksum) return fail(MI355LZ4_E_ARG, "%s: block checksums are on; pages carry no trailer", who);
+    if (fast && c->compLevel != 0) return fail(MI355LZ4_E_ARG, "%s: compression level %d; fast pages are level 0's encoder", who, c->compLevel);
     if (nInputs == 0) return MI355LZ4_OK;
     if (!src || !srcLen || !pages || !pageSrcLen || !pageCompLen || !nPages || !consumed)
-        return fail(MI355LZ4_E_ARG, "compress_pages: null pointer");
+        return fail(MI355LZ4_E_ARG, "%s: null pointer", who);
     const size_t n = (size_t)nInputs, np = n * (size_t)maxPages;
     std::vector<uint64_t> off(n);
     uint64_t total = 0;
     for (size_t i = 0; i < n; i++) {
         if (srcLen[i] < 0 || srcLen[i] > MI355LZ4_MAX_INPUT_SIZE || (srcLen[i] > 0 && !src[i]))
-            return fail(MI355LZ4_E_ARG, "compress_pages: input %zu: bad length or null pointer", i);
+            return fail(MI355LZ4_E_ARG, "%s: input %zu: bad length or null pointer", who, i);
         off[i] = total;
         total += (uint64_t)srcLen[i];
     }
@@ -896,9 +898,14 @@ extern "C" int mi355lz4_compress_pages(mi355lz4_ctx *c, const uint8_t *const *sr
     HIP_TRY(hipMemcpyAsync(c->lenB.p, ps.data(), n * 4, hipMemcpyHostToDevice, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));          // (the vectors are pageable memory)
     int32_t *dSrcLen = (int32_t *)c->res.p, *dCompLen = dSrcLen + np, *dPages = dCompLen + np, *dCons = dPages + n;
-    r = mi355lz4_compress_pages_device(c, (const uint8_t *)c->in.p, (const uint64_t *)c->offA.p, (const int32_t *)c->lenA.p, nInputs,
-                                       (const int32_t *)c->lenB.p, maxPages, headerKind, (uint8_t *)c->out.p, pageStride, dSrcLen,
-                                       dCompLen, dPages, dCons);
+    if (fast)
+        r = mi355lz4_compress_pages_fast_device(c, (const uint8_t *)c->in.p, (const uint64_t *)c->offA.p, (const int32_t *)c->lenA.p,
+                                                nInputs, (const int32_t *)c->lenB.p, maxPages, accel, headerKind, (uint8_t *)c->out.p,
+                                                pageStride, dSrcLen, dCompLen, dPages, dCons);
+    else
+        r = mi355lz4_compress_pages_device(c, (const uint8_t *)c->in.p, (const uint64_t *)c->offA.p, (const int32_t *)c->lenA.p, nInputs,
+                                           (const int32_t *)c->lenB.p, maxPages, headerKind, (uint8_t *)c->out.p, pageStride, dSrcLen,
+                                           dCompLen, dPages, dCons);
     if (r) return r;
     std::vector<int32_t> back(2 * np + 2 * n);
     HIP_TRY(hipMemcpyAsync(back.data(), c->res.p, back.size() * 4, hipMemcpyDeviceToHost, c->stream));
@@ -917,6 +924,23 @@ extern "C" int mi355lz4_compress_pages(mi355lz4_ctx *c, const uint8_t *const *sr
     }
     HIP_TRY(hipStreamSynchronize(c->stream));
     return MI355LZ4_OK;
+}
+
+extern "C" int mi355lz4_compress_pages(mi355lz4_ctx *c, const uint8_t *const *src, const int32_t *srcLen, int nInputs, int pageSize,
+                                       int maxPages, int headerKind, uint8_t *pages, size_t pageStride, int32_t *pageSrcLen,
+                                       int32_t *pageCompLen, int32_t *nPages, int32_t *consumed)
+{
+    return pages_host(c, "compress_pages", false, 0, src, srcLen, nInputs, pageSize, maxPages, headerKind, pages, pageStride, pageSrcLen,
+                      pageCompLen, nPages, consumed);
+}
+
+// Host-buffer form of mi355lz4_compress_pages_fast_device: the same single group, the pages by the wave encoder at `accel`.
+extern "C" int mi355lz4_compress_pages_fast(mi355lz4_ctx *c, const uint8_t *const *src, const int32_t *srcLen, int nInputs, int pageSize,
+                                            int maxPages, int accel, int headerKind, uint8_t *pages, size_t pageStride,
+                                            int32_t *pageSrcLen, int32_t *pageCompLen, int32_t *nPages, int32_t *consumed)
+{
+    return pages_host(c, "compress_pages_fast", true, accel, src, srcLen, nInputs, pageSize, maxPages, headerKind, pages, pageStride,
+                      pageSrcLen, pageCompLen, nPages, consumed);
 }
 
 // the size pass over blocks in host memory: H2D, mi355lz4_decoded_size_device, sizes back; synchronous

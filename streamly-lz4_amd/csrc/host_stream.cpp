@@ -320,18 +320,19 @@ std::vector<Array> Engine::compressWithDictFast(const BlockConfig &cfg, const st
     return out;
 }
 
-// host arrays -> device, one chain of pages per array, the written pages back (mi355lz4_compress_pages)
-std::vector<std::vector<Array>> Engine::compressPages(const BlockConfig &cfg, const std::vector<Array> &arrays, int pageSize, int maxPages,
-                                                      std::vector<int32_t> *consumed)
+// host arrays -> device, one chain of pages per array, the written pages back (mi355lz4_compress_pages; accel > 0:
+// mi355lz4_compress_pages_fast at that acceleration)
+static std::vector<std::vector<Array>> pages_arrays(mi355lz4_ctx *ctx_, const char *who, int accel, const BlockConfig &cfg,
+                                                    const std::vector<Array> &arrays, int pageSize, int maxPages, std::vector<int32_t> *consumed)
 {
-    if (cfg.blockChecksum) throw Error("compressPages: pages carry no block checksum");
-    if (pageSize < 1 || maxPages < 1) throw Error("compressPages: pageSize and maxPages must be at least 1");
+    if (cfg.blockChecksum) throw Error(std::string(who) + ": pages carry no block checksum");
+    if (pageSize < 1 || maxPages < 1) throw Error(std::string(who) + ": pageSize and maxPages must be at least 1");
     const int meta = metaSize(cfg);
     const size_t n = arrays.size(), stride = (size_t)meta + (size_t)pageSize;
     std::vector<const uint8_t *> ptrs;
     std::vector<int32_t> lens;
     for (const Array &a : arrays) {
-        if (a.size() > (size_t)MI355LZ4_MAX_INPUT_SIZE) throw Error("compressPages: array of " + std::to_string(a.size()) + " bytes");
+        if (a.size() > (size_t)MI355LZ4_MAX_INPUT_SIZE) throw Error(std::string(who) + ": array of " + std::to_string(a.size()) + " bytes");
         ptrs.push_back(a.data());
         lens.push_back((int32_t)a.size());
     }
@@ -339,9 +340,12 @@ std::vector<std::vector<Array>> Engine::compressPages(const BlockConfig &cfg, co
     lens.push_back(0);
     std::vector<uint8_t> pages(n * (size_t)maxPages * stride + 1);
     std::vector<int32_t> srcLen(n * (size_t)maxPages + 1), compLen(n * (size_t)maxPages + 1), count(n + 1), cons(n + 1);
-    if (mi355lz4_compress_pages(ctx_, ptrs.data(), lens.data(), (int)n, pageSize, maxPages, meta, pages.data(), stride, srcLen.data(),
-                                compLen.data(), count.data(), cons.data()) != MI355LZ4_OK)
-        throw Error(std::string("compressPages: ") + mi355lz4_last_error());
+    const int rc = accel > 0 ? mi355lz4_compress_pages_fast(ctx_, ptrs.data(), lens.data(), (int)n, pageSize, maxPages, accel, meta, pages.data(),
+                                                            stride, srcLen.data(), compLen.data(), count.data(), cons.data())
+                             : mi355lz4_compress_pages(ctx_, ptrs.data(), lens.data(), (int)n, pageSize, maxPages, meta, pages.data(), stride,
+                                                       srcLen.data(), compLen.data(), count.data(), cons.data());
+    if (rc != MI355LZ4_OK)
+        throw Error(std::string(who) + ": " + mi355lz4_last_error());
     std::vector<std::vector<Array>> out(n);
     for (size_t i = 0; i < n; i++)
         for (size_t k = 0; k < (size_t)count[i]; k++) {
@@ -350,6 +354,19 @@ std::vector<std::vector<Array>> Engine::compressPages(const BlockConfig &cfg, co
         }
     if (consumed) consumed->assign(cons.begin(), cons.begin() + (long)n);
     return out;
+}
+
+std::vector<std::vector<Array>> Engine::compressPages(const BlockConfig &cfg, const std::vector<Array> &arrays, int pageSize, int maxPages,
+                                                      std::vector<int32_t> *consumed)
+{
+    return pages_arrays(ctx_, "compressPages", 0, cfg, arrays, pageSize, maxPages, consumed);
+}
+
+// ... the pages by the engine's own encoder with an output budget (mi355lz4_compress_pages_fast)
+std::vector<std::vector<Array>> Engine::compressPagesFast(const BlockConfig &cfg, const std::vector<Array> &arrays, int pageSize, int maxPages,
+                                                          std::vector<int32_t> *consumed, int accel)
+{
+    return pages_arrays(ctx_, "compressPagesFast", accel < 1 ? 1 : accel, cfg, arrays, pageSize, maxPages, consumed);
 }
 
 std::vector<Array> Engine::decompressWithDict(const BlockConfig &cfg, const std::vector<Array> &blocks, const Array &dict)

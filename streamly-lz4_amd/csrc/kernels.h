@@ -207,6 +207,12 @@ struct PagesArgs {
     int32_t *consumed;           // [nInputs]
 };
 #define PAGES_MAX_INPUT 0x7E000000   // LZ4_MAX_INPUT_SIZE (MI355LZ4_MAX_INPUT_SIZE in include/mi355lz4.h)
+// the same pages from the wave encoder with an output budget (mi355lz4_compress_pages_fast_device; kernels/encode.inc, k_pages_fast):
+// pageCompLen is the page's length, pageSize[i] its budget
+struct PagesFastArgs {
+    PagesArgs p;
+    int accel;                   // clamped to 1..65537
+};
 
 // a prepared high-compression dictionary (mi355lz4_hcdict; kernels/encode.inc, k_hcdict_build): the image of encode_hc.hpp's chain[]
 // and head[] after the inserts of the kept bytes' positions [0, keep - 3), the count, and the object's own copy of the bytes
@@ -318,6 +324,8 @@ void launch_cstreams_load_dict(uint8_t *slotState, const uint8_t *dict, int len,
 void launch_exact_dict(const ExactDictArgs &a, hipStream_t s);
 // fixed-size output pages: one wave per input walks its chain of pages, each from a zeroed table
 void launch_exact_pages(const PagesArgs &a, hipStream_t s);
+// the same chains, each page by the wave encoder with an output budget: one wave per input at k_encode's occupancy
+void launch_pages_fast(const PagesFastArgs &a, hipStream_t s);
 // a prepared high-compression dictionary: one workgroup builds the image (HCDICT_IMAGE_BYTES) from the last min(len, 65536) bytes of dict
 void launch_hcdict_build(uint8_t *image, const uint8_t *dict, int len, hipStream_t s);
 // compression levels 1..12 against that image: a persistent grid of encode_hc_dict_grid(nBlocks) workgroups, one window of a.stage each

@@ -759,3 +759,56 @@ void launch_exact_pages(const PagesArgs &a, hipStream_t s)
     if (a.nInputs <= 0) return;
     hipLaunchKernelGGL(k_exact_pages, dim3((unsigned)a.nInputs), dim3(LZ4_WAVE), 0, s, a);
 }
+
+// ---------------------------------------------------------------------------
+// K2, fast fixed-size output pages (mi355lz4_compress_pages_fast_device, DESIGN.md 7m).  k_exact_pages' chain, layout and stops;
+// a page is made by the wave encoder with an output budget (encode_block_wave<.., BUDGET>): of the block that compress_batch_device
+// writes for the next min(rem, 65536) bytes it holds the longest prefix of sequences that leaves room for a valid end, closed by the
+// literal run that fills the page.  k_encode's occupancy and table, which the encoder zeroes per page.
+// ---------------------------------------------------------------------------
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(ENC_WAVES_PER_EU, ENC_WAVES_PER_EU))) void k_pages_fast(PagesFastArgs y)
+{
+    __shared__ __attribute__((aligned(16))) uint16_t table[ENC_TABLE_ENTRIES + ENC_LDS_PAD + (ENC_STAGE ? 128 : 0)];
+    const PagesArgs x = y.p;
+    const int lane = lane_id();
+    const int i = (int)blockIdx.x;
+    const int n = uni(x.srcLen[i]);
+    const int T = uni(x.pageSize[i]);
+    if (n < 0 || n > PAGES_MAX_INPUT || (T > 0 && (uint64_t)x.headerKind + (uint64_t)T > (uint64_t)x.pageStride)) {
+        if (lane == 0) x.nPages[i] = 0;
+        return;
+    }
+    const uint8_t *src = x.src + uni64((int64_t)x.srcOff[i]);
+    const uint64_t first = (uint64_t)i * (uint64_t)x.maxPages;
+    int pos = 0, k = 0;
+    while (k < x.maxPages && T >= 1) {                                  // T < 1: no page
+        const int rem = n - pos;
+        uint8_t *page = x.pages + (first + (uint64_t)k) * (uint64_t)x.pageStride;
+        uint8_t *dst = page + x.headerKind;
+        int c, used = 0;
+        if (rem == 0 || T == 1) {
+            c = enc_empty_block(dst, lane == 0);                        // an empty input, or room for the zero token alone: takes nothing
+        } else {
+            // (one call site: the encoder is inlined, and its scalar operands stay scalar)
+            c = encode_block_wave<uint16_t, false, false, true, false, true>(src + pos, min(rem, 65536), dst, y.accel, table, nullptr, 0,
+                                                                             nullptr, T, &used);
+            wave_fence();                                               // the next page zeroes the table this one read
+        }
+        if (lane == 0) {
+            if (x.headerKind >= 4) store_le32(page, c);
+            if (x.headerKind == 8) store_le32(page + 4, used);
+            x.pageCompLen[first + (uint64_t)k] = c;
+            x.pageSrcLen[first + (uint64_t)k] = used;
+        }
+        k++;
+        pos += used;
+        if (pos >= n || used == 0) break;
+    }
+    if (lane == 0) { x.nPages[i] = k; x.consumed[i] = pos; }
+}
+
+void launch_pages_fast(const PagesFastArgs &a, hipStream_t s)
+{
+    if (a.p.nInputs <= 0) return;
+    hipLaunchKernelGGL(k_pages_fast, dim3((unsigned)a.p.nInputs), dim3(64), 0, s, a);
+}

@@ -182,6 +182,10 @@ def _load():
     sig("mi355lz4_compress_pages_device", C.c_int, vp, vp, vp, vp, C.c_int, vp, C.c_int, C.c_int, vp, C.c_size_t, vp, vp, vp, vp)
     sig("mi355lz4_compress_pages", C.c_int, vp, C.POINTER(_u8p), _i32p, C.c_int, C.c_int, C.c_int, C.c_int, _u8p, C.c_size_t,
         _i32p, _i32p, _i32p, _i32p)
+    sig("mi355lz4_compress_pages_fast_device", C.c_int, vp, vp, vp, vp, C.c_int, vp, C.c_int, C.c_int, C.c_int, vp, C.c_size_t,
+        vp, vp, vp, vp)
+    sig("mi355lz4_compress_pages_fast", C.c_int, vp, C.POINTER(_u8p), _i32p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _u8p,
+        C.c_size_t, _i32p, _i32p, _i32p, _i32p)
     # legacy face (include/lz4.h)
     sig("LZ4_createStream", vp)
     sig("LZ4_freeStream", C.c_int, vp)
@@ -245,6 +249,7 @@ DECLARED_SYMBOLS = [
     "mi355lz4_compress_hcdict_device", "mi355lz4_compress_hcdict",
     "mi355lz4_compress_fastdict_device", "mi355lz4_compress_fastdict",
     "mi355lz4_compress_pages_device", "mi355lz4_compress_pages",
+    "mi355lz4_compress_pages_fast_device", "mi355lz4_compress_pages_fast",
     "LZ4_createStream", "LZ4_freeStream", "LZ4_createStreamDecode", "LZ4_freeStreamDecode", "LZ4_compressBound",
     "LZ4_compress_fast_continue", "LZ4_decompress_safe_continue",
 ]
@@ -1014,7 +1019,24 @@ class Engine:
             int(header_kind), _dptr(pages), int(page_stride), _dptr(page_src_len), _dptr(page_comp_len), _dptr(n_pages),
             _dptr(consumed)), "compress_pages_device")
 
-    def compress_pages(self, inputs, page_size, max_pages, header_kind=8, page_stride=None):
+    def compress_pages_fast_device(self, src, src_off, src_len, n_inputs, page_size, max_pages, pages, page_stride, page_src_len,
+                                   page_comp_len, n_pages, consumed, header_kind=8, accel=1):
+        """compress_pages_device at the engine's speed: the same arguments, layout, chains and result arrays, every page made by
+        the level-0 wave encoder with page_size[i] as its output budget -- a prefix of the sequences of the block that
+        compress_batch_device writes for the next min(remaining, 65536) bytes, closed by the literal run that fills the page.
+        Valid, independently decodable pages; not LZ4_compress_destSize's bytes.  Only enqueues (include/mi355lz4.h,
+        mi355lz4_compress_pages_fast_device)."""
+        self._follow_torch()
+        _check(lib.mi355lz4_compress_pages_fast_device(
+            self.ctx, _dptr(src), _dptr(src_off), _dptr(src_len), int(n_inputs), _dptr(page_size), int(max_pages), int(accel),
+            int(header_kind), _dptr(pages), int(page_stride), _dptr(page_src_len), _dptr(page_comp_len), _dptr(n_pages),
+            _dptr(consumed)), "compress_pages_fast_device")
+
+    def compress_pages_fast(self, inputs, page_size, max_pages, header_kind=8, page_stride=None, accel=1):
+        """compress_pages with the pages of compress_pages_fast_device; mi355lz4_compress_pages_fast."""
+        return self.compress_pages(inputs, page_size, max_pages, header_kind, page_stride, _fast_accel=int(accel))
+
+    def compress_pages(self, inputs, page_size, max_pages, header_kind=8, page_stride=None, _fast_accel=None):
         """inputs: list of bytes-like, every one cut into pages of page_size compressed bytes.  Returns a list, per input, of
         (pages, consumed): pages a list of (page bytes with its header, bytes of the input it holds); mi355lz4_compress_pages."""
         n = len(inputs)
@@ -1029,10 +1051,14 @@ class Engine:
         pcomp = np.zeros(np_, dtype=np.int32)
         cnt = np.zeros(max(n, 1), dtype=np.int32)
         cons = np.zeros(max(n, 1), dtype=np.int32)
-        _check(lib.mi355lz4_compress_pages(self.ctx, ptrs, lens.ctypes.data_as(_i32p), n, int(page_size), int(max_pages),
-                                           int(header_kind), pages.ctypes.data_as(_u8p), int(page_stride),
-                                           psrc.ctypes.data_as(_i32p), pcomp.ctypes.data_as(_i32p), cnt.ctypes.data_as(_i32p),
-                                           cons.ctypes.data_as(_i32p)), "compress_pages")
+        tail = (int(header_kind), pages.ctypes.data_as(_u8p), int(page_stride), psrc.ctypes.data_as(_i32p),
+                pcomp.ctypes.data_as(_i32p), cnt.ctypes.data_as(_i32p), cons.ctypes.data_as(_i32p))
+        if _fast_accel is None:
+            _check(lib.mi355lz4_compress_pages(self.ctx, ptrs, lens.ctypes.data_as(_i32p), n, int(page_size), int(max_pages),
+                                               *tail), "compress_pages")
+        else:
+            _check(lib.mi355lz4_compress_pages_fast(self.ctx, ptrs, lens.ctypes.data_as(_i32p), n, int(page_size), int(max_pages),
+                                                    _fast_accel, *tail), "compress_pages_fast")
         res = []
         for i in range(n):
             pl = []
