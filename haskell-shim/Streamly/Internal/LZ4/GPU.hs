@@ -64,6 +64,8 @@ module Streamly.Internal.LZ4.GPU
     , compressChunksPaged
     , c_compressPagesFastDevice
     , compressChunksPagedFast
+    , c_compressPagesFastDictDevice
+    , compressChunksPagedWithDictFast
     , DecompressStreams
     , newDecompressStreams
     , freeDecompressStreams
@@ -239,6 +241,15 @@ foreign import ccall safe "mi355lz4.h mi355lz4_compress_pages_fast_device"
 foreign import ccall safe "mi355lz4.h mi355lz4_compress_pages_fast"
     c_compressPagesFast
         :: Ptr C_Engine -> Ptr (Ptr Word8) -> Ptr Int32 -> CInt -> CInt -> CInt -> CInt -> CInt
+        -> Ptr Word8 -> CSize -> Ptr Int32 -> Ptr Int32 -> Ptr Int32 -> Ptr Int32 -> IO CInt
+-- ... and with the dictionary of a loaded 'HcDict' in front of every page: the object in front of the inputs, the rest as above.
+foreign import ccall safe "mi355lz4.h mi355lz4_compress_pages_fastdict_device"
+    c_compressPagesFastDictDevice
+        :: Ptr C_Engine -> Ptr C_HcDict -> Ptr Word8 -> Ptr Word64 -> Ptr Int32 -> CInt -> Ptr Int32 -> CInt -> CInt -> CInt
+        -> Ptr Word8 -> CSize -> Ptr Int32 -> Ptr Int32 -> Ptr Int32 -> Ptr Int32 -> IO CInt
+foreign import ccall safe "mi355lz4.h mi355lz4_compress_pages_fastdict"
+    c_compressPagesFastDict
+        :: Ptr C_Engine -> Ptr C_HcDict -> Ptr (Ptr Word8) -> Ptr Int32 -> CInt -> CInt -> CInt -> CInt -> CInt
         -> Ptr Word8 -> CSize -> Ptr Int32 -> Ptr Int32 -> Ptr Int32 -> Ptr Int32 -> IO CInt
 
 -- Decoded sizes without decoding (device pointers in, device pointers out; only enqueues): what every block of a
@@ -656,6 +667,16 @@ compressChunksPagedFast
     :: Engine -> Int -> BlockConfig -> Int -> Int -> [Array.Array Word8] -> IO [([Array.Array Word8], Int)]
 compressChunksPagedFast (Engine eng) accel =
     pagedWith "compressChunksPagedFast" (\pSrc pLen n ps mp -> c_compressPagesFast eng pSrc pLen n ps mp (fromIntegral accel))
+
+-- | 'compressChunksPagedFast' with the dictionary of a loaded 'HcDict' in front of every page
+-- (@mi355lz4_compress_pages_fastdict@): a page is a prefix of the block 'compressChunksWithDictFast' writes for the next 64 KiB at
+-- the most, closed by the literal run that fills the page, and decodes with the same dictionary.  Small records fill about half
+-- as many pages as without the dictionary.  The engine must be at level 0, block checksums off; the object is only read.
+compressChunksPagedWithDictFast
+    :: Engine -> HcDict -> Int -> BlockConfig -> Int -> Int -> [Array.Array Word8] -> IO [([Array.Array Word8], Int)]
+compressChunksPagedWithDictFast (Engine eng) (HcDict hd) accel =
+    pagedWith "compressChunksPagedWithDictFast"
+        (\pSrc pLen n ps mp -> c_compressPagesFastDict eng hd pSrc pLen n ps mp (fromIntegral accel))
 
 pagedWith
     :: String

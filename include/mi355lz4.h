@@ -116,7 +116,8 @@ typedef struct mi355lz4_ctx mi355lz4_ctx;
  *   pageSrcLen[] and pageCompLen[] only at the entries of pages written; nPages[i]; consumed[i] unless the input is skipped
  *   (nPages[i] = 0 is then all that is written for it).  Never src, srcOff, srcLen or pageSize.  _compress_pages writes the same
  *   ranges of the caller's host arrays and nothing else.  _compress_pages_fast_device and _compress_pages_fast: the same ranges
- *   and the same rules.
+ *   and the same rules.  _compress_pages_fastdict_device and _compress_pages_fastdict: the same ranges and the same rules again,
+ *   and never the mi355lz4_hcdict, which is only read.
  * Scratch that a call needs is the engine's own. */
 
 /* ---- engine lifecycle ------------------------------------------------ */
@@ -852,6 +853,55 @@ int mi355lz4_compress_pages_fast_device(mi355lz4_ctx *ctx, const uint8_t *src, c
 int mi355lz4_compress_pages_fast(mi355lz4_ctx *ctx, const uint8_t *const *src, const int32_t *srcLen, int nInputs, int pageSize,
                                  int maxPages, int accel, int headerKind, uint8_t *pages, size_t pageStride,
                                  int32_t *pageSrcLen, int32_t *pageCompLen, int32_t *nPages, int32_t *consumed);
+
+/* ---- fast fixed-size output pages against a prepared dictionary ---------------------------------------------------------
+ * Every page of the calls above starts from an empty table, which costs small records most of what a dictionary gives them.
+ * These calls put the dictionary of a loaded mi355lz4_hcdict in front of every page.  Everything that
+ * mi355lz4_compress_pages_fast_device and mi355lz4_compress_pages_fast define stays: the layout pages + (i*maxPages + k) *
+ * pageStride, headerKind 0 / 4 / 8, pageSrcLen, pageCompLen, nPages and consumed, the chain stops (input consumed; maxPages
+ * reached; pageSize < 1: no page; pageSize == 1: a zero token that consumes 0, counted, the chain ends), the per-input skips
+ * (nPages[i] = 0 and nothing else), accel clamped to 1..65537, the enqueue-only behaviour with srcLen and pageSize unread on the
+ * host.  hd is checked as in mi355lz4_compress_fastdict_device: a null hd or one created on another device is MI355LZ4_E_ARG.
+ * The compression level must be 0 and block checksums off: both are MI355LZ4_E_ARG before any device work.  The object is only
+ * read, and the sharing rule of a loaded mi355lz4_hcdict applies.  A headerKind 8 page is an ordinary block for
+ * mi355lz4_decompress_dict_device with the same dictionary, and every page decodes with LZ4_decompress_safe_usingDict.
+ * DESIGN.md 7n.  What a page holds:
+ * Let keep be the bytes the last mi355lz4_hcdict_load kept, pos what pages 0..k-1 consumed, n = min(srcLen[i] - pos, 65536),
+ * T = pageSize[i], and E the block that mi355lz4_compress_fastdict_device writes for src_i[pos, pos + n) with the same hd and the
+ * same accel at a maxBlockLen of at most 65536: sequences s_0 .. s_{m-1} and a last literal run.  If E is at most T bytes, the
+ * page is E and consumes n.  Otherwise the page is s_0 .. s_j of E, byte for byte, and one literal run of
+ * r_j = min(n - inEnd_j, lit(T - outEnd_j)) bytes behind them, with outEnd_j, inEnd_j and lit() as above; it consumes
+ * inEnd_j + r_j.  A cut behind s_j is valid when outEnd_j + 1 <= T, r_j >= 5, matchStart_j + 12 <= inEnd_j + r_j and
+ * inEnd_j + r_j >= 13.  j + 1 is the number of leading sequences whose cuts are all valid; j = -1 is the all-literals page.
+ * Two points differ from the calls above, both because of the dictionary.  The fourth condition: a block against a dictionary
+ * may open with a match at its first byte, and a page that consumes fewer than 13 bytes must be literals only (the rule
+ * LZ4_compress_fast keeps, cbits/lz4.c:221).  The leading run instead of the last valid cut: with the fourth condition valid cuts
+ * no longer form a prefix -- a match of 4 bytes at position 0 and one of 7 directly behind it, T = 12: the cut behind the first
+ * is not valid, the one behind the second is -- and the page must not depend on how the encoder batches its sequences.
+ * Every page is a valid LZ4 block on its own given the dictionary (keep bytes of window in front of it), and the decoded pages of an
+ * input concatenate to its consumed prefix.  A page that leaves input behind and was cut by T (not by the 64 KiB bound) has
+ * compLen >= T - 1 and consumes at least (T - 1) - (T + 240) / 256.
+ * With keep == 0 the calls are legal: E is then mi355lz4_compress_fastdict_device's block for an empty dictionary.
+ * A persistent grid of single waves walks the chains (k_pages_fastdict: mi355lz4_compress_fastdict_device's grid and staging
+ * windows, MI355LZ4_FASTDICT_WAVES included; one chain at a time per wave; every page of 13 input bytes and more copies its slice
+ * of the input, 64 KiB at the most, behind the dictionary).  Measured once (scripts/dictpages_rate.py, profiles/dictpages_rate.json;
+ * medians of 5 event-timed calls, all three calls in one session, a 64 KiB dictionary): 16384 text records of 4 KiB into 1 KiB pages in
+ * 0.84 ms, 48816 pages, 70.0 % full, ratio 1.917, where mi355lz4_compress_pages_fast_device takes 0.66 ms for 65536 pages, 88.6 % full,
+ * ratio 1.129, and mi355lz4_compress_fastdict_device without pages 0.61 ms at ratio 1.921; 2560 records of 64 KiB into 4 KiB pages in
+ * 1.92 ms, 23040 pages, 93.1 % full, ratio 1.909, against 1.46 ms, 30720 pages, 95.6 % full, ratio 1.395, and 1.47 ms at 1.928.
+ * No rate is part of the contract. */
+int mi355lz4_compress_pages_fastdict_device(mi355lz4_ctx *ctx, const mi355lz4_hcdict *hd,
+                                            const uint8_t *src, const uint64_t *srcOff, const int32_t *srcLen, int nInputs,
+                                            const int32_t *pageSize, int maxPages, int accel, int headerKind,
+                                            uint8_t *pages, size_t pageStride,
+                                            int32_t *pageSrcLen, int32_t *pageCompLen, int32_t *nPages, int32_t *consumed);
+/* Host-buffer form, synchronous: mi355lz4_compress_pages_fast with hd in front of src, the device call above in its one group,
+ * and its host-side checks; a null hd, a compression level other than 0 or block checksums are MI355LZ4_E_ARG before anything is
+ * enqueued. */
+int mi355lz4_compress_pages_fastdict(mi355lz4_ctx *ctx, const mi355lz4_hcdict *hd,
+                                     const uint8_t *const *src, const int32_t *srcLen, int nInputs, int pageSize, int maxPages,
+                                     int accel, int headerKind, uint8_t *pages, size_t pageStride,
+                                     int32_t *pageSrcLen, int32_t *pageCompLen, int32_t *nPages, int32_t *consumed);
 
 /* ---- many linked decode streams, continued across calls ---------------------------------------------------------------
  * The decode-side counterpart of mi355lz4_cstreams, and the device-resident form of the reference's one LZ4_streamDecode_t

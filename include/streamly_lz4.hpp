@@ -138,6 +138,12 @@ public:
     // decodable pages, not LZ4_compress_destSize's bytes; highly compressible input gives pages that are not full.  Level 0 only.
     std::vector<std::vector<Array>> compressPagesFast(const BlockConfig &cfg, const std::vector<Array> &arrays, int pageSize, int maxPages,
                                                       std::vector<int32_t> *consumed = nullptr, int accel = 1);
+    // ... with the dictionary of a loaded HcDict in front of every page (mi355lz4_compress_pages_fastdict): a page is a prefix of the
+    // block compressWithDictFast writes for the next 64 KiB at the most, and decodes with decompressWithDict and the same dictionary.
+    // Small records fill about half as many pages as without the dictionary.  Level 0 only; the object is only read.
+    std::vector<std::vector<Array>> compressPagesWithDictFast(const BlockConfig &cfg, const std::vector<Array> &arrays, const class HcDict &hd,
+                                                              int pageSize, int maxPages, std::vector<int32_t> *consumed = nullptr,
+                                                              int accel = 1);
 private:
     mi355lz4_ctx *ctx_ = nullptr;
     size_t batch_;

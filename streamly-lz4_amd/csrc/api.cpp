@@ -1248,6 +1248,40 @@ extern "C" int mi355lz4_compress_fastdict_device(mi355lz4_ctx *c, const mi355lz4
     return encode_launched(c, x.e, "fast dict launch");
 }
 
+// Fast pages against the same object: mi355lz4_compress_pages_fast_device's chains, every page made by the wave
+// encoder with the dictionary in front of it and an output budget (k_pages_fastdict: the grid and the windows of the call above,
+// sized for a block of 65536 bytes, which is the most a page holds).  Enqueues only; srcLen and pageSize stay unread on the host.
+extern "C" int mi355lz4_compress_pages_fastdict_device(mi355lz4_ctx *c, const mi355lz4_hcdict *hd, const uint8_t *src,
+                                                       const uint64_t *srcOff, const int32_t *srcLen, int nInputs,
+                                                       const int32_t *pageSize, int maxPages, int accel, int headerKind,
+                                                       uint8_t *pages, size_t pageStride, int32_t *pageSrcLen, int32_t *pageCompLen,
+                                                       int32_t *nPages, int32_t *consumed)
+{
+    if (int r = hcdict_same_device(c, hd, "compress_pages_fastdict_device")) return r;
+    if (nInputs < 0 || maxPages < 1 || (headerKind != 0 && headerKind != 4 && headerKind != 8) || pageStride < (size_t)headerKind + 1)
+        return fail(MI355LZ4_E_ARG, "compress_pages_fastdict_device: bad arguments");
+    if (c->blockChecksum) return fail(MI355LZ4_E_ARG, "compress_pages_fastdict_device: block checksums are on; pages carry no trailer");
+    if (c->compLevel != 0)
+        return fail(MI355LZ4_E_ARG, "compress_pages_fastdict_device: compression level %d; dictionary pages are level 0's encoder", c->compLevel);
+    if (nInputs == 0) return MI355LZ4_OK;
+    if (!src || !srcOff || !srcLen || !pageSize || !pages || !pageSrcLen || !pageCompLen || !nPages || !consumed)
+        return fail(MI355LZ4_E_ARG, "compress_pages_fastdict_device: null pointer");
+    HIP_TRY(hipSetDevice(c->device));
+    if (accel < 1) accel = 1;                 // cbits/lz4.c:1577
+    if (accel > 65537) accel = 65537;         // cbits/lz4.c:1578
+    PagesFastDictArgs x;
+    x.p = PagesArgs{src, srcOff, srcLen, nInputs, pageSize, maxPages, headerKind, pages, pageStride, pageSrcLen, pageCompLen,
+                    nPages, consumed};
+    x.accel = accel;
+    x.image = hd->image;
+    x.fast = hd->fastImage;
+    x.stageStride = 65536 + (((size_t)65536 + 64 + 255) & ~(size_t)255);       // compress_fastdict_device's, for maxBlockLen 65536
+    const int grid = encode_fastdict_grid(nInputs, env_int("MI355LZ4_FASTDICT_WAVES", 0), x.stageStride);
+    if (int r = hcdict_stage(c, (size_t)grid * x.stageStride, &x.stage)) return r;
+    launch_pages_fastdict(x, grid, c->stream);
+    return check_launch("fast dict pages launch");
+}
+
 extern "C" int mi355lz4_compact_device(mi355lz4_ctx *c, const uint8_t *slots, size_t slotStride,
                                        const int32_t *framedLen, int nBlocks, uint8_t *dense, size_t denseCap,
                                        uint64_t *denseOff)

@@ -443,12 +443,16 @@ __device__ __forceinline__ uint8_t *enc_page_close(EncPage &pg, uint8_t *op, con
 // the longest prefix of its sequences that leaves room in `budget` bytes for a valid last literal run (page_lit_fit and flush_queue
 // below), closed by that run.  The whole block when it fits.  *consumed is the input the output stands for; nothing
 // behind the returned length is written.  budget >= 1.
+// BUDGET with DICT and PREP (k_pages_fastdict, a page against a prepared dictionary): the block is the one
+// k_encode_fastdict writes; *consumed counts the block's bytes, not the dictionary's.  Two rules differ, because such a block may open
+// with a match at its first byte: a cut is valid only if the page then consumes 13 bytes or more (a shorter block is literals only),
+// and the page holds the LEADING run of sequences whose cuts are all valid, since valid cuts no longer form a prefix.
 template <typename TabT, bool DICT = false, bool SEG = false, bool PAIR = false, bool PREP = false, bool BUDGET = false>
 __device__ int encode_block_wave(const uint8_t *src, int n, uint8_t *dst, int accel, TabT *table,
                                  unsigned long long *stats = nullptr, int dictLen = 0, SegOut *seg = nullptr,
                                  int budget = 0, int *consumed = nullptr)
 {
-    static_assert(!BUDGET || (!DICT && !SEG && PAIR), "BUDGET: independent blocks of up to 64 KiB");
+    static_assert(!BUDGET || (!SEG && PAIR && (!DICT || PREP)), "BUDGET: blocks of up to 64 KiB, independent or against a prepared dictionary");
     const int lane = lane_id();
     if (!DICT) dictLen = 0;
     const int blockLen = n;
@@ -482,6 +486,8 @@ __device__ int encode_block_wave(const uint8_t *src, int n, uint8_t *dst, int ac
     // other instantiations do not even capture it.)
     EncPage pg{false, 0, LZ4_WAVE};
     if constexpr (BUDGET) pg.qMax = enc_page_queue_max(budget);
+    bool pgLast = false;                               // BUDGET && DICT: the flush under way is the block's last
+    if constexpr (BUDGET && DICT) pg.in = dictLen;
     auto flush_queue = [&]() {
         commit_pending();
         if constexpr (BUDGET) { if (pg.done) qCnt = 0; }   // (parked behind the page's end by the window that closed it)
@@ -501,15 +507,34 @@ __device__ int encode_block_wave(const uint8_t *src, int n, uint8_t *dst, int ac
             const int room = budget - (int)(op - dst) - enc_scan_incl((int)esz);
             const int inEnd = qStart + qLen;
             const int r = min(n - inEnd, page_lit_fit(room));
-            const uint64_t vm = enc_ballot(act && room >= 1 && r >= LZ4_LASTLITERALS && qLen + r >= LZ4_MFLIMIT);
+            uint64_t vm = enc_ballot(act && room >= 1 && r >= LZ4_LASTLITERALS && qLen + r >= LZ4_MFLIMIT);
             const uint64_t all = (qCnt >= LZ4_WAVE) ? ~0ull : ((1ull << qCnt) - 1ull);
+            if constexpr (BUDGET && DICT) {
+                // A block against a dictionary may open with a match at its first byte: a page that consumes fewer than 13 bytes
+                // must not hold one (positions here count from the dictionary's first byte).  That condition can fail for an early
+                // sequence and hold for a later one, so the page ends in front of the FIRST lane without a valid cut.
+                // The block itself is valid: where this is its last flush and all of it fits, all of it goes out.
+                vm &= enc_ballot(inEnd + r - dictLen >= LZ4_MFLIMIT + 1);
+                if (pgLast && vm != all) {
+                    const int run = n - __builtin_amdgcn_readlane(inEnd, qCnt - 1);
+                    if (run + 1 + (int)ext_len_bytes((uint32_t)run) <= __builtin_amdgcn_readlane(room, qCnt - 1)) vm = all;
+                }
+            }
             if (vm != all) {
+                if constexpr (BUDGET && DICT) {
+                    const int j = (int)__builtin_ctzll(~vm) - 1;
+                    if (j >= 0) {
+                        op = emit_sequences(src, op, qPrev, qStart, qLen, qOff, j + 1);
+                        pg.in = __builtin_amdgcn_readlane(inEnd, j);
+                    }
+                } else
                 if (vm) {
                     const int j = 63 - (int)__builtin_clzll(vm);
                     op = emit_sequences(src, op, qPrev, qStart, qLen, qOff, j + 1);
                     pg.in = __builtin_amdgcn_readlane(inEnd, j);
                 }
                 op = enc_page_close(pg, op, dst, src, n, budget, consumed);
+                if constexpr (BUDGET && DICT) *consumed -= dictLen;
                 qCnt = 0;
                 return;
             }
@@ -1462,6 +1487,7 @@ __device__ int encode_block_wave(const uint8_t *src, int n, uint8_t *dst, int ac
     if (stats && lane == 0) for (int i = 0; i < 8; i++) atomicAdd(&stats[i], est[i]);
 #endif
     if constexpr (BUDGET) {
+        if constexpr (DICT) pgLast = true;
         if (!pg.done) flush_queue();
         if (!pg.done) {
             // every sequence is out, with a valid cut behind the last (pageIn == anchor): the block's own end if it fits
@@ -1470,6 +1496,7 @@ __device__ int encode_block_wave(const uint8_t *src, int n, uint8_t *dst, int ac
                 op = emit_last_literals(op, src + anchor, (uint32_t)run);
                 *consumed = n;
             } else op = enc_page_close(pg, op, dst, src, n, budget, consumed);
+            if constexpr (DICT) *consumed -= dictLen;
         }
         return (int)(op - dst);
     }

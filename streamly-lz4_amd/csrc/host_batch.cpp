@@ -856,10 +856,11 @@ extern "C" int mi355lz4_decompress_dict(mi355lz4_ctx *c, const uint8_t *framedIn
 // Host-buffer form of mi355lz4_compress_pages_device: inputs in host memory, one pageSize for all.  One group, synchronous, as the
 // partial form: the inputs go up packed back to back, the device call fills engine-owned pages, the four arrays come back, and of
 // every page that was written its bytes [0, headerKind + compLen) -- the rest of the caller's `pages` stays as it was.
-// (fast: mi355lz4_compress_pages_fast_device with `accel` makes the pages; `who` names the caller in the messages)
+// (fast: mi355lz4_compress_pages_fast_device with `accel` makes the pages; with hcd, mi355lz4_compress_pages_fastdict_device against
+// that prepared dictionary; `who` names the caller in the messages)
 static int pages_host(mi355lz4_ctx *c, const char *who, bool fast, int accel, const uint8_t *const *src, const int32_t *srcLen,
                       int nInputs, int pageSize, int maxPages, int headerKind, uint8_t *pages, size_t pageStride, int32_t *pageSrcLen,
-                      int32_t *pageCompLen, int32_t *nPages, int32_t *consumed)
+                      int32_t *pageCompLen, int32_t *nPages, int32_t *consumed, const mi355lz4_hcdict *hcd = nullptr)
 {
     if (!c) return fail(MI355LZ4_E_ARG, "null ctx");
     if (nInputs < 0 || maxPages < 1 || pageSize < 1 || (headerKind != 0 && headerKind != 4 && headerKind != 8) ||
@@ -898,7 +899,11 @@ static int pages_host(mi355lz4_ctx *c, const char *who, bool fast, int accel, co
     HIP_TRY(hipMemcpyAsync(c->lenB.p, ps.data(), n * 4, hipMemcpyHostToDevice, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));          // (the vectors are pageable memory)
     int32_t *dSrcLen = (int32_t *)c->res.p, *dCompLen = dSrcLen + np, *dPages = dCompLen + np, *dCons = dPages + n;
-    if (fast)
+    if (hcd)
+        r = mi355lz4_compress_pages_fastdict_device(c, hcd, (const uint8_t *)c->in.p, (const uint64_t *)c->offA.p, (const int32_t *)c->lenA.p,
+                                                    nInputs, (const int32_t *)c->lenB.p, maxPages, accel, headerKind, (uint8_t *)c->out.p,
+                                                    pageStride, dSrcLen, dCompLen, dPages, dCons);
+    else if (fast)
         r = mi355lz4_compress_pages_fast_device(c, (const uint8_t *)c->in.p, (const uint64_t *)c->offA.p, (const int32_t *)c->lenA.p,
                                                 nInputs, (const int32_t *)c->lenB.p, maxPages, accel, headerKind, (uint8_t *)c->out.p,
                                                 pageStride, dSrcLen, dCompLen, dPages, dCons);
@@ -941,6 +946,17 @@ extern "C" int mi355lz4_compress_pages_fast(mi355lz4_ctx *c, const uint8_t *cons
 {
     return pages_host(c, "compress_pages_fast", true, accel, src, srcLen, nInputs, pageSize, maxPages, headerKind, pages, pageStride,
                       pageSrcLen, pageCompLen, nPages, consumed);
+}
+
+// Host-buffer form of mi355lz4_compress_pages_fastdict_device: the same single group, the pages against the prepared dictionary.
+extern "C" int mi355lz4_compress_pages_fastdict(mi355lz4_ctx *c, const mi355lz4_hcdict *hcd, const uint8_t *const *src,
+                                                const int32_t *srcLen, int nInputs, int pageSize, int maxPages, int accel, int headerKind,
+                                                uint8_t *pages, size_t pageStride, int32_t *pageSrcLen, int32_t *pageCompLen,
+                                                int32_t *nPages, int32_t *consumed)
+{
+    if (!c || !hcd) return fail(MI355LZ4_E_ARG, "compress_pages_fastdict: null argument");
+    return pages_host(c, "compress_pages_fastdict", true, accel, src, srcLen, nInputs, pageSize, maxPages, headerKind, pages, pageStride,
+                      pageSrcLen, pageCompLen, nPages, consumed, hcd);
 }
 
 // the size pass over blocks in host memory: H2D, mi355lz4_decoded_size_device, sizes back; synchronous

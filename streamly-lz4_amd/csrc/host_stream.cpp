@@ -321,9 +321,10 @@ std::vector<Array> Engine::compressWithDictFast(const BlockConfig &cfg, const st
 }
 
 // host arrays -> device, one chain of pages per array, the written pages back (mi355lz4_compress_pages; accel > 0:
-// mi355lz4_compress_pages_fast at that acceleration)
+// mi355lz4_compress_pages_fast at that acceleration; with hd, mi355lz4_compress_pages_fastdict against that prepared dictionary)
 static std::vector<std::vector<Array>> pages_arrays(mi355lz4_ctx *ctx_, const char *who, int accel, const BlockConfig &cfg,
-                                                    const std::vector<Array> &arrays, int pageSize, int maxPages, std::vector<int32_t> *consumed)
+                                                    const std::vector<Array> &arrays, int pageSize, int maxPages, std::vector<int32_t> *consumed,
+                                                    const mi355lz4_hcdict *hd = nullptr)
 {
     if (cfg.blockChecksum) throw Error(std::string(who) + ": pages carry no block checksum");
     if (pageSize < 1 || maxPages < 1) throw Error(std::string(who) + ": pageSize and maxPages must be at least 1");
@@ -340,7 +341,9 @@ static std::vector<std::vector<Array>> pages_arrays(mi355lz4_ctx *ctx_, const ch
     lens.push_back(0);
     std::vector<uint8_t> pages(n * (size_t)maxPages * stride + 1);
     std::vector<int32_t> srcLen(n * (size_t)maxPages + 1), compLen(n * (size_t)maxPages + 1), count(n + 1), cons(n + 1);
-    const int rc = accel > 0 ? mi355lz4_compress_pages_fast(ctx_, ptrs.data(), lens.data(), (int)n, pageSize, maxPages, accel, meta, pages.data(),
+    const int rc = hd ? mi355lz4_compress_pages_fastdict(ctx_, hd, ptrs.data(), lens.data(), (int)n, pageSize, maxPages, accel, meta, pages.data(),
+                                                         stride, srcLen.data(), compLen.data(), count.data(), cons.data())
+                 : accel > 0 ? mi355lz4_compress_pages_fast(ctx_, ptrs.data(), lens.data(), (int)n, pageSize, maxPages, accel, meta, pages.data(),
                                                             stride, srcLen.data(), compLen.data(), count.data(), cons.data())
                              : mi355lz4_compress_pages(ctx_, ptrs.data(), lens.data(), (int)n, pageSize, maxPages, meta, pages.data(), stride,
                                                        srcLen.data(), compLen.data(), count.data(), cons.data());
@@ -367,6 +370,13 @@ std::vector<std::vector<Array>> Engine::compressPagesFast(const BlockConfig &cfg
                                                           std::vector<int32_t> *consumed, int accel)
 {
     return pages_arrays(ctx_, "compressPagesFast", accel < 1 ? 1 : accel, cfg, arrays, pageSize, maxPages, consumed);
+}
+
+// ... and with a prepared dictionary in front of every page (mi355lz4_compress_pages_fastdict)
+std::vector<std::vector<Array>> Engine::compressPagesWithDictFast(const BlockConfig &cfg, const std::vector<Array> &arrays, const HcDict &hd,
+                                                                  int pageSize, int maxPages, std::vector<int32_t> *consumed, int accel)
+{
+    return pages_arrays(ctx_, "compressPagesWithDictFast", accel < 1 ? 1 : accel, cfg, arrays, pageSize, maxPages, consumed, hd.handle());
 }
 
 std::vector<Array> Engine::decompressWithDict(const BlockConfig &cfg, const std::vector<Array> &blocks, const Array &dict)

@@ -253,6 +253,18 @@ struct FastDictArgs {
     size_t stageStride;          // >= 65536 + e.uniformLen + 64
 };
 
+// fixed-size output pages against the same object (mi355lz4_compress_pages_fastdict_device; kernels/encode.inc, k_pages_fastdict):
+// PagesFastArgs' chains by FastDictArgs' grid -- wave w walks inputs w, w + grid, .. and stages every page's slice of the input
+// behind the kept bytes in its window
+struct PagesFastDictArgs {
+    PagesArgs p;
+    int accel;                   // clamped to 1..65537
+    const uint8_t *image;        // HCDICT_IMAGE_BYTES, read-only: the kept bytes
+    const uint8_t *fast;         // FASTDICT_IMAGE_BYTES, read-only
+    uint8_t *stage;              // one window per wave of the grid
+    size_t stageStride;          // >= 65536 + 65536 + 64: a page never holds more than 65536 input bytes
+};
+
 // many linked decode streams continued across calls (mi355lz4_decompress_dstreams_device; kernels/linked_walk.inc, k_decode_dstreams).
 // One slot of a mi355lz4_dstreams is the device form of LZ4_streamDecode_t for separately allocated blocks: the last
 // min(r, 65536) bytes of the stream's last block that decoded to r > 0 bytes, at the slot's start, and that count.
@@ -337,6 +349,8 @@ void launch_hcdict_build_fast(uint8_t *fast, const uint8_t *dict, int len, hipSt
 // MI355LZ4_FASTDICT_WAVES (> 0 waves per CU, < 0 waves in all, 0 the default); the grid shrinks to FASTDICT_SCRATCH_MAX of windows
 int encode_fastdict_grid(int nBlocks, int knob, size_t stageStride);
 void launch_encode_fastdict(const FastDictArgs &a, int grid, hipStream_t s);
+// fixed-size output pages against both images: the same grid over inputs (encode_fastdict_grid(nInputs, ..)), one chain at a time per wave
+void launch_pages_fastdict(const PagesFastDictArgs &a, int grid, hipStream_t s);
 // independent blocks against one external dictionary (a.dict0, a.dict0Len; a.linked is not used): one wave per block
 void launch_decode_dict(const DecodeArgs &a, hipStream_t s);
 // many linked decode streams: one wave per entry of a.work walks its blocks from its slot's dictionary and stores the tail back;

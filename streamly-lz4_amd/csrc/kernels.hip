@@ -13,6 +13,7 @@
 //                          k_encode_seg, k_seg_sizes, k_emit_seg: small batches, waves per block       encode_wave.hpp
 //                          k_exact_pages: fixed-size output pages, LZ4_compress_destSize      encode_fill.hpp
 //                          k_pages_fast: the same pages from the wave encoder with a budget   encode_wave.hpp, BUDGET
+//                          k_pages_fastdict: such pages against a prepared dictionary         encode_wave.hpp, DICT + PREP + BUDGET
 //   compact.inc            k_scan_u64, k_copy_slots, k_interleave, k_header_sizes, k_decoded_size       size_walk.hpp
 //   checksum.inc           k_xxh32_ranges / _append / _verify: four lanes per range          checksum.hpp
 //   generate.inc           k_generate: synthetic inputs (bench and test support)

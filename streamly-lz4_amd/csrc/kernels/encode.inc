@@ -812,3 +812,79 @@ void launch_pages_fast(const PagesFastArgs &a, hipStream_t s)
     if (a.p.nInputs <= 0) return;
     hipLaunchKernelGGL(k_pages_fast, dim3((unsigned)a.p.nInputs), dim3(64), 0, s, a);
 }
+
+// ---------------------------------------------------------------------------
+// K2, fast fixed-size output pages against a prepared dictionary (mi355lz4_compress_pages_fastdict_device, DESIGN.md 7n).
+// k_encode_fastdict's persistent grid of single waves, one window of y.stage per wave with the kept bytes ending at its byte 65536,
+// and k_pages_fast's walk per input.  A page of 13 input bytes and more copies the next min(rem, 65536) bytes behind the dictionary,
+// reloads the table image, replays the seam steps and runs encode_block_wave<.., DICT, PREP, BUDGET>: of the block that
+// compress_fastdict_device writes for those bytes it holds the leading sequences whose cuts are all valid, closed by the literal run
+// that fills the page.  Shorter remainders, and every page of an empty dictionary, are encoded where they lie.  Nothing of the
+// object is written.
+// ---------------------------------------------------------------------------
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(ENC_WAVES_PER_EU, ENC_WAVES_PER_EU))) void k_pages_fastdict(PagesFastDictArgs y)
+{
+    __shared__ __attribute__((aligned(16))) uint16_t table[ENC_TABLE_ENTRIES + ENC_LDS_PAD + (ENC_STAGE ? 128 : 0)];
+    const PagesArgs x = y.p;
+    const int lane = lane_id();
+    const LZ4_GLOBAL uint32_t *hdr = as_global((const uint32_t *)(y.fast + FASTDICT_KEEP_OFF));
+    const int keep = (int)min(ex_uni(hdr[0]), 65536u);
+    const int seam0 = (int)min(ex_uni(hdr[1]), 65536u);
+    uint8_t *blockAt = y.stage + (uint64_t)blockIdx.x * (uint64_t)y.stageStride + 65536;
+    if (keep > 0) wave_copy_bytes(blockAt - keep, y.image + HCDICT_DICT_OFF, (uint32_t)keep);
+    dev_v4 *tab4 = (dev_v4 *)table;
+    for (int i = (int)blockIdx.x; i < x.nInputs; i += (int)gridDim.x) {
+        const int n = uni(x.srcLen[i]);
+        const int T = uni(x.pageSize[i]);
+        if (n < 0 || n > PAGES_MAX_INPUT || (T > 0 && (uint64_t)x.headerKind + (uint64_t)T > (uint64_t)x.pageStride)) {
+            if (lane == 0) x.nPages[i] = 0;
+            continue;
+        }
+        const uint8_t *src = x.src + uni64((int64_t)x.srcOff[i]);
+        const uint64_t first = (uint64_t)i * (uint64_t)x.maxPages;
+        int pos = 0, k = 0;
+        while (k < x.maxPages && T >= 1) {                              // T < 1: no page
+            const int rem = n - pos;
+            uint8_t *page = x.pages + (first + (uint64_t)k) * (uint64_t)x.pageStride;
+            uint8_t *dst = page + x.headerKind;
+            int c, used = 0;
+            if (rem == 0 || T == 1) {
+                c = enc_empty_block(dst, lane == 0);                    // an empty input, or room for the zero token alone: takes nothing
+            } else {
+                const int m = min(rem, 65536);
+                const uint8_t *from = src + pos;
+                int dictLen = 0;
+                if (m >= LZ4_MFLIMIT + 1 && keep > 0) {
+                    wave_copy_bytes(blockAt, from, (uint32_t)m);
+                    for (int j = lane; j < (int)(FASTDICT_TABLE_BYTES / 16); j += LZ4_WAVE) tab4[j] = as_global((const dev_v4 *)y.fast)[j];
+                    // the slice's bytes are read back by other lanes than wrote them, and the steps below enter into the loaded table
+                    wave_fence();
+                    for (int q0 = seam0; q0 < keep; q0 += ENC_SEED_SPAN) enc_seed_step<false>(table, blockAt - keep, q0, keep);
+                    from = blockAt;
+                    dictLen = keep;
+                } else if (m >= LZ4_MFLIMIT + 1) {                      // no dictionary: from an empty table, where the bytes lie
+                    for (int j = lane; j < (int)(FASTDICT_TABLE_BYTES / 16); j += LZ4_WAVE) tab4[j] = dev_v4{0u, 0u, 0u, 0u};
+                }                                                       // (shorter remainders are literals: no window, no table)
+                // (one call site: the encoder is inlined, and its scalar operands stay scalar)
+                c = encode_block_wave<uint16_t, true, false, true, true, true>(from, m, dst, y.accel, table, nullptr, dictLen, nullptr, T, &used);
+                wave_fence();                                           // the next page reloads the table and the window this one read
+            }
+            if (lane == 0) {
+                if (x.headerKind >= 4) store_le32(page, c);
+                if (x.headerKind == 8) store_le32(page + 4, used);
+                x.pageCompLen[first + (uint64_t)k] = c;
+                x.pageSrcLen[first + (uint64_t)k] = used;
+            }
+            k++;
+            pos += used;
+            if (pos >= n || used == 0) break;
+        }
+        if (lane == 0) { x.nPages[i] = k; x.consumed[i] = pos; }
+    }
+}
+
+void launch_pages_fastdict(const PagesFastDictArgs &a, int grid, hipStream_t s)
+{
+    if (a.p.nInputs <= 0 || grid <= 0) return;
+    hipLaunchKernelGGL(k_pages_fastdict, dim3((unsigned)grid), dim3(64), 0, s, a);
+}

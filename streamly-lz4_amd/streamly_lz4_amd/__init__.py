@@ -186,6 +186,10 @@ def _load():
         vp, vp, vp, vp)
     sig("mi355lz4_compress_pages_fast", C.c_int, vp, C.POINTER(_u8p), _i32p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _u8p,
         C.c_size_t, _i32p, _i32p, _i32p, _i32p)
+    sig("mi355lz4_compress_pages_fastdict_device", C.c_int, vp, vp, vp, vp, vp, C.c_int, vp, C.c_int, C.c_int, C.c_int, vp,
+        C.c_size_t, vp, vp, vp, vp)
+    sig("mi355lz4_compress_pages_fastdict", C.c_int, vp, vp, C.POINTER(_u8p), _i32p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
+        _u8p, C.c_size_t, _i32p, _i32p, _i32p, _i32p)
     # legacy face (include/lz4.h)
     sig("LZ4_createStream", vp)
     sig("LZ4_freeStream", C.c_int, vp)
@@ -250,6 +254,7 @@ DECLARED_SYMBOLS = [
     "mi355lz4_compress_fastdict_device", "mi355lz4_compress_fastdict",
     "mi355lz4_compress_pages_device", "mi355lz4_compress_pages",
     "mi355lz4_compress_pages_fast_device", "mi355lz4_compress_pages_fast",
+    "mi355lz4_compress_pages_fastdict_device", "mi355lz4_compress_pages_fastdict",
     "LZ4_createStream", "LZ4_freeStream", "LZ4_createStreamDecode", "LZ4_freeStreamDecode", "LZ4_compressBound",
     "LZ4_compress_fast_continue", "LZ4_decompress_safe_continue",
 ]
@@ -1036,7 +1041,24 @@ class Engine:
         """compress_pages with the pages of compress_pages_fast_device; mi355lz4_compress_pages_fast."""
         return self.compress_pages(inputs, page_size, max_pages, header_kind, page_stride, _fast_accel=int(accel))
 
-    def compress_pages(self, inputs, page_size, max_pages, header_kind=8, page_stride=None, _fast_accel=None):
+    def compress_pages_fastdict_device(self, hd, src, src_off, src_len, n_inputs, page_size, max_pages, pages, page_stride,
+                                       page_src_len, page_comp_len, n_pages, consumed, header_kind=8, accel=1):
+        """compress_pages_fast_device with the dictionary of the HcDict hd in front of every page: the same arguments, layout,
+        chains and result arrays; a page holds the leading sequences of the block that compress_fastdict_device writes for the
+        next min(remaining, 65536) bytes whose cuts are all valid, closed by the literal run that fills the page.  A page decodes
+        with the same dictionary (decompress_dict_device); hd is only read.  Only enqueues (include/mi355lz4.h,
+        mi355lz4_compress_pages_fastdict_device)."""
+        self._follow_torch()
+        _check(lib.mi355lz4_compress_pages_fastdict_device(
+            self.ctx, hd._h if hd is not None else None, _dptr(src), _dptr(src_off), _dptr(src_len), int(n_inputs),
+            _dptr(page_size), int(max_pages), int(accel), int(header_kind), _dptr(pages), int(page_stride), _dptr(page_src_len),
+            _dptr(page_comp_len), _dptr(n_pages), _dptr(consumed)), "compress_pages_fastdict_device")
+
+    def compress_pages_fastdict(self, inputs, hd, page_size, max_pages, header_kind=8, page_stride=None, accel=1):
+        """compress_pages with the pages of compress_pages_fastdict_device; mi355lz4_compress_pages_fastdict."""
+        return self.compress_pages(inputs, page_size, max_pages, header_kind, page_stride, _fast_accel=int(accel), _hd=(hd,))
+
+    def compress_pages(self, inputs, page_size, max_pages, header_kind=8, page_stride=None, _fast_accel=None, _hd=None):
         """inputs: list of bytes-like, every one cut into pages of page_size compressed bytes.  Returns a list, per input, of
         (pages, consumed): pages a list of (page bytes with its header, bytes of the input it holds); mi355lz4_compress_pages."""
         n = len(inputs)
@@ -1053,7 +1075,11 @@ class Engine:
         cons = np.zeros(max(n, 1), dtype=np.int32)
         tail = (int(header_kind), pages.ctypes.data_as(_u8p), int(page_stride), psrc.ctypes.data_as(_i32p),
                 pcomp.ctypes.data_as(_i32p), cnt.ctypes.data_as(_i32p), cons.ctypes.data_as(_i32p))
-        if _fast_accel is None:
+        if _hd is not None:
+            _check(lib.mi355lz4_compress_pages_fastdict(self.ctx, _hd[0]._h if _hd[0] is not None else None, ptrs,
+                                                        lens.ctypes.data_as(_i32p), n, int(page_size), int(max_pages), _fast_accel,
+                                                        *tail), "compress_pages_fastdict")
+        elif _fast_accel is None:
             _check(lib.mi355lz4_compress_pages(self.ctx, ptrs, lens.ctypes.data_as(_i32p), n, int(page_size), int(max_pages),
                                                *tail), "compress_pages")
         else:
