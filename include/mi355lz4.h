@@ -627,7 +627,7 @@ int mi355lz4_compress_dict_device(mi355lz4_ctx *ctx, const mi355lz4_cstreams *cs
 /* Decode nBlocks independent blocks, every one against the dictionary dictDevice[0, dictLen) (device memory, any length).
  * result[i] and out[outOff[i] ..) are those of LZ4_decompress_safe_usingDict(data_i, dst_i, compLen_i, cap_i, dict, dictLen)
  * on its external-dictionary path (LZ4_decompress_safe_forceExtDict, cbits/lz4.c:2404-2417), for well-formed and malformed
- * blocks alike: only the last 64 KiB of the dictionary can be reached, and a dictionary under 64 KiB arms the offset check
+ * blocks alike (tests/test_seam_decode_gpu.py holds the call to it on hand-built and corrupted blocks): only the last 64 KiB of the dictionary can be reached, and a dictionary under 64 KiB arms the offset check
  * (:1764).  The prefix mode the reference takes when a destination happens to lie directly behind the dictionary is not
  * restated, here or elsewhere in this engine: wherever the outputs lie, the dictionary is external.  dictLen == 0 is
  * LZ4_decompress_safe: the results of mi355lz4_decompress_batch_device with linked == 0.
@@ -936,7 +936,8 @@ int mi355lz4_dstreams_set_dict(mi355lz4_ctx *ctx, mi355lz4_dstreams *ds, int slo
  * an empty stream leaves its slot untouched.  The slot owns its copy: `out` and `framed` may be overwritten or freed once
  * the call has run.  (The reference takes its prefix path when outputs happen to lie back to back; that mode is not
  * restated, here or elsewhere in this engine.)  However a stream is cut into calls, result[] and the bytes are those of ONE
- * mi355lz4_decompress_streams_device call on the whole stream.
+ * mi355lz4_decompress_streams_device call on the whole stream, for well-formed and malformed blocks alike
+ * (tests/test_seam_decode_gpu.py holds the call to it on hand-built and corrupted blocks, the dictionary in the slot and in `out`).
  * Enqueue only: no host wait, no read of device memory on the host, no standalone first pass -- every block is decoded
  * once, with its dictionary.  The call returns MI355LZ4_OK once it is enqueued (beyond four calls in flight it waits for
  * the oldest one's stream table); per-block failures are in result[], as with the partial call.  This is the first linked

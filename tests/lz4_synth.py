@@ -8,6 +8,18 @@ extension bytes -- and each case says which edge it aims at.  tests/test_lz4_syn
 the oracle and the reference, and that every named edge is hit; tests/test_synth_decode_gpu.py feeds the cases to the GPU
 decoders.  Expected results always come from the oracle: plain_decode only checks the writer.
 
+Two generators aim at the DICTIONARY form of the lane-parallel decoder (decode_par.hpp, decode_block_par<false, true>: the
+calls with a prepared dictionary, the streams continued across calls and the linked second pass), which the families above
+never reach.  seam_cuts() cuts every block above at sequence boundaries: the suffix behind a boundary at output position k,
+decoded with the first k bytes as its dictionary, yields the rest, and every structural edge of the case now lies behind a
+dictionary -- far matches that the `ok` expression takes (wholly inside the dictionary, spos >= dictLo && spos + ml <= 0) or
+hands to decode_block_seq (straddling the seam) in whatever lane, batch and ring position the case had put them.
+seam_family() places ONE probe match on the dictionary's edges -- 0..17 bytes in front of its end with every copy width (the
+PAR_FAR_WIDE condition spos + 16 <= 0 from both sides, the second load re-anchored at min(16, ml - 16)), straddling its end
+by 1..17 bytes, on dictLo and one byte in front of it -- at chosen lanes of a batch, behind PAR_BATCH_OUT and PAR_RING, near
+the block's end (outEnd + 64 >= cap) and in blocks too small for the batch loop (cap < 128, srcLen < 64).
+tests/test_seam_decode_gpu.py feeds both to the GPU.
+
 Test infrastructure only (imported by tests, like corpus.py).
 """
 import random
@@ -164,6 +176,10 @@ def plain_decode(block, cap, dict_bytes=b""):
                 return -1, b""
             if off == 0:                              # the reference (v1.9.3) writes zeros for offset 0
                 out += bytes(ml)
+                continue
+            s = len(out) - off
+            if s >= 0 and off >= ml:                  # (the source lies in the output and ends before the match starts: a slice)
+                out += out[s:s + ml]
                 continue
             for _ in range(ml):                       # one byte at a time: overlapping matches repeat their source
                 s = len(out) - off
@@ -583,3 +599,189 @@ def sparse_dependence_stream(nblk=5, stop_after=None, seed=9):
             seqs += _filler_seqs(rng, BIG - tail - op)
         blocks.append(write_block(seqs, bytes(rng.randrange(1, 256) for _ in range(tail))))
     return blocks
+
+
+# ---- blocks cut at a sequence boundary: the rest of the block behind a dictionary -------------------------------------------------
+
+CUT_POSITIONS = (15, 16, 17, 64, 1000, 65535, 65536, 70000)
+CUT_SMALL_CAP = 262144
+_CUTS = {}
+
+
+def literal_block(data):
+    """a literals-only block of any length: it decodes to data"""
+    return write_block([], bytes(data))
+
+
+def _cut_indices(seqs):
+    """which sequences of a parsed block to cut in front of: the first, the middle and the last one, and the ones that start
+    nearest to the output positions CUT_POSITIONS"""
+    n = len(seqs)
+    idx = {0, n // 2, n - 1}
+    ops = [q[5] for q in seqs]
+    for p in CUT_POSITIONS:
+        idx.add(min(range(n), key=lambda i: (abs(ops[i] - p), i)))
+    return sorted(idx)
+
+
+def seam_cuts(cases=None, seed=10):
+    """[(name, dict_bytes, block, cap, valid)]: every case with a match, cut in front of chosen sequences (_cut_indices).  LZ4
+    offsets are relative: where the block B decodes to X and a sequence starts at token position tp and output position k,
+    B[tp:] decoded with the dictionary X[:k] into cap - k bytes yields X[k:], and every match that reached in front of k now
+    reads the dictionary.  A case that plain_decode rejects is cut the same way with k printable bytes as its dictionary; such
+    a cut is valid where plain_decode takes it (the offending sequence was cut off).  The name ends in the case's k."""
+    key = seed if cases is None else None
+    if key is not None and key in _CUTS:
+        return _CUTS[key]
+    rng = random.Random(seed)
+    cuts = []
+    for c in (independent_cases() if cases is None else cases):
+        seqs = parse(c.block)
+        if not any(q[3] is not None for q in seqs):
+            continue
+        code, X = plain_decode(c.block, c.cap)
+        for i in _cut_indices(seqs):
+            tp, k = seqs[i][0], seqs[i][5]
+            if k > c.cap:
+                continue
+            blk = c.block[tp:]
+            if code >= 0:
+                d, valid = X[:k], True
+            else:
+                d = bytes(rng.randrange(0x20, 0x7F) for _ in range(k))
+                valid = plain_decode(blk, c.cap - k, d)[0] >= 0
+            cuts.append(("%s/%s @%d" % (c.family, c.name, k), d, blk, c.cap - k, valid))
+    if key is not None:
+        _CUTS[key] = cuts
+    return cuts
+
+
+def seam_cuts_small(seed=10):
+    """the cuts with a capacity of at most CUT_SMALL_CAP bytes"""
+    return [c for c in seam_cuts(seed=seed) if c[3] <= CUT_SMALL_CAP]
+
+
+# ---- one probe match on the dictionary's edges, at chosen places of a block ---------------------------------------------------------
+
+SEAM_DICT_LENS = (1, 4, 15, 16, 17, 31, 100, 4095, 65534, 65535, 65536, 65537, 70000)
+SEAM_ML = (4, 5, 7, 8, 9, 15, 16, 17, 24, 31, 32, 33, 48, 273, 274)
+SEAM_GAPS = tuple(range(18))                  # e: bytes between the match's end and the dictionary's end
+SEAM_STRADDLES = tuple(range(1, 18))          # s: the match starts s bytes in front of the dictionary's end
+SEAM_INDICES = (0, 1, 31, 62, 63, 64, 65)     # the probe's sequence index (lanes 0, 1, 31, 62, 63 of a batch, 0 and 1 of the next)
+SEAM_DEPTHS = (PAR_BATCH_OUT + 8, 2 * PAR_BATCH_OUT, PAR_RING + 8)
+SEAM_END_DISTANCES = (12, 63, 64, 65, 127, 128, 129)
+SEAM_TINY_CAPS = (13, 20, 64, 127, 128, 129)
+# what the places other than index 0 and the depths take: (spos + ml, ml) of matches inside the dictionary -- the 4-, 8- and
+# 16-byte copies and the two-load one, e = 0, 15, 16 -- and (s, ml) of straddling ones
+SEAM_SUBSET_INSIDE = ((0, 4), (-15, 8), (-16, 16), (-15, 33), (-16, 7), (0, 17))
+SEAM_SUBSET_STRADDLE = ((1, 5), (15, 19), (16, 17))
+_SEAM, _SEAM_DICTS = {}, {}
+
+
+def seam_dictionary(dict_len):
+    """the seam family's dictionary of dict_len bytes (any byte value, from a seed of its own)"""
+    if dict_len not in _SEAM_DICTS:
+        _SEAM_DICTS[dict_len] = bytes(random.Random(7000 + dict_len).getrandbits(8) for _ in range(dict_len))
+    return _SEAM_DICTS[dict_len]
+
+
+def seam_probes(dict_len):
+    """[(label, spos, match_len, valid)] for a dictionary of dict_len bytes: spos = the match's source relative to the block's
+    first output byte"""
+    reach = min(dict_len, 65535)
+    probes = []
+    for e in SEAM_GAPS:
+        for ml in SEAM_ML:
+            if ml + e <= reach:
+                probes.append(("inside e %d ml %d" % (e, ml), -(ml + e), ml, True))
+    for s in SEAM_STRADDLES:
+        if s <= reach:
+            for ml in (s + 1, s + 4, s + 20, 300):
+                probes.append(("straddle s %d ml %d" % (s, max(ml, MINMATCH)), -s, max(ml, MINMATCH), True))
+    for ml in (4, 20):
+        probes.append(("first byte ml %d" % ml, -reach, ml, True))
+    if dict_len + 1 <= 65535:
+        probes.append(("one in front", -dict_len - 1, 20, False))
+    return probes
+
+
+def _probe(b, spos, ml):
+    """the probe sequence at the builder's position: 2 literals (none where the offset would not fit otherwise); False where
+    the offset does not fit 16 bits"""
+    lit = 2 if b.op + 2 - spos <= 0xFFFF else 0
+    if b.op + lit - spos > 0xFFFF:
+        return False
+    b.add(lit, b.op + lit - spos, ml)
+    return True
+
+
+def _fillers(b, n):
+    """n minimal self-contained sequences: 1..4 literals and a match of 4..8 bytes from the block's own output"""
+    for _ in range(n):
+        lit = b.rng.randrange(1, 5) if b.op else 4
+        b.add(lit, b.rng.randint(1, b.op + lit), b.rng.randint(4, 8))
+    return b
+
+
+def seam_family(seed=12):
+    """[(name, dict_len, block, cap, valid)]: one probe match per block on the dictionary's edges (seam_probes), everything else
+    in the block self-contained.  Places: as sequence 0, 1, 31, 62, 63, 64, 65 of the block; behind PAR_BATCH_OUT + 8,
+    2 * PAR_BATCH_OUT and PAR_RING + 8 output bytes; with the match ending 12 .. 129 bytes before the block's end; as the only
+    match of blocks of 13 .. 129 bytes and of blocks with fewer than 64 compressed bytes.  Index 0 and the depths take every
+    probe, each (e, ml) and (s, ml) with one dictionary length that has room for it, in rotation, and the first-byte and
+    one-in-front probes with every length; the other places take SEAM_SUBSET_* with every length.  Not a full product: the
+    test recomputes what is hit."""
+    if seed in _SEAM:
+        return _SEAM[seed]
+    rng = random.Random(seed)
+    out = []
+
+    def emit(dl, place, label, b, valid, last=12):
+        blk, n = b.block(last)
+        out.append(("d%d/%s/%s" % (dl, place, label), dl, blk, n, valid))
+
+    # every probe at index 0 and at the depths
+    table = {dl: seam_probes(dl) for dl in SEAM_DICT_LENS}
+    labels = []
+    for dl in SEAM_DICT_LENS:
+        for p in table[dl]:
+            if p[0] not in labels:
+                labels.append(p[0])
+    for pi, depth in enumerate((0,) + SEAM_DEPTHS):
+        for j, label in enumerate(labels):
+            have = [dl for dl in SEAM_DICT_LENS if any(p[0] == label for p in table[dl])]
+            if label.startswith(("inside", "straddle")):
+                have = [have[(j + pi) % len(have)]]
+            for dl in have:
+                _, spos, ml, valid = next(p for p in table[dl] if p[0] == label)
+                b = Builder(rng, dl)
+                if depth:
+                    b.fill(out_bytes=depth - 100).pad_out(depth)
+                if not _probe(b, spos, ml):
+                    continue
+                b.fill(out_bytes=400)
+                emit(dl, "depth %d" % depth if depth else "index 0", label, b, valid)
+    # the subset at the other places
+    for dl in SEAM_DICT_LENS:
+        reach = min(dl, 65535)
+        subset = [("inside e %d ml %d" % (-end, ml), end - ml, ml) for end, ml in SEAM_SUBSET_INSIDE if ml - end <= reach]
+        subset += [("straddle s %d ml %d" % (s, ml), -s, ml) for s, ml in SEAM_SUBSET_STRADDLE if s <= reach]
+        for label, spos, ml in subset:
+            for i in SEAM_INDICES[1:]:
+                b = _fillers(Builder(rng, dl), i)
+                if _probe(b, spos, ml):
+                    emit(dl, "index %d" % i, label, b.fill(out_bytes=400), True)
+            for dist in SEAM_END_DISTANCES:
+                b = Builder(rng, dl).fill(out_bytes=700)
+                if _probe(b, spos, ml):
+                    emit(dl, "end %d" % dist, label, b.pad_out(b.op + dist - 12), True)
+            for cap in SEAM_TINY_CAPS:
+                lit = min(2, cap - 12)
+                if lit + ml + LASTLITERALS <= cap:
+                    b = Builder(rng, dl).add(lit, lit - spos, ml)
+                    emit(dl, "cap %d" % cap, label, b, True, last=cap - b.op)
+            if ml >= 16:
+                b = Builder(rng, dl).add(3, 3 - spos, ml)
+                emit(dl, "short input", label, b, True, last=40)
+    _SEAM[seed] = out
+    return out

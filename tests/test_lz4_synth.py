@@ -1,6 +1,13 @@
 """The hand-built LZ4 blocks of tests/lz4_synth.py, on the host: the writer writes what the format says (plain_decode, the
 oracle and the reference agree on every block, code and bytes), and every family still reaches the edges it names -- recomputed
-from the written blocks, so that an edit of the generator cannot quietly lose coverage."""
+from the written blocks, so that an edit of the generator cannot quietly lose coverage.  The same for the two sets aimed at the
+decoders' dictionary form: the blocks cut at a sequence boundary (seam_cuts) and the probes on the dictionary's edges
+(seam_family).
+
+What the two sets held when they were written: 1212 cuts from the 225 cases with a match (1167 valid; 45 of the 11 invalid
+cases stay invalid behind the cut), with 1297 matches that straddle the seam and 711 inside the dictionary that end less than
+16 bytes before its end; 3022 probe blocks of at most 2063 compressed bytes.  plain_decode, the oracle and the reference agreed
+on every one of them, code and bytes."""
 import numpy as np
 import pytest
 
@@ -191,3 +198,151 @@ def test_sparse_dependence_stream(oracle, stop_after):
             if stop_after is None:
                 assert all(dec[p:p + 4] == quad for p in deps)
         d = dec
+
+
+# ---- the dictionary form: blocks cut at a sequence boundary, probes on the dictionary's edges ------------------------------------
+
+@pytest.fixture(scope="module")
+def cuts():
+    return S.seam_cuts()
+
+
+@pytest.fixture(scope="module")
+def seam():
+    return S.seam_family()
+
+
+def _dict_matches(block, dict_len):
+    """(sequence index, offset, match_len, spos, out_pos, match_end) of every match of a block that starts in front of its first
+    output byte; spos = its source relative to that byte, out_pos = where its sequence starts in the output"""
+    for i, (tp, ls, lit, off, ml, op) in enumerate(S.parse(block)):
+        if off is not None and off > op + lit:
+            yield i, off, ml, op + lit - off, op, op + lit + ml
+
+
+def test_seam_cuts_decode_as_written(oracle, cases, cuts):
+    """Every cut: plain_decode and the oracle agree on code and bytes, validity is as written, and the suffix of a valid case
+    behind the boundary at k, with the case's first k bytes as its dictionary, decodes to the rest of the case."""
+    whole = {"%s/%s" % (c.family, c.name): (c, oracle.decompress_block(c.block, c.cap)) for c in cases}
+    assert len(whole) == len(cases)                          # (the names tell the cases apart)
+    for name, d, blk, cap, valid in cuts:
+        code, dec = oracle.decompress_block(blk, cap, d)
+        assert (code >= 0) == valid, (name, code)
+        pcode, pdec = S.plain_decode(blk, cap, d)
+        assert pcode == code if code >= 0 else pcode < 0, (name, code, pcode)
+        base, k = name.rsplit(" @", 1)
+        k = int(k)
+        c, (wcode, wdec) = whole[base]
+        assert len(d) == k and cap == c.cap - k, name
+        if code >= 0:
+            assert pdec == dec, name
+        if wcode >= 0:
+            assert valid and d == wdec[:k] and (code, dec) == (wcode - k, wdec[k:]), (name, code, wcode)
+
+
+def test_seam_cuts_decode_as_the_reference_does(oracle, reference, cuts):
+    for name, d, blk, cap, valid in cuts:
+        assert reference.decompress_block(blk, cap, d) == oracle.decompress_block(blk, cap, d), name
+
+
+def test_seam_cuts_cover_the_cases(cases, cuts):
+    """Every valid case with a match is cut at three places at least; only the cases without a match yield nothing; and the set
+    holds what it is for: matches that straddle the seam and matches inside the dictionary's last 16 bytes, in numbers."""
+    per = {}
+    for name, d, blk, cap, valid in cuts:
+        per.setdefault(name.rsplit(" @", 1)[0], set()).add(len(d))
+    none = 0
+    for c in cases:
+        n = len(per.get("%s/%s" % (c.family, c.name), ()))
+        has_match = any(q[3] is not None for q in S.parse(c.block))
+        none += n == 0
+        assert n > 0 or not has_match, c
+        assert n >= 3 or not (c.valid and has_match), (c, n)
+    assert none <= 39, none
+    straddle = near_end = first = plain = 0
+    for name, d, blk, cap, valid in cuts:
+        if not valid:
+            continue
+        for i, off, ml, spos, op, end in _dict_matches(blk, len(d)):
+            straddle += spos + ml > 0
+            near_end += spos + ml <= 0 and -(spos + ml) < 16
+            first += spos == -len(d)
+            plain += spos + ml <= 0
+    assert straddle >= 1000 and near_end >= 150 and first >= 20 and plain >= 20000, (straddle, near_end, first, plain)
+
+
+def test_seam_family_decodes_as_written(oracle, seam):
+    assert 2500 < len(seam) < 4100
+    assert max(len(blk) for _, _, blk, _, _ in seam) <= 16384
+    assert {dl for _, dl, _, _, _ in seam} == set(S.SEAM_DICT_LENS)
+    for name, dl, blk, cap, valid in seam:
+        d = S.seam_dictionary(dl)
+        code, dec = oracle.decompress_block(blk, cap, d)
+        assert (code >= 0) == valid, (name, code)
+        pcode, pdec = S.plain_decode(blk, cap, d)
+        assert pcode == code if code >= 0 else pcode < 0, (name, code, pcode)
+        if code >= 0:
+            assert code == cap and pdec == dec, name
+
+
+def test_seam_family_decodes_as_the_reference_does(oracle, reference, seam):
+    for name, dl, blk, cap, valid in seam:
+        d = S.seam_dictionary(dl)
+        assert reference.decompress_block(blk, cap, d) == oracle.decompress_block(blk, cap, d), name
+
+
+def test_seam_family_reaches_its_edges(seam):
+    """Recomputed from the written blocks: every end gap e with every copy width, every straddle, the dictionary's first byte
+    and the byte in front of it, and every place -- each shown by the one match of a block that starts in the dictionary."""
+    hit = set()
+    for name, dl, blk, cap, valid in seam:
+        probes = list(_dict_matches(blk, dl))
+        assert len(probes) == 1, name                        # (everything else in the block is self-contained)
+        i, off, ml, spos, op, end = probes[0]
+        reach = min(dl, 65535)
+        n_matches = sum(1 for q in S.parse(blk) if q[3] is not None)
+        if spos == -dl - 1 and not valid:
+            hit.add("one in front")
+            hit.add("one in front at %s" % ("index 0" if i == 0 else "depth %d" % op))
+            continue
+        assert valid and spos >= -reach, name
+        if spos + ml <= 0:
+            e = -(spos + ml)
+            cls = "4..7" if ml < 8 else "8..15" if ml < 16 else "16" if ml == 16 else "17..32" if ml <= 32 else "above 32"
+            hit.add("e %d, ml %s" % (e, cls))
+            what = "inside e %d" % e
+        else:
+            hit.add("straddle %d" % -spos)
+            if off < ml:
+                hit.add("straddle with offset < ml")
+            what = "straddle %d" % -spos
+        if spos == -reach:
+            hit.add("first byte, dictionary %s 65535" % ("shorter than" if dl < 65535 else "of" if dl == 65535 else "longer than"))
+        hit.add("index %d" % i)
+        hit.add("depth %d" % op)
+        hit.add("end %d" % (cap - end))
+        if n_matches == 1:
+            hit.add("cap %d" % cap)
+            if len(blk) < 64:
+                hit.add("short input")
+        for place in ["index %d" % i, "depth %d" % op, "end %d" % (cap - end)] + \
+                     (["cap %d" % cap] if n_matches == 1 else []):
+            hit.add("%s at %s" % (what, place))
+    want = {"e %d, ml %s" % (e, cls) for e in S.SEAM_GAPS for cls in ("4..7", "8..15", "16", "17..32", "above 32")}
+    want |= {"straddle %d" % s for s in S.SEAM_STRADDLES} | {"straddle with offset < ml", "one in front", "short input"}
+    want |= {"first byte, dictionary %s 65535" % w for w in ("shorter than", "of", "longer than")}
+    want |= {"index %d" % i for i in S.SEAM_INDICES} | {"depth %d" % p for p in S.SEAM_DEPTHS}
+    want |= {"end %d" % p for p in S.SEAM_END_DISTANCES} | {"cap %d" % c for c in S.SEAM_TINY_CAPS}
+    # index 0 and the depths see every end gap and every straddle; every other place the three copy widths' worth of
+    # e in {0, 15, 16} and s in {1, 15, 16}
+    for place in ["index 0"] + ["depth %d" % p for p in S.SEAM_DEPTHS]:
+        want |= {"inside e %d at %s" % (e, place) for e in S.SEAM_GAPS} | {"straddle %d at %s" % (s, place) for s in S.SEAM_STRADDLES}
+        want.add("one in front at %s" % place)
+    for place in ["index %d" % i for i in S.SEAM_INDICES[1:]] + ["end %d" % p for p in S.SEAM_END_DISTANCES] + \
+                 ["cap %d" % c for c in S.SEAM_TINY_CAPS[2:]]:
+        want |= {"inside e %d at %s" % (e, place) for e in (0, 15, 16)} | {"straddle %d at %s" % (s, place) for s in (1, 15, 16)}
+    # (a straddle of 15 bytes is a match of 16 at least: with the 5 last literals it does not fit 13 or 20 bytes; nor does the
+    # 8-byte match with its 1 literal fit 13)
+    want |= {"inside e 0 at cap 13", "inside e 16 at cap 13", "straddle 1 at cap 13"}
+    want |= {"inside e 0 at cap 20", "inside e 15 at cap 20", "inside e 16 at cap 20", "straddle 1 at cap 20"}
+    assert want <= hit, sorted(want - hit)
