@@ -97,7 +97,9 @@ namespace lz4dev {
 #define PAR_WAVES 5         // occupancy target (waves per SIMD) the register allocator is held to (<= 102 VGPRs)
 #endif
 #ifndef PAR_WAVES_MAIN
-#define PAR_WAVES_MAIN (PAR_WAVES > 7 ? PAR_WAVES : 7)    // ... of k_decode_par<STATS> and k_decode_par_redo alone (<= 72 VGPRs): 28 waves per CU, which four LDS granules allow
+#define PAR_WAVES_MAIN 8    // ... of k_decode_par<STATS> and k_decode_par_redo alone (<= 64 VGPRs): 32 waves per CU, all a CU holds, and 32 x 5120 bytes
+                            // are all of its LDS.  The batch loop has no scratch access at 64 registers because the speculative parse takes the
+                            // lane id afresh (MAIN in decode_block_par); the check to run again is profiles/par_32w_kernel_resources.txt
 #endif
 
 // jump[] is the successor table of step 3.  Entries are BYTE offsets into jump[] itself (2 x node
@@ -140,7 +142,9 @@ struct __attribute__((aligned(16))) ParLds {
 // its 160 KiB out in granules of 1280 bytes (measured, docs/MEASUREMENT_LOG.md 15: footprints of 8272 and 8192 bytes both keep
 // SQ_WAVE_CYCLES / SQ_BUSY_CYCLES at 33.59 = 18 waves per CU -- seven granules --, 7664 bytes gives 37.47 = 20; the runtime's occupancy
 // query divides 160 KiB by the bytes and says 19 / 20 / 20).  Five granules, 6400 bytes, allowed 24 (docs/MEASUREMENT_LOG.md 16);
-// FOUR are 5120: what 28 waves per CU (seven per SIMD: k_decode_par and k_decode_par_redo, PAR_WAVES_MAIN) may use.
+// FOUR are 5120: what 28 waves per CU may use, and 32 too -- 32 x 5120 bytes are exactly the CU's 160 KiB, and 32 waves are all a CU
+// holds (eight per SIMD: k_decode_par and k_decode_par_redo, PAR_WAVES_MAIN; docs/MEASUREMENT_LOG.md 20).  Not a byte is left: the
+// byte behind one wave's ring is another wave's.
 #ifndef PAR_LDS_LIMIT
 #define PAR_LDS_LIMIT 5120  // (experiments with a larger footprint raise it)
 #endif
@@ -319,6 +323,9 @@ __device__ int decode_block_par(const uint8_t *src, int srcLen, uint8_t *dst, in
     // profiles/par_28w_kernel_resources.txt (scripts/kernel_resources.sh and a disassembly of k_decode_par<false>: no scratch
     // instruction between the batch loop's head and its back edge).
     auto fresh = [](int v) -> int { asm volatile("" : "+v"(v)); return v; };
+    // MAIN: the forms that k_decode_par<STATS> and k_decode_par_redo run at EIGHT waves per SIMD, 64 registers.  The other forms keep
+    // five and compile to what they were.
+    constexpr bool MAIN = !DICT && !TOL && !PARTIAL;
     auto win_lane = [&]() -> int { return (PAR_WIN_LANES < LZ4_WAVE) ? min(lane, PAR_WIN_LANES - 1) : lane; };
     // 16 bytes of the compressed stream for this lane's slot of the window that starts at `base`
     auto fetch_window = [&](uintptr_t base) -> uint4 {
@@ -415,9 +422,16 @@ __device__ int decode_block_par(const uint8_t *src, int srcLen, uint8_t *dst, in
             // proportional to NL -- NL gathers per squaring round -- while a batch takes at most 64 sequences: NL = 8 covers 64
             // sequences of 8 compressed bytes; text (5.9 bytes per sequence) fills its 64 lanes from 6 nodes per lane, the
             // lzsynth stream (9.2) needs 10 to get past 55 sequences per batch.  NL follows the batch before (below).
+            const int &laneId = lane;                      // (parse_square has a `lane` of its own)
             auto parse_square = [&](auto NC) {
                 constexpr int NL = decltype(NC)::value;
                 static_assert(NL % 2 == 0 && NL * LZ4_WAVE <= PAR_MAXNODES, "pairs of nodes, table size");
+                // MAIN: the speculative parse and the squaring rounds take the lane id afresh.  What they make of it -- the seven
+                // packed node bases of the two forms (six and eight nodes per lane), the table's and the window's addresses -- was
+                // hoisted out of the batch loop, nine registers of it spilled at 64, and reloaded here with a wait for every load in
+                // flight.  Made here, they die with the phase.  (Every other phase keeps the lane id itself: the same copy in the
+                // tail round's and the self-overlapping matches' loops measured 1 % slower, docs/MEASUREMENT_LOG.md 20.)
+                const int lane = MAIN ? fresh(laneId) : laneId;
                 uint32_t J[NL];
                 // Two nodes per instruction (16-bit halves, v_pk_*).  The absorbing state is the node behind the last one
                 // that may be a token, nodeLim + 1: every successor beyond nodeLim is clamped to it, its own included (a

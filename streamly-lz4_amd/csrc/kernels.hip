@@ -17,7 +17,7 @@
 //   compact.inc            k_scan_u64, k_copy_slots, k_interleave, k_header_sizes, k_decoded_size       size_walk.hpp
 //   checksum.inc           k_xxh32_ranges / _append / _verify: four lanes per range          checksum.hpp
 //   generate.inc           k_generate: synthetic inputs (bench and test support)
-//   decode_par_cu.inc      k_decode_par<STATS>, k_decode_par_redo: one wave per block (PAR_OCC)         decode_par.hpp
+//   decode_par_cu.inc      k_decode_par<STATS>, k_decode_par_redo: one wave per block, 32 to a CU       decode_par.hpp
 //                          k_decode_cu: one workgroup per block                              decode_cu.hpp
 //                          k_decode_cu_linked, k_cu_tails, k_cu_publish: big linked blocks, guessed dictionaries
 //   decode_partial.inc     k_decode_seq_partial, k_decode_par_partial<REDO>, k_decode_cu_partial: the first N bytes

@@ -6,7 +6,7 @@
 #else
 #define PAR_OCC __launch_bounds__(64, PAR_WAVES)
 #endif
-// The two kernels of this file that decode whole independent blocks run at seven waves per SIMD; every other user of ParLds keeps PAR_OCC.
+// The two kernels of this file that decode whole independent blocks run at eight waves per SIMD (PAR_WAVES_MAIN: 64 registers, 32 waves and all of the LDS of a CU); every other user of ParLds keeps PAR_OCC.
 #ifdef PAR_WAVES_MAX
 #define PAR_OCC_MAIN __attribute__((amdgpu_flat_work_group_size(64, 64), amdgpu_waves_per_eu(PAR_WAVES_MAIN, (PAR_WAVES_MAX > PAR_WAVES_MAIN ? PAR_WAVES_MAX : PAR_WAVES_MAIN))))
 #else
