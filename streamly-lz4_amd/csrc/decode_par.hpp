@@ -12,6 +12,8 @@
 //                 the next window is prefetched into registers while this one is used).
 //   2. speculate  every lane parses 8 candidate token positions (512 candidates)
 //                 from registers: where would the next token be if one started here?
+//                 Lane l owns the node PAIRS 128p + 2l, 128p + 2l + 1 (p < 4): its gathers
+//                 of step 3 then lie a dword from its neighbours', not four (bank conflicts).
 //   3. chain      pointer jumping over that successor table: after round k lanes
 //                 0..2^k-1 hold the first 2^k real token positions.  Three rounds give
 //                 jump^8 for every node and lanes 0..7; then lanes 8g..8g+7 follow the
@@ -206,6 +208,55 @@ __device__ __forceinline__ int par_scan_incl(int x)
     x += __builtin_amdgcn_update_dpp(0, x, 0x142, 0xa, 0xf, false);   // row_bcast:15 -> rows 1,3
     x += __builtin_amdgcn_update_dpp(0, x, 0x143, 0xc, 0xf, false);   // row_bcast:31 -> rows 2,3
     return x;
+}
+
+// The successor table's stores.  Lane l owns, for pair p < NL / 2, the nodes 128p + 2l and 128p + 2l + 1: the dword at byte 256p + 4l
+// of jump[], the lanes one behind the other in a row, so no store has a bank conflict.  (The gathers of the squaring rounds are what
+// this ownership is for: with NL nodes in a row per lane, neighbouring lanes' gathers lay NL / 2 dwords apart, a four-way conflict on
+// 32 banks before the successors' jitter; docs/MEASUREMENT_LOG.md 21, scripts/par_bank_model.py.)  P[p] = the two entries of pair p.
+#ifndef PAR_TW
+#define PAR_TW 2            // 2: where the table lies below 64 KiB of LDS (TID below), a ds_write_addtid_b32 per pair (address = M0[15:0] +
+                            // offset + 4 x lane: no address register goes to the LDS, half a ds_write_b32's cycles); 1: plain stores everywhere,
+                            // which the compiler pairs into ds_write2st64_b32 (rows p, p + 1 are 64 dwords apart).  Measured (decoder 2, 65 536
+                            // blocks, lzsynth / text GB/s, two passes, docs/MEASUREMENT_LOG.md 21): 2: 1266-1268 / 790-792, 1: 1254-1257 /
+                            // 786-790; a ds_write_b32 per pair, which is what form 1 is without the pairing: 1234-1244 / 780-784
+#endif
+// TID: the caller's ParLds is all the LDS of its kernel (k_decode_par, k_decode_par_redo, k_decode_tok: 5120 bytes, which
+// tests/test_par_node_pairs_gpu.py asks the runtime), so the table's address fits the 16 bits of M0 that the add-TID store takes as its
+// base.  The forms that are called from kernels with LDS of their own around ParLds do not qualify -- k_decode_fixup_regions holds
+// ParLds at 0x20040 of its 140 528 bytes -- and keep the plain stores.
+template <int NL, bool TID>
+__device__ __forceinline__ void par_table_store(uint16_t *jump, int lane, const uint32_t (&P)[NL / 2])
+{
+    static_assert(NL == 6 || NL == 8 || NL == 10, "three, four or five pairs");
+    if (PAR_TW == 2 && TID) {
+        // The table's LDS address is the same in every lane and goes to M0, the row is the instruction's offset.  One statement: M0
+        // is the compiler's to use, so it is given back as it was, and nothing of the compiler's comes between the move and the
+        // stores.  The compiler's hazard recogniser sees neither write of M0: the first s_nop is the wait state a store that adds the
+        // lane id needs behind a write of M0, the last one stands for whatever user of M0 the compiler may place right behind the
+        // statement (none today).  LDS operations of a wave execute in order: the gathers behind these stores read what they
+        // wrote, counted by the compiler or not.
+        const uint32_t jb = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(uintptr_t)jump);
+        const uint32_t p3 = P[NL / 2 > 3 ? 3 : 0], p4 = P[NL / 2 > 4 ? 4 : 0];
+        uint32_t m0keep;
+        if (NL == 6)
+            asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %1\n\ts_nop 0\n\tds_write_addtid_b32 %2\n\tds_write_addtid_b32 %3 offset:256\n\t"
+                         "ds_write_addtid_b32 %4 offset:512\n\ts_mov_b32 m0, %0\n\ts_nop 0"
+                         : "=&s"(m0keep) : "s"(jb), "v"(P[0]), "v"(P[1]), "v"(P[2]) : "memory");
+        else if (NL == 8)
+            asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %1\n\ts_nop 0\n\tds_write_addtid_b32 %2\n\tds_write_addtid_b32 %3 offset:256\n\t"
+                         "ds_write_addtid_b32 %4 offset:512\n\tds_write_addtid_b32 %5 offset:768\n\ts_mov_b32 m0, %0\n\ts_nop 0"
+                         : "=&s"(m0keep) : "s"(jb), "v"(P[0]), "v"(P[1]), "v"(P[2]), "v"(p3) : "memory");
+        else
+            asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %1\n\ts_nop 0\n\tds_write_addtid_b32 %2\n\tds_write_addtid_b32 %3 offset:256\n\t"
+                         "ds_write_addtid_b32 %4 offset:512\n\tds_write_addtid_b32 %5 offset:768\n\tds_write_addtid_b32 %6 offset:1024\n\t"
+                         "s_mov_b32 m0, %0\n\ts_nop 0"
+                         : "=&s"(m0keep) : "s"(jb), "v"(P[0]), "v"(P[1]), "v"(P[2]), "v"(p3), "v"(p4) : "memory");
+    } else {
+        uint32_t *tw = (uint32_t *)&jump[2 * lane];
+#pragma unroll
+        for (int p = 0; p < NL / 2; p++) tw[64 * p] = P[p];
+    }
 }
 
 // A window slot [q, q + 16) that is not wholly inside the framed buffer [bufLo, bufHi): the buffer's bytes, zeros outside.  Only the
@@ -426,11 +477,12 @@ __device__ int decode_block_par(const uint8_t *src, int srcLen, uint8_t *dst, in
             auto parse_square = [&](auto NC) {
                 constexpr int NL = decltype(NC)::value;
                 static_assert(NL % 2 == 0 && NL * LZ4_WAVE <= PAR_MAXNODES, "pairs of nodes, table size");
-                // MAIN: the speculative parse and the squaring rounds take the lane id afresh.  What they make of it -- the seven
-                // packed node bases of the two forms (six and eight nodes per lane), the table's and the window's addresses -- was
-                // hoisted out of the batch loop, nine registers of it spilled at 64, and reloaded here with a wait for every load in
-                // flight.  Made here, they die with the phase.  (Every other phase keeps the lane id itself: the same copy in the
-                // tail round's and the self-overlapping matches' loops measured 1 % slower, docs/MEASUREMENT_LOG.md 20.)
+                // MAIN: the speculative parse and the squaring rounds take the lane id afresh.  What they make of it -- the packed
+                // node base, the window's address and funnel shift (with the nodes in rows: seven packed bases of the two forms and
+                // the table's address) -- was hoisted out of the batch loop, nine registers of it spilled at 64, and reloaded here
+                // with a wait for every load in flight.  Made here, they die with the phase.  (Every other phase keeps the lane id
+                // itself: the same copy in the tail round's and the self-overlapping matches' loops measured 1 % slower,
+                // docs/MEASUREMENT_LOG.md 20.)
                 const int lane = MAIN ? fresh(laneId) : laneId;
                 uint32_t J[NL];
                 // Two nodes per instruction (16-bit halves, v_pk_*).  The absorbing state is the node behind the last one
@@ -440,41 +492,33 @@ __device__ int decode_block_par(const uint8_t *src, int srcLen, uint8_t *dst, in
                 absorb = 2u * ((uint32_t)min(inLim, NL * LZ4_WAVE - 1) + 1u);
                 {
                     typedef unsigned short par_h2 __attribute__((ext_vector_type(2)));
-                    uint32_t w0, w1, w2;                      // my NL bytes and the one behind them, from byte 0 of w0 on
-                    if (NL == 8) {
-                        const uint64_t lo = *(const uint64_t *)&L.win()[8 * lane];
-                        w0 = (uint32_t)lo; w1 = (uint32_t)(lo >> 32);
-                        w2 = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)w0, 0x130, 0xf, 0xf, false);   // next lane's first bytes
-                    } else {
-                        const uint32_t a = (uint32_t)(NL * lane);
-                        const uint32_t *q = (const uint32_t *)&L.win()[a & ~3u];
-                        const uint32_t d0 = q[0], d1 = q[1], d2 = q[2], d3 = q[3];
-                        const uint32_t sh = a & 3u;
-                        w0 = __builtin_amdgcn_alignbyte(d1, d0, sh);
-                        w1 = __builtin_amdgcn_alignbyte(d2, d1, sh);
-                        w2 = __builtin_amdgcn_alignbyte(d3, d2, sh);
-                    }
                     auto h2 = [](uint32_t x) { par_h2 r; __builtin_memcpy(&r, &x, 4); return r; };
                     auto u32 = [](par_h2 x) { uint32_t r; __builtin_memcpy(&r, &x, 4); return r; };
                     const par_h2 one = {1, 1}, lim = h2((absorb >> 1) * 0x00010001u);
-                    const uint32_t base3 = ((uint32_t)(NL * lane) + 3u) * 0x00010001u + 0x00010000u;   // nodes 2p, 2p + 1 of pair p: + 2p
+                    // Window bytes n, n + 1, n + 2 at n = 128p + 2 * lane: the even lane of a lane pair reads the aligned dword that
+                    // holds all three, the odd lane the dword BEHIND it (its byte n + 2; lane 63's is byte 0 of the next row, in the
+                    // window like any other) and takes the pair's own dword from its even neighbour by DPP.  One aligned
+                    // ds_read_b32 per pair, two lanes to a dword and no bank conflict; a byte funnel by 2 on the odd lanes.
+                    const uint32_t *wq = (const uint32_t *)&L.win()[4 * ((lane + 1) >> 1)];
+                    const uint32_t wsh = 2u * ((uint32_t)lane & 1u);
+                    const uint32_t base3 = (2u * (uint32_t)lane + 3u) * 0x00010001u + 0x00010000u;       // nodes 128p + 2 * lane and the next: + 128p
                     uint32_t P[NL / 2];
 #pragma unroll
                     for (int p = 0; p < NL / 2; p++) {
+                        const uint32_t dn = wq[32 * p];
+                        const uint32_t de = (uint32_t)__builtin_amdgcn_update_dpp((int)dn, (int)dn, 0xa0 /* quad_perm:[0,0,2,2] */, 0xf, 0xf, false);
+                        const uint32_t ws = __builtin_amdgcn_alignbyte(dn, de, wsh);                    // bytes n .. n + 3
                         // tokens of the two nodes and the byte behind each, zero-extended into the halves
-                        const uint32_t ws = (p < 2) ? w0 : ((p < 4) ? w1 : w2), wn = (p < 2) ? w1 : w2;
-                        const par_h2 T = h2(__builtin_amdgcn_perm(0u, ws, (p & 1) ? 0x0c030c02u : 0x0c010c00u));
-                        const par_h2 B = h2((p & 1) ? __builtin_amdgcn_perm(wn, ws, 0x0c040c03u) : __builtin_amdgcn_perm(0u, ws, 0x0c020c01u));
+                        const par_h2 T = h2(__builtin_amdgcn_perm(0u, ws, 0x0c010c00u));
+                        const par_h2 B = h2(__builtin_amdgcn_perm(0u, ws, 0x0c020c01u));
                         const par_h2 lit0 = T >> 4;
                         const par_h2 ext = (lit0 + one) >> 4;                       // 1 when the literal nibble is 15
                         const par_h2 term = ext * (B + one) + lit0;                 // 15 + 1 + b1, or the nibble
                         const par_h2 mlx = ((T & (par_h2){15, 15}) + one) >> 4;     // 1 when the match nibble is 15
-                        const par_h2 nxt = term + mlx + h2(base3 + 0x00020002u * (uint32_t)p);
+                        const par_h2 nxt = term + mlx + h2(base3 + 0x00800080u * (uint32_t)p);
                         P[p] = u32(__builtin_elementwise_min(nxt, lim) << 1);
                     }
-                    uint32_t *tw = (uint32_t *)&L.jump()[NL * lane];
-#pragma unroll
-                    for (int p = 0; p < NL / 2; p++) tw[p] = P[p];
+                    par_table_store<NL, MAIN>(L.jump(), lane, P);
                     if (lane == 0) L.jump()[NL * LZ4_WAVE + lane] = (uint16_t)(2 * NL * LZ4_WAVE);   // absorbing state behind the table (the address from the lane id: no register held at zero for it; see `fresh`)
 #pragma unroll
                     for (int p = 0; p < NL / 2; p++) { J[2 * p] = P[p] & 0xffffu; J[2 * p + 1] = P[p] >> 16; }
@@ -503,9 +547,10 @@ __device__ int decode_block_par(const uint8_t *src, int srcLen, uint8_t *dst, in
                     else sh = par_row_shr<8>(cj);
                     if (lane >= d && lane < 2 * d) c2 = (uint32_t)sh;
                     wave_fence();
-                    uint32_t *tw = (uint32_t *)&L.jump()[NL * lane];
+                    uint32_t P[NL / 2];
 #pragma unroll
-                    for (int p = 0; p < NL / 2; p++) tw[p] = J[2 * p] | (J[2 * p + 1] << 16);
+                    for (int p = 0; p < NL / 2; p++) P[p] = J[2 * p] | (J[2 * p + 1] << 16);
+                    par_table_store<NL, MAIN>(L.jump(), lane, P);
                     wave_fence();
                 }
             };
