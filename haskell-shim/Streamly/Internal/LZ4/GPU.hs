@@ -60,6 +60,14 @@ module Streamly.Internal.LZ4.GPU
     , compressChunksWithDictHC
     , c_compressFastDictDevice
     , compressChunksWithDictFast
+    , DictSet
+    , newDictSet
+    , freeDictSet
+    , dictSetCount
+    , c_compressFastDictMultiDevice
+    , c_decompressDictMultiDevice
+    , compressChunksWithDictsFast
+    , decompressChunksWithDicts
     , c_compressPagesDevice
     , compressChunksPaged
     , c_compressPagesFastDevice
@@ -89,7 +97,7 @@ import Data.Int (Int32)
 import Data.Word (Word8, Word64)
 import Foreign.C (CInt(..), CSize(..))
 import Foreign.Marshal.Alloc (alloca)
-import Foreign.Marshal.Array (allocaArray, peekArray, pokeArray)
+import Foreign.Marshal.Array (allocaArray, peekArray, pokeArray, withArrayLen)
 import Foreign.Marshal.Utils (copyBytes)
 import Foreign.Ptr (Ptr, nullPtr, plusPtr, castPtr)
 import Foreign.Storable (peek)
@@ -220,6 +228,35 @@ foreign import ccall safe "mi355lz4.h mi355lz4_compress_fastdict"
     c_compressFastDict
         :: Ptr C_Engine -> Ptr C_HcDict -> Ptr (Ptr Word8) -> Ptr Int32 -> CInt -> CInt -> CInt
         -> Ptr Word8 -> CSize -> Ptr CSize -> Ptr Int32 -> Ptr Int32 -> IO CInt
+
+-- Dictionary sets (include/mi355lz4.h, "dictionary sets"): a table of prepared dictionaries on the device and, per block, an index
+-- into it (-1: none).  The members are borrowed: they must outlive the set.  ds and dictIdx stand where the single-dictionary
+-- calls have their dictionary.
+data C_DictSet
+newtype DictSet = DictSet (Ptr C_DictSet)
+
+foreign import ccall safe "mi355lz4.h mi355lz4_dictset_create"
+    c_dictsetCreate :: Ptr C_Engine -> Ptr (Ptr C_HcDict) -> CInt -> Ptr (Ptr C_DictSet) -> IO CInt
+foreign import ccall safe "mi355lz4.h mi355lz4_dictset_destroy"
+    c_dictsetDestroy :: Ptr C_DictSet -> IO ()
+foreign import ccall unsafe "mi355lz4.h mi355lz4_dictset_count"
+    c_dictsetCount :: Ptr C_DictSet -> IO CInt
+foreign import ccall safe "mi355lz4.h mi355lz4_compress_fastdict_multi_device"
+    c_compressFastDictMultiDevice
+        :: Ptr C_Engine -> Ptr C_DictSet -> Ptr Int32 -> Ptr Word8 -> Ptr Word64 -> Ptr Int32 -> Word64 -> CInt -> CInt
+        -> CInt -> CInt -> Ptr Word8 -> CSize -> Ptr Int32 -> IO CInt
+foreign import ccall safe "mi355lz4.h mi355lz4_compress_fastdict_multi"
+    c_compressFastDictMulti
+        :: Ptr C_Engine -> Ptr C_DictSet -> Ptr Int32 -> Ptr (Ptr Word8) -> Ptr Int32 -> CInt -> CInt -> CInt
+        -> Ptr Word8 -> CSize -> Ptr CSize -> Ptr Int32 -> Ptr Int32 -> IO CInt
+foreign import ccall safe "mi355lz4.h mi355lz4_decompress_dict_multi_device"
+    c_decompressDictMultiDevice
+        :: Ptr C_Engine -> Ptr Word8 -> Word64 -> Ptr Word64 -> CInt -> CInt -> CInt -> Ptr C_DictSet -> Ptr Int32
+        -> Ptr Word8 -> Ptr Word64 -> Ptr Int32 -> Ptr Int32 -> IO CInt
+foreign import ccall safe "mi355lz4.h mi355lz4_decompress_dict_multi"
+    c_decompressDictMulti
+        :: Ptr C_Engine -> Ptr Word8 -> CSize -> CInt -> CInt -> Ptr C_DictSet -> Ptr Int32
+        -> Ptr Word8 -> CSize -> Ptr CSize -> Ptr Int32 -> CInt -> Ptr CInt -> IO CInt
 
 -- Fixed-size output pages (LZ4_compress_destSize, N inputs per call): input i is cut into at most maxPages pages of
 -- pageSize[i] compressed bytes, page (i, k) at pages + (i * maxPages + k) * pageStride behind a header of headerKind (0, 4, 8)
@@ -651,6 +688,48 @@ compressChunksWithDictFast (Engine eng) (HcDict hd) accel cfg arrs = do
                    `seq` Array.Array cont (dstBegin `plusPtr` o) (dstBegin `plusPtr` (o + l))
                | (o, l) <- zip offs flens ]
 
+-- | A set of prepared dictionaries for 'compressChunksWithDictsFast' and 'decompressChunksWithDicts'.  The members are borrowed:
+-- free them after the set.  The same 'HcDict' may stand at several indices, and 'loadHcDict' on a member is seen by the set.
+newDictSet :: Engine -> [HcDict] -> IO DictSet
+newDictSet (Engine p) members = withArrayLen [hd | HcDict hd <- members] $ \n pMembers -> alloca $ \pp -> do
+    rc <- c_dictsetCreate p pMembers (fromIntegral n) pp
+    when (rc /= 0) $ error "newDictSet: mi355lz4_dictset_create failed"
+    DictSet <$> peek pp
+
+freeDictSet :: DictSet -> IO ()
+freeDictSet (DictSet ds) = c_dictsetDestroy ds
+
+dictSetCount :: DictSet -> IO Int
+dictSetCount (DictSet ds) = fromIntegral <$> c_dictsetCount ds
+
+-- | 'compressChunksWithDictFast' with a dictionary per array: @(index, array)@ pairs, the index naming a member of the set or
+-- @-1@ for none.  Every array comes out as 'compressChunksWithDictFast' writes it against that member alone.
+compressChunksWithDictsFast
+    :: Engine -> DictSet -> Int -> BlockConfig -> [(Int, Array.Array Word8)] -> IO [Array.Array Word8]
+compressChunksWithDictsFast (Engine eng) (DictSet ds) accel cfg pairs = do
+    let arrs = map snd pairs
+        n = length arrs
+        meta = metaSizeOf cfg
+        lens = map Array.byteLength arrs
+        cap = sum (map (\l -> fromIntegral (c_bound (fromIntegral l)) + meta + 4) lens)
+    (MArray.Array cont dstBegin_ dstBegin dstMax) <- MArray.newArray (max cap 1)
+    allocaArray n $ \pSrc -> allocaArray n $ \pLen -> allocaArray n $ \pIdx -> allocaArray n $ \pFlen ->
+      allocaArray n $ \pStatus -> alloca $ \pOutLen -> do
+        let withAll [] k = k []
+            withAll (a:as) k = Array.asPtrUnsafe (Array.unsafeCast a) $ \p -> withAll as (k . (p :))
+        withAll arrs $ \ptrs -> do
+            pokeArray pSrc ptrs
+            pokeArray pLen (map fromIntegral lens)
+            pokeArray pIdx (map (fromIntegral . fst) pairs)
+            rc <- c_compressFastDictMulti eng ds pIdx pSrc pLen (fromIntegral n) (fromIntegral accel) (fromIntegral meta) dstBegin
+                      (fromIntegral cap) pOutLen pFlen pStatus
+            when (rc /= 0) $ error "compressChunksWithDictsFast: mi355lz4_compress_fastdict_multi failed"
+        flens <- map fromIntegral <$> peekArray n pFlen
+        let offs = scanl (+) 0 flens
+        return [ Array.unsafeFreeze (MArray.Array cont dstBegin_ (dstBegin `plusPtr` (o + l)) dstMax)
+                   `seq` Array.Array cont (dstBegin `plusPtr` o) (dstBegin `plusPtr` (o + l))
+               | (o, l) <- zip offs flens ]
+
 -- | Fixed-size output pages: every array cut into a chain of at most @maxPages@ pages whose blocks are at most @pageSize@
 -- bytes; page k is what @LZ4_compress_destSize@ makes of the bytes behind pages 0..k-1.  Per input: its pages in order, each with
 -- the configuration's header in front of its block, and the bytes of the input they hold (less than its length when
@@ -729,6 +808,29 @@ decompressChunksWithDict (Engine eng) cfg dict blocks = do
                   (fromIntegral (fixedUncompOf cfg)) pDict (fromIntegral (Array.byteLength dict))
                   b (fromIntegral cap) pOutLen pBlen (fromIntegral n) pN
         when (rc /= 0) $ error "decompressChunksWithDict: mi355lz4_decompress_dict failed"
+        lens <- map fromIntegral <$> peekArray n pBlen
+        let offs = scanl (+) 0 lens
+        return [ Array.Array cont (b `plusPtr` o) (b `plusPtr` (o + l)) | (o, l) <- zip offs lens ]
+
+-- | 'decompressChunksWithDict' with a dictionary per block: @(index, block)@ pairs, every block decoded against the kept bytes of
+-- the member it names (@-1@: none).  One decoded array per block.
+decompressChunksWithDicts
+    :: Engine -> DictSet -> BlockConfig -> [(Int, Array.Array Word8)] -> IO [Array.Array Word8]
+decompressChunksWithDicts (Engine eng) (DictSet ds) cfg pairs = do
+    let blocks = map snd pairs
+        n = length blocks
+        meta = metaSizeOf cfg
+    framed <- concatArrays blocks
+    cap <- sum <$> forM blocks (\a -> Array.asPtrUnsafe (Array.unsafeCast a) $ \p ->
+               if meta == 8 then fromIntegral <$> (peek (castPtr p `plusPtr` 4) :: IO Int32)
+                            else return (fixedUncompOf cfg))
+    (MArray.Array cont _ b _) <- MArray.newArray (max cap 1)
+    allocaArray (max n 1) $ \pBlen -> allocaArray (max n 1) $ \pIdx -> alloca $ \pOutLen -> alloca $ \pN ->
+      Array.asPtrUnsafe (Array.unsafeCast framed) $ \pIn -> do
+        pokeArray pIdx (map (fromIntegral . fst) pairs)
+        rc <- c_decompressDictMulti eng pIn (fromIntegral (Array.byteLength framed)) (fromIntegral meta)
+                  (fromIntegral (fixedUncompOf cfg)) ds pIdx b (fromIntegral cap) pOutLen pBlen (fromIntegral n) pN
+        when (rc /= 0) $ error "decompressChunksWithDicts: mi355lz4_decompress_dict_multi failed"
         lens <- map fromIntegral <$> peekArray n pBlen
         let offs = scanl (+) 0 lens
         return [ Array.Array cont (b `plusPtr` o) (b `plusPtr` (o + l)) | (o, l) <- zip offs lens ]

@@ -60,6 +60,7 @@ extern "C" {
 #define MI355LZ4_BLK_E_UNCOMPLEN (-0x7F000003)  /* negative uncompLen / exceeds output capacity */
 #define MI355LZ4_BLK_E_CHECKSUM (-0x7F000004)   /* data does not match its trailer (mi355lz4_set_block_checksum) */
 #define MI355LZ4_BLK_E_SIZE_UNKNOWN (-0x7F000005) /* mi355lz4_decoded_size_device: the token chain gives no size the call vouches for */
+#define MI355LZ4_BLK_E_DICT (-0x7F000006)       /* mi355lz4_decompress_dict_multi_device: dictIdx[i] names no member of the set */
 
 #define MI355LZ4_MAX_INPUT_SIZE 0x7E000000      /* = LZ4_MAX_INPUT_SIZE, cbits/lz4.h:170 */
 
@@ -118,6 +119,12 @@ typedef struct mi355lz4_ctx mi355lz4_ctx;
  *   ranges of the caller's host arrays and nothing else.  _compress_pages_fast_device and _compress_pages_fast: the same ranges
  *   and the same rules.  _compress_pages_fastdict_device and _compress_pages_fastdict: the same ranges and the same rules again,
  *   and never the mi355lz4_hcdict, which is only read.
+ * Dictionary sets: _dictset_create writes the set it returns and nothing else.  _compress_fastdict_multi_device: the slot ranges
+ *   of _compress_fastdict_device and framedLen[0, nBlocks) (a length outside 0..maxBlockLen or an index outside -1..n-1:
+ *   framedLen[i] = 0, the slot untouched); never a member of the set or its images, never dictIdx, src, srcOff or srcLen.
+ *   _decompress_dict_multi_device: the ranges of _decompress_dict_device, and nothing of `out` for a block whose index names no
+ *   member (result[i] = MI355LZ4_BLK_E_DICT); never a member, dictIdx, framed, blockOff, outOff or outCap.  Of the set itself the
+ *   compress call writes two diagnostic words.  _compress_fastdict_multi and _decompress_dict_multi are host-buffer calls as above.
  * Scratch that a call needs is the engine's own. */
 
 /* ---- engine lifecycle ------------------------------------------------ */
@@ -762,6 +769,82 @@ int mi355lz4_compress_fastdict_device(mi355lz4_ctx *ctx, const mi355lz4_hcdict *
 int mi355lz4_compress_fastdict(mi355lz4_ctx *ctx, const mi355lz4_hcdict *hd, const uint8_t *const *src,
                                const int32_t *srcLen, int nBlocks, int accel, int headerKind, uint8_t *framedOut, size_t cap,
                                size_t *outLen, int32_t *blockFramedLen, int32_t *status);
+
+/* ---- dictionary sets: a batch in which every block names its dictionary ---------------------------------------------------------
+ * The calls above take one dictionary.  A store of small records has one per table, column, tenant or message type, and under
+ * those calls its batch falls apart into one call per dictionary, a few hundred blocks each -- the shape this engine is worst at.
+ * These calls take a SET of prepared dictionaries and, per block, an index into it.  Level 0's wave encoder
+ * (mi355lz4_compress_fastdict_device) and the dictionary decoder (mi355lz4_decompress_dict_device) have the form; the HC levels,
+ * the reference-exact mi355lz4_compress_dict_device, the page calls, the multi-device handle and the legacy LZ4_* face do not.
+ * DESIGN.md 7o.
+ *
+ * A mi355lz4_dictset is an opaque table on the device of the engine it was created with: n entries, 1 <= n <= 65536, one per
+ * member, each the member's two images by address.  _dictset_create uploads it (and waits for that copy).  The members are
+ * BORROWED: the set neither copies nor owns them, they must outlive it, and destroying a member before the set is the caller's
+ * error -- calls through the set would read freed memory.  The same object may stand at several indices.  mi355lz4_hcdict_load on a
+ * member rebuilds its images in place, so the set sees the new dictionary without being recreated; the sharing rule is that of a
+ * single mi355lz4_hcdict: no _hcdict_load of a member may be in flight beside a call that reads the set.  Calls only read the set
+ * (but for two diagnostic words of the compress call), so it may serve any number of calls.  _dictset_destroy waits for the device
+ * first, as _hcdict_destroy does, and leaves the members alone.  _dictset_count: n.
+ * MI355LZ4_E_ARG: _create: a null ctx, hd or out, n outside 1..65536, a null member, a member created on another device than the
+ * engine's; _count: a null set. */
+typedef struct mi355lz4_dictset mi355lz4_dictset;
+int mi355lz4_dictset_create(mi355lz4_ctx *ctx, const mi355lz4_hcdict *const *hd, int n, mi355lz4_dictset **out);
+void mi355lz4_dictset_destroy(mi355lz4_dictset *ds);
+int mi355lz4_dictset_count(const mi355lz4_dictset *ds);
+/* mi355lz4_compress_fastdict_device with `ds` in place of the dictionary and dictIdx[0, nBlocks) (device memory) beside the blocks.
+ * With k = dictIdx[i]: for k in 0..n-1 the slot bytes, header, trailer and framedLen[i] of block i are exactly what
+ * mi355lz4_compress_fastdict_device writes for that block alone against member k, with the same accel, maxBlockLen, headerKind and
+ * checksum switch; k == -1 is no dictionary: that call's bytes against an object that holds the empty dictionary.  Any other k
+ * gives framedLen[i] = 0 and an untouched slot range, like a length outside 0..maxBlockLen; the other blocks are unaffected.
+ * The level (0), the switches, the 4 MiB limit, slotStride and the error codes are those of mi355lz4_compress_fastdict_device, with
+ * a null ds or dictIdx (nBlocks > 0) and a set created on another device as further MI355LZ4_E_ARG.  Enqueue only: nothing of
+ * dictIdx or srcLen is read on the host.
+ * How: a grouping pass on the device (a histogram of dictIdx, a scan, a scatter: four small launches, scratch of the engine's) orders
+ * the blocks by member; then mi355lz4_compress_fastdict_device's grid of single wavefronts and staging windows, wave w taking the
+ * w-th of `grid` equal parts of that order.  A wave stages a dictionary when its next block names another member than its window
+ * holds, so a call stages at most grid + G - 1 times for G distinct indices, where one call per dictionary would stage grid times
+ * each.  Equal block counts per wave: lengths that go with the dictionary can unbalance the waves (byte-weighted parts are not
+ * built).  MI355LZ4_FASTDICT_WAVES applies as it does there.
+ * Measured once (scripts/dictset_rate.py, profiles/dictset_rate.json; one session, medians of 5 event-timed calls after a warm-up, the
+ * forms alternated): 16384 text records of 4 KiB, 64 members of 64 KiB, 256 records a member.  One call with the members' records
+ * shuffled through the batch: 0.74 ms (4096 stagings by 4096 waves); 64 mi355lz4_compress_fastdict_device calls of 256 records back
+ * to back: 6.83 ms -- the five values of each lie apart.  Sorted by member: 0.84 ms against 0.62 ms for one single-dictionary call
+ * over all records, so the grouping pass and the indirection cost 0.22 ms, a factor 1.35.  Lengths that go with the member (32
+ * members with 1 KiB records, 32 with 16 KiB records, the same 64 MiB): 3.04 ms against 0.79 ms for one single-dictionary call on the
+ * same lengths, a factor 3.85 -- what equal block counts per wave cost there. */
+int mi355lz4_compress_fastdict_multi_device(mi355lz4_ctx *ctx, const mi355lz4_dictset *ds, const int32_t *dictIdx,
+                                            const uint8_t *src, const uint64_t *srcOff, const int32_t *srcLen,
+                                            uint64_t blockStride, int maxBlockLen, int nBlocks, int accel, int headerKind,
+                                            uint8_t *slots, size_t slotStride, int32_t *framedLen);
+/* Host-buffer form, synchronous: mi355lz4_compress_fastdict's group pipeline with the device call above per group; dictIdx is host
+ * memory, nBlocks entries, and each group's part of it goes to the device with its lengths.  dictIdx and the lengths are checked on
+ * the host before anything is queued: an index outside -1..n-1 or a length outside 0..4 MiB is MI355LZ4_E_ARG, nothing is enqueued
+ * or written, and *outLen is 0. */
+int mi355lz4_compress_fastdict_multi(mi355lz4_ctx *ctx, const mi355lz4_dictset *ds, const int32_t *dictIdx,
+                                     const uint8_t *const *src, const int32_t *srcLen, int nBlocks, int accel, int headerKind,
+                                     uint8_t *framedOut, size_t cap, size_t *outLen, int32_t *blockFramedLen, int32_t *status);
+/* mi355lz4_decompress_dict_device with (ds, dictIdx) in place of (dictDevice, dictLen); dictIdx[0, nBlocks) is device memory.
+ * With k = dictIdx[i]: for k in 0..n-1, result[i] and the bytes written for block i are those of mi355lz4_decompress_dict_device
+ * on that block with member k's kept bytes -- the last keep = min(len, 65536) bytes of what was loaded -- as the dictionary, for
+ * well-formed and malformed blocks alike.  Only the last 64 KiB of a dictionary can be reached and a dictionary of 65536 bytes
+ * leaves the offset check unarmed as a longer one does, so this is also the result against the dictionary that was loaded.
+ * k == -1 is dictLen == 0.  Any other k gives result[i] = MI355LZ4_BLK_E_DICT, and nothing is read or written for that block.
+ * Header rejections, cap_i, checksum verification, what the call may write, the errors and the enqueue-only rule are those of
+ * mi355lz4_decompress_dict_device, with a null ds or dictIdx (nBlocks > 0) and a set created on another device as further
+ * MI355LZ4_E_ARG.  One wavefront per block, the member's bytes read in place: nothing is staged and nothing is grouped.
+ * Measured once (the same script and shape): one call with shuffled indices 0.27 ms; 64 mi355lz4_decompress_dict_device calls of 256
+ * blocks back to back 3.03 ms, the five values of each apart; one such call over all blocks against one dictionary 0.26 ms. */
+int mi355lz4_decompress_dict_multi_device(mi355lz4_ctx *ctx, const uint8_t *framed, uint64_t framedLen, const uint64_t *blockOff,
+                                          int nBlocks, int headerKind, int fixedUncomp, const mi355lz4_dictset *ds,
+                                          const int32_t *dictIdx, uint8_t *out, const uint64_t *outOff,
+                                          const int32_t *outCap /* may be NULL */, int32_t *result);
+/* Host-buffer form, synchronous: as mi355lz4_decompress_dict (a single group) with dictIdx, host memory of maxBlocks entries, in
+ * place of the dictionary.  The first nBlocks entries -- one per block of the chain -- are checked on the host: one outside -1..n-1
+ * is MI355LZ4_E_ARG and nothing is enqueued or written. */
+int mi355lz4_decompress_dict_multi(mi355lz4_ctx *ctx, const uint8_t *framedIn, size_t inLen, int headerKind, int fixedUncomp,
+                                   const mi355lz4_dictset *ds, const int32_t *dictIdx, uint8_t *out, size_t cap, size_t *outLen,
+                                   int32_t *blockLen, int maxBlocks, int *nBlocks);
 
 /* ---- fixed-size output pages: LZ4_compress_destSize for batches ---------------------------------------------------------
  * Every other compress call takes a block of a given size and writes what that needs.  This one takes a destination of a given

@@ -25,6 +25,7 @@
 struct mi355lz4_ctx;
 struct mi355lz4_cstreams;
 struct mi355lz4_hcdict;
+struct mi355lz4_dictset;
 struct mi355lz4_dstreams;
 
 namespace streamly_lz4 {
@@ -126,6 +127,14 @@ public:
     // The same batch at level 0 by the wave encoder (mi355lz4_compress_fastdict): the engine's own fast parse against the
     // dictionary of `hd`, not the reference's bytes (compressWithDict has those); decompressWithDict reads the result.
     std::vector<Array> compressWithDictFast(const BlockConfig &cfg, const std::vector<Array> &arrays, const class HcDict &hd, int accel = 1);
+    // The same batch with a dictionary per array (mi355lz4_compress_fastdict_multi): array i against member dictIdx[i] of `ds`
+    // (-1: none), the bytes compressWithDictFast writes for it against that member alone.  decompressWithDicts reads the result:
+    // block i against the kept bytes of member dictIdx[i] (mi355lz4_decompress_dict_multi).  One index per array; an index that
+    // names no member throws Error before anything runs.  The set and its members are only read.
+    std::vector<Array> compressWithDictsFast(const BlockConfig &cfg, const std::vector<Array> &arrays, const class DictSet &ds,
+                                             const std::vector<int32_t> &dictIdx, int accel = 1);
+    std::vector<Array> decompressWithDicts(const BlockConfig &cfg, const std::vector<Array> &blocks, const class DictSet &ds,
+                                           const std::vector<int32_t> &dictIdx);
     // Fixed-size output pages (mi355lz4_compress_pages): every array cut into a chain of at most maxPages pages whose blocks are
     // at most pageSize bytes -- page k is what LZ4_compress_destSize makes of the bytes behind pages 0..k-1.  Per input the pages in
     // order, each with cfg's header in front of its block (an ordinary block for decompressChunks when the header carries both
@@ -185,6 +194,21 @@ public:
 private:
     Engine &eng_;
     mi355lz4_hcdict *hd_ = nullptr;
+};
+
+// A set of prepared dictionaries (mi355lz4_dictset), for Engine::compressWithDictsFast / decompressWithDicts, where every array
+// names its member.  The members are borrowed: they must outlive the set (the same one may stand at several indices), and
+// HcDict::load on a member is seen by the set without a new one.
+class DictSet {
+public:
+    DictSet(Engine &eng, const std::vector<const HcDict *> &members);   // 1..65536 members on the engine's device; throws Error
+    ~DictSet();
+    DictSet(const DictSet &) = delete;
+    DictSet &operator=(const DictSet &) = delete;
+    mi355lz4_dictset *handle() const { return ds_; }
+    int count() const;
+private:
+    mi355lz4_dictset *ds_ = nullptr;
 };
 
 // A set of nSlots device-resident linked decode streams (mi355lz4_dstreams: about 64 KiB a slot -- the last block's last

@@ -1282,6 +1282,109 @@ extern "C" int mi355lz4_compress_pages_fastdict_device(mi355lz4_ctx *c, const mi
     return check_launch("fast dict pages launch");
 }
 
+// ---------------------------------------------------------------------------
+// Dictionary sets: a batch in which every block names its dictionary.  A mi355lz4_dictset is a table on the device
+// of the members' image pointers; the members are borrowed (mi355lz4_hcdict_load rebuilds their images in place, so the set follows
+// a reload without being recreated).  Level 0's wave encoder and the dictionary decoder take it; both only enqueue.
+// ---------------------------------------------------------------------------
+extern "C" int mi355lz4_dictset_create(mi355lz4_ctx *c, const mi355lz4_hcdict *const *hd, int n, mi355lz4_dictset **out)
+{
+    if (out) *out = nullptr;
+    if (!c || !hd || !out) return fail(MI355LZ4_E_ARG, "dictset_create: null argument");
+    if (n < 1 || n > DICTSET_MAX) return fail(MI355LZ4_E_ARG, "dictset_create: %d members outside 1..%d", n, DICTSET_MAX);
+    for (int i = 0; i < n; i++) {
+        if (!hd[i]) return fail(MI355LZ4_E_ARG, "dictset_create: member %d is null", i);
+        if (hd[i]->device != c->device)
+            return fail(MI355LZ4_E_ARG, "dictset_create: member %d lives on device %d, the engine on %d", i, hd[i]->device, c->device);
+    }
+    HIP_TRY(hipSetDevice(c->device));
+    mi355lz4_dictset *ds = new (std::nothrow) mi355lz4_dictset();
+    if (!ds) return fail(MI355LZ4_E_ARG, "out of host memory");
+    ds->device = c->device;
+    ds->n = n;
+    std::vector<DictSetEntry> host((size_t)n + 1);                    // (the last entry's bytes: the two diagnostic words, zero)
+    for (int i = 0; i < n; i++) host[(size_t)i] = DictSetEntry{hd[i]->image, hd[i]->fastImage};
+    host[(size_t)n] = DictSetEntry{nullptr, nullptr};
+    const size_t bytes = ((size_t)n + 1) * sizeof(DictSetEntry);
+    hipError_t e = hipMalloc((void **)&ds->table, bytes);
+    if (e == hipSuccess) e = hipMemcpyAsync(ds->table, host.data(), bytes, hipMemcpyHostToDevice, c->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);           // (host is pageable memory, and gone at the return)
+    if (e != hipSuccess) {
+        if (ds->table) hipFree(ds->table);
+        delete ds;
+        return fail(MI355LZ4_E_HIP, "dictset_create: %zu bytes: %s", bytes, hipGetErrorString(e));
+    }
+    *out = ds;
+    return MI355LZ4_OK;
+}
+
+extern "C" void mi355lz4_dictset_destroy(mi355lz4_dictset *ds)
+{
+    if (!ds) return;
+    hipSetDevice(ds->device);
+    hipDeviceSynchronize();                 // calls that still read the table
+    if (ds->table) hipFree(ds->table);
+    delete ds;
+}
+
+extern "C" int mi355lz4_dictset_count(const mi355lz4_dictset *ds) { return ds ? ds->n : fail(MI355LZ4_E_ARG, "dictset_count: null set"); }
+
+static int dictset_same_device(const mi355lz4_ctx *c, const mi355lz4_dictset *ds, const char *who)
+{
+    if (!c || !ds) return fail(MI355LZ4_E_ARG, "%s: null argument", who);
+    if (ds->device != c->device) return fail(MI355LZ4_E_ARG, "%s: the set lives on device %d, the engine on %d", who, ds->device, c->device);
+    return MI355LZ4_OK;
+}
+
+// Diagnostic hook (not part of the public header): out = {stagings, grid} of the last mi355lz4_compress_fastdict_multi_device call
+// that read the set -- how often its waves staged a dictionary (or dropped to none), and how many waves there were -- after
+// everything queued on the device has run.  The tests hold the call to stagings <= grid + distinct indices - 1 with it.
+extern "C" int mi355lz4_debug_dictset_last(mi355lz4_dictset *ds, int out[2])
+{
+    if (!ds || !out) return fail(MI355LZ4_E_ARG, "debug_dictset_last: bad arguments");
+    HIP_TRY(hipSetDevice(ds->device));
+    HIP_TRY(hipDeviceSynchronize());
+    HIP_TRY(hipMemcpy(out, ds->last(), 8, hipMemcpyDeviceToHost));
+    return MI355LZ4_OK;
+}
+
+// mi355lz4_compress_fastdict_device with a dictionary per block: the same checks, grid and windows; behind the windows the scratch
+// holds the grouping pass's order[], bins[] and range[].  Enqueues only; nothing of dictIdx or srcLen is read on the host.
+extern "C" int mi355lz4_compress_fastdict_multi_device(mi355lz4_ctx *c, const mi355lz4_dictset *ds, const int32_t *dictIdx,
+                                                       const uint8_t *src, const uint64_t *srcOff, const int32_t *srcLen,
+                                                       uint64_t blockStride, int maxBlockLen, int nBlocks, int accel, int headerKind,
+                                                       uint8_t *slots, size_t slotStride, int32_t *framedLen)
+{
+    if (int r = dictset_same_device(c, ds, "compress_fastdict_multi_device")) return r;
+    if (c->compLevel != 0)
+        return fail(MI355LZ4_E_ARG, "compress_fastdict_multi_device: compression level %d; a dictionary set is level 0's encoder", c->compLevel);
+    if (int r = batch_shape_check("compress_fastdict_multi_device", nBlocks, headerKind, maxBlockLen, INT_MAX)) return r;
+    if (maxBlockLen > HCDICT_MAX_BLOCK)
+        return fail(MI355LZ4_E_ARG, "compress_fastdict_multi_device: maxBlockLen %d above the %d bytes a dictionary batch takes", maxBlockLen, HCDICT_MAX_BLOCK);
+    if (nBlocks == 0) return MI355LZ4_OK;
+    if (!dictIdx) return fail(MI355LZ4_E_ARG, "compress_fastdict_multi_device: null dictIdx");
+    if (int r = batch_buffers_check(c, "compress_fastdict_multi_device", src, maxBlockLen, headerKind, slots, slotStride, framedLen)) return r;
+    HIP_TRY(hipSetDevice(c->device));
+    FastDictMultiArgs x;
+    x.e = make_encode_args(src, srcOff, srcLen, blockStride, maxBlockLen, nBlocks, accel, headerKind, slots, slotStride, framedLen);
+    x.e.stats = c->stats;
+    x.set = ds->table;
+    x.nDicts = ds->n;
+    x.dictIdx = dictIdx;
+    x.last = ds->last();
+    x.stageStride = 65536 + (((size_t)maxBlockLen + 64 + 255) & ~(size_t)255);       // compress_fastdict_device's
+    const int grid = encode_fastdict_grid(nBlocks, env_int("MI355LZ4_FASTDICT_WAVES", 0), x.stageStride);
+    const size_t windows = (size_t)grid * x.stageStride, orderBytes = ((size_t)nBlocks * 4 + 255) & ~(size_t)255;
+    if (int r = hcdict_stage(c, windows + orderBytes + ((size_t)ds->n + 2 + (size_t)grid + 1) * 4, &x.stage)) return r;
+    x.order = (int32_t *)(x.stage + windows);
+    x.bins = (uint32_t *)(x.stage + windows + orderBytes);
+    x.range = (int32_t *)(x.bins + ds->n + 2);
+    launch_dictset_group(x, grid, c->stream);
+    if (int r = check_launch("dictionary set grouping launch")) return r;
+    launch_encode_fastdict_multi(x, grid, c->stream);
+    return encode_launched(c, x.e, "fast dict multi launch");
+}
+
 extern "C" int mi355lz4_compact_device(mi355lz4_ctx *c, const uint8_t *slots, size_t slotStride,
                                        const int32_t *framedLen, int nBlocks, uint8_t *dense, size_t denseCap,
                                        uint64_t *denseOff)
@@ -1836,6 +1939,34 @@ extern "C" int mi355lz4_decompress_dict_device(mi355lz4_ctx *c, const uint8_t *f
     if (int rc = ck_flags(c, a)) return rc;
     launch_decode_dict(a, c->stream);
     const int rc = check_launch("decode dict launch");
+    ck_done(c);
+    return rc;
+}
+
+// ... and every block against the member of a dictionary set that it names: the call above with (ds, dictIdx) in
+// place of (dict, dictLen), k_decode_dict_multi.  Enqueues only; nothing of dictIdx is read on the host.
+extern "C" int mi355lz4_decompress_dict_multi_device(mi355lz4_ctx *c, const uint8_t *framed, uint64_t framedLen,
+                                                     const uint64_t *blockOff, int nBlocks, int headerKind, int fixedUncomp,
+                                                     const mi355lz4_dictset *ds, const int32_t *dictIdx, uint8_t *out,
+                                                     const uint64_t *outOff, const int32_t *outCap, int32_t *result)
+{
+    if (int r = dictset_same_device(c, ds, "decompress_dict_multi_device")) return r;
+    if (c->plan.active)
+        return fail(MI355LZ4_E_ARG, "decompress_dict_multi_device: a linked decode begun with mi355lz4_decompress_linked_begin is still open");
+    if (nBlocks < 0 || (headerKind != 4 && headerKind != 8) || fixedUncomp < 0)
+        return fail(MI355LZ4_E_ARG, "decompress_dict_multi_device: bad arguments");
+    if (nBlocks == 0) return MI355LZ4_OK;
+    if (!framed || !blockOff || !outOff || !result || !dictIdx) return fail(MI355LZ4_E_ARG, "decompress_dict_multi_device: null pointer");
+    HIP_TRY(hipSetDevice(c->device));
+    DictMultiArgs x{};
+    DecodeArgs &a = x.d;
+    a.framed = framed; a.framedLen = framedLen; a.blockOff = blockOff; a.nBlocks = nBlocks; a.segEnd = nBlocks;
+    a.headerKind = headerKind; a.fixedUncomp = fixedUncomp;
+    a.out = out; a.outOff = outOff; a.outCap = outCap; a.result = result; a.onlyBlk = -1;
+    x.set = ds->table; x.nDicts = ds->n; x.dictIdx = dictIdx;
+    if (int rc = ck_flags(c, a)) return rc;
+    launch_decode_dict_multi(x, c->stream);
+    const int rc = check_launch("decode dict multi launch");
     ck_done(c);
     return rc;
 }

@@ -447,7 +447,10 @@ __device__ __forceinline__ uint8_t *enc_page_close(EncPage &pg, uint8_t *op, con
 // k_encode_fastdict writes; *consumed counts the block's bytes, not the dictionary's.  Two rules differ, because such a block may open
 // with a match at its first byte: a cut is valid only if the page then consumes 13 bytes or more (a shorter block is literals only),
 // and the page holds the LEADING run of sequences whose cuts are all valid, since valid cuts no longer form a prefix.
-template <typename TabT, bool DICT = false, bool SEG = false, bool PAIR = false, bool PREP = false, bool BUDGET = false>
+// SITE changes nothing: it gives a kernel an instantiation of its own.  The encoder must be inlined into its kernel (its scalar
+// operands stay scalar only then), and the inliner does that for an instantiation with ONE caller; k_encode_fastdict_multi shares
+// every other argument with k_encode_fastdict and takes SITE 1.
+template <typename TabT, bool DICT = false, bool SEG = false, bool PAIR = false, bool PREP = false, bool BUDGET = false, int SITE = 0>
 __device__ int encode_block_wave(const uint8_t *src, int n, uint8_t *dst, int accel, TabT *table,
                                  unsigned long long *stats = nullptr, int dictLen = 0, SegOut *seg = nullptr,
                                  int budget = 0, int *consumed = nullptr)

@@ -106,6 +106,16 @@ struct mi355lz4_hcdict {
     uint8_t *fastImage = nullptr;
 };
 
+// A set of prepared dictionaries (api.cpp, "dictionary sets"): n entries of kernels.h's DictSetEntry on the device, filled from
+// the members' image pointers at creation -- the members are borrowed, and a _hcdict_load rebuilds their images in place -- and
+// behind them the two words {stagings, grid} of the last multi compress call.
+struct mi355lz4_dictset {
+    int device = 0;
+    int n = 0;
+    DictSetEntry *table = nullptr;         // n entries, then uint32 last[2]
+    uint32_t *last() const { return (uint32_t *)(table + n); }
+};
+
 namespace mi355lz4_detail {
 
 // pageable host memory <-> device through pinned staging, on the engine's stream (api.cpp)

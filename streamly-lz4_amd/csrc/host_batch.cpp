@@ -180,7 +180,11 @@ template <class Set> struct HostStreams { Set *set; const int32_t *first, *slot;
 // the loaded slot of a mi355lz4_compress_dict call: every block of every group from a copy of it (null: no dictionary)
 // (hc: a mi355lz4_compress_hcdict call instead, every block against that prepared dictionary at the engine's level)
 // (fast: a mi355lz4_compress_fastdict call, the same object at level 0 with the call's accel)
-struct HostDict { const mi355lz4_cstreams *set; int slot; const mi355lz4_hcdict *hc = nullptr; bool fast = false; };
+// (dset: a mi355lz4_compress_fastdict_multi call, block i against member dictIdx[i] of that set; the indices go up with the lengths)
+struct HostDict {
+    const mi355lz4_cstreams *set; int slot; const mi355lz4_hcdict *hc = nullptr; bool fast = false;
+    const mi355lz4_dictset *dset = nullptr; const int32_t *dictIdx = nullptr;
+};
 
 static int compress_host(mi355lz4_ctx *c, const uint8_t *const *src, const int32_t *srcLen,
                          int nBlocks, int accel, int headerKind, uint8_t *framedOut, size_t cap,
@@ -230,12 +234,14 @@ static int compress_host(mi355lz4_ctx *c, const uint8_t *const *src, const int32
         (r = dev_reserve(c->lenB, (size_t)nBlocks * 4)) || (r = dev_reserve(c->slots, (size_t)nBlocks * stride)) ||
         (r = dev_reserve(c->dense, (size_t)nBlocks * stride)) || (r = dev_reserve(c->offB, ((size_t)nBlocks + (size_t)G) * 8)))
         return r;
+    if (hd && hd->dset && (r = dev_reserve(c->res, (size_t)nBlocks * 4))) return r;
 
     DrainOnExit drain{c};
     EventSet evs(G);
     std::vector<hipEvent_t> &evIn = evs.in, &evK = evs.k, &evOut = evs.out;
     HIP_TRY(hipMemcpyAsync(c->offA.p, offs.data(), (size_t)nBlocks * 8, hipMemcpyHostToDevice, c->stream));
     HIP_TRY(hipMemcpyAsync(c->lenA.p, srcLen, (size_t)nBlocks * 4, hipMemcpyHostToDevice, c->stream));
+    if (hd && hd->dset) HIP_TRY(hipMemcpyAsync(c->res.p, hd->dictIdx, (size_t)nBlocks * 4, hipMemcpyHostToDevice, c->stream));
     // offs / srcLen are pageable: make sure the copies have consumed them before they go away
     HIP_TRY(hipStreamSynchronize(c->stream));
 
@@ -281,6 +287,11 @@ static int compress_host(mi355lz4_ctx *c, const uint8_t *const *src, const int32
                                                   0, maxLen, b1 - b0, accel, headerKind, (uint8_t *)c->slots.p + (size_t)b0 * stride,
                                                   stride, (int32_t *)c->lenB.p + b0);
             r = streams_enqueue(c, hs->set, a, b0, b1, hs->first, hs->slot, hs->n);
+        } else if (hd && hd->dset) {               // (every block against the member it names; the set and its members only read)
+            r = mi355lz4_compress_fastdict_multi_device(c, hd->dset, (const int32_t *)c->res.p + b0, (const uint8_t *)c->in.p,
+                                                        (const uint64_t *)c->offA.p + b0, (const int32_t *)c->lenA.p + b0, 0, maxLen,
+                                                        b1 - b0, accel, headerKind, (uint8_t *)c->slots.p + (size_t)b0 * stride, stride,
+                                                        (int32_t *)c->lenB.p + b0);
         } else if (hd && hd->hc && hd->fast) {     // (the same, by the wave encoder)
             r = mi355lz4_compress_fastdict_device(c, hd->hc, (const uint8_t *)c->in.p, (const uint64_t *)c->offA.p + b0,
                                                   (const int32_t *)c->lenA.p + b0, 0, maxLen, b1 - b0, accel, headerKind,
@@ -427,6 +438,32 @@ extern "C" int mi355lz4_compress_fastdict(mi355lz4_ctx *c, const mi355lz4_hcdict
     HostDict hd{nullptr, 0};
     hd.hc = hcd;
     hd.fast = true;
+    return compress_host(c, src, srcLen, nBlocks, accel, headerKind, framedOut, cap, outLen, blockFramedLen, status, nullptr, &hd);
+}
+
+// Host-buffer form of mi355lz4_compress_fastdict_multi_device: the same pipeline, block i against member dictIdx[i] of the set (-1:
+// none).  The indices and the lengths are the caller's host arrays: checked before anything is queued.
+extern "C" int mi355lz4_compress_fastdict_multi(mi355lz4_ctx *c, const mi355lz4_dictset *ds, const int32_t *dictIdx,
+                                                const uint8_t *const *src, const int32_t *srcLen, int nBlocks, int accel,
+                                                int headerKind, uint8_t *framedOut, size_t cap, size_t *outLen,
+                                                int32_t *blockFramedLen, int32_t *status)
+{
+    if (outLen) *outLen = 0;
+    if (!c || !ds) return fail(MI355LZ4_E_ARG, "compress_fastdict_multi: null argument");
+    if (engine_compression_level(c) != 0)
+        return fail(MI355LZ4_E_ARG, "compress_fastdict_multi: compression level %d; a dictionary set is level 0's encoder",
+                    engine_compression_level(c));
+    if (nBlocks > 0 && !dictIdx) return fail(MI355LZ4_E_ARG, "compress_fastdict_multi: null dictIdx");
+    const int nDicts = mi355lz4_dictset_count(ds);
+    for (int i = 0; i < nBlocks; i++)
+        if (dictIdx[i] < -1 || dictIdx[i] >= nDicts)
+            return fail(MI355LZ4_E_ARG, "compress_fastdict_multi: block %d names dictionary %d of %d", i, dictIdx[i], nDicts);
+    for (int i = 0; srcLen && i < nBlocks; i++)
+        if (srcLen[i] < 0 || srcLen[i] > HCDICT_MAX_BLOCK)
+            return fail(MI355LZ4_E_ARG, "compress_fastdict_multi: block %d length %d outside 0..%d", i, srcLen[i], HCDICT_MAX_BLOCK);
+    HostDict hd{nullptr, 0};
+    hd.dset = ds;
+    hd.dictIdx = dictIdx;
     return compress_host(c, src, srcLen, nBlocks, accel, headerKind, framedOut, cap, outLen, blockFramedLen, status, nullptr, &hd);
 }
 
@@ -851,6 +888,44 @@ extern "C" int mi355lz4_decompress_dict(mi355lz4_ctx *c, const uint8_t *framedIn
                                         (const uint64_t *)c->offB.p, nullptr, (int32_t *)c->res.p);
     if (r) return r;
     return host_tail(c, "decompress_dict", h, out, cap, outLen, blockLen, nBlocksOut);
+}
+
+// Host-buffer form of mi355lz4_decompress_dict_multi_device: mi355lz4_decompress_dict's single group with the first nBlocks entries
+// of dictIdx (of maxBlocks) in place of the dictionary.  The chain is walked and the indices are checked on the host first.
+extern "C" int mi355lz4_decompress_dict_multi(mi355lz4_ctx *c, const uint8_t *framedIn, size_t inLen, int headerKind, int fixedUncomp,
+                                              const mi355lz4_dictset *ds, const int32_t *dictIdx, uint8_t *out, size_t cap,
+                                              size_t *outLen, int32_t *blockLen, int maxBlocks, int *nBlocksOut)
+{
+    if (outLen) *outLen = 0;
+    if (nBlocksOut) *nBlocksOut = 0;
+    if (!c || !ds) return fail(MI355LZ4_E_ARG, "decompress_dict_multi: null argument");
+    if (!outLen || !nBlocksOut || maxBlocks < 0 || fixedUncomp < 0 || (headerKind != 4 && headerKind != 8))
+        return fail(MI355LZ4_E_ARG, "decompress_dict_multi: bad arguments");
+    if (c->plan.active) return fail(MI355LZ4_E_ARG, "a linked decode begun with mi355lz4_decompress_linked_begin is still open");
+    HostChain h;
+    int r = host_chain(h, "decompress_dict_multi", MI355LZ4_E_STREAM, framedIn, inLen, headerKind, fixedUncomp, c->blockChecksum, maxBlocks, at_capacity);
+    if (r) return r;
+    const int n = h.n;
+    if (n == 0) return MI355LZ4_OK;
+    if (!dictIdx) return fail(MI355LZ4_E_ARG, "decompress_dict_multi: null dictIdx");
+    const int nDicts = mi355lz4_dictset_count(ds);
+    for (int i = 0; i < n; i++)
+        if (dictIdx[i] < -1 || dictIdx[i] >= nDicts)
+            return fail(MI355LZ4_E_ARG, "decompress_dict_multi: block %d names dictionary %d of %d", i, dictIdx[i], nDicts);
+    HIP_TRY(hipSetDevice(c->device));
+    if ((r = dev_reserve(c->in, inLen + 16)) || (r = dev_reserve(c->offA, (size_t)n * 8)) || (r = dev_reserve(c->offB, ((size_t)n + 1) * 8)) ||
+        (r = dev_reserve(c->res, (size_t)n * 4)) || (r = dev_reserve(c->lenA, (size_t)n * 4)) || (r = dev_reserve(c->out, (size_t)h.total + 16)))
+        return r;
+    if ((r = h2d_staged(c, c->in.p, framedIn, inLen))) return r;
+    HIP_TRY(hipMemcpyAsync(c->offA.p, h.boff.data(), (size_t)n * 8, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipMemcpyAsync(c->offB.p, h.ooff.data(), ((size_t)n + 1) * 8, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipMemcpyAsync(c->lenA.p, dictIdx, (size_t)n * 4, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));          // (the vectors and the indices are pageable memory)
+    r = mi355lz4_decompress_dict_multi_device(c, (const uint8_t *)c->in.p, inLen, (const uint64_t *)c->offA.p, n, headerKind, fixedUncomp,
+                                              ds, (const int32_t *)c->lenA.p, (uint8_t *)c->out.p, (const uint64_t *)c->offB.p, nullptr,
+                                              (int32_t *)c->res.p);
+    if (r) return r;
+    return host_tail(c, "decompress_dict_multi", h, out, cap, outLen, blockLen, nBlocksOut);
 }
 
 // Host-buffer form of mi355lz4_compress_pages_device: inputs in host memory, one pageSize for all.  One group, synchronous, as the

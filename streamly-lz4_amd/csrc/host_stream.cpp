@@ -410,6 +410,85 @@ std::vector<Array> Engine::decompressWithDict(const BlockConfig &cfg, const std:
     return res;
 }
 
+DictSet::DictSet(Engine &eng, const std::vector<const HcDict *> &members)
+{
+    std::vector<const mi355lz4_hcdict *> h;
+    for (const HcDict *m : members) h.push_back(m ? m->handle() : nullptr);
+    if (mi355lz4_dictset_create(eng.ctx(), h.data(), (int)h.size(), &ds_) != MI355LZ4_OK)
+        throw Error(std::string("streamly_lz4::DictSet: ") + mi355lz4_last_error());
+}
+DictSet::~DictSet() { mi355lz4_dictset_destroy(ds_); }
+int DictSet::count() const { return mi355lz4_dictset_count(ds_); }
+
+std::vector<Array> Engine::compressWithDictsFast(const BlockConfig &cfg, const std::vector<Array> &arrays, const DictSet &ds,
+                                                 const std::vector<int32_t> &dictIdx, int accel)
+{
+    if (dictIdx.size() != arrays.size()) throw Error("compressWithDictsFast: one dictionary index per array");
+    const int meta = metaSize(cfg);
+    std::vector<const uint8_t *> ptrs;
+    std::vector<int32_t> lens, idx(dictIdx);
+    size_t cap = 16;
+    for (const Array &a : arrays) {
+        if (a.size() > (size_t)maxBlockSize(cfg))                               // compressChunk, Internal/LZ4.hs:237-241
+            throw Error("compressChunk: Source array length " + std::to_string(a.size()) +
+                        " exceeds the maximum block size of " + std::to_string(maxBlockSize(cfg)));
+        ptrs.push_back(a.data());
+        lens.push_back((int32_t)a.size());
+        cap += (size_t)mi355lz4_compress_bound((int)a.size()) + (size_t)meta + 4;
+    }
+    const int n = (int)lens.size();
+    std::vector<uint8_t> framed(cap);
+    std::vector<int32_t> flen((size_t)n + 1), status((size_t)n + 1);
+    ptrs.push_back(nullptr);
+    lens.push_back(0);
+    idx.push_back(-1);
+    size_t outLen = 0;
+    if (mi355lz4_compress_fastdict_multi(ctx_, ds.handle(), idx.data(), ptrs.data(), lens.data(), n, accel, meta, framed.data(), cap,
+                                         &outLen, flen.data(), status.data()) != MI355LZ4_OK)
+        throw Error(std::string("compressWithDictsFast: ") + mi355lz4_last_error());
+    std::vector<Array> out;
+    size_t pos = 0;
+    for (int k = 0; k < n; k++) {
+        out.emplace_back(framed.begin() + (long)pos, framed.begin() + (long)(pos + (size_t)flen[(size_t)k]));
+        pos += (size_t)flen[(size_t)k];
+    }
+    return out;
+}
+
+std::vector<Array> Engine::decompressWithDicts(const BlockConfig &cfg, const std::vector<Array> &blocks, const DictSet &ds,
+                                               const std::vector<int32_t> &dictIdx)
+{
+    if (dictIdx.size() != blocks.size()) throw Error("decompressWithDicts: one dictionary index per block");
+    const int meta = metaSize(cfg);
+    const BlockChecksumScope scope(ctx_, cfg.blockChecksum);
+    Array framed;
+    size_t cap = 16;
+    for (const Array &a : blocks) {
+        if (a.size() < (size_t)meta) throw Error("decompressWithDicts: an array shorter than a block header");
+        const int64_t u = (meta == 8) ? (int64_t)(int32_t)((uint32_t)a[4] | ((uint32_t)a[5] << 8) | ((uint32_t)a[6] << 16) |
+                                                           ((uint32_t)a[7] << 24))
+                                      : (int64_t)fixedUncompSize(cfg);
+        if (u > 0) cap += (size_t)u;
+        framed.insert(framed.end(), a.begin(), a.end());
+    }
+    const int n = (int)blocks.size();
+    Array out(cap);
+    std::vector<int32_t> blen((size_t)n + 1), idx(dictIdx);
+    idx.push_back(-1);
+    size_t outLen = 0;
+    int got = 0;
+    if (mi355lz4_decompress_dict_multi(ctx_, framed.data(), framed.size(), meta, fixedUncompSize(cfg), ds.handle(), idx.data(), out.data(),
+                                       cap, &outLen, blen.data(), n, &got) != MI355LZ4_OK)
+        throw Error(std::string("decompressWithDicts: ") + mi355lz4_last_error());
+    std::vector<Array> res;
+    size_t pos = 0;
+    for (int k = 0; k < got; k++) {
+        res.emplace_back(out.begin() + (long)pos, out.begin() + (long)(pos + (size_t)blen[(size_t)k]));
+        pos += (size_t)blen[(size_t)k];
+    }
+    return res;
+}
+
 DecompressStreams::DecompressStreams(Engine &eng, int nSlots) : eng_(eng)
 {
     if (mi355lz4_dstreams_create(eng.ctx(), nSlots, &ds_) != MI355LZ4_OK)

@@ -265,6 +265,41 @@ struct PagesFastDictArgs {
     size_t stageStride;          // >= 65536 + 65536 + 64: a page never holds more than 65536 input bytes
 };
 
+// a set of prepared dictionaries (mi355lz4_dictset): a table on the device, one entry per member, that holds
+// the members' two images by pointer -- the set owns neither -- and, behind the entries, two words {stagings, grid} of the last
+// mi355lz4_compress_fastdict_multi_device call (diagnostics: mi355lz4_debug_dictset_last)
+struct DictSetEntry {
+    const uint8_t *image;        // HCDICT_IMAGE_BYTES: the kept bytes and their count
+    const uint8_t *fast;         // FASTDICT_IMAGE_BYTES
+};
+#define DICTSET_MAX 65536
+
+// a level-0 batch in which block i names its dictionary (mi355lz4_compress_fastdict_multi_device; kernels/encode.inc,
+// k_encode_fastdict_multi): FastDictArgs' grid and windows; wave w takes order[w * nBlocks / grid, (w + 1) * nBlocks / grid), the
+// blocks grouped by dictIdx (launch_dictset_group), and restages its window when the member changes
+struct FastDictMultiArgs {
+    EncodeArgs e;                // as FastDictArgs'
+    const DictSetEntry *set;     // nDicts entries
+    int nDicts;
+    const int32_t *dictIdx;      // per block: a member, or -1 (no dictionary); anything else: framedLen 0, the slot untouched
+    int32_t *order;              // scratch, nBlocks: the block numbers grouped by dictIdx
+    uint32_t *bins;              // scratch, nDicts + 2: counts, then cursors, of the groups {-1, 0 .. nDicts - 1, out of range}
+    int32_t *range;              // scratch, grid + 1: wave w takes order[range[w], range[w + 1])
+    uint32_t *last;              // the set's {stagings, grid}
+    uint8_t *stage;              // one window per wave of the grid
+    size_t stageStride;          // >= 65536 + e.uniformLen + 64
+};
+
+// independent blocks, each against the kept bytes of the member it names (mi355lz4_decompress_dict_multi_device;
+// kernels/linked_walk.inc, k_decode_dict_multi): d.dict0 / d.dict0Len are not used
+#define BLK_E_DICT (-0x7F000006)
+struct DictMultiArgs {
+    DecodeArgs d;
+    const DictSetEntry *set;
+    int nDicts;
+    const int32_t *dictIdx;      // per block: a member, or -1 (no dictionary); anything else: result BLK_E_DICT, nothing written
+};
+
 // many linked decode streams continued across calls (mi355lz4_decompress_dstreams_device; kernels/linked_walk.inc, k_decode_dstreams).
 // One slot of a mi355lz4_dstreams is the device form of LZ4_streamDecode_t for separately allocated blocks: the last
 // min(r, 65536) bytes of the stream's last block that decoded to r > 0 bytes, at the slot's start, and that count.
@@ -351,8 +386,14 @@ int encode_fastdict_grid(int nBlocks, int knob, size_t stageStride);
 void launch_encode_fastdict(const FastDictArgs &a, int grid, hipStream_t s);
 // fixed-size output pages against both images: the same grid over inputs (encode_fastdict_grid(nInputs, ..)), one chain at a time per wave
 void launch_pages_fastdict(const PagesFastDictArgs &a, int grid, hipStream_t s);
+// level 0 with a dictionary per block: the grouping pass (a.bins, a.order, a.last from a.dictIdx; four small launches, nothing
+// read on the host), then the grid above over the grouped blocks
+void launch_dictset_group(const FastDictMultiArgs &a, int grid, hipStream_t s);
+void launch_encode_fastdict_multi(const FastDictMultiArgs &a, int grid, hipStream_t s);
 // independent blocks against one external dictionary (a.dict0, a.dict0Len; a.linked is not used): one wave per block
 void launch_decode_dict(const DecodeArgs &a, hipStream_t s);
+// ... each against the member of a set that it names: one wave per block
+void launch_decode_dict_multi(const DictMultiArgs &a, hipStream_t s);
 // many linked decode streams: one wave per entry of a.work walks its blocks from its slot's dictionary and stores the tail back;
 // launch_dstreams_set: slots [first, first + count) take the keep <= 65536 bytes at src as their dictionary (0: reset)
 void launch_decode_dstreams(const DStreamsArgs &a, int nWork, hipStream_t s);

@@ -14,6 +14,7 @@
 //                          k_exact_pages: fixed-size output pages, LZ4_compress_destSize      encode_fill.hpp
 //                          k_pages_fast: the same pages from the wave encoder with a budget   encode_wave.hpp, BUDGET
 //                          k_pages_fastdict: such pages against a prepared dictionary         encode_wave.hpp, DICT + PREP + BUDGET
+//                          k_dictset_zero / _hist / _scan / _scatter, k_encode_fastdict_multi<PAIR>: a dictionary per block
 //   compact.inc            k_scan_u64, k_copy_slots, k_interleave, k_header_sizes, k_decoded_size       size_walk.hpp
 //   checksum.inc           k_xxh32_ranges / _append / _verify: four lanes per range          checksum.hpp
 //   generate.inc           k_generate: synthetic inputs (bench and test support)
@@ -24,6 +25,7 @@
 //   decode_tok.inc         k_walk_tokens, k_decode_tok<STATS>: token lists (MI355LZ4_EXPERIMENTS only)   decode_par.hpp, LIST
 //   linked_walk.inc        k_decode_fixup_linked: a wave per stream; k_decode_dstreams, k_dstreams_set: streams continued
 //                          across calls; k_run_starts, k_decode_fixup_runs: a wave per short run        decode_par.hpp
+//                          k_decode_dict, k_decode_dict_multi: independent blocks against one dictionary, or one each
 //   runin.inc              k_runin_decode / _verify / _fix / _publish: long streams in pieces (RUNIN_OCC)
 //   linked_tolerant.inc    k_decode_tolerant: deferred lists; k_decode_fixup_regions: their replay      linked_replay.hpp
 //   linked_ptr.inc         k_ptr_expand / _jump / _fetch<CHASE> / _finish: the pointer passes           linked_ptr.hpp

@@ -888,3 +888,145 @@ void launch_pages_fastdict(const PagesFastDictArgs &a, int grid, hipStream_t s)
     if (a.p.nInputs <= 0 || grid <= 0) return;
     hipLaunchKernelGGL(k_pages_fastdict, dim3((unsigned)grid), dim3(64), 0, s, a);
 }
+
+// ---------------------------------------------------------------------------
+// K2, the wave encoder against a SET of prepared dictionaries (mi355lz4_compress_fastdict_multi_device, DESIGN.md 7o): block i
+// names member dictIdx[i] of a mi355lz4_dictset, or -1 for none.  A wave that met its blocks in call order would restage up to
+// 64 KiB of dictionary for every block, so the blocks are grouped by member first and a wave takes a contiguous range of the
+// grouped order: it stages once, and once more per group boundary inside its range.
+//
+// The grouping pass: bins {-1, 0 .. nDicts - 1, anything else}; a histogram with global atomics, an exclusive scan by one
+// workgroup, a scatter through the scanned counts as per-group cursors.  Not stable, and it need not be: a block's bytes do not
+// depend on where it runs.  Nothing of it is read on the host.
+// ---------------------------------------------------------------------------
+__device__ __forceinline__ int dictset_bin(int k, int nDicts) { return (k < -1 || k >= nDicts) ? nDicts + 1 : k + 1; }
+
+// zeroed counts and stagings, and the waves' ranges of order[]: wave w takes [range[w], range[w + 1]) = [w * nBlocks / grid, ..)
+__global__ __launch_bounds__(256) void k_dictset_zero(FastDictMultiArgs x, int grid)
+{
+    const int i = (int)(blockIdx.x * 256u + threadIdx.x);
+    if (i < x.nDicts + 2) x.bins[i] = 0u;
+    if (i <= grid) x.range[i] = (int32_t)((int64_t)i * x.e.nBlocks / grid);
+    if (i == 0) { x.last[0] = 0u; x.last[1] = (uint32_t)grid; }
+}
+
+__global__ __launch_bounds__(256) void k_dictset_hist(FastDictMultiArgs x)
+{
+    const int i = (int)(blockIdx.x * 256u + threadIdx.x);
+    if (i < x.e.nBlocks) atomicAdd(&x.bins[dictset_bin(x.dictIdx[i], x.nDicts)], 1u);
+}
+
+// counts -> first positions, in place: thread t sums a run of bins, the runs' sums are scanned in LDS
+#define DICTSET_SCAN_THREADS 1024
+__global__ __launch_bounds__(DICTSET_SCAN_THREADS) void k_dictset_scan(FastDictMultiArgs x)
+{
+    __shared__ uint32_t part[DICTSET_SCAN_THREADS];
+    const int t = (int)threadIdx.x, nBins = x.nDicts + 2;
+    const int per = (nBins + DICTSET_SCAN_THREADS - 1) / DICTSET_SCAN_THREADS;
+    const int lo = min(t * per, nBins), hi = min(lo + per, nBins);
+    uint32_t sum = 0;
+    for (int i = lo; i < hi; i++) sum += x.bins[i];
+    part[t] = sum;
+    __syncthreads();
+    for (int d = 1; d < DICTSET_SCAN_THREADS; d <<= 1) {
+        const uint32_t v = t >= d ? part[t - d] : 0u;
+        __syncthreads();
+        part[t] += v;
+        __syncthreads();
+    }
+    uint32_t at = part[t] - sum;
+    for (int i = lo; i < hi; i++) { const uint32_t c = x.bins[i]; x.bins[i] = at; at += c; }
+}
+
+__global__ __launch_bounds__(256) void k_dictset_scatter(FastDictMultiArgs x)
+{
+    const int i = (int)(blockIdx.x * 256u + threadIdx.x);
+    if (i >= x.e.nBlocks) return;
+    const uint32_t at = atomicAdd(&x.bins[dictset_bin(x.dictIdx[i], x.nDicts)], 1u);
+    if (at < (uint32_t)x.e.nBlocks) x.order[at] = i;                   // (always: the counts sum to nBlocks)
+}
+
+void launch_dictset_group(const FastDictMultiArgs &a, int grid, hipStream_t s)
+{
+    if (a.e.nBlocks <= 0) return;
+    const unsigned perBlock = (unsigned)((a.e.nBlocks + 255) / 256), perBin = (unsigned)((max(a.nDicts + 2, grid + 1) + 255) / 256);
+    hipLaunchKernelGGL(k_dictset_zero, dim3(perBin), dim3(256), 0, s, a, grid);
+    hipLaunchKernelGGL(k_dictset_hist, dim3(perBlock), dim3(256), 0, s, a);
+    hipLaunchKernelGGL(k_dictset_scan, dim3(1), dim3(DICTSET_SCAN_THREADS), 0, s, a);
+    hipLaunchKernelGGL(k_dictset_scatter, dim3(perBlock), dim3(256), 0, s, a);
+}
+
+// k_encode_fastdict's grid, occupancy, window and call site.  Wave w takes order[w * nBlocks / grid, (w + 1) * nBlocks / grid) (x.range) and
+// remembers which member its window holds (`held`; -1: none, which needs no window; -2: nothing yet).  When the next block names another member the
+// wave reads that member's {keep, seam0} and copies its kept bytes so that they end at byte 65536 of the window -- in front of the
+// block copy and of the fence that orders both against the reads.  A shorter dictionary behind a longer one leaves stale bytes in
+// front of blockAt - keep: the seam steps read from blockAt - keep on, and the encoder takes src - dictLen as position 0 and never
+// forms a candidate below it (tab_candidate).  Every (re)staging counts in x.last[0].  An index outside -1 .. nDicts - 1 or a
+// length outside 0..uniformLen gives framedLen 0 and leaves the slot alone.  Nothing of any member is written.
+template <bool PAIR>
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(ENC_WAVES_PER_EU, ENC_WAVES_PER_EU))) void k_encode_fastdict_multi(FastDictMultiArgs x)
+{
+    __shared__ __attribute__((aligned(16))) uint16_t table[ENC_TABLE_ENTRIES + ENC_LDS_PAD + ((PAIR && ENC_STAGE) ? 128 : 0)];
+    const int lane = lane_id();
+    const EncodeArgs a = x.e;
+    const int j0 = min(max(uni(x.range[blockIdx.x]), 0), a.nBlocks), j1 = min(max(uni(x.range[blockIdx.x + 1u]), j0), a.nBlocks);
+    uint8_t *blockAt = x.stage + (uint64_t)blockIdx.x * (uint64_t)x.stageStride + 65536;
+    int held = -2, keep = 0, seam0 = 0;                                 // (-2: nothing yet, so the first block counts as a staging)
+    const uint8_t *fast = nullptr;
+    dev_v4 *tab4 = (dev_v4 *)table;
+    for (int j = j0; j < j1; j++) {
+        const int blk = uni(x.order[j]);
+        if ((unsigned)blk >= (unsigned)a.nBlocks) continue;             // (never: the grouping pass wrote a permutation)
+        const int k = uni(x.dictIdx[blk]);
+        const EncBlock b = enc_block(a, blk);
+        const int n = uni(b.n);
+        if (k < -1 || k >= x.nDicts || n < 0 || n > a.uniformLen) {
+            if (lane == 0) a.framedLen[blk] = 0;
+            continue;
+        }
+        // (what the wave carries from block to block is wave-uniform, but the lane-0 store above joins the loop's back edge, and a
+        // value that lives across such a join counts as divergent: said again here, they stay scalar operands of the encoder)
+        held = uni(held); keep = uni(keep); seam0 = uni(seam0);
+        fast = (const uint8_t *)(uintptr_t)uni64((int64_t)(uintptr_t)fast);
+        if (k != held) {
+            keep = 0; seam0 = 0; fast = nullptr;
+            if (k >= 0) {
+                const DictSetEntry m = x.set[k];
+                fast = (const uint8_t *)(uintptr_t)uni64((int64_t)(uintptr_t)m.fast);
+                const uint8_t *image = (const uint8_t *)(uintptr_t)uni64((int64_t)(uintptr_t)m.image);
+                const LZ4_GLOBAL uint32_t *hdr = as_global((const uint32_t *)(fast + FASTDICT_KEEP_OFF));
+                keep = (int)min(ex_uni(hdr[0]), 65536u);
+                seam0 = (int)min(ex_uni(hdr[1]), 65536u);
+                if (keep > 0) wave_copy_bytes(blockAt - keep, image + HCDICT_DICT_OFF, (uint32_t)keep);
+            }
+            held = k;
+            if (lane == 0) atomicAdd(&x.last[0], 1u);
+        }
+        const uint8_t *src = a.src + uni64((int64_t)b.off);
+        uint8_t *slot = a.slots + (size_t)blk * a.slotStride;
+        int dictLen = 0;
+        if (n >= LZ4_MFLIMIT + 1 && keep > 0) {
+            wave_copy_bytes(blockAt, src, (uint32_t)n);
+            for (int i = lane; i < (int)(FASTDICT_TABLE_BYTES / 16); i += LZ4_WAVE) tab4[i] = as_global((const dev_v4 *)fast)[i];
+            // the block's bytes -- and, behind a restaging, the dictionary's -- are read back by other lanes than wrote them, and the
+            // steps below enter into the loaded table
+            wave_fence();
+            for (int q0 = seam0; q0 < keep; q0 += ENC_SEED_SPAN) enc_seed_step<false>(table, blockAt - keep, q0, keep);
+            src = blockAt;
+            dictLen = keep;
+        } else if (n >= LZ4_MFLIMIT + 1) {                              // no dictionary: the block of a one-block linked call, where it lies
+            for (int i = lane; i < (int)(FASTDICT_TABLE_BYTES / 16); i += LZ4_WAVE) tab4[i] = dev_v4{0u, 0u, 0u, 0u};
+        }                                                               // (shorter blocks are literals: no window, no table)
+        // (one call site of an instantiation of its own -- SITE 1, encode_wave.hpp: the encoder is inlined, and its scalar operands
+        // stay scalar, here and in k_encode_fastdict)
+        const int c = encode_block_wave<uint16_t, true, false, PAIR, true, false, 1>(src, n, slot + a.headerKind, a.accel, table, a.stats, dictLen);
+        enc_finish_slot(a, blk, slot, c, n, lane == 0);
+    }
+}
+
+void launch_encode_fastdict_multi(const FastDictMultiArgs &a, int grid, hipStream_t s)
+{
+    if (a.e.nBlocks <= 0 || grid <= 0) return;
+    if (a.e.uniformLen > 65536) hipLaunchKernelGGL((k_encode_fastdict_multi<false>), dim3((unsigned)grid), dim3(64), 0, s, a);
+    else hipLaunchKernelGGL((k_encode_fastdict_multi<true>), dim3((unsigned)grid), dim3(64), 0, s, a);
+}

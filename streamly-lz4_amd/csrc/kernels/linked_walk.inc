@@ -190,3 +190,39 @@ void launch_linked_runs(const DecodeArgs &a, hipStream_t s)
     hipLaunchKernelGGL(k_run_starts, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, a);
     hipLaunchKernelGGL(k_decode_fixup_runs, dim3((unsigned)min(n, a.runs.cap)), dim3(64), 0, s, a);
 }
+
+// k_decode_dict with a dictionary per block (mi355lz4_decompress_dict_multi_device, DESIGN.md 7o): block blockIdx.x is decoded
+// against the kept bytes of member dictIdx[blk] of a mi355lz4_dictset -- the bytes and their count read wave-uniformly from the
+// member's image -- or against none (-1).  Any other index: BLK_E_DICT, and nothing of the block is read or written.  The same
+// one wavefront per block, the same decoder; the members are only read.
+__global__ PAR_OCC void k_decode_dict_multi(DictMultiArgs x)
+{
+    __shared__ ParLds lds;
+    const int blk = (int)blockIdx.x;
+    const int k = uni(x.dictIdx[blk]);
+    if (k < -1 || k >= x.nDicts) {
+        if (lane_id() == 0) x.d.result[blk] = BLK_E_DICT;
+        return;
+    }
+    const uint8_t *dict = nullptr;
+    uint32_t dictLen = 0;
+    if (k >= 0) {
+        const uint8_t *image = (const uint8_t *)(uintptr_t)uni64((int64_t)(uintptr_t)x.set[k].image);
+        dictLen = min((uint32_t)uni((int)as_global((const uint32_t *)(image + HCDICT_KEEP_OFF))[0]), 65536u);
+        dict = image + HCDICT_DICT_OFF;
+    }
+    const uint8_t *data = nullptr;
+    int compLen = 0, cap = 0;
+    int r = read_block_header(x.d, blk, data, compLen, cap);
+    if (r == 0)
+        r = decode_block_par<false, true>(data, compLen, x.d.out + x.d.outOff[blk], cap, dict, dictLen, x.d.framed,
+                                          x.d.framed + x.d.framedLen, lds, nullptr);
+    r = uni(r);
+    if (lane_id() == 0) x.d.result[blk] = r;
+}
+
+void launch_decode_dict_multi(const DictMultiArgs &a, hipStream_t s)
+{
+    if (a.d.nBlocks <= 0) return;
+    hipLaunchKernelGGL(k_decode_dict_multi, dim3((unsigned)a.d.nBlocks), dim3(64), 0, s, a);
+}

@@ -178,6 +178,18 @@ def _load():
         C.c_size_t, vp)
     sig("mi355lz4_compress_fastdict", C.c_int, vp, vp, C.POINTER(_u8p), _i32p, C.c_int, C.c_int, C.c_int, _u8p, C.c_size_t,
         C.POINTER(C.c_size_t), _i32p, _i32p)
+    # dictionary sets: a batch in which every block names its dictionary
+    sig("mi355lz4_dictset_create", C.c_int, vp, C.POINTER(vp), C.c_int, C.POINTER(vp))
+    sig("mi355lz4_dictset_destroy", None, vp)
+    sig("mi355lz4_dictset_count", C.c_int, vp)
+    sig("mi355lz4_debug_dictset_last", C.c_int, vp, C.POINTER(C.c_int))
+    sig("mi355lz4_compress_fastdict_multi_device", C.c_int, vp, vp, vp, vp, vp, vp, C.c_uint64, C.c_int, C.c_int, C.c_int, C.c_int,
+        vp, C.c_size_t, vp)
+    sig("mi355lz4_compress_fastdict_multi", C.c_int, vp, vp, _i32p, C.POINTER(_u8p), _i32p, C.c_int, C.c_int, C.c_int, _u8p,
+        C.c_size_t, C.POINTER(C.c_size_t), _i32p, _i32p)
+    sig("mi355lz4_decompress_dict_multi_device", C.c_int, vp, vp, C.c_uint64, vp, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp, vp, vp)
+    sig("mi355lz4_decompress_dict_multi", C.c_int, vp, _u8p, C.c_size_t, C.c_int, C.c_int, vp, _i32p, _u8p, C.c_size_t,
+        C.POINTER(C.c_size_t), _i32p, C.c_int, C.POINTER(C.c_int))
     # fixed-size output pages
     sig("mi355lz4_compress_pages_device", C.c_int, vp, vp, vp, vp, C.c_int, vp, C.c_int, C.c_int, vp, C.c_size_t, vp, vp, vp, vp)
     sig("mi355lz4_compress_pages", C.c_int, vp, C.POINTER(_u8p), _i32p, C.c_int, C.c_int, C.c_int, C.c_int, _u8p, C.c_size_t,
@@ -252,6 +264,9 @@ DECLARED_SYMBOLS = [
     "mi355lz4_hcdict_create", "mi355lz4_hcdict_destroy", "mi355lz4_hcdict_load", "mi355lz4_hcdict_size",
     "mi355lz4_compress_hcdict_device", "mi355lz4_compress_hcdict",
     "mi355lz4_compress_fastdict_device", "mi355lz4_compress_fastdict",
+    "mi355lz4_dictset_create", "mi355lz4_dictset_destroy", "mi355lz4_dictset_count",
+    "mi355lz4_compress_fastdict_multi_device", "mi355lz4_compress_fastdict_multi",
+    "mi355lz4_decompress_dict_multi_device", "mi355lz4_decompress_dict_multi",
     "mi355lz4_compress_pages_device", "mi355lz4_compress_pages",
     "mi355lz4_compress_pages_fast_device", "mi355lz4_compress_pages_fast",
     "mi355lz4_compress_pages_fastdict_device", "mi355lz4_compress_pages_fastdict",
@@ -1120,6 +1135,77 @@ class Engine:
         return out[: out_len.value].tobytes(), blen[: got.value].tolist()
 
 
+    def compress_fastdict_multi_device(self, ds, dict_idx, src, n_blocks, max_block_len, slots, slot_stride_, framed_len, accel=1,
+                                       header_kind=8, src_off=None, src_len=None, block_stride=None):
+        """compress_fastdict_device with a dictionary per block: block i is compressed against member dict_idx[i] (an int32
+        device tensor; -1: no dictionary) of the DictSet ds and comes out as compress_fastdict_device writes it against that
+        member alone.  Any other index gives framed_len[i] = 0 and an untouched slot.  The set and its members are only read.
+        Only enqueues (include/mi355lz4.h, mi355lz4_compress_fastdict_multi_device)."""
+        self._follow_torch()
+        _check(lib.mi355lz4_compress_fastdict_multi_device(
+            self.ctx, ds._h if ds is not None else None, _dptr(dict_idx), _dptr(src), _dptr(src_off), _dptr(src_len),
+            int(max_block_len if block_stride is None else block_stride), int(max_block_len), int(n_blocks), int(accel),
+            int(header_kind), _dptr(slots), int(slot_stride_), _dptr(framed_len)), "compress_fastdict_multi_device")
+
+    def compress_fastdict_multi(self, blocks, ds, dict_idx, accel=1, header_kind=8):
+        """blocks: list of bytes-like, block i compressed at level 0 by the wave encoder against member dict_idx[i] of the
+        DictSet ds (-1: none).  Returns (framed bytes, [framed length per block]); mi355lz4_compress_fastdict_multi."""
+        n = len(blocks)
+        arrs = [np.frombuffer(bytes(b), dtype=np.uint8) if not isinstance(b, np.ndarray) else b for b in blocks]
+        ptrs = (_u8p * max(n, 1))(*[a.ctypes.data_as(_u8p) for a in arrs])
+        lens = np.array([a.size for a in arrs] + [0], dtype=np.int32)
+        idx = np.ascontiguousarray(np.asarray(list(dict_idx) + [0], dtype=np.int64).astype(np.int32))
+        if idx.size != n + 1:
+            raise ValueError("compress_fastdict_multi: one index per block")
+        cap = int(sum(compress_bound(max(int(x), 0)) + header_kind + 4 for x in lens[:n])) + 16
+        out = np.empty(cap, dtype=np.uint8)
+        out_len = C.c_size_t()
+        flen = np.zeros(max(n, 1), dtype=np.int32)
+        status = np.zeros(max(n, 1), dtype=np.int32)
+        _check(lib.mi355lz4_compress_fastdict_multi(self.ctx, ds._h if ds is not None else None, idx.ctypes.data_as(_i32p), ptrs,
+                                                    lens.ctypes.data_as(_i32p), n, int(accel), int(header_kind),
+                                                    out.ctypes.data_as(_u8p), cap, C.byref(out_len), flen.ctypes.data_as(_i32p),
+                                                    status.ctypes.data_as(_i32p)), "compress_fastdict_multi")
+        return out[: out_len.value].tobytes(), flen[:n].tolist()
+
+    def decompress_dict_multi_device(self, framed, framed_len, block_off, n_blocks, ds, dict_idx, out, out_off, result,
+                                     header_kind=8, fixed_uncomp=0, out_cap=None):
+        """decompress_dict_device with a dictionary per block: block i is decoded against the kept bytes of member dict_idx[i]
+        (an int32 device tensor; -1: no dictionary) of the DictSet ds.  Any other index gives result[i] = BLK_E_DICT and writes
+        nothing.  Only enqueues (include/mi355lz4.h, mi355lz4_decompress_dict_multi_device)."""
+        self._follow_torch()
+        _check(lib.mi355lz4_decompress_dict_multi_device(
+            self.ctx, _dptr(framed), int(framed_len), _dptr(block_off), int(n_blocks), int(header_kind), int(fixed_uncomp),
+            ds._h if ds is not None else None, _dptr(dict_idx), _dptr(out), _dptr(out_off), _dptr(out_cap), _dptr(result)),
+            "decompress_dict_multi_device")
+
+    def decompress_dict_multi(self, framed, ds, dict_idx, header_kind=8, fixed_uncomp=0, max_blocks=None,
+                              raise_on_block_error=True, cap=None):
+        """A framed chain in host memory, block i decoded against member dict_idx[i] of the DictSet ds (-1: none).  Returns
+        (decoded bytes, [decoded length or negative code per block]); mi355lz4_decompress_dict_multi."""
+        src = np.frombuffer(bytes(framed), dtype=np.uint8)
+        if max_blocks is None:
+            max_blocks = src.size // (header_kind + 1) + 1
+        if cap is None:
+            _, ulen = index_host(framed, header_kind, fixed_uncomp, self._block_checksum)
+            cap = int(np.asarray(ulen, dtype=np.int64).clip(min=0).sum()) + 16
+        cap = int(cap)
+        out = np.empty(max(cap, 1), dtype=np.uint8)
+        out_len = C.c_size_t()
+        blen = np.zeros(max(max_blocks, 1), dtype=np.int32)
+        got = C.c_int()
+        idx = np.zeros(max(max_blocks, 1), dtype=np.int32)
+        given = np.asarray(list(dict_idx), dtype=np.int64).astype(np.int32)[: idx.size]
+        idx[: given.size] = given
+        rc = lib.mi355lz4_decompress_dict_multi(self.ctx, src.ctypes.data_as(_u8p) if src.size else None, src.size,
+                                                int(header_kind), int(fixed_uncomp), ds._h if ds is not None else None,
+                                                idx.ctypes.data_as(_i32p), out.ctypes.data_as(_u8p), cap, C.byref(out_len),
+                                                blen.ctypes.data_as(_i32p), int(max_blocks), C.byref(got))
+        if rc != 0 and (raise_on_block_error or rc != -5):
+            _check(rc, "decompress_dict_multi")
+        return out[: out_len.value].tobytes(), blen[: got.value].tolist()
+
+
 class HcDict:
     """A prepared high-compression dictionary on the engine's device (mi355lz4_hcdict, about 216 KiB): the dictionary's last
     64 KiB and the image of the hash-chain encoder's tables after its inserts, for Engine.compress_hcdict_device /
@@ -1161,6 +1247,48 @@ class HcDict:
         if self._h:
             lib.mi355lz4_hcdict_destroy(self._h)
             self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class DictSet:
+    """A set of prepared dictionaries on the engine's device (mi355lz4_dictset): a table of the members' images, for
+    Engine.compress_fastdict_multi_device / compress_fastdict_multi and Engine.decompress_dict_multi_device /
+    decompress_dict_multi, where every block names its member.  The members (HcDict objects; the same one may stand at several
+    indices) are borrowed by the C object; this class keeps them alive.  HcDict.load on a member is seen without a new set."""
+
+    BLK_E_DICT = -0x7F000006    # include/mi355lz4.h, MI355LZ4_BLK_E_DICT
+
+    def __init__(self, engine, members):
+        self._h = C.c_void_p()
+        self._engine = engine
+        self._members = list(members)
+        engine._follow_torch()
+        n = len(self._members)
+        arr = (C.c_void_p * max(n, 1))(*[m._h if m is not None else None for m in self._members])
+        _check(lib.mi355lz4_dictset_create(engine.ctx, arr, n, C.byref(self._h)), "dictset_create")
+
+    def __len__(self):
+        return int(lib.mi355lz4_dictset_count(self._h))
+
+    def members(self):
+        return list(self._members)
+
+    def last(self):
+        """Diagnostics: (stagings, grid) of the last compress_fastdict_multi_device call that read the set, after the device is idle."""
+        out = (C.c_int * 2)()
+        _check(lib.mi355lz4_debug_dictset_last(self._h, out), "debug_dictset_last")
+        return int(out[0]), int(out[1])
+
+    def close(self):
+        if self._h:
+            lib.mi355lz4_dictset_destroy(self._h)
+            self._h = C.c_void_p()
+        self._members = []
 
     def __del__(self):
         try:
