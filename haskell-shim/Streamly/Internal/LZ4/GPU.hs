@@ -74,6 +74,13 @@ module Streamly.Internal.LZ4.GPU
     , compressChunksPagedFast
     , c_compressPagesFastDictDevice
     , compressChunksPagedWithDictFast
+    , FastStreams
+    , newFastStreams
+    , freeFastStreams
+    , resetFastStreams
+    , fastStreamsSetDict
+    , c_compressStreamsFastDevice
+    , compressChunksManyFast
     , DecompressStreams
     , newDecompressStreams
     , freeDecompressStreams
@@ -330,6 +337,31 @@ foreign import ccall safe "mi355lz4.h mi355lz4_decompress_streams"
 -- calls"): a set of device-resident @LZ4_streamDecode_t@s, one slot per pipeline -- the last block's last 64 KiB and their
 -- count.  Stream s of a call = blocks [streamFirst[s], streamFirst[s+1]), continuing slot streamSlot[s]: the next blocks of
 -- all pipelines in one FFI call, as they arrive, instead of one engine call per stream with a host-side dictionary.
+-- Many fast linked compress streams continued across calls (include/mi355lz4.h, "many fast linked compress streams"): the wave
+-- encoder's counterpart of the set above.  A slot is the last array's last 64 KiB and their count.
+data C_FStreams
+newtype FastStreams = FastStreams (Ptr C_FStreams)
+
+foreign import ccall safe "mi355lz4.h mi355lz4_fstreams_create"
+    c_fstreamsCreate :: Ptr C_Engine -> CInt -> Ptr (Ptr C_FStreams) -> IO CInt
+foreign import ccall safe "mi355lz4.h mi355lz4_fstreams_destroy"
+    c_fstreamsDestroy :: Ptr C_FStreams -> IO ()
+foreign import ccall unsafe "mi355lz4.h mi355lz4_fstreams_count"
+    c_fstreamsCount :: Ptr C_FStreams -> IO CInt
+foreign import ccall safe "mi355lz4.h mi355lz4_fstreams_reset"
+    c_fstreamsReset :: Ptr C_Engine -> Ptr C_FStreams -> Ptr Int32 -> CInt -> IO CInt
+foreign import ccall safe "mi355lz4.h mi355lz4_fstreams_set_dict"
+    c_fstreamsSetDict :: Ptr C_Engine -> Ptr C_FStreams -> CInt -> Ptr Word8 -> CInt -> IO CInt
+-- device pointers in, device pointers out; only enqueues
+foreign import ccall safe "mi355lz4.h mi355lz4_compress_streams_fast_device"
+    c_compressStreamsFastDevice
+        :: Ptr C_Engine -> Ptr C_FStreams -> Ptr Word8 -> Ptr Word64 -> Ptr Int32 -> Word64 -> CInt -> CInt
+        -> Ptr Int32 -> Ptr Int32 -> CInt -> CInt -> CInt -> Ptr Word8 -> CSize -> Ptr Int32 -> IO CInt
+foreign import ccall safe "mi355lz4.h mi355lz4_compress_streams_fast"
+    c_compressStreamsFast
+        :: Ptr C_Engine -> Ptr C_FStreams -> Ptr (Ptr Word8) -> Ptr Int32 -> CInt -> Ptr Int32 -> Ptr Int32 -> CInt
+        -> CInt -> CInt -> Ptr Word8 -> CSize -> Ptr CSize -> Ptr Int32 -> Ptr Int32 -> IO CInt
+
 data C_DStreams
 newtype DecompressStreams = DecompressStreams (Ptr C_DStreams)
 
@@ -483,6 +515,32 @@ resetCompressStreams (Engine p) (CompressStreams cs) (Just slots) =
         when (rc /= 0) $ error "mi355lz4_cstreams_reset: a slot is out of range"
 
 -- | A set of @n@ device-resident decode streams (about 64 KiB each), every one reset.
+newFastStreams :: Engine -> Int -> IO FastStreams
+newFastStreams (Engine p) n = alloca $ \pp -> do
+    rc <- c_fstreamsCreate p (fromIntegral n) pp
+    when (rc /= 0) $ error "mi355lz4_fstreams_create failed"
+    FastStreams <$> peek pp
+
+freeFastStreams :: FastStreams -> IO ()
+freeFastStreams (FastStreams p) = c_fstreamsDestroy p
+
+-- | Forget the dictionaries of the listed slots (@Nothing@: all of them); enqueued.
+resetFastStreams :: Engine -> FastStreams -> Maybe [Int] -> IO ()
+resetFastStreams (Engine p) (FastStreams fs) Nothing = do
+    rc <- c_fstreamsReset p fs nullPtr 0
+    when (rc /= 0) $ error "mi355lz4_fstreams_reset failed"
+resetFastStreams (Engine p) (FastStreams fs) (Just slots) =
+    allocaArray (max 1 (length slots)) $ \ps -> do
+        pokeArray ps (map fromIntegral slots)
+        rc <- c_fstreamsReset p fs ps (fromIntegral (length slots))
+        when (rc /= 0) $ error "mi355lz4_fstreams_reset: a slot is out of range"
+
+-- | The slot becomes the last 64 KiB of the @len@ bytes of DEVICE memory at @dict@; enqueued, the slot keeps its own copy.
+fastStreamsSetDict :: Engine -> FastStreams -> Int -> Ptr Word8 -> Int -> IO ()
+fastStreamsSetDict (Engine p) (FastStreams fs) slot dict len = do
+    rc <- c_fstreamsSetDict p fs (fromIntegral slot) dict (fromIntegral len)
+    when (rc /= 0) $ error "mi355lz4_fstreams_set_dict failed"
+
 newDecompressStreams :: Engine -> Int -> IO DecompressStreams
 newDecompressStreams (Engine p) n = alloca $ \pp -> do
     rc <- c_dstreamsCreate p (fromIntegral n) pp
@@ -572,6 +630,42 @@ compressChunksMany (Engine eng) (CompressStreams cs) cfg speed pipes = do
             rc <- c_compressStreams eng cs pSrc pLen (fromIntegral n) pFirst pSlot (fromIntegral ns)
                       (fromIntegral speed) (fromIntegral meta) dstBegin (fromIntegral cap) pOutLen pFlen pStatus
             when (rc /= 0) $ error "compressChunksMany: mi355lz4_compress_streams failed"
+        flens <- map fromIntegral <$> peekArray n pFlen
+        let offs = scanl (+) 0 flens
+            outs = [ Array.unsafeFreeze (MArray.Array cont dstBegin_ (dstBegin `plusPtr` (o + l)) dstMax)
+                       `seq` Array.Array cont (dstBegin `plusPtr` o) (dstBegin `plusPtr` (o + l))
+                   | (o, l) <- zip offs flens ]
+            split [] _ = []
+            split (c : rest) xs = let (h, t) = splitAt c xs in h : split rest t
+        return (split counts outs)
+
+-- | 'compressChunksMany' by the wave encoder (level 0): @(slot, arrays)@ per pipeline, every pipeline continuing its slot of
+-- the set, every array compressed with the last 64 KiB of the array before it in its pipeline as dictionary.  Each pipeline's
+-- result is a linked stream that 'decompressChunksMany' reads however it is cut -- not the reference's bytes -- and all
+-- arrays of all pipelines are compressed at once.
+compressChunksManyFast
+    :: Engine -> FastStreams -> BlockConfig -> Int -> [(Int, [Array.Array Word8])] -> IO [[Array.Array Word8]]
+compressChunksManyFast (Engine eng) (FastStreams cs) cfg speed pipes = do
+    let arrs = concatMap snd pipes
+        counts = map (length . snd) pipes
+        n = length arrs
+        ns = length pipes
+        meta = metaSizeOf cfg
+        lens = map Array.byteLength arrs
+        cap = sum (map (\l -> fromIntegral (c_bound (fromIntegral l)) + meta + 4) lens)
+    (MArray.Array cont dstBegin_ dstBegin dstMax) <- MArray.newArray (max cap 1)
+    allocaArray n $ \pSrc -> allocaArray n $ \pLen -> allocaArray n $ \pFlen ->
+      allocaArray n $ \pStatus -> allocaArray (ns + 1) $ \pFirst -> allocaArray ns $ \pSlot -> alloca $ \pOutLen -> do
+        let withAll [] k = k []
+            withAll (a:as) k = Array.asPtrUnsafe (Array.unsafeCast a) $ \p -> withAll as (k . (p :))
+        withAll arrs $ \ptrs -> do
+            pokeArray pSrc ptrs
+            pokeArray pLen (map fromIntegral lens)
+            pokeArray pFirst (map fromIntegral (scanl (+) 0 counts))
+            pokeArray pSlot (map (fromIntegral . fst) pipes)
+            rc <- c_compressStreamsFast eng cs pSrc pLen (fromIntegral n) pFirst pSlot (fromIntegral ns)
+                      (fromIntegral speed) (fromIntegral meta) dstBegin (fromIntegral cap) pOutLen pFlen pStatus
+            when (rc /= 0) $ error "compressChunksManyFast: mi355lz4_compress_streams_fast failed"
         flens <- map fromIntegral <$> peekArray n pFlen
         let offs = scanl (+) 0 flens
             outs = [ Array.unsafeFreeze (MArray.Array cont dstBegin_ (dstBegin `plusPtr` (o + l)) dstMax)

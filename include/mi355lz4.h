@@ -100,6 +100,11 @@ typedef struct mi355lz4_ctx mi355lz4_ctx;
  *   streamSlot[] names for a stream with blocks -- never a slot the call does not name, never framed, blockOff, outOff or
  *   outCap.  _dstreams_reset / _dstreams_set_dict write the slots they name and nothing else (never the dictionary handed
  *   in).  _decompress_dstreams is a host-buffer call as above.
+ * Many fast linked streams (_compress_streams_fast_device): slots[i*slotStride, i*slotStride + framedLen[i]) inside the slot ranges
+ *   of _compress_batch_device, framedLen[0, nBlocks) (a stream stopped by a bad length leaves its remaining slots untouched
+ *   and sets their framedLen to 0), the slots of `fs` that streamSlot[] names for a stream with blocks, and engine scratch;
+ *   never a slot of `fs` the call does not name, never src, srcOff or srcLen.  _fstreams_reset / _fstreams_set_dict write the
+ *   slots they name and nothing else (never the dictionary handed in).  _compress_streams_fast is a host-buffer call as above.
  * Shared-dictionary batches: _cstreams_load_dict writes the slot of `cs` it names and nothing else (never the dictionary
  *   handed in).  _compress_dict_device: the slot ranges of _compress_batch_device and framedLen[0, nBlocks); never any
  *   slot of `cs` -- the loaded slot is only read -- never src, srcOff or srcLen.  _decompress_dict_device: no byte of `out`
@@ -1049,6 +1054,64 @@ int mi355lz4_decompress_dstreams(mi355lz4_ctx *ctx, mi355lz4_dstreams *ds, const
                                  int headerKind, int fixedUncomp, const int32_t *streamFirst, const int32_t *streamSlot,
                                  int nStreams, uint8_t *out, size_t cap, size_t *outLen, int32_t *blockLen, int maxBlocks,
                                  int *nBlocks);
+
+/* ---- many fast linked compress streams, continued across calls ------------------------------------------------------------
+ * The wave encoder's counterpart of mi355lz4_cstreams and the write side of mi355lz4_dstreams: a host that runs many pipelines
+ * (connections, log shards, files) keeps one slot per pipeline and compresses the next separately allocated arrays of all of
+ * them in ONE call, as they arrive -- the reference's compressChunksD situation -- at the speed of the other fast forms instead
+ * of one serial chain per stream.
+ *
+ * A mi355lz4_fstreams is an opaque set of nSlots device-resident streams, owned by the caller and bound to the device of the
+ * engine it was created with (any engine on that device may use it; one call at a time).  One slot holds the last
+ * min(n, 65536) bytes of the stream's last good block and that count -- the mi355lz4_dstreams slot, 65600 bytes (2560 slots:
+ * about 160 MiB) -- all of it on the device.  _create leaves every slot reset (no dictionary); _reset does that for
+ * slots[0..n) (slots == NULL: all of them), enqueued on the engine's stream; _destroy waits for the device.
+ * _set_dict is the write-side twin of mi355lz4_dstreams_set_dict: slot `slot` becomes the last 64 KiB of dictDevice[0, len)
+ * (device memory; the slot keeps its own copy); len == 0 equals a reset.  The call only enqueues. */
+typedef struct mi355lz4_fstreams mi355lz4_fstreams;
+int mi355lz4_fstreams_create(mi355lz4_ctx *ctx, int nSlots, mi355lz4_fstreams **out);
+void mi355lz4_fstreams_destroy(mi355lz4_fstreams *fs);
+int mi355lz4_fstreams_count(const mi355lz4_fstreams *fs);
+int mi355lz4_fstreams_reset(mi355lz4_ctx *ctx, mi355lz4_fstreams *fs, const int32_t *slots, int n);
+int mi355lz4_fstreams_set_dict(mi355lz4_ctx *ctx, mi355lz4_fstreams *fs, int slot, const uint8_t *dictDevice, int len);
+/* Compress nBlocks blocks that belong to nStreams linked streams.  The argument list, the stream table rules and the error
+ * cases are those of mi355lz4_compress_streams_device with `fs` in place of `cs`: streamFirst and streamSlot are HOST arrays,
+ * the table ascending over [0, nBlocks], a slot named only once per call, the set bound to its device, only level 0 accepted
+ * (MI355LZ4_E_ARG otherwise).  maxBlockLen is bounded as in mi355lz4_compress_fastdict_device (4 MiB).  The linked switch,
+ * segments and the exact switch are ignored; block checksums apply.
+ * Dictionary of a block: block k of a stream is compressed with D as its dictionary, D being the last min(len, 65536) bytes
+ * of the block before it in its stream -- for a stream's first block in a call, what the slot holds.  There is no dictionary
+ * when there is no block before it, when that block was empty, or after a reset: a zero-length array resets a stream's
+ * dictionary, as it does LZ4_stream_t's and the linked switch's.
+ * Bytes: block k is, byte for byte, what mi355lz4_compress_batch_device with the linked switch on writes for the second block
+ * of the contiguous two-block call [D, B_k] at level 0 with the same accel and maxBlockLen = max(|D|, maxBlockLen); with an
+ * empty D, the block of the one-block linked call.  So a stream's bytes do not depend on how it is cut into calls -- one block
+ * per call, one call for all, or any mix -- nor on where its blocks lie: they equal one linked mi355lz4_compress_batch_device
+ * call over the stream laid out contiguously.
+ * Interop: the output is a linked stream in the reference's sense with separately allocated blocks, read by
+ * mi355lz4_decompress_dstreams_device however the stream is cut, by mi355lz4_decompress_streams_device, by
+ * mi355lz4_decompress_batch_device(linked != 0) and by LZ4_decompress_safe_continue.
+ * Asynchronous: the call only enqueues and reads no device memory on the host (beyond four calls in flight it waits for the
+ * oldest one's stream table).  A srcLen outside 0..maxBlockLen can therefore be no error code: that block and the rest of its
+ * stream's blocks in the call get framedLen = 0 and their slots in the output are not written, the stream's state slot stays
+ * as it was after the last good block, and other streams are unaffected -- the rule of mi355lz4_compress_streams_device.
+ * An empty stream leaves its slot untouched.  The slot owns its copy: src may be overwritten once the call has run.
+ * What the call may write: see the top.  All blocks of all streams of a call are compressed at once: a stream of many blocks
+ * in one call costs no more than as many streams of one.  Rates (profiles/fstreams_rate.json, scripts/fstreams_rate.py): 16 streams
+ * of 160 text blocks of 64 KiB in 1.65 ms where mi355lz4_compress_streams_device takes 1850 ms; 2560 streams of one such block in
+ * 1.47 ms against 30.2 ms. */
+int mi355lz4_compress_streams_fast_device(mi355lz4_ctx *ctx, mi355lz4_fstreams *fs, const uint8_t *src,
+                                          const uint64_t *srcOff, const int32_t *srcLen, uint64_t blockStride,
+                                          int maxBlockLen, int nBlocks, const int32_t *streamFirst,
+                                          const int32_t *streamSlot, int nStreams, int accel, int headerKind,
+                                          uint8_t *slots, size_t slotStride, int32_t *framedLen);
+/* Host-buffer form: as mi355lz4_compress_streams (one dense framed stream in block order, blockFramedLen and status per
+ * block, synchronous, the same group pipeline; a group seam inside a stream continues through its slot).  The lengths are
+ * checked on the host: a bad one is MI355LZ4_E_ARG and nothing is enqueued. */
+int mi355lz4_compress_streams_fast(mi355lz4_ctx *ctx, mi355lz4_fstreams *fs, const uint8_t *const *src,
+                                   const int32_t *srcLen, int nBlocks, const int32_t *streamFirst,
+                                   const int32_t *streamSlot, int nStreams, int accel, int headerKind, uint8_t *framedOut,
+                                   size_t cap, size_t *outLen, int32_t *blockFramedLen, int32_t *status);
 
 /* mi355lz4_slot_stride with room for the trailer when blockChecksum != 0. */
 size_t mi355lz4_slot_stride_ex(int blockLen, int headerKind, int blockChecksum);

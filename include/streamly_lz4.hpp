@@ -27,6 +27,7 @@ struct mi355lz4_cstreams;
 struct mi355lz4_hcdict;
 struct mi355lz4_dictset;
 struct mi355lz4_dstreams;
+struct mi355lz4_fstreams;
 
 namespace streamly_lz4 {
 
@@ -106,6 +107,12 @@ public:
     // them at this point of that pipeline's stream.  Throws Error.
     std::vector<std::vector<Array>> compressStreams(const BlockConfig &cfg, int speed, const std::vector<std::vector<Array>> &streams,
                                                     class CompressStreams &cs, const std::vector<int32_t> &slots);
+    // Many fast linked streams in one call (mi355lz4_compress_streams_fast): compressStreams' arguments and result with a
+    // FastCompressStreams -- the wave encoder at level 0, every array compressed with the last 64 KiB of the array before it in
+    // its pipeline as dictionary; not the reference's bytes (compressStreams has those), a linked stream all the same, which
+    // decompressStreams reads however it is cut.  All arrays of all pipelines are compressed at once.  Throws Error.
+    std::vector<std::vector<Array>> compressStreamsFast(const BlockConfig &cfg, int speed, const std::vector<std::vector<Array>> &streams,
+                                                        class FastCompressStreams &fs, const std::vector<int32_t> &slots);
     // Many linked decode streams continued across calls (mi355lz4_decompress_dstreams): streams[s] are the next resized
     // blocks (header + data each) of the pipeline that owns slot slots[s] of ds; the result holds, per stream, one decoded
     // array per block -- what decompressChunksRawD yields for them at this point of that pipeline's stream; the previous
@@ -177,6 +184,26 @@ public:
 private:
     Engine &eng_;
     mi355lz4_cstreams *cs_ = nullptr;
+};
+
+// A set of nSlots device-resident fast linked compress streams (mi355lz4_fstreams: about 64 KiB a slot, the last array's last
+// 64 KiB and their count), one per pipeline a host runs at once; Engine::compressStreamsFast continues many of them in one call.
+class FastCompressStreams {
+public:
+    FastCompressStreams(Engine &eng, int nSlots);      // every slot reset; throws Error
+    ~FastCompressStreams();
+    FastCompressStreams(const FastCompressStreams &) = delete;
+    FastCompressStreams &operator=(const FastCompressStreams &) = delete;
+    mi355lz4_fstreams *handle() const { return fs_; }
+    int count() const;
+    void reset();                                       // no dictionary, all slots
+    void reset(const std::vector<int32_t> &slots);      // ... the listed ones
+    // mi355lz4_fstreams_set_dict: the slot becomes the last 64 KiB of dictDevice[0, len) (DEVICE memory; len 0 equals a
+    // reset); enqueued, the slot keeps its own copy
+    void setDict(int slot, const uint8_t *dictDevice, int len);
+private:
+    Engine &eng_;
+    mi355lz4_fstreams *fs_ = nullptr;
 };
 
 // A prepared high-compression dictionary on the engine's device (mi355lz4_hcdict: about 216 KiB -- the dictionary's last 64 KiB

@@ -777,30 +777,7 @@ extern "C" int mi355lz4_compress_batch_device(mi355lz4_ctx *c, const uint8_t *sr
 // The small per-call table {first block, end block, slot} per stream goes through a ring of pinned buffers: an entry is
 // reused once the launch that read it is done (four calls may be in flight before a call waits for the oldest).
 // ---------------------------------------------------------------------------
-struct StreamTableRing {                    // (shared with mi355lz4_dstreams, the decode side's set)
-    struct Ring { DevBuf pin, dev; hipEvent_t ev = nullptr; bool busy = false; } ring[4];
-    int next = 0;
-    void release()
-    {
-        for (auto &r : ring) {
-            if (r.ev) hipEventDestroy(r.ev);
-            r.ev = nullptr; r.busy = false;
-            pin_release(r.pin);
-            dev_release(r.dev);
-        }
-    }
-};
-
-// A set of slots on one device, written once for both sides: the compress side's slot is CSTREAM_SLOT_BYTES, the decode side's
-// (mi355lz4_dstreams, below) DSTREAM_SLOT_BYTES.  `who` names the calling entry point in the messages.
-struct SlotSet {
-    int device = 0;
-    int nSlots = 0;
-    uint8_t *state = nullptr;               // nSlots * the side's slot size
-    StreamTableRing table;
-};
-struct mi355lz4_cstreams : SlotSet {};
-struct mi355lz4_dstreams : SlotSet {};
+// (StreamTableRing, SlotSet and the three sets built on it: engine.hpp)
 
 template <class Set>
 static int slots_create(mi355lz4_ctx *c, int nSlots, size_t slotBytes, Set **out, const char *who)
@@ -916,13 +893,27 @@ static int stream_table_check(int nSlots, int nBlocks, const int32_t *streamFirs
     return MI355LZ4_OK;
 }
 
+// the checks both compress-side sets share (mi355lz4_cstreams, mi355lz4_fstreams): the set on the engine's device, level 0, the table
+// over the set's nSlots slots.  `what` names the form in the level's message.
+static int compress_streams_check(const mi355lz4_ctx *c, const SlotSet *s, int nSlots, int nBlocks, const int32_t *streamFirst,
+                                  const int32_t *streamSlot, int nStreams, const char *who, const char *what)
+{
+    if (int r = slots_same_device(c, s, who)) return r;
+    if (c->compLevel != 0)
+        return fail(MI355LZ4_E_ARG, "%s: compression level %d; %s streams are level 0's encoder", who, c->compLevel, what);
+    return stream_table_check(nSlots, nBlocks, streamFirst, streamSlot, nStreams, who);
+}
+
 int mi355lz4_detail::streams_check(const mi355lz4_ctx *c, const mi355lz4_cstreams *cs, int nBlocks, const int32_t *streamFirst,
                                    const int32_t *streamSlot, int nStreams, const char *who)
 {
-    if (int r = slots_same_device(c, cs, who)) return r;
-    if (c->compLevel != 0)
-        return fail(MI355LZ4_E_ARG, "%s: compression level %d; exact streams are level 0's encoder", who, c->compLevel);
-    return stream_table_check(cs->nSlots, nBlocks, streamFirst, streamSlot, nStreams, who);
+    return compress_streams_check(c, cs, cs ? cs->nSlots : 0, nBlocks, streamFirst, streamSlot, nStreams, who, "exact");
+}
+
+int mi355lz4_detail::fstreams_check(const mi355lz4_ctx *c, const mi355lz4_fstreams *fs, int nBlocks, const int32_t *streamFirst,
+                                    const int32_t *streamSlot, int nStreams, const char *who)
+{
+    return compress_streams_check(c, fs, fs ? fs->nSlots : 0, nBlocks, streamFirst, streamSlot, nStreams, who, "fast");
 }
 
 // The upload: {first block, end block, slot} per stream with blocks in [b0, b1), relative to b0, longer parts first, through
@@ -1383,6 +1374,111 @@ extern "C" int mi355lz4_compress_fastdict_multi_device(mi355lz4_ctx *c, const mi
     if (int r = check_launch("dictionary set grouping launch")) return r;
     launch_encode_fastdict_multi(x, grid, c->stream);
     return encode_launched(c, x.e, "fast dict multi launch");
+}
+
+// ---------------------------------------------------------------------------
+// Many fast linked streams continued across calls (mi355lz4_fstreams, mi355lz4_compress_streams_fast_device): the
+// wave encoder's counterpart of mi355lz4_cstreams, and the write side of mi355lz4_dstreams -- a slot is that set's slot, the last
+// good block's last 64 KiB and their count.  A block's bytes depend on the tail of the block before it, on itself and on accel, so
+// all blocks of all streams of a call are compressed at once (k_encode_fstreams); the slots are read by that launch and written by
+// the one behind it.  The per-call table goes through the same ring as the other two sets' (stream_table_upload); the windows and
+// the plan's scratch come from the dictionary calls' pool.  Everything only enqueues.  MI355LZ4_FSTREAMS_WAVES is read per call.
+// ---------------------------------------------------------------------------
+extern "C" int mi355lz4_fstreams_create(mi355lz4_ctx *c, int nSlots, mi355lz4_fstreams **out)
+{
+    return slots_create(c, nSlots, FSTREAM_SLOT_BYTES, out, "fstreams_create");
+}
+extern "C" void mi355lz4_fstreams_destroy(mi355lz4_fstreams *fs) { slots_destroy(fs); }
+extern "C" int mi355lz4_fstreams_count(const mi355lz4_fstreams *fs) { return slots_count(fs, "fstreams_count"); }
+
+extern "C" int mi355lz4_fstreams_reset(mi355lz4_ctx *c, mi355lz4_fstreams *fs, const int32_t *slots, int n)
+{
+    if (int r = slots_reset_check(c, fs, slots, n, "fstreams_reset")) return r;
+    if (!slots) {
+        launch_dstreams_set(fs->state, 0, fs->nSlots, nullptr, 0, c->stream);
+        return check_launch("fstreams reset launch");
+    }
+    for (int i = 0; i < n; i++)             // the count: a dictionary of 0 bytes needs no bytes cleared
+        HIP_TRY(hipMemsetAsync(fs->state + (size_t)slots[i] * FSTREAM_SLOT_BYTES + FSTREAM_COUNT_OFF, 0, 4, c->stream));
+    return MI355LZ4_OK;
+}
+
+// the write-side twin of mi355lz4_dstreams_set_dict: the slot becomes the last 64 KiB of dictDevice[0, len)
+extern "C" int mi355lz4_fstreams_set_dict(mi355lz4_ctx *c, mi355lz4_fstreams *fs, int slot, const uint8_t *dictDevice, int len)
+{
+    if (int r = slots_same_device(c, fs, "fstreams_set_dict")) return r;
+    if (slot < 0 || slot >= fs->nSlots) return fail(MI355LZ4_E_ARG, "fstreams_set_dict: slot %d of %d", slot, fs->nSlots);
+    if (len < 0 || (len > 0 && !dictDevice)) return fail(MI355LZ4_E_ARG, "fstreams_set_dict: bad dictionary");
+    HIP_TRY(hipSetDevice(c->device));
+    const int keep = len > FSTREAM_DICT_BYTES ? FSTREAM_DICT_BYTES : len;
+    launch_dstreams_set(fs->state, slot, 1, keep ? dictDevice + (len - keep) : nullptr, (uint32_t)keep, c->stream);
+    return check_launch("fstreams set_dict launch");
+}
+
+// Diagnostic hook (not part of the public header): slot `slot` as it is after everything queued on the device has run -- *count =
+// its dictionary bytes, hostBytes65536 (may be null) = the slot's whole dictionary area, of which the first *count bytes are kept.
+extern "C" int mi355lz4_debug_fstreams_peek(mi355lz4_fstreams *fs, int slot, uint8_t *hostBytes65536, int *count)
+{
+    if (!fs || slot < 0 || slot >= fs->nSlots) return fail(MI355LZ4_E_ARG, "debug_fstreams_peek: bad arguments");
+    HIP_TRY(hipSetDevice(fs->device));
+    HIP_TRY(hipDeviceSynchronize());
+    const uint8_t *st = fs->state + (size_t)slot * FSTREAM_SLOT_BYTES;
+    if (count) HIP_TRY(hipMemcpy(count, st + FSTREAM_COUNT_OFF, 4, hipMemcpyDeviceToHost));
+    if (hostBytes65536) HIP_TRY(hipMemcpy(hostBytes65536, st, FSTREAM_DICT_BYTES, hipMemcpyDeviceToHost));
+    return MI355LZ4_OK;
+}
+
+// the size checks of a call's blocks, shared by the device call and the host-buffer form: compress_fastdict_device's
+int mi355lz4_detail::fstreams_shape_check(const char *who, int nBlocks, int headerKind, int maxBlockLen)
+{
+    if (int r = batch_shape_check(who, nBlocks, headerKind, maxBlockLen, INT_MAX)) return r;
+    if (maxBlockLen > HCDICT_MAX_BLOCK)
+        return fail(MI355LZ4_E_ARG, "%s: maxBlockLen %d above the %d bytes a fast stream's block takes", who, maxBlockLen, HCDICT_MAX_BLOCK);
+    return MI355LZ4_OK;
+}
+
+// Enqueue the streams' parts that fall into blocks [b0, b1) of the table (a.* describes exactly those blocks), as streams_enqueue
+// does: a stream cut by b0 or b1 continues through its slot in the next launch, which runs behind this one's k_fstreams_save.
+int mi355lz4_detail::fstreams_enqueue(mi355lz4_ctx *c, mi355lz4_fstreams *fs, const EncodeArgs &a, int b0, int b1,
+                                      const int32_t *streamFirst, const int32_t *streamSlot, int nStreams)
+{
+    if (a.nBlocks <= 0) return MI355LZ4_OK;
+    FStreamsArgs x;
+    int rc;
+    StreamTableRing::Ring *used = nullptr;
+    if ((rc = stream_table_upload(c, fs->table, b0, b1, streamFirst, streamSlot, nStreams, &x.work, &x.nWork, &used))) return rc;
+    if (x.nWork == 0) return MI355LZ4_OK;
+    x.e = a;
+    x.e.stats = c->stats;
+    x.e.linked = 0; x.e.lookBack = 0;
+    x.state = fs->state;
+    x.stageStride = 65536 + (((size_t)a.uniformLen + 64 + 255) & ~(size_t)255);        // compress_fastdict_device's
+    const int grid = encode_fastdict_grid(a.nBlocks, env_int("MI355LZ4_FSTREAMS_WAVES", 0), x.stageStride);
+    const size_t windows = (size_t)grid * x.stageStride;
+    if ((rc = hcdict_stage(c, windows + ((size_t)x.nWork + (size_t)a.nBlocks) * 4, &x.stage))) return rc;
+    x.good = (int32_t *)(x.stage + windows);
+    x.blockStream = x.good + x.nWork;
+    launch_fstreams(x, grid, c->stream);
+    if ((rc = check_launch("fast streams launch"))) return rc;
+    if ((rc = stream_table_launched(c, used))) return rc;       // (the ring entry is busy from here on, whatever the trailers do)
+    return encode_trailers(c, x.e);
+}
+
+extern "C" int mi355lz4_compress_streams_fast_device(mi355lz4_ctx *c, mi355lz4_fstreams *fs, const uint8_t *src,
+                                                     const uint64_t *srcOff, const int32_t *srcLen, uint64_t blockStride,
+                                                     int maxBlockLen, int nBlocks, const int32_t *streamFirst,
+                                                     const int32_t *streamSlot, int nStreams, int accel, int headerKind,
+                                                     uint8_t *slots, size_t slotStride, int32_t *framedLen)
+{
+    int r = fstreams_check(c, fs, nBlocks, streamFirst, streamSlot, nStreams, "compress_streams_fast_device");
+    if (r) return r;
+    // (nBlocks < 0 has gone to the stream-table check above)
+    if ((r = fstreams_shape_check("compress_streams_fast_device", nBlocks, headerKind, maxBlockLen))) return r;
+    if (nBlocks == 0) return MI355LZ4_OK;
+    if ((r = batch_buffers_check(c, "compress_streams_fast_device", src, maxBlockLen, headerKind, slots, slotStride, framedLen))) return r;
+    HIP_TRY(hipSetDevice(c->device));
+    const EncodeArgs a = make_encode_args(src, srcOff, srcLen, blockStride, maxBlockLen, nBlocks, accel, headerKind, slots, slotStride, framedLen);
+    return fstreams_enqueue(c, fs, a, 0, nBlocks, streamFirst, streamSlot, nStreams);
 }
 
 extern "C" int mi355lz4_compact_device(mi355lz4_ctx *c, const uint8_t *slots, size_t slotStride,

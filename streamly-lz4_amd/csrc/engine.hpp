@@ -116,6 +116,34 @@ struct mi355lz4_dictset {
     uint32_t *last() const { return (uint32_t *)(table + n); }
 };
 
+// The per-call stream table of the three sets of slots (api.cpp, stream_table_upload): {first block, end block, slot} per stream
+// goes through a ring of pinned buffers; an entry is reused once the launch that read it is done.
+struct StreamTableRing {                    // (shared with mi355lz4_dstreams, the decode side's set)
+    struct Ring { mi355lz4_detail::DevBuf pin, dev; hipEvent_t ev = nullptr; bool busy = false; } ring[4];
+    int next = 0;
+    void release()
+    {
+        for (auto &r : ring) {
+            if (r.ev) hipEventDestroy(r.ev);
+            r.ev = nullptr; r.busy = false;
+            mi355lz4_detail::pin_release(r.pin);
+            mi355lz4_detail::dev_release(r.dev);
+        }
+    }
+};
+
+// A set of slots on one device, written once for both sides: the compress side's slot is CSTREAM_SLOT_BYTES, the decode side's
+// (mi355lz4_dstreams, below) DSTREAM_SLOT_BYTES.  `who` names the calling entry point in the messages.
+struct SlotSet {
+    int device = 0;
+    int nSlots = 0;
+    uint8_t *state = nullptr;               // nSlots * the side's slot size
+    StreamTableRing table;
+};
+struct mi355lz4_cstreams : SlotSet {};
+struct mi355lz4_dstreams : SlotSet {};
+struct mi355lz4_fstreams : SlotSet {};      // (the fast compress side's set: a slot is the decode side's, FSTREAM_SLOT_BYTES)
+
 namespace mi355lz4_detail {
 
 // pageable host memory <-> device through pinned staging, on the engine's stream (api.cpp)
@@ -139,6 +167,11 @@ int streams_check(const mi355lz4_ctx *c, const mi355lz4_cstreams *cs, int nBlock
                   const int32_t *streamSlot, int nStreams, const char *who);
 int streams_enqueue(mi355lz4_ctx *c, mi355lz4_cstreams *cs, const EncodeArgs &a, int b0, int b1, const int32_t *streamFirst,
                     const int32_t *streamSlot, int nStreams);
+int fstreams_check(const mi355lz4_ctx *c, const mi355lz4_fstreams *fs, int nBlocks, const int32_t *streamFirst,
+                   const int32_t *streamSlot, int nStreams, const char *who);
+int fstreams_shape_check(const char *who, int nBlocks, int headerKind, int maxBlockLen);
+int fstreams_enqueue(mi355lz4_ctx *c, mi355lz4_fstreams *fs, const EncodeArgs &a, int b0, int b1, const int32_t *streamFirst,
+                     const int32_t *streamSlot, int nStreams);
 int dstreams_check(const mi355lz4_ctx *c, const mi355lz4_dstreams *ds, int nBlocks, const int32_t *streamFirst,
                    const int32_t *streamSlot, int nStreams, const char *who);
 int dstreams_enqueue(mi355lz4_ctx *c, mi355lz4_dstreams *ds, const DecodeCall &d, int b0, int b1, const int32_t *streamFirst,

@@ -185,11 +185,13 @@ struct HostDict {
     const mi355lz4_cstreams *set; int slot; const mi355lz4_hcdict *hc = nullptr; bool fast = false;
     const mi355lz4_dictset *dset = nullptr; const int32_t *dictIdx = nullptr;
 };
+// the set of a mi355lz4_compress_streams_fast call, in the place of HostStreams' exact set (null: the exact form)
+typedef HostStreams<mi355lz4_fstreams> HostFastStreams;
 
 static int compress_host(mi355lz4_ctx *c, const uint8_t *const *src, const int32_t *srcLen,
                          int nBlocks, int accel, int headerKind, uint8_t *framedOut, size_t cap,
                          size_t *outLen, int32_t *blockFramedLen, int32_t *status, const HostStreams<mi355lz4_cstreams> *hs,
-                         const HostDict *hd = nullptr)
+                         const HostDict *hd = nullptr, const HostFastStreams *hf = nullptr)
 {
     if (!c) return fail(MI355LZ4_E_ARG, "null ctx");
     if (nBlocks < 0 || (headerKind != 4 && headerKind != 8) || !outLen)
@@ -211,7 +213,7 @@ static int compress_host(mi355lz4_ctx *c, const uint8_t *const *src, const int32
         offs[(size_t)i] = total;
         if (i > 0 && src[i] != src[0] + total) contiguous = false;
         // 16-aligned block starts; back to back for a linked stream (a block's dictionary lies directly in front of it)
-        total += (c->linkedCompress && !hs && !hd) ? (size_t)srcLen[i] : (((size_t)srcLen[i] + 15) & ~(size_t)15);
+        total += (c->linkedCompress && !hs && !hd && !hf) ? (size_t)srcLen[i] : (((size_t)srcLen[i] + 15) & ~(size_t)15);
         if (srcLen[i] > maxLen) maxLen = srcLen[i];
     }
     const size_t stride = mi355lz4_slot_stride_ex(maxLen, headerKind, c->blockChecksum);
@@ -278,7 +280,7 @@ static int compress_host(mi355lz4_ctx *c, const uint8_t *const *src, const int32
             }
         }
         HIP_TRY(hipEventRecord(evIn[(size_t)g], c->sIn));
-        StreamSwap on(c, c->sK[(c->compExact || hs) ? 0 : (g & 1)]);   // an exact stream's groups follow each other
+        StreamSwap on(c, c->sK[(c->compExact || hs || hf) ? 0 : (g & 1)]);   // an exact stream's groups follow each other, and a slot's
         HIP_TRY(hipStreamWaitEvent(c->stream, evIn[(size_t)g], 0));
         PTRACE("compress: group %d H2D enqueued (%zu bytes, direct %d)", g, hi - lo, (int)directIn);
         // (a linked stream: the last block of the group before is this group's first dictionary)
@@ -287,6 +289,11 @@ static int compress_host(mi355lz4_ctx *c, const uint8_t *const *src, const int32
                                                   0, maxLen, b1 - b0, accel, headerKind, (uint8_t *)c->slots.p + (size_t)b0 * stride,
                                                   stride, (int32_t *)c->lenB.p + b0);
             r = streams_enqueue(c, hs->set, a, b0, b1, hs->first, hs->slot, hs->n);
+        } else if (hf) {                           // (the same seam rule; the staging is not contiguous per stream: the kernel stages)
+            const EncodeArgs a = make_encode_args((const uint8_t *)c->in.p, (const uint64_t *)c->offA.p + b0, (const int32_t *)c->lenA.p + b0,
+                                                  0, maxLen, b1 - b0, accel, headerKind, (uint8_t *)c->slots.p + (size_t)b0 * stride,
+                                                  stride, (int32_t *)c->lenB.p + b0);
+            r = fstreams_enqueue(c, hf->set, a, b0, b1, hf->first, hf->slot, hf->n);
         } else if (hd && hd->dset) {               // (every block against the member it names; the set and its members only read)
             r = mi355lz4_compress_fastdict_multi_device(c, hd->dset, (const int32_t *)c->res.p + b0, (const uint8_t *)c->in.p,
                                                         (const uint64_t *)c->offA.p + b0, (const int32_t *)c->lenA.p + b0, 0, maxLen,
@@ -385,6 +392,29 @@ extern "C" int mi355lz4_compress_streams(mi355lz4_ctx *c, mi355lz4_cstreams *cs,
     if (r) return r;
     const HostStreams<mi355lz4_cstreams> hs{cs, streamFirst, streamSlot, nStreams};
     return compress_host(c, src, srcLen, nBlocks, accel, headerKind, framedOut, cap, outLen, blockFramedLen, status, &hs);
+}
+
+// Host-buffer form of mi355lz4_compress_streams_fast_device: the same pipeline, the groups one behind the other on one compute
+// stream (a group's first blocks read the slots the group before saved).  The lengths are the caller's host array: checked before
+// anything is queued.
+extern "C" int mi355lz4_compress_streams_fast(mi355lz4_ctx *c, mi355lz4_fstreams *fs, const uint8_t *const *src,
+                                              const int32_t *srcLen, int nBlocks, const int32_t *streamFirst,
+                                              const int32_t *streamSlot, int nStreams, int accel, int headerKind,
+                                              uint8_t *framedOut, size_t cap, size_t *outLen, int32_t *blockFramedLen,
+                                              int32_t *status)
+{
+    if (outLen) *outLen = 0;
+    int r = fstreams_check(c, fs, nBlocks, streamFirst, streamSlot, nStreams, "compress_streams_fast");
+    if (r) return r;
+    int maxLen = 0;
+    for (int i = 0; srcLen && i < nBlocks; i++) {
+        if (srcLen[i] < 0 || srcLen[i] > HCDICT_MAX_BLOCK)
+            return fail(MI355LZ4_E_ARG, "compress_streams_fast: block %d length %d outside 0..%d", i, srcLen[i], HCDICT_MAX_BLOCK);
+        if (srcLen[i] > maxLen) maxLen = srcLen[i];
+    }
+    if ((r = fstreams_shape_check("compress_streams_fast", nBlocks, headerKind, maxLen))) return r;
+    const HostFastStreams hf{fs, streamFirst, streamSlot, nStreams};
+    return compress_host(c, src, srcLen, nBlocks, accel, headerKind, framedOut, cap, outLen, blockFramedLen, status, nullptr, nullptr, &hf);
 }
 
 // Host-buffer form of mi355lz4_compress_dict_device: the group pipeline of mi355lz4_compress_batch, every group's blocks from a

@@ -205,6 +205,69 @@ std::vector<std::vector<Array>> Engine::compressStreams(const BlockConfig &cfg, 
     return out;
 }
 
+FastCompressStreams::FastCompressStreams(Engine &eng, int nSlots) : eng_(eng)
+{
+    if (mi355lz4_fstreams_create(eng.ctx(), nSlots, &fs_) != MI355LZ4_OK)
+        throw Error(std::string("streamly_lz4::FastCompressStreams: ") + mi355lz4_last_error());
+}
+FastCompressStreams::~FastCompressStreams() { mi355lz4_fstreams_destroy(fs_); }
+int FastCompressStreams::count() const { return mi355lz4_fstreams_count(fs_); }
+void FastCompressStreams::reset()
+{
+    if (mi355lz4_fstreams_reset(eng_.ctx(), fs_, nullptr, 0) != MI355LZ4_OK)
+        throw Error(std::string("streamly_lz4::FastCompressStreams::reset: ") + mi355lz4_last_error());
+}
+void FastCompressStreams::reset(const std::vector<int32_t> &slots)
+{
+    if (slots.empty()) return;
+    if (mi355lz4_fstreams_reset(eng_.ctx(), fs_, slots.data(), (int)slots.size()) != MI355LZ4_OK)
+        throw Error(std::string("streamly_lz4::FastCompressStreams::reset: ") + mi355lz4_last_error());
+}
+void FastCompressStreams::setDict(int slot, const uint8_t *dictDevice, int len)
+{
+    if (mi355lz4_fstreams_set_dict(eng_.ctx(), fs_, slot, dictDevice, len) != MI355LZ4_OK)
+        throw Error(std::string("streamly_lz4::FastCompressStreams::setDict: ") + mi355lz4_last_error());
+}
+
+std::vector<std::vector<Array>> Engine::compressStreamsFast(const BlockConfig &cfg, int speed, const std::vector<std::vector<Array>> &streams,
+                                                        FastCompressStreams &fs, const std::vector<int32_t> &slots)
+{
+    if (slots.size() != streams.size()) throw Error("compressStreamsFast: one slot per stream");
+    const int meta = metaSize(cfg);
+    std::vector<const uint8_t *> ptrs;
+    std::vector<int32_t> lens, first{0};
+    size_t cap = 16;
+    for (const auto &st : streams) {
+        for (const Array &a : st) {
+            if (a.size() > (size_t)maxBlockSize(cfg))                           // compressChunk, Internal/LZ4.hs:237-241
+                throw Error("compressChunk: Source array length " + std::to_string(a.size()) +
+                            " exceeds the maximum block size of " + std::to_string(maxBlockSize(cfg)));
+            ptrs.push_back(a.data());
+            lens.push_back((int32_t)a.size());
+            cap += (size_t)mi355lz4_compress_bound((int)a.size()) + (size_t)meta + 4;
+        }
+        first.push_back((int32_t)lens.size());
+    }
+    const int n = (int)lens.size();
+    std::vector<uint8_t> framed(cap);
+    std::vector<int32_t> flen((size_t)n + 1), status((size_t)n + 1);
+    ptrs.push_back(nullptr);
+    lens.push_back(0);
+    size_t outLen = 0;
+    if (mi355lz4_compress_streams_fast(ctx_, fs.handle(), ptrs.data(), lens.data(), n, first.data(), slots.data(), (int)streams.size(),
+                                  speed < 0 ? 0 : speed, meta, framed.data(), cap, &outLen, flen.data(), status.data()) != MI355LZ4_OK)
+        throw Error(std::string("compressStreamsFast: ") + mi355lz4_last_error());
+    std::vector<std::vector<Array>> out(streams.size());
+    size_t pos = 0;
+    int k = 0;
+    for (size_t s = 0; s < streams.size(); s++)
+        for (size_t i = 0; i < streams[s].size(); i++, k++) {
+            out[s].emplace_back(framed.begin() + (long)pos, framed.begin() + (long)(pos + (size_t)flen[(size_t)k]));
+            pos += (size_t)flen[(size_t)k];
+        }
+    return out;
+}
+
 void CompressStreams::loadDict(int slot, const uint8_t *dictDevice, int len)
 {
     if (mi355lz4_cstreams_load_dict(eng_.ctx(), cs_, slot, dictDevice, len) != MI355LZ4_OK)

@@ -313,6 +313,26 @@ struct DStreamsArgs {
     uint8_t *state;              // the set's slots, DSTREAM_SLOT_BYTES each
 };
 
+// many fast linked compress streams continued across calls (mi355lz4_compress_streams_fast_device; kernels/encode.inc,
+// k_fstreams_plan / k_encode_fstreams / k_fstreams_save).  One slot of a mi355lz4_fstreams is the dstreams slot:
+// the last min(n, 65536) bytes of the stream's last good block at the slot's start, and that count (0: no dictionary) --
+// launch_dstreams_set serves _reset and _set_dict of both sets.
+#define FSTREAM_DICT_BYTES DSTREAM_DICT_BYTES
+#define FSTREAM_COUNT_OFF  DSTREAM_COUNT_OFF
+#define FSTREAM_SLOT_BYTES DSTREAM_SLOT_BYTES
+#define FSTREAMS_WAVES_DEFAULT FASTDICT_WAVES_DEFAULT             // waves per CU of k_encode_fstreams' grid (MI355LZ4_FSTREAMS_WAVES)
+
+struct FStreamsArgs {
+    EncodeArgs e;                // blocks, slots, headers, framedLen, accel (clamped); e.uniformLen bounds every length; linked, lookBack unused
+    const int32_t *work;         // per stream with blocks in the call {first block, end block, slot of the set}
+    int nWork;
+    uint8_t *state;              // the set's slots, FSTREAM_SLOT_BYTES each
+    int32_t *good;               // scratch, nWork: the stream's first block with a bad length, or its end block
+    int32_t *blockStream;        // scratch, nBlocks: the entry of work[] a block belongs to
+    uint8_t *stage;              // one window per wave of the grid
+    size_t stageStride;          // >= 65536 + e.uniformLen + 64
+};
+
 // small batches: a block's segments are compressed by several waves (kernels/encode.inc, "K2, small batches")
 struct EncodeSegArgs {
     EncodeArgs e;
@@ -390,6 +410,10 @@ void launch_pages_fastdict(const PagesFastDictArgs &a, int grid, hipStream_t s);
 // read on the host), then the grid above over the grouped blocks
 void launch_dictset_group(const FastDictMultiArgs &a, int grid, hipStream_t s);
 void launch_encode_fastdict_multi(const FastDictMultiArgs &a, int grid, hipStream_t s);
+// many fast linked streams: the plan (a.good, a.blockStream from the lengths; one wave per entry of a.work), the persistent grid of
+// single waves over all blocks of all streams (the slots only read), then the slots' new tails (one workgroup per entry of
+// a.work), one behind the other on s.  Nothing is read on the host.
+void launch_fstreams(const FStreamsArgs &a, int grid, hipStream_t s);
 // independent blocks against one external dictionary (a.dict0, a.dict0Len; a.linked is not used): one wave per block
 void launch_decode_dict(const DecodeArgs &a, hipStream_t s);
 // ... each against the member of a set that it names: one wave per block

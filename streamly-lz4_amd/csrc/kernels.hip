@@ -15,6 +15,7 @@
 //                          k_pages_fast: the same pages from the wave encoder with a budget   encode_wave.hpp, BUDGET
 //                          k_pages_fastdict: such pages against a prepared dictionary         encode_wave.hpp, DICT + PREP + BUDGET
 //                          k_dictset_zero / _hist / _scan / _scatter, k_encode_fastdict_multi<PAIR>: a dictionary per block
+//                          k_fstreams_plan, k_encode_fstreams<PAIR>, k_fstreams_save: linked streams continued across calls
 //   compact.inc            k_scan_u64, k_copy_slots, k_interleave, k_header_sizes, k_decoded_size       size_walk.hpp
 //   checksum.inc           k_xxh32_ranges / _append / _verify: four lanes per range          checksum.hpp
 //   generate.inc           k_generate: synthetic inputs (bench and test support)

@@ -1030,3 +1030,114 @@ void launch_encode_fastdict_multi(const FastDictMultiArgs &a, int grid, hipStrea
     if (a.e.uniformLen > 65536) hipLaunchKernelGGL((k_encode_fastdict_multi<false>), dim3((unsigned)grid), dim3(64), 0, s, a);
     else hipLaunchKernelGGL((k_encode_fastdict_multi<true>), dim3((unsigned)grid), dim3(64), 0, s, a);
 }
+
+// ---------------------------------------------------------------------------
+// K2, many fast linked streams continued across calls (mi355lz4_compress_streams_fast_device, DESIGN.md 7p).  Under DICT the wave
+// encoder seeds its table from the dictionary's bytes, so block k of a stream depends on the last 64 KiB of block k - 1, on itself
+// and on accel, and on nothing else: every block of every stream of a call is compressed at once, as the second block of the
+// linked call [D, block], where D is the tail of the block before it -- the slot's bytes for a stream's first block of the call.
+// Three launches, one behind the other: the plan reads the lengths, the encoder reads the slots, k_fstreams_save writes them.
+// ---------------------------------------------------------------------------
+// Entry w of x.work, one wavefront: good[w] = the stream's first block of the call whose length lies outside 0..uniformLen, or its
+// end block -- that block and the ones behind it are not compressed -- and blockStream[b] = w for its blocks.
+__global__ __launch_bounds__(LZ4_WAVE) void k_fstreams_plan(FStreamsArgs x)
+{
+    const int lane = lane_id();
+    const int w = (int)blockIdx.x;
+    const int32_t *e = x.work + 3 * (size_t)w;
+    const int b0 = min(max(uni(e[0]), 0), x.e.nBlocks), b1 = min(max(uni(e[1]), b0), x.e.nBlocks);
+    int good = b1;
+    for (int j0 = b0; j0 < b1; j0 += LZ4_WAVE) {
+        const int j = j0 + lane;
+        bool bad = false;
+        if (j < b1) {
+            const int n = enc_block(x.e, j).n;
+            bad = n < 0 || n > x.e.uniformLen;
+            x.blockStream[j] = w;
+        }
+        const uint64_t m = __ballot(bad);
+        if (m && good == b1) good = j0 + (int)__builtin_ctzll(m);
+    }
+    if (lane == 0) x.good[w] = good;
+}
+
+// k_encode_fastdict's persistent grid of single waves, occupancy and windows, over all blocks of the call.  A block at or behind
+// its stream's good[] gets framedLen 0 and nothing else.  A block under 13 bytes is literals, and one with an empty D is the block
+// of a one-block linked call: both are encoded where they lie.  So is a block whose D ends exactly where it starts -- the block
+// before it in the call, when the caller's arrays are contiguous.  Every other block is staged: D so that it ends at byte 65536 of
+// the wave's window, the block behind it.  The encoder zeroes and seeds its table itself, as in the linked call (not PREP).
+// The slots are only read here.
+template <bool PAIR>
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(ENC_WAVES_PER_EU, ENC_WAVES_PER_EU))) void k_encode_fstreams(FStreamsArgs x)
+{
+    __shared__ __attribute__((aligned(16))) uint16_t table[ENC_TABLE_ENTRIES + ENC_LDS_PAD + ((PAIR && ENC_STAGE) ? 128 : 0)];
+    const int lane = lane_id();
+    const EncodeArgs a = x.e;
+    uint8_t *blockAt = x.stage + (uint64_t)blockIdx.x * (uint64_t)x.stageStride + 65536;
+    for (int blk = (int)blockIdx.x; blk < a.nBlocks; blk += (int)gridDim.x) {
+        const int w = min(max(uni(x.blockStream[blk]), 0), x.nWork - 1);
+        const int32_t *e = x.work + 3 * (size_t)w;
+        const int b0 = uni(e[0]);
+        if (blk >= uni(x.good[w])) {
+            if (lane == 0) a.framedLen[blk] = 0;
+            continue;
+        }
+        const EncBlock b = enc_block(a, blk);
+        const int n = min(max(uni(b.n), 0), a.uniformLen);              // (inside already: the block is in front of good[w])
+        const uint8_t *src = a.src + uni64((int64_t)b.off);
+        uint8_t *slot = a.slots + (size_t)blk * a.slotStride;
+        int dictLen = 0;
+        if (n >= LZ4_MFLIMIT + 1) {
+            const uint8_t *dEnd;                                        // D = [dEnd - dictLen, dEnd)
+            if (blk <= b0) {                                            // the stream's first block of the call: what the slot holds
+                const uint8_t *st = x.state + (size_t)uni(e[2]) * FSTREAM_SLOT_BYTES;
+                dictLen = (int)min(ex_uni(as_global((const uint32_t *)(st + FSTREAM_COUNT_OFF))[0]), (uint32_t)FSTREAM_DICT_BYTES);
+                dEnd = st + dictLen;
+            } else {                                                    // the block before it (a good one: its length is inside)
+                const EncBlock p = enc_block(a, blk - 1);
+                const int pn = min(max(uni(p.n), 0), a.uniformLen);
+                dictLen = min(pn, 65536);
+                dEnd = a.src + uni64((int64_t)p.off) + pn;
+            }
+            if (dictLen > 0 && dEnd != src) {
+                wave_copy_bytes(blockAt - dictLen, dEnd - dictLen, (uint32_t)dictLen);
+                wave_copy_bytes(blockAt, src, (uint32_t)n);
+                wave_fence();                                           // the bytes are read back by other lanes than wrote them
+                src = blockAt;
+            }
+        }
+        // (one call site of an instantiation of its own -- SITE 2, encode_wave.hpp: the encoder is inlined, and its scalar operands
+        // stay scalar)
+        const int c = encode_block_wave<uint16_t, true, false, PAIR, false, false, 2>(src, n, slot + a.headerKind, a.accel, table, a.stats, dictLen);
+        enc_finish_slot(a, blk, slot, c, n, lane == 0);
+        wave_fence();                                                   // the next block's staging overwrites the window this one read
+    }
+}
+
+// Entry w of x.work, one workgroup, behind the encoder on the same stream -- a first block's read of the old tail cannot meet the
+// write of the new one: the slot takes the last min(n, 65536) bytes of the stream's last good block of the call and their count
+// (0 for an empty block: no dictionary).  No good block: the slot is as it was.
+#define FSTREAMS_SAVE_THREADS 256
+__global__ __launch_bounds__(FSTREAMS_SAVE_THREADS) void k_fstreams_save(FStreamsArgs x)
+{
+    const int w = (int)blockIdx.x;
+    const int32_t *e = x.work + 3 * (size_t)w;
+    const int b0 = max(uni(e[0]), 0), good = min(uni(x.good[w]), x.e.nBlocks);
+    if (good <= b0) return;
+    uint8_t *st = x.state + (size_t)uni(e[2]) * FSTREAM_SLOT_BYTES;
+    const EncBlock b = enc_block(x.e, good - 1);
+    const int n = min(max(uni(b.n), 0), x.e.uniformLen);
+    const uint32_t keep = (uint32_t)min(n, FSTREAM_DICT_BYTES);
+    const uint8_t *from = x.e.src + uni64((int64_t)b.off) + ((uint32_t)n - keep);
+    wg_copy_pieces(st, from, keep, 4096u, threadIdx.x / LZ4_WAVE, FSTREAMS_SAVE_THREADS / LZ4_WAVE);
+    if (threadIdx.x == 0) as_global((uint32_t *)(st + FSTREAM_COUNT_OFF))[0] = keep;
+}
+
+void launch_fstreams(const FStreamsArgs &a, int grid, hipStream_t s)
+{
+    if (a.e.nBlocks <= 0 || a.nWork <= 0 || grid <= 0) return;
+    hipLaunchKernelGGL(k_fstreams_plan, dim3((unsigned)a.nWork), dim3(LZ4_WAVE), 0, s, a);
+    if (a.e.uniformLen > 65536) hipLaunchKernelGGL((k_encode_fstreams<false>), dim3((unsigned)grid), dim3(64), 0, s, a);
+    else hipLaunchKernelGGL((k_encode_fstreams<true>), dim3((unsigned)grid), dim3(64), 0, s, a);
+    hipLaunchKernelGGL(k_fstreams_save, dim3((unsigned)a.nWork), dim3(FSTREAMS_SAVE_THREADS), 0, s, a);
+}

@@ -18,7 +18,7 @@ import os
 import numpy as np
 
 __all__ = [
-    "lib", "lib_path", "Engine", "CompressStreams", "DecompressStreams", "LZ4Error", "BlockSize", "BlockConfig", "FrameConfig",
+    "lib", "lib_path", "Engine", "CompressStreams", "FastCompressStreams", "DecompressStreams", "LZ4Error", "BlockSize", "BlockConfig", "FrameConfig",
     "defaultBlockConfig", "defaultFrameConfig", "setBlockMaxSize", "setFrameEndMark", "setBlockChecksum",
     "compressChunks", "decompressChunks", "decompressChunksRaw", "resizeChunks",
     "decompressChunksWith", "decompressChunksStream", "simpleFrameParser", "compress_bound", "slot_stride", "slot_stride_ex", "device_count",
@@ -141,6 +141,17 @@ def _load():
         C.c_int, C.c_int, C.c_int, vp, C.c_size_t, vp)
     sig("mi355lz4_compress_streams", C.c_int, vp, vp, C.POINTER(_u8p), _i32p, C.c_int, _i32p, _i32p, C.c_int, C.c_int,
         C.c_int, _u8p, C.c_size_t, C.POINTER(C.c_size_t), _i32p, _i32p)
+    # many fast linked compress streams, continued across calls
+    sig("mi355lz4_fstreams_create", C.c_int, vp, C.c_int, C.POINTER(vp))
+    sig("mi355lz4_fstreams_destroy", None, vp)
+    sig("mi355lz4_fstreams_count", C.c_int, vp)
+    sig("mi355lz4_fstreams_reset", C.c_int, vp, vp, _i32p, C.c_int)
+    sig("mi355lz4_fstreams_set_dict", C.c_int, vp, vp, C.c_int, vp, C.c_int)
+    sig("mi355lz4_debug_fstreams_peek", C.c_int, vp, C.c_int, _u8p, C.POINTER(C.c_int))
+    sig("mi355lz4_compress_streams_fast_device", C.c_int, vp, vp, vp, vp, vp, C.c_uint64, C.c_int, C.c_int, _i32p, _i32p,
+        C.c_int, C.c_int, C.c_int, vp, C.c_size_t, vp)
+    sig("mi355lz4_compress_streams_fast", C.c_int, vp, vp, C.POINTER(_u8p), _i32p, C.c_int, _i32p, _i32p, C.c_int, C.c_int,
+        C.c_int, _u8p, C.c_size_t, C.POINTER(C.c_size_t), _i32p, _i32p)
     # many linked decode streams, continued across calls
     sig("mi355lz4_dstreams_create", C.c_int, vp, C.c_int, C.POINTER(vp))
     sig("mi355lz4_dstreams_destroy", None, vp)
@@ -255,6 +266,8 @@ DECLARED_SYMBOLS = [
     "mi355lz4_set_compress_exact", "mi355lz4_get_compress_exact", "mi355lz4_compress_exact_reset",
     "mi355lz4_cstreams_create", "mi355lz4_cstreams_destroy", "mi355lz4_cstreams_count", "mi355lz4_cstreams_reset",
     "mi355lz4_compress_streams_device", "mi355lz4_compress_streams",
+    "mi355lz4_fstreams_create", "mi355lz4_fstreams_destroy", "mi355lz4_fstreams_count", "mi355lz4_fstreams_reset",
+    "mi355lz4_fstreams_set_dict", "mi355lz4_compress_streams_fast_device", "mi355lz4_compress_streams_fast",
     "mi355lz4_decoded_size_device", "mi355lz4_decoded_sizes_host",
     "mi355lz4_decompress_partial_device", "mi355lz4_decompress_partial",
     "mi355lz4_dstreams_create", "mi355lz4_dstreams_destroy", "mi355lz4_dstreams_count", "mi355lz4_dstreams_reset",
@@ -855,6 +868,48 @@ class Engine:
                                              status.ctypes.data_as(_i32p)), "compress_streams")
         return out[: out_len.value].tobytes(), flen[:n].tolist()
 
+    def compress_streams_fast_device(self, fs, src, n_blocks, max_block_len, stream_first, stream_slot, slots, slot_stride_,
+                                     framed_len, accel=1, header_kind=8, src_off=None, src_len=None, block_stride=None):
+        """Many fast linked streams in one call (include/mi355lz4.h, mi355lz4_compress_streams_fast_device): the arguments of
+        compress_streams_device with a FastCompressStreams in place of the CompressStreams.  Only enqueues."""
+        self._follow_torch()
+        sf = np.ascontiguousarray(stream_first, dtype=np.int32)
+        sl = np.ascontiguousarray(stream_slot, dtype=np.int32)
+        if sf.size != sl.size + 1:
+            raise ValueError("stream_first needs one entry more than stream_slot")
+        _check(lib.mi355lz4_compress_streams_fast_device(
+            self.ctx, fs._h, _dptr(src), _dptr(src_off), _dptr(src_len),
+            int(max_block_len if block_stride is None else block_stride), int(max_block_len), int(n_blocks),
+            sf.ctypes.data_as(_i32p), sl.ctypes.data_as(_i32p), int(sl.size), int(accel), int(header_kind), _dptr(slots),
+            int(slot_stride_), _dptr(framed_len)), "compress_streams_fast_device")
+
+    def compress_streams_fast(self, streams, fs, slots=None, accel=1, header_kind=8):
+        """streams: list of lists of bytes-like, stream s continuing slot slots[s] of fs (default: slot s).  Returns
+        (framed bytes of all blocks in order, [framed length per block], [status per block]);
+        mi355lz4_compress_streams_fast."""
+        if slots is None:
+            slots = list(range(len(streams)))
+        blocks = [b for st in streams for b in st]
+        n = len(blocks)
+        sf = np.cumsum([0] + [len(st) for st in streams]).astype(np.int32)
+        sl = np.ascontiguousarray(slots, dtype=np.int32)
+        if sl.size != len(streams):
+            raise ValueError("one slot per stream")
+        arrs = [np.frombuffer(bytes(b), dtype=np.uint8) if not isinstance(b, np.ndarray) else b for b in blocks]
+        ptrs = (_u8p * max(n, 1))(*[a.ctypes.data_as(_u8p) for a in arrs])
+        lens = np.array([a.size for a in arrs] + [0], dtype=np.int32)
+        cap = int(sum(compress_bound(int(x)) + header_kind + 4 for x in lens[:n])) + 16
+        out = np.empty(cap, dtype=np.uint8)
+        out_len = C.c_size_t()
+        flen = np.zeros(max(n, 1), dtype=np.int32)
+        status = np.zeros(max(n, 1), dtype=np.int32)
+        _check(lib.mi355lz4_compress_streams_fast(self.ctx, fs._h, ptrs, lens.ctypes.data_as(_i32p), n,
+                                                  sf.ctypes.data_as(_i32p), sl.ctypes.data_as(_i32p), int(sl.size), int(accel),
+                                                  int(header_kind), out.ctypes.data_as(_u8p), cap, C.byref(out_len),
+                                                  flen.ctypes.data_as(_i32p), status.ctypes.data_as(_i32p)),
+               "compress_streams_fast")
+        return out[: out_len.value].tobytes(), flen[:n].tolist(), status[:n].tolist()
+
     def decompress_streams(self, framed, stream_first, header_kind=8, fixed_uncomp=0, raise_on_block_error=True):
         """Many linked streams, host buffers: stream s = blocks [stream_first[s], stream_first[s+1]).
         Returns (decoded bytes, [decoded length or negative code per block])."""
@@ -1348,6 +1403,58 @@ class CompressStreams:
     def close(self):
         if self._h:
             lib.mi355lz4_cstreams_destroy(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class FastCompressStreams:
+    """A set of n_slots device-resident fast linked compress streams (mi355lz4_fstreams, about 64 KiB a slot: the last
+    block's last 64 KiB and their count), for Engine.compress_streams_fast / compress_streams_fast_device.  Bound to the
+    engine's device; every slot starts reset."""
+
+    def __init__(self, engine, n_slots):
+        self._h = C.c_void_p()
+        self._engine = engine
+        engine._follow_torch()
+        _check(lib.mi355lz4_fstreams_create(engine.ctx, int(n_slots), C.byref(self._h)), "fstreams_create")
+
+    def __len__(self):
+        return int(lib.mi355lz4_fstreams_count(self._h))
+
+    def reset(self, slots=None):
+        """Forget the listed slots' dictionaries (None: all), enqueued on the engine's stream."""
+        self._engine._follow_torch()
+        if slots is None:
+            _check(lib.mi355lz4_fstreams_reset(self._engine.ctx, self._h, None, 0), "fstreams_reset")
+        else:
+            a = np.ascontiguousarray(slots, dtype=np.int32)
+            _check(lib.mi355lz4_fstreams_reset(self._engine.ctx, self._h, a.ctypes.data_as(_i32p), int(a.size)),
+                   "fstreams_reset")
+
+    def set_dict(self, slot, dict_device, length=None):
+        """The slot's state becomes the last 64 KiB of dict_device[:length] (a uint8 device tensor; length defaults to all of
+        it, 0 equals a reset).  Enqueued; the slot keeps its own copy."""
+        self._engine._follow_torch()
+        n = int(dict_device.numel() if length is None else length) if dict_device is not None else 0
+        _check(lib.mi355lz4_fstreams_set_dict(self._engine.ctx, self._h, int(slot), _dptr(dict_device) if n else None, n),
+               "fstreams_set_dict")
+
+    def peek(self, slot):
+        """Diagnostics: (dictionary bytes held, those bytes), after the device is idle."""
+        cnt = C.c_int()
+        buf = np.empty(65536, dtype=np.uint8)
+        _check(lib.mi355lz4_debug_fstreams_peek(self._h, int(slot), buf.ctypes.data_as(_u8p), C.byref(cnt)),
+               "debug_fstreams_peek")
+        return int(cnt.value), buf[: max(0, min(int(cnt.value), 65536))].tobytes()
+
+    def close(self):
+        if self._h:
+            lib.mi355lz4_fstreams_destroy(self._h)
             self._h = C.c_void_p()
 
     def __del__(self):
