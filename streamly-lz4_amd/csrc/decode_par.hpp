@@ -691,9 +691,12 @@ __device__ int decode_block_par(const uint8_t *src, int srcLen, uint8_t *dst, in
             const uint32_t flast = ml - fstep;
             // Each chunk class loads into registers of its own: classes that shared destination registers made
             // the compiler wait for one class's loads before it issued the next one's (three round trips, not one).
-            par_v4 f0 = {0u, 0u, 0u, 0u}, f1 = {0u, 0u, 0u, 0u};
-            uint64_t fa = 0, fb = 0;
-            uint32_t fw0 = 0, fw1 = 0;
+            // (In the lanes without a far match they hold whatever the registers held: an empty `asm` defines them without an
+            // instruction, where `= 0` was fourteen v_mov_b32 in every batch; the stores below stand under the loads' conditions.)
+            par_v4 f0, f1;
+            uint64_t fa, fb;
+            uint32_t fw0, fw1;
+            asm volatile("" : "=v"(f0), "=v"(f1), "=v"(fa), "=v"(fb), "=v"(fw0), "=v"(fw1));
             if (farm) {
                 if (STATS) sc[PS_FAR] += (unsigned)__builtin_popcountll(farm);
 #if PAR_FAR_WIDE
@@ -804,7 +807,8 @@ __device__ int decode_block_par(const uint8_t *src, int srcLen, uint8_t *dst, in
                 const uint32_t dA = (uint32_t)(outStart - ringBase) + A;
                 const uint32_t n = act ? lit : 0u;
                 const uint8_t *W = L.win();
-                par_v4 r0 = {0u, 0u, 0u, 0u}, r1 = {0u, 0u, 0u, 0u};
+                par_v4 r0, r1;                                  // (defined without an instruction: the stores stand under the loads' conditions)
+                asm volatile("" : "=v"(r0), "=v"(r1));
                 if (n > 8) {
                     if (n + ml >= 16) {
                         // 9..16 literals as one 16-byte chunk: its tail falls into my own match area, written afterwards.  More than
@@ -879,9 +883,13 @@ __device__ int decode_block_par(const uint8_t *src, int srcLen, uint8_t *dst, in
                     *(par_u32u *)&L.ring[mdA + flast] = fw1;
                 }
                 // matches longer than 32 bytes: 32 more per step, every load of a step issued before its first store
-                for (uint32_t base = 32; __ballot(farMine && base < ml); base += 32) {
-                    par_v4 v0 = {0u, 0u, 0u, 0u}, v1 = {0u, 0u, 0u, 0u};
-                    const bool on = farMine && base < ml;
+                // (the loop's head is ONE v_cmp on a length that is 0 in the lanes that do not take part: see the near matches' steps)
+                uint32_t farMl = farMine ? ml : 0u;
+                asm volatile("" : "+v"(farMl));
+                for (uint32_t base = 32; __ballot(base < farMl); base += 32) {
+                    par_v4 v0, v1;
+                    asm volatile("" : "=v"(v0), "=v"(v1));
+                    const bool on = base < farMl;
                     const uint32_t o0 = min(base, flast), o1 = min(base + 16u, flast);
                     if (on) {
                         __builtin_memcpy(&v0, gsrc_at(o0), 16);
@@ -953,21 +961,32 @@ __device__ int decode_block_par(const uint8_t *src, int srcLen, uint8_t *dst, in
                 // lanes whose chunks never read their own writes: two chunks per step (2 x 16, 2 x 8 or 2 x 4
                 // bytes by class), every lane's reads issued before the first write, so that a round costs
                 // one LDS round trip per 32 bytes whatever mix of classes is ready
-                for (uint32_t base = 0; __ballot(mine && fastc && base < ml); base += 32) {
+                // The head of a step is ONE v_cmp: the ballot of a single comparison is that comparison's result as it stands in its
+                // SGPR pair.  The ballot of a conjunction goes through a vector register instead -- v_cndmask_b32 0 / 1, then
+                // v_cmp_ne_u32, two instructions of the 4-cycle class behind the v_cmp -- in every step (9.5 per lzsynth batch).  So
+                // the lanes that do not copy in this round get the length 0, once per round -- behind an empty `asm`, or the compiler
+                // folds the select into the comparison and the conjunction is back (profiles/par_sel_loop_selects.txt: the
+                // blocks of line 125 of HIP's warp functions, its __ballot, are the ones to check again).
+                uint32_t stepMl = (mine && fastc) ? ml : 0u;
+                asm volatile("" : "+v"(stepMl));
+                for (uint32_t base = 0; __ballot(base < stepMl); base += 32) {
                     if (STATS) sc[PS_MATCH_ITERS]++;
-                    const bool on = mine && fastc && base < ml;
+                    const bool on = base < stepMl;
                     const uint32_t cs = g16 ? 16u : (g8 ? 8u : 4u);
                     const uint32_t lastc = ml - cs;
                     const uint32_t o0 = g16 ? min(base, lastc) : 0u;
                     const uint32_t o1 = g16 ? min(base + 16u, lastc) : lastc;
                     // one 16-byte read serves every class (the bytes past a short match are read and dropped); the second
                     // chunk of the short classes -- the match's last 8 / 4 bytes -- is cut out of it in registers
-                    par_v4 v0 = {0u, 0u, 0u, 0u}, v1 = {0u, 0u, 0u, 0u};
+                    // v0 and v1 are defined by an empty `asm`, not zeroed: every store below stands under its load's condition, and a
+                    // match of exactly 16 bytes reads its second chunk (o1 = 0) instead of copying v0.  The listing to check again:
+                    // profiles/par_sel_loop_selects.txt (no v_mov_b32 0 and no v_cndmask_b32 in the step's common part).
+                    par_v4 v0, v1;
+                    asm volatile("" : "=v"(v0), "=v"(v1));
                     uint64_t na = 0, nc = 0;
                     uint32_t nw0 = 0, nw1 = 0;
                     if (on) v0 = *(const par_v4u *)&L.ring[msA + o0];
-                    if (on && g16 && ml > 16u) v1 = *(const par_v4u *)&L.ring[msA + o1];
-                    if (g16 && ml <= 16u) v1 = v0;                                   // (ml == 16: both chunks are the same 16 bytes)
+                    if (on && g16) v1 = *(const par_v4u *)&L.ring[msA + o1];
                     {
                         const uint32_t sh = ml - 8u;                                     // g8: 0..7
                         const bool up = (sh & 4u) != 0u;
