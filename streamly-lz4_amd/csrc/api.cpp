@@ -618,14 +618,15 @@ static int exact_encode(mi355lz4_ctx *c, EncodeArgs a, const int32_t *hostLen)
     return MI355LZ4_OK;
 }
 
+// LZ4_compress_fast_continue's clamp (cbits/lz4.c:1577-1578), for every call that takes accel
+static int accel_clamped(int accel) { return accel < 1 ? 1 : (accel > 65537 ? 65537 : accel); }
+
 EncodeArgs mi355lz4_detail::make_encode_args(const uint8_t *src, const uint64_t *srcOff, const int32_t *srcLen, uint64_t blockStride,
                                              int maxBlockLen, int nBlocks, int accel, int headerKind, uint8_t *slots,
                                              size_t slotStride, int32_t *framedLen)
 {
-    if (accel < 1) accel = 1;                 // cbits/lz4.c:1577
-    if (accel > 65537) accel = 65537;         // cbits/lz4.c:1578
-    return EncodeArgs{src, srcOff, srcLen, blockStride, maxBlockLen, nBlocks, accel, headerKind, slots, slotStride, framedLen,
-                      nullptr, 0, 0};
+    return EncodeArgs{src, srcOff, srcLen, blockStride, maxBlockLen, nBlocks, accel_clamped(accel), headerKind, slots, slotStride,
+                      framedLen, nullptr, 0, 0};
 }
 
 // The argument contract of a device batch, written once for the four entry points; `who` names the caller in the messages.  In two
@@ -636,6 +637,16 @@ static int batch_shape_check(const char *who, int nBlocks, int headerKind, int m
 {
     if (nBlocks < 0 || (headerKind != 4 && headerKind != 8) || maxBlockLen < 0 || (unsigned)maxBlockLen > (unsigned)limit)
         return fail(MI355LZ4_E_ARG, "%s: bad arguments", who);
+    return MI355LZ4_OK;
+}
+// The shape check of the calls that stage every block behind a dictionary (the HC and the fast dictionary batch, the dictionary
+// set, the fast streams; device and host-buffer forms): no block length is "bad" here but a negative one, and the limit of
+// HCDICT_MAX_BLOCK has its own message, in front of the empty call.  `what` names what takes the bytes.
+int mi355lz4_detail::dict_batch_shape_check(const char *who, const char *what, int nBlocks, int headerKind, int maxBlockLen)
+{
+    if (int r = batch_shape_check(who, nBlocks, headerKind, maxBlockLen, INT_MAX)) return r;
+    if (maxBlockLen > HCDICT_MAX_BLOCK)
+        return fail(MI355LZ4_E_ARG, "%s: maxBlockLen %d above the %d bytes %s takes", who, maxBlockLen, HCDICT_MAX_BLOCK, what);
     return MI355LZ4_OK;
 }
 static int batch_buffers_check(const mi355lz4_ctx *c, const char *who, const uint8_t *src, int maxBlockLen, int headerKind,
@@ -812,16 +823,23 @@ static void slots_destroy(Set *s)
     delete s;
 }
 static int slots_count(const SlotSet *s, const char *who) { return s ? s->nSlots : fail(MI355LZ4_E_ARG, "%s: null set", who); }
-static int slots_same_device(const mi355lz4_ctx *c, const SlotSet *s, const char *who)
+// an object of the engine's device (a set of slots, a prepared dictionary, a dictionary set): `what` names it in the message
+template <class Obj>
+static int same_device(const mi355lz4_ctx *c, const Obj *o, const char *who, const char *what = "set")
 {
-    if (!c || !s) return fail(MI355LZ4_E_ARG, "%s: null argument", who);
-    if (s->device != c->device) return fail(MI355LZ4_E_ARG, "%s: the set lives on device %d, the engine on %d", who, s->device, c->device);
+    if (!c || !o) return fail(MI355LZ4_E_ARG, "%s: null argument", who);
+    if (o->device != c->device) return fail(MI355LZ4_E_ARG, "%s: the %s lives on device %d, the engine on %d", who, what, o->device, c->device);
+    return MI355LZ4_OK;
+}
+static int slot_range_check(const SlotSet *s, int slot, const char *who)
+{
+    if (slot < 0 || slot >= s->nSlots) return fail(MI355LZ4_E_ARG, "%s: slot %d of %d", who, slot, s->nSlots);
     return MI355LZ4_OK;
 }
 // the arguments of a _reset: the set on the engine's device and, with a list, every slot of it in range
 static int slots_reset_check(const mi355lz4_ctx *c, const SlotSet *s, const int32_t *slots, int n, const char *who)
 {
-    if (int r = slots_same_device(c, s, who)) return r;
+    if (int r = same_device(c, s, who)) return r;
     HIP_TRY(hipSetDevice(c->device));
     if (!slots) return MI355LZ4_OK;
     if (n < 0) return fail(MI355LZ4_E_ARG, "%s: bad count", who);
@@ -898,7 +916,7 @@ static int stream_table_check(int nSlots, int nBlocks, const int32_t *streamFirs
 static int compress_streams_check(const mi355lz4_ctx *c, const SlotSet *s, int nSlots, int nBlocks, const int32_t *streamFirst,
                                   const int32_t *streamSlot, int nStreams, const char *who, const char *what)
 {
-    if (int r = slots_same_device(c, s, who)) return r;
+    if (int r = same_device(c, s, who)) return r;
     if (c->compLevel != 0)
         return fail(MI355LZ4_E_ARG, "%s: compression level %d; %s streams are level 0's encoder", who, c->compLevel, what);
     return stream_table_check(nSlots, nBlocks, streamFirst, streamSlot, nStreams, who);
@@ -1005,8 +1023,8 @@ extern "C" int mi355lz4_compress_streams_device(mi355lz4_ctx *c, mi355lz4_cstrea
 // ---------------------------------------------------------------------------
 extern "C" int mi355lz4_cstreams_load_dict(mi355lz4_ctx *c, mi355lz4_cstreams *cs, int slot, const uint8_t *dictDevice, int len)
 {
-    if (int r = slots_same_device(c, cs, "cstreams_load_dict")) return r;
-    if (slot < 0 || slot >= cs->nSlots) return fail(MI355LZ4_E_ARG, "cstreams_load_dict: slot %d of %d", slot, cs->nSlots);
+    if (int r = same_device(c, cs, "cstreams_load_dict")) return r;
+    if (int r = slot_range_check(cs, slot, "cstreams_load_dict")) return r;
     if (len < 0 || (len > 0 && !dictDevice)) return fail(MI355LZ4_E_ARG, "cstreams_load_dict: bad dictionary");
     HIP_TRY(hipSetDevice(c->device));
     launch_cstreams_load_dict(cs->state + (size_t)slot * CSTREAM_SLOT_BYTES, dictDevice, len, c->stream);
@@ -1018,10 +1036,10 @@ extern "C" int mi355lz4_compress_dict_device(mi355lz4_ctx *c, const mi355lz4_cst
                                              int maxBlockLen, int nBlocks, int accel, int headerKind, uint8_t *slots,
                                              size_t slotStride, int32_t *framedLen)
 {
-    if (int r = slots_same_device(c, cs, "compress_dict_device")) return r;
+    if (int r = same_device(c, cs, "compress_dict_device")) return r;
     if (c->compLevel != 0)
         return fail(MI355LZ4_E_ARG, "compress_dict_device: compression level %d; the dictionary batch is level 0's encoder", c->compLevel);
-    if (dictSlot < 0 || dictSlot >= cs->nSlots) return fail(MI355LZ4_E_ARG, "compress_dict_device: slot %d of %d", dictSlot, cs->nSlots);
+    if (int r = slot_range_check(cs, dictSlot, "compress_dict_device")) return r;
     if (int r = batch_shape_check("compress_dict_device", nBlocks, headerKind, maxBlockLen, MI355LZ4_MAX_INPUT_SIZE)) return r;
     if (nBlocks == 0) return MI355LZ4_OK;
     if (int r = batch_buffers_check(c, "compress_dict_device", src, maxBlockLen, headerKind, slots, slotStride, framedLen)) return r;
@@ -1037,47 +1055,55 @@ extern "C" int mi355lz4_compress_dict_device(mi355lz4_ctx *c, const mi355lz4_cst
 // Fixed-size output pages: LZ4_compress_destSize for a batch, and chains of such pages per input (k_exact_pages:
 // one wave per input, every page from a zeroed table).  Enqueues only; srcLen and pageSize stay unread on the host.
 // ---------------------------------------------------------------------------
+// (the three page calls' arguments in one place: pages_args makes the kernels' struct of them, pages_check holds it to the calls'
+// contract, `who` naming the caller in the messages -- the counts, the header kind and the stride; no block checksums; level 0 for
+// the wave encoder's forms, `fastKind` naming theirs ("fast", "dictionary"; null: the exact form, any level); then, behind the empty
+// call, which the caller returns from as well, the nine pointers)
+static PagesArgs pages_args(const uint8_t *src, const uint64_t *srcOff, const int32_t *srcLen, int nInputs, const int32_t *pageSize,
+                            int maxPages, int headerKind, uint8_t *pages, size_t pageStride, int32_t *pageSrcLen,
+                            int32_t *pageCompLen, int32_t *nPages, int32_t *consumed)
+{
+    return PagesArgs{src, srcOff, srcLen, nInputs, pageSize, maxPages, headerKind, pages, pageStride, pageSrcLen, pageCompLen, nPages, consumed};
+}
+static int pages_check(const mi355lz4_ctx *c, const char *who, const char *fastKind, const PagesArgs &x)
+{
+    if (!c) return fail(MI355LZ4_E_ARG, "null ctx");
+    if (x.nInputs < 0 || x.maxPages < 1 || (x.headerKind != 0 && x.headerKind != 4 && x.headerKind != 8) || x.pageStride < (size_t)x.headerKind + 1)
+        return fail(MI355LZ4_E_ARG, "%s: bad arguments", who);
+    if (c->blockChecksum) return fail(MI355LZ4_E_ARG, "%s: block checksums are on; pages carry no trailer", who);
+    if (fastKind && c->compLevel != 0)
+        return fail(MI355LZ4_E_ARG, "%s: compression level %d; %s pages are level 0's encoder", who, c->compLevel, fastKind);
+    if (x.nInputs == 0) return MI355LZ4_OK;
+    if (!x.src || !x.srcOff || !x.srcLen || !x.pageSize || !x.pages || !x.pageSrcLen || !x.pageCompLen || !x.nPages || !x.consumed)
+        return fail(MI355LZ4_E_ARG, "%s: null pointer", who);
+    return MI355LZ4_OK;
+}
+
 extern "C" int mi355lz4_compress_pages_device(mi355lz4_ctx *c, const uint8_t *src, const uint64_t *srcOff, const int32_t *srcLen,
                                               int nInputs, const int32_t *pageSize, int maxPages, int headerKind,
                                               uint8_t *pages, size_t pageStride, int32_t *pageSrcLen, int32_t *pageCompLen,
                                               int32_t *nPages, int32_t *consumed)
 {
-    if (!c) return fail(MI355LZ4_E_ARG, "null ctx");
-    if (nInputs < 0 || maxPages < 1 || (headerKind != 0 && headerKind != 4 && headerKind != 8) || pageStride < (size_t)headerKind + 1)
-        return fail(MI355LZ4_E_ARG, "compress_pages_device: bad arguments");
-    if (c->blockChecksum) return fail(MI355LZ4_E_ARG, "compress_pages_device: block checksums are on; pages carry no trailer");
+    const PagesArgs x = pages_args(src, srcOff, srcLen, nInputs, pageSize, maxPages, headerKind, pages, pageStride, pageSrcLen, pageCompLen, nPages, consumed);
+    if (int r = pages_check(c, "compress_pages_device", nullptr, x)) return r;
     if (nInputs == 0) return MI355LZ4_OK;
-    if (!src || !srcOff || !srcLen || !pageSize || !pages || !pageSrcLen || !pageCompLen || !nPages || !consumed)
-        return fail(MI355LZ4_E_ARG, "compress_pages_device: null pointer");
     HIP_TRY(hipSetDevice(c->device));
-    const PagesArgs x{src, srcOff, srcLen, nInputs, pageSize, maxPages, headerKind, pages, pageStride, pageSrcLen, pageCompLen,
-                      nPages, consumed};
     launch_exact_pages(x, c->stream);
     return check_launch("exact pages launch");
 }
 
 // The same chains at the engine's speed: every page by the wave encoder with an output budget (k_pages_fast), this
-// engine's bytes and not LZ4_compress_destSize's.  Level 0 only; the arguments and their checks are the call's above, plus accel.
+// engine's bytes and not LZ4_compress_destSize's.  Level 0 only; accel is added.
 extern "C" int mi355lz4_compress_pages_fast_device(mi355lz4_ctx *c, const uint8_t *src, const uint64_t *srcOff, const int32_t *srcLen,
                                                    int nInputs, const int32_t *pageSize, int maxPages, int accel, int headerKind,
                                                    uint8_t *pages, size_t pageStride, int32_t *pageSrcLen, int32_t *pageCompLen,
                                                    int32_t *nPages, int32_t *consumed)
 {
-    if (!c) return fail(MI355LZ4_E_ARG, "null ctx");
-    if (nInputs < 0 || maxPages < 1 || (headerKind != 0 && headerKind != 4 && headerKind != 8) || pageStride < (size_t)headerKind + 1)
-        return fail(MI355LZ4_E_ARG, "compress_pages_fast_device: bad arguments");
-    if (c->blockChecksum) return fail(MI355LZ4_E_ARG, "compress_pages_fast_device: block checksums are on; pages carry no trailer");
-    if (c->compLevel != 0)
-        return fail(MI355LZ4_E_ARG, "compress_pages_fast_device: compression level %d; fast pages are level 0's encoder", c->compLevel);
+    const PagesFastArgs x{pages_args(src, srcOff, srcLen, nInputs, pageSize, maxPages, headerKind, pages, pageStride, pageSrcLen, pageCompLen, nPages, consumed),
+                          accel_clamped(accel)};
+    if (int r = pages_check(c, "compress_pages_fast_device", "fast", x.p)) return r;
     if (nInputs == 0) return MI355LZ4_OK;
-    if (!src || !srcOff || !srcLen || !pageSize || !pages || !pageSrcLen || !pageCompLen || !nPages || !consumed)
-        return fail(MI355LZ4_E_ARG, "compress_pages_fast_device: null pointer");
     HIP_TRY(hipSetDevice(c->device));
-    if (accel < 1) accel = 1;                 // cbits/lz4.c:1577
-    if (accel > 65537) accel = 65537;         // cbits/lz4.c:1578
-    const PagesFastArgs x{PagesArgs{src, srcOff, srcLen, nInputs, pageSize, maxPages, headerKind, pages, pageStride, pageSrcLen,
-                                    pageCompLen, nPages, consumed},
-                          accel};
     launch_pages_fast(x, c->stream);
     return check_launch("fast pages launch");
 }
@@ -1125,16 +1151,9 @@ extern "C" void mi355lz4_hcdict_destroy(mi355lz4_hcdict *hd)
 
 extern "C" int mi355lz4_hcdict_size(const mi355lz4_hcdict *hd) { return hd ? hd->keep : fail(MI355LZ4_E_ARG, "hcdict_size: null object"); }
 
-static int hcdict_same_device(const mi355lz4_ctx *c, const mi355lz4_hcdict *hd, const char *who)
-{
-    if (!c || !hd) return fail(MI355LZ4_E_ARG, "%s: null argument", who);
-    if (hd->device != c->device) return fail(MI355LZ4_E_ARG, "%s: the dictionary lives on device %d, the engine on %d", who, hd->device, c->device);
-    return MI355LZ4_OK;
-}
-
 extern "C" int mi355lz4_hcdict_load(mi355lz4_ctx *c, mi355lz4_hcdict *hd, const uint8_t *dictDevice, int len)
 {
-    if (int r = hcdict_same_device(c, hd, "hcdict_load")) return r;
+    if (int r = same_device(c, hd, "hcdict_load", "dictionary")) return r;
     if (len < 0 || (len > 0 && !dictDevice)) return fail(MI355LZ4_E_ARG, "hcdict_load: bad dictionary");
     HIP_TRY(hipSetDevice(c->device));
     launch_hcdict_build(hd->image, dictDevice, len, c->stream);
@@ -1187,14 +1206,11 @@ extern "C" int mi355lz4_compress_hcdict_device(mi355lz4_ctx *c, const mi355lz4_h
                                                int maxBlockLen, int nBlocks, int headerKind, uint8_t *slots,
                                                size_t slotStride, int32_t *framedLen)
 {
-    if (int r = hcdict_same_device(c, hd, "compress_hcdict_device")) return r;
+    if (int r = same_device(c, hd, "compress_hcdict_device", "dictionary")) return r;
     if (c->compLevel < 1)
         return fail(MI355LZ4_E_ARG, "compress_hcdict_device: compression level %d; level 0 against a dictionary is mi355lz4_compress_dict_device",
                     c->compLevel);
-    // (no block length is "bad" here but a negative one: this call's own limit has its own message, in front of the empty call)
-    if (int r = batch_shape_check("compress_hcdict_device", nBlocks, headerKind, maxBlockLen, INT_MAX)) return r;
-    if (maxBlockLen > HCDICT_MAX_BLOCK)
-        return fail(MI355LZ4_E_ARG, "compress_hcdict_device: maxBlockLen %d above the %d bytes a dictionary batch takes", maxBlockLen, HCDICT_MAX_BLOCK);
+    if (int r = dict_batch_shape_check("compress_hcdict_device", "a dictionary batch", nBlocks, headerKind, maxBlockLen)) return r;
     if (nBlocks == 0) return MI355LZ4_OK;
     if (int r = batch_buffers_check(c, "compress_hcdict_device", src, maxBlockLen, headerKind, slots, slotStride, framedLen)) return r;
     HIP_TRY(hipSetDevice(c->device));
@@ -1215,13 +1231,11 @@ extern "C" int mi355lz4_compress_fastdict_device(mi355lz4_ctx *c, const mi355lz4
                                                  int maxBlockLen, int nBlocks, int accel, int headerKind, uint8_t *slots,
                                                  size_t slotStride, int32_t *framedLen)
 {
-    if (int r = hcdict_same_device(c, hd, "compress_fastdict_device")) return r;
+    if (int r = same_device(c, hd, "compress_fastdict_device", "dictionary")) return r;
     if (c->compLevel != 0)
         return fail(MI355LZ4_E_ARG, "compress_fastdict_device: compression level %d; levels 1..12 against a dictionary are mi355lz4_compress_hcdict_device",
                     c->compLevel);
-    if (int r = batch_shape_check("compress_fastdict_device", nBlocks, headerKind, maxBlockLen, INT_MAX)) return r;
-    if (maxBlockLen > HCDICT_MAX_BLOCK)
-        return fail(MI355LZ4_E_ARG, "compress_fastdict_device: maxBlockLen %d above the %d bytes a dictionary batch takes", maxBlockLen, HCDICT_MAX_BLOCK);
+    if (int r = dict_batch_shape_check("compress_fastdict_device", "a dictionary batch", nBlocks, headerKind, maxBlockLen)) return r;
     if (nBlocks == 0) return MI355LZ4_OK;
     if (int r = batch_buffers_check(c, "compress_fastdict_device", src, maxBlockLen, headerKind, slots, slotStride, framedLen)) return r;
     HIP_TRY(hipSetDevice(c->device));
@@ -1230,9 +1244,7 @@ extern "C" int mi355lz4_compress_fastdict_device(mi355lz4_ctx *c, const mi355lz4
     x.e.stats = c->stats;
     x.image = hd->image;
     x.fast = hd->fastImage;
-    // the dictionary, the block, and what the encoder may ask for around a position near the block's end (the 56 bytes behind a
-    // candidate, the 8 in front of the next one), in whole 256-byte lines
-    x.stageStride = 65536 + (((size_t)maxBlockLen + 64 + 255) & ~(size_t)255);
+    x.stageStride = fastdict_window_stride(maxBlockLen);
     const int grid = encode_fastdict_grid(nBlocks, env_int("MI355LZ4_FASTDICT_WAVES", 0), x.stageStride);
     if (int r = hcdict_stage(c, (size_t)grid * x.stageStride, &x.stage)) return r;
     launch_encode_fastdict(x, grid, c->stream);
@@ -1240,7 +1252,7 @@ extern "C" int mi355lz4_compress_fastdict_device(mi355lz4_ctx *c, const mi355lz4
 }
 
 // Fast pages against the same object: mi355lz4_compress_pages_fast_device's chains, every page made by the wave
-// encoder with the dictionary in front of it and an output budget (k_pages_fastdict: the grid and the windows of the call above,
+// encoder with the dictionary in front of it and an output budget (k_pages_fastdict: compress_fastdict_device's grid and windows,
 // sized for a block of 65536 bytes, which is the most a page holds).  Enqueues only; srcLen and pageSize stay unread on the host.
 extern "C" int mi355lz4_compress_pages_fastdict_device(mi355lz4_ctx *c, const mi355lz4_hcdict *hd, const uint8_t *src,
                                                        const uint64_t *srcOff, const int32_t *srcLen, int nInputs,
@@ -1248,25 +1260,16 @@ extern "C" int mi355lz4_compress_pages_fastdict_device(mi355lz4_ctx *c, const mi
                                                        uint8_t *pages, size_t pageStride, int32_t *pageSrcLen, int32_t *pageCompLen,
                                                        int32_t *nPages, int32_t *consumed)
 {
-    if (int r = hcdict_same_device(c, hd, "compress_pages_fastdict_device")) return r;
-    if (nInputs < 0 || maxPages < 1 || (headerKind != 0 && headerKind != 4 && headerKind != 8) || pageStride < (size_t)headerKind + 1)
-        return fail(MI355LZ4_E_ARG, "compress_pages_fastdict_device: bad arguments");
-    if (c->blockChecksum) return fail(MI355LZ4_E_ARG, "compress_pages_fastdict_device: block checksums are on; pages carry no trailer");
-    if (c->compLevel != 0)
-        return fail(MI355LZ4_E_ARG, "compress_pages_fastdict_device: compression level %d; dictionary pages are level 0's encoder", c->compLevel);
-    if (nInputs == 0) return MI355LZ4_OK;
-    if (!src || !srcOff || !srcLen || !pageSize || !pages || !pageSrcLen || !pageCompLen || !nPages || !consumed)
-        return fail(MI355LZ4_E_ARG, "compress_pages_fastdict_device: null pointer");
-    HIP_TRY(hipSetDevice(c->device));
-    if (accel < 1) accel = 1;                 // cbits/lz4.c:1577
-    if (accel > 65537) accel = 65537;         // cbits/lz4.c:1578
+    if (int r = same_device(c, hd, "compress_pages_fastdict_device", "dictionary")) return r;
     PagesFastDictArgs x;
-    x.p = PagesArgs{src, srcOff, srcLen, nInputs, pageSize, maxPages, headerKind, pages, pageStride, pageSrcLen, pageCompLen,
-                    nPages, consumed};
-    x.accel = accel;
+    x.p = pages_args(src, srcOff, srcLen, nInputs, pageSize, maxPages, headerKind, pages, pageStride, pageSrcLen, pageCompLen, nPages, consumed);
+    if (int r = pages_check(c, "compress_pages_fastdict_device", "dictionary", x.p)) return r;
+    if (nInputs == 0) return MI355LZ4_OK;
+    HIP_TRY(hipSetDevice(c->device));
+    x.accel = accel_clamped(accel);
     x.image = hd->image;
     x.fast = hd->fastImage;
-    x.stageStride = 65536 + (((size_t)65536 + 64 + 255) & ~(size_t)255);       // compress_fastdict_device's, for maxBlockLen 65536
+    x.stageStride = fastdict_window_stride(65536);                      // (the most a page holds)
     const int grid = encode_fastdict_grid(nInputs, env_int("MI355LZ4_FASTDICT_WAVES", 0), x.stageStride);
     if (int r = hcdict_stage(c, (size_t)grid * x.stageStride, &x.stage)) return r;
     launch_pages_fastdict(x, grid, c->stream);
@@ -1320,13 +1323,6 @@ extern "C" void mi355lz4_dictset_destroy(mi355lz4_dictset *ds)
 
 extern "C" int mi355lz4_dictset_count(const mi355lz4_dictset *ds) { return ds ? ds->n : fail(MI355LZ4_E_ARG, "dictset_count: null set"); }
 
-static int dictset_same_device(const mi355lz4_ctx *c, const mi355lz4_dictset *ds, const char *who)
-{
-    if (!c || !ds) return fail(MI355LZ4_E_ARG, "%s: null argument", who);
-    if (ds->device != c->device) return fail(MI355LZ4_E_ARG, "%s: the set lives on device %d, the engine on %d", who, ds->device, c->device);
-    return MI355LZ4_OK;
-}
-
 // Diagnostic hook (not part of the public header): out = {stagings, grid} of the last mi355lz4_compress_fastdict_multi_device call
 // that read the set -- how often its waves staged a dictionary (or dropped to none), and how many waves there were -- after
 // everything queued on the device has run.  The tests hold the call to stagings <= grid + distinct indices - 1 with it.
@@ -1346,12 +1342,10 @@ extern "C" int mi355lz4_compress_fastdict_multi_device(mi355lz4_ctx *c, const mi
                                                        uint64_t blockStride, int maxBlockLen, int nBlocks, int accel, int headerKind,
                                                        uint8_t *slots, size_t slotStride, int32_t *framedLen)
 {
-    if (int r = dictset_same_device(c, ds, "compress_fastdict_multi_device")) return r;
+    if (int r = same_device(c, ds, "compress_fastdict_multi_device")) return r;
     if (c->compLevel != 0)
         return fail(MI355LZ4_E_ARG, "compress_fastdict_multi_device: compression level %d; a dictionary set is level 0's encoder", c->compLevel);
-    if (int r = batch_shape_check("compress_fastdict_multi_device", nBlocks, headerKind, maxBlockLen, INT_MAX)) return r;
-    if (maxBlockLen > HCDICT_MAX_BLOCK)
-        return fail(MI355LZ4_E_ARG, "compress_fastdict_multi_device: maxBlockLen %d above the %d bytes a dictionary batch takes", maxBlockLen, HCDICT_MAX_BLOCK);
+    if (int r = dict_batch_shape_check("compress_fastdict_multi_device", "a dictionary batch", nBlocks, headerKind, maxBlockLen)) return r;
     if (nBlocks == 0) return MI355LZ4_OK;
     if (!dictIdx) return fail(MI355LZ4_E_ARG, "compress_fastdict_multi_device: null dictIdx");
     if (int r = batch_buffers_check(c, "compress_fastdict_multi_device", src, maxBlockLen, headerKind, slots, slotStride, framedLen)) return r;
@@ -1363,7 +1357,7 @@ extern "C" int mi355lz4_compress_fastdict_multi_device(mi355lz4_ctx *c, const mi
     x.nDicts = ds->n;
     x.dictIdx = dictIdx;
     x.last = ds->last();
-    x.stageStride = 65536 + (((size_t)maxBlockLen + 64 + 255) & ~(size_t)255);       // compress_fastdict_device's
+    x.stageStride = fastdict_window_stride(maxBlockLen);
     const int grid = encode_fastdict_grid(nBlocks, env_int("MI355LZ4_FASTDICT_WAVES", 0), x.stageStride);
     const size_t windows = (size_t)grid * x.stageStride, orderBytes = ((size_t)nBlocks * 4 + 255) & ~(size_t)255;
     if (int r = hcdict_stage(c, windows + orderBytes + ((size_t)ds->n + 2 + (size_t)grid + 1) * 4, &x.stage)) return r;
@@ -1406,8 +1400,8 @@ extern "C" int mi355lz4_fstreams_reset(mi355lz4_ctx *c, mi355lz4_fstreams *fs, c
 // the write-side twin of mi355lz4_dstreams_set_dict: the slot becomes the last 64 KiB of dictDevice[0, len)
 extern "C" int mi355lz4_fstreams_set_dict(mi355lz4_ctx *c, mi355lz4_fstreams *fs, int slot, const uint8_t *dictDevice, int len)
 {
-    if (int r = slots_same_device(c, fs, "fstreams_set_dict")) return r;
-    if (slot < 0 || slot >= fs->nSlots) return fail(MI355LZ4_E_ARG, "fstreams_set_dict: slot %d of %d", slot, fs->nSlots);
+    if (int r = same_device(c, fs, "fstreams_set_dict")) return r;
+    if (int r = slot_range_check(fs, slot, "fstreams_set_dict")) return r;
     if (len < 0 || (len > 0 && !dictDevice)) return fail(MI355LZ4_E_ARG, "fstreams_set_dict: bad dictionary");
     HIP_TRY(hipSetDevice(c->device));
     const int keep = len > FSTREAM_DICT_BYTES ? FSTREAM_DICT_BYTES : len;
@@ -1428,15 +1422,6 @@ extern "C" int mi355lz4_debug_fstreams_peek(mi355lz4_fstreams *fs, int slot, uin
     return MI355LZ4_OK;
 }
 
-// the size checks of a call's blocks, shared by the device call and the host-buffer form: compress_fastdict_device's
-int mi355lz4_detail::fstreams_shape_check(const char *who, int nBlocks, int headerKind, int maxBlockLen)
-{
-    if (int r = batch_shape_check(who, nBlocks, headerKind, maxBlockLen, INT_MAX)) return r;
-    if (maxBlockLen > HCDICT_MAX_BLOCK)
-        return fail(MI355LZ4_E_ARG, "%s: maxBlockLen %d above the %d bytes a fast stream's block takes", who, maxBlockLen, HCDICT_MAX_BLOCK);
-    return MI355LZ4_OK;
-}
-
 // Enqueue the streams' parts that fall into blocks [b0, b1) of the table (a.* describes exactly those blocks), as streams_enqueue
 // does: a stream cut by b0 or b1 continues through its slot in the next launch, which runs behind this one's k_fstreams_save.
 int mi355lz4_detail::fstreams_enqueue(mi355lz4_ctx *c, mi355lz4_fstreams *fs, const EncodeArgs &a, int b0, int b1,
@@ -1452,7 +1437,7 @@ int mi355lz4_detail::fstreams_enqueue(mi355lz4_ctx *c, mi355lz4_fstreams *fs, co
     x.e.stats = c->stats;
     x.e.linked = 0; x.e.lookBack = 0;
     x.state = fs->state;
-    x.stageStride = 65536 + (((size_t)a.uniformLen + 64 + 255) & ~(size_t)255);        // compress_fastdict_device's
+    x.stageStride = fastdict_window_stride(a.uniformLen);
     const int grid = encode_fastdict_grid(a.nBlocks, env_int("MI355LZ4_FSTREAMS_WAVES", 0), x.stageStride);
     const size_t windows = (size_t)grid * x.stageStride;
     if ((rc = hcdict_stage(c, windows + ((size_t)x.nWork + (size_t)a.nBlocks) * 4, &x.stage))) return rc;
@@ -1473,7 +1458,7 @@ extern "C" int mi355lz4_compress_streams_fast_device(mi355lz4_ctx *c, mi355lz4_f
     int r = fstreams_check(c, fs, nBlocks, streamFirst, streamSlot, nStreams, "compress_streams_fast_device");
     if (r) return r;
     // (nBlocks < 0 has gone to the stream-table check above)
-    if ((r = fstreams_shape_check("compress_streams_fast_device", nBlocks, headerKind, maxBlockLen))) return r;
+    if ((r = dict_batch_shape_check("compress_streams_fast_device", "a fast stream's block", nBlocks, headerKind, maxBlockLen))) return r;
     if (nBlocks == 0) return MI355LZ4_OK;
     if ((r = batch_buffers_check(c, "compress_streams_fast_device", src, maxBlockLen, headerKind, slots, slotStride, framedLen))) return r;
     HIP_TRY(hipSetDevice(c->device));
@@ -1917,8 +1902,8 @@ extern "C" int mi355lz4_dstreams_reset(mi355lz4_ctx *c, mi355lz4_dstreams *ds, c
 // LZ4_setStreamDecode (cbits/lz4.c:2292-2300) for one slot: only the last 64 KiB of a dictionary can be referenced
 extern "C" int mi355lz4_dstreams_set_dict(mi355lz4_ctx *c, mi355lz4_dstreams *ds, int slot, const uint8_t *dictDevice, int len)
 {
-    if (int r = slots_same_device(c, ds, "dstreams_set_dict")) return r;
-    if (slot < 0 || slot >= ds->nSlots) return fail(MI355LZ4_E_ARG, "dstreams_set_dict: slot %d of %d", slot, ds->nSlots);
+    if (int r = same_device(c, ds, "dstreams_set_dict")) return r;
+    if (int r = slot_range_check(ds, slot, "dstreams_set_dict")) return r;
     if (len < 0 || (len > 0 && !dictDevice)) return fail(MI355LZ4_E_ARG, "dstreams_set_dict: bad dictionary");
     HIP_TRY(hipSetDevice(c->device));
     const int keep = len > DSTREAM_DICT_BYTES ? DSTREAM_DICT_BYTES : len;
@@ -1944,7 +1929,7 @@ extern "C" int mi355lz4_debug_dstream_state(mi355lz4_dstreams *ds, int slot, uin
 int mi355lz4_detail::dstreams_check(const mi355lz4_ctx *c, const mi355lz4_dstreams *ds, int nBlocks, const int32_t *streamFirst,
                                     const int32_t *streamSlot, int nStreams, const char *who)
 {
-    if (int r = slots_same_device(c, ds, who)) return r;
+    if (int r = same_device(c, ds, who)) return r;
     if (c->plan.active) return fail(MI355LZ4_E_ARG, "%s: a linked decode begun with mi355lz4_decompress_linked_begin is still open", who);
     return stream_table_check(ds->nSlots, nBlocks, streamFirst, streamSlot, nStreams, who);
 }
@@ -2046,7 +2031,7 @@ extern "C" int mi355lz4_decompress_dict_multi_device(mi355lz4_ctx *c, const uint
                                                      const mi355lz4_dictset *ds, const int32_t *dictIdx, uint8_t *out,
                                                      const uint64_t *outOff, const int32_t *outCap, int32_t *result)
 {
-    if (int r = dictset_same_device(c, ds, "decompress_dict_multi_device")) return r;
+    if (int r = same_device(c, ds, "decompress_dict_multi_device")) return r;
     if (c->plan.active)
         return fail(MI355LZ4_E_ARG, "decompress_dict_multi_device: a linked decode begun with mi355lz4_decompress_linked_begin is still open");
     if (nBlocks < 0 || (headerKind != 4 && headerKind != 8) || fixedUncomp < 0)

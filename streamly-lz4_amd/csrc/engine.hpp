@@ -169,7 +169,7 @@ int streams_enqueue(mi355lz4_ctx *c, mi355lz4_cstreams *cs, const EncodeArgs &a,
                     const int32_t *streamSlot, int nStreams);
 int fstreams_check(const mi355lz4_ctx *c, const mi355lz4_fstreams *fs, int nBlocks, const int32_t *streamFirst,
                    const int32_t *streamSlot, int nStreams, const char *who);
-int fstreams_shape_check(const char *who, int nBlocks, int headerKind, int maxBlockLen);
+int dict_batch_shape_check(const char *who, const char *what, int nBlocks, int headerKind, int maxBlockLen);
 int fstreams_enqueue(mi355lz4_ctx *c, mi355lz4_fstreams *fs, const EncodeArgs &a, int b0, int b1, const int32_t *streamFirst,
                      const int32_t *streamSlot, int nStreams);
 int dstreams_check(const mi355lz4_ctx *c, const mi355lz4_dstreams *ds, int nBlocks, const int32_t *streamFirst,

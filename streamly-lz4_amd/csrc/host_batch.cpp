@@ -412,7 +412,7 @@ extern "C" int mi355lz4_compress_streams_fast(mi355lz4_ctx *c, mi355lz4_fstreams
             return fail(MI355LZ4_E_ARG, "compress_streams_fast: block %d length %d outside 0..%d", i, srcLen[i], HCDICT_MAX_BLOCK);
         if (srcLen[i] > maxLen) maxLen = srcLen[i];
     }
-    if ((r = fstreams_shape_check("compress_streams_fast", nBlocks, headerKind, maxLen))) return r;
+    if ((r = dict_batch_shape_check("compress_streams_fast", "a fast stream's block", nBlocks, headerKind, maxLen))) return r;
     const HostFastStreams hf{fs, streamFirst, streamSlot, nStreams};
     return compress_host(c, src, srcLen, nBlocks, accel, headerKind, framedOut, cap, outLen, blockFramedLen, status, nullptr, nullptr, &hf);
 }

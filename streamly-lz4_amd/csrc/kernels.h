@@ -403,6 +403,10 @@ void launch_hcdict_build_fast(uint8_t *fast, const uint8_t *dict, int len, hipSt
 // level 0 against both images: a persistent grid of encode_fastdict_grid(..) single waves, one window of a.stage each.  knob:
 // MI355LZ4_FASTDICT_WAVES (> 0 waves per CU, < 0 waves in all, 0 the default); the grid shrinks to FASTDICT_SCRATCH_MAX of windows
 int encode_fastdict_grid(int nBlocks, int knob, size_t stageStride);
+// a window of that grid (the stageStride of the four argument structs that have one): the dictionary, the block, and what the
+// encoder may ask for around a position near the block's end (the 56 bytes behind a candidate, the 8 in front of the next one),
+// in whole 256-byte lines
+inline size_t fastdict_window_stride(int maxBlockLen) { return 65536 + (((size_t)maxBlockLen + 64 + 255) & ~(size_t)255); }
 void launch_encode_fastdict(const FastDictArgs &a, int grid, hipStream_t s);
 // fixed-size output pages against both images: the same grid over inputs (encode_fastdict_grid(nInputs, ..)), one chain at a time per wave
 void launch_pages_fastdict(const PagesFastDictArgs &a, int grid, hipStream_t s);

@@ -256,22 +256,63 @@ void launch_hcdict_build_fast(uint8_t *fast, const uint8_t *dict, int len, hipSt
     hipLaunchKernelGGL(k_hcdict_build_fast, dim3(1), dim3(LZ4_WAVE), 0, s, fast, dict, len);
 }
 
-// A persistent grid of single waves, k_encode's occupancy, one window of x.stage per wave.  The kept bytes go into the window once,
-// ending at byte 65536 of it.  For every block of 13 bytes and more the wave copies the block behind them, loads the image into its
-// table, replays the seam steps and runs encode_block_wave<.., PREP> on the staged bytes as the linked call would on its own; the
-// output goes straight to the slot.  Shorter blocks, and every block of an empty dictionary, are encoded where they lie.  A length
-// outside 0..uniformLen gives framedLen 0 and leaves the slot alone.  Nothing of the object is written.
+// ---- the window of a wave of the persistent grids (k_encode_fastdict, k_pages_fastdict, k_encode_fastdict_multi, k_encode_fstreams) ----
+// Wave blockIdx.x owns stageStride bytes of a call's staging area; a dictionary ends, and the block behind it starts, at byte 65536 of them.
+__device__ __forceinline__ uint8_t *enc_window_block_at(uint8_t *stage, size_t stageStride)
+{
+    return stage + (uint64_t)blockIdx.x * (uint64_t)stageStride + 65536;
+}
+
+// The window's head, in two small steps that a kernel calls in the order `keep, seam0, blockAt, dictionary` (one helper for all
+// of it -- by value, by reference, or with blockAt in its result -- moved the instructions of k_encode_fastdict, which then ran 1 to
+// 1.6 % slower: docs/MEASUREMENT_LOG.md section 24).  Word i of the header of the table image `fast`, {keep, first position of the
+// first seam step}: neither above 65536, whatever the image holds ...
+__device__ __forceinline__ int enc_window_header(const uint8_t *fast, int i)
+{
+    return (int)min(ex_uni(as_global((const uint32_t *)(fast + FASTDICT_KEEP_OFF))[i]), 65536u);
+}
+// ... and the kept bytes of `image`, laid so that they end at blockAt.
+__device__ __forceinline__ void enc_window_dict(uint8_t *blockAt, const uint8_t *image, int keep)
+{
+    if (keep > 0) wave_copy_bytes(blockAt - keep, image + HCDICT_DICT_OFF, (uint32_t)keep);
+}
+
+// The prepared window of one block (or of one page's slice) of n >= 13 bytes at src, against a dictionary of keep > 0 bytes: the
+// bytes go behind the kept ones, the table is the image again (the block before has written into it), and the seam steps are
+// replayed against the staged bytes.  The caller then encodes at blockAt with keep bytes of dictionary.  (The decision stays with
+// the caller -- `if (n >= 13 && keep > 0) { prepare; src = blockAt; dictLen = keep; } else if (n >= 13) clear;` -- and the caller's
+// tab4 and lane come in: docs/MEASUREMENT_LOG.md section 24 has what the other forms moved.)
+__device__ __forceinline__ void enc_window_prepare(uint16_t *table, dev_v4 *tab4, int lane, uint8_t *blockAt, const uint8_t *fast,
+                                                   const uint8_t *src, int n, int keep, int seam0)
+{
+    wave_copy_bytes(blockAt, src, (uint32_t)n);
+    for (int i = lane; i < (int)(FASTDICT_TABLE_BYTES / 16); i += LZ4_WAVE) tab4[i] = as_global((const dev_v4 *)fast)[i];
+    // the bytes -- and, behind a restaging, the dictionary's -- are read back by other lanes than wrote them, and the steps below
+    // enter into the loaded table
+    wave_fence();
+    for (int q0 = seam0; q0 < keep; q0 += ENC_SEED_SPAN) enc_seed_step<false>(table, blockAt - keep, q0, keep);
+}
+// ... and without a dictionary: the block of a one-block linked call, from an empty table, where it lies.  (A block under 13 bytes
+// is literals and needs neither window nor table.)
+__device__ __forceinline__ void enc_window_clear(dev_v4 *tab4, int lane)
+{
+    for (int i = lane; i < (int)(FASTDICT_TABLE_BYTES / 16); i += LZ4_WAVE) tab4[i] = dev_v4{0u, 0u, 0u, 0u};
+}
+
+// A persistent grid of single waves, k_encode's occupancy, one window of x.stage per wave.  The kept bytes go into the window once
+// (enc_window_dict).  For every block of 13 bytes and more the wave prepares the window (enc_window_prepare) and runs
+// encode_block_wave<.., PREP> on the staged bytes as the linked call would on its own; the output goes straight to the slot.
+// Shorter blocks, and every block of an empty dictionary, are encoded where they lie.  A length outside 0..uniformLen gives
+// framedLen 0 and leaves the slot alone.  Nothing of the object is written.
 template <bool PAIR>
 __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(ENC_WAVES_PER_EU, ENC_WAVES_PER_EU))) void k_encode_fastdict(FastDictArgs x)
 {
     __shared__ __attribute__((aligned(16))) uint16_t table[ENC_TABLE_ENTRIES + ENC_LDS_PAD + ((PAIR && ENC_STAGE) ? 128 : 0)];
     const int lane = lane_id();
     const EncodeArgs a = x.e;
-    const LZ4_GLOBAL uint32_t *hdr = as_global((const uint32_t *)(x.fast + FASTDICT_KEEP_OFF));
-    const int keep = (int)min(ex_uni(hdr[0]), 65536u);
-    const int seam0 = (int)min(ex_uni(hdr[1]), 65536u);
-    uint8_t *blockAt = x.stage + (uint64_t)blockIdx.x * (uint64_t)x.stageStride + 65536;
-    if (keep > 0) wave_copy_bytes(blockAt - keep, x.image + HCDICT_DICT_OFF, (uint32_t)keep);
+    const int keep = enc_window_header(x.fast, 0), seam0 = enc_window_header(x.fast, 1);
+    uint8_t *blockAt = enc_window_block_at(x.stage, x.stageStride);
+    enc_window_dict(blockAt, x.image, keep);
     dev_v4 *tab4 = (dev_v4 *)table;
     for (int blk = (int)blockIdx.x; blk < a.nBlocks; blk += (int)gridDim.x) {
         const EncBlock b = enc_block(a, blk);
@@ -284,16 +325,10 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(ENC_WAVES_PE
         uint8_t *slot = a.slots + (size_t)blk * a.slotStride;
         int dictLen = 0;
         if (n >= LZ4_MFLIMIT + 1 && keep > 0) {
-            wave_copy_bytes(blockAt, src, (uint32_t)n);
-            for (int i = lane; i < (int)(FASTDICT_TABLE_BYTES / 16); i += LZ4_WAVE) tab4[i] = as_global((const dev_v4 *)x.fast)[i];
-            // the block's bytes are read back by other lanes than wrote them, and the steps below enter into the loaded table
-            wave_fence();
-            for (int q0 = seam0; q0 < keep; q0 += ENC_SEED_SPAN) enc_seed_step<false>(table, blockAt - keep, q0, keep);
+            enc_window_prepare(table, tab4, lane, blockAt, x.fast, src, n, keep, seam0);
             src = blockAt;
             dictLen = keep;
-        } else if (n >= LZ4_MFLIMIT + 1) {                              // no dictionary: the block of a one-block linked call, where it lies
-            for (int i = lane; i < (int)(FASTDICT_TABLE_BYTES / 16); i += LZ4_WAVE) tab4[i] = dev_v4{0u, 0u, 0u, 0u};
-        }                                                               // (shorter blocks are literals: no window, no table)
+        } else if (n >= LZ4_MFLIMIT + 1) enc_window_clear(tab4, lane);
         // (one call site: the encoder is inlined, and its scalar operands stay scalar)
         const int c = encode_block_wave<uint16_t, true, false, PAIR, true>(src, n, slot + a.headerKind, a.accel, table, a.stats, dictLen);
         enc_finish_slot(a, blk, slot, c, n, lane == 0);
@@ -711,12 +746,14 @@ void launch_encode_seg(const EncodeSegArgs &a, hipStream_t s)
 // page that took nothing (pageSize 1: a zero token).  A chain is serial: a call's parallelism is its number of inputs.
 // A length outside 0..LZ4_MAX_INPUT_SIZE or a page that does not fit its stride: nPages[i] = 0 and nothing else.
 // ---------------------------------------------------------------------------
-__global__ __launch_bounds__(LZ4_WAVE) void k_exact_pages(PagesArgs x)
+// One input's chain (DESIGN.md 7k), for the three page kernels: input i of x checked, its pages made one behind the other by
+// make(from, rem, dst, T, used) -> c -- the page of budget T over the rem > 0 bytes at `from`, written at dst; it sets used, the bytes
+// the page took -- each recorded by lane 0 in its header words, pageCompLen and pageSrcLen, then nPages[i] and consumed[i].  A page
+// that has nothing to take is the zero token and is made here: an empty input, and under ONE_IS_EMPTY (the wave encoder's pages) a
+// budget of 1.  A length outside 0..LZ4_MAX_INPUT_SIZE or a page that does not fit its stride: nPages[i] = 0 and nothing else.
+template <bool ONE_IS_EMPTY, class MakePage>
+__device__ __forceinline__ void pages_walk(const PagesArgs x, int i, int lane, MakePage make)
 {
-    __shared__ dev_v4 tab4[EXACT_TABLE / 4];
-    uint32_t *tab = (uint32_t *)tab4;
-    const int lane = lane_id();
-    const int i = (int)blockIdx.x;
     const int n = uni(x.srcLen[i]);
     const int T = uni(x.pageSize[i]);
     if (n < 0 || n > PAGES_MAX_INPUT || (T > 0 && (uint64_t)x.headerKind + (uint64_t)T > (uint64_t)x.pageStride)) {
@@ -731,16 +768,8 @@ __global__ __launch_bounds__(LZ4_WAVE) void k_exact_pages(PagesArgs x)
         uint8_t *page = x.pages + (first + (uint64_t)k) * (uint64_t)x.pageStride;
         uint8_t *dst = page + x.headerKind;
         int c, used = 0;
-        if (rem == 0) {
-            c = enc_empty_block(dst, lane == 0);                        // :1263-1273 (only an empty input gets here)
-        } else {
-            for (int j = lane; j < EXACT_TABLE / 4; j += LZ4_WAVE) tab4[j] = dev_v4{0u, 0u, 0u, 0u};
-            __syncthreads();
-            const bool fill = T < rem + rem / 255 + 16;                 // :1387, LZ4_compressBound
-            if (rem < FILL_64K_LIMIT) c = fill_encode_page<byU16>(tab, src + pos, rem, dst, T, fill, used);    // :1390
-            else c = fill_encode_page<byU32>(tab, src + pos, rem, dst, T, fill, used);
-            __syncthreads();
-        }
+        if (rem == 0 || (ONE_IS_EMPTY && T == 1)) c = enc_empty_block(dst, lane == 0);     // :1263-1273: takes nothing
+        else c = make(src + pos, rem, dst, T, used);
         if (lane == 0) {
             if (x.headerKind >= 4) store_le32(page, c);
             if (x.headerKind == 8) store_le32(page + 4, used);
@@ -752,6 +781,23 @@ __global__ __launch_bounds__(LZ4_WAVE) void k_exact_pages(PagesArgs x)
         if (pos >= n || used == 0) break;
     }
     if (lane == 0) { x.nPages[i] = k; x.consumed[i] = pos; }
+}
+
+__global__ __launch_bounds__(LZ4_WAVE) void k_exact_pages(PagesArgs x)
+{
+    __shared__ dev_v4 tab4[EXACT_TABLE / 4];
+    uint32_t *tab = (uint32_t *)tab4;
+    const int lane = lane_id();
+    pages_walk<false>(x, (int)blockIdx.x, lane, [&](const uint8_t *from, int rem, uint8_t *dst, int T, int &used) -> int {
+        for (int j = lane; j < EXACT_TABLE / 4; j += LZ4_WAVE) tab4[j] = dev_v4{0u, 0u, 0u, 0u};
+        __syncthreads();
+        const bool fill = T < rem + rem / 255 + 16;                     // :1387, LZ4_compressBound
+        int c;
+        if (rem < FILL_64K_LIMIT) c = fill_encode_page<byU16>(tab, from, rem, dst, T, fill, used);      // :1390
+        else c = fill_encode_page<byU32>(tab, from, rem, dst, T, fill, used);
+        __syncthreads();
+        return c;
+    });
 }
 
 void launch_exact_pages(const PagesArgs &a, hipStream_t s)
@@ -761,7 +807,7 @@ void launch_exact_pages(const PagesArgs &a, hipStream_t s)
 }
 
 // ---------------------------------------------------------------------------
-// K2, fast fixed-size output pages (mi355lz4_compress_pages_fast_device, DESIGN.md 7m).  k_exact_pages' chain, layout and stops;
+// K2, fast fixed-size output pages (mi355lz4_compress_pages_fast_device, DESIGN.md 7m).  The same chain, layout and stops (pages_walk);
 // a page is made by the wave encoder with an output budget (encode_block_wave<.., BUDGET>): of the block that compress_batch_device
 // writes for the next min(rem, 65536) bytes it holds the longest prefix of sequences that leaves room for a valid end, closed by the
 // literal run that fills the page.  k_encode's occupancy and table, which the encoder zeroes per page.
@@ -769,42 +815,14 @@ void launch_exact_pages(const PagesArgs &a, hipStream_t s)
 __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(ENC_WAVES_PER_EU, ENC_WAVES_PER_EU))) void k_pages_fast(PagesFastArgs y)
 {
     __shared__ __attribute__((aligned(16))) uint16_t table[ENC_TABLE_ENTRIES + ENC_LDS_PAD + (ENC_STAGE ? 128 : 0)];
-    const PagesArgs x = y.p;
     const int lane = lane_id();
-    const int i = (int)blockIdx.x;
-    const int n = uni(x.srcLen[i]);
-    const int T = uni(x.pageSize[i]);
-    if (n < 0 || n > PAGES_MAX_INPUT || (T > 0 && (uint64_t)x.headerKind + (uint64_t)T > (uint64_t)x.pageStride)) {
-        if (lane == 0) x.nPages[i] = 0;
-        return;
-    }
-    const uint8_t *src = x.src + uni64((int64_t)x.srcOff[i]);
-    const uint64_t first = (uint64_t)i * (uint64_t)x.maxPages;
-    int pos = 0, k = 0;
-    while (k < x.maxPages && T >= 1) {                                  // T < 1: no page
-        const int rem = n - pos;
-        uint8_t *page = x.pages + (first + (uint64_t)k) * (uint64_t)x.pageStride;
-        uint8_t *dst = page + x.headerKind;
-        int c, used = 0;
-        if (rem == 0 || T == 1) {
-            c = enc_empty_block(dst, lane == 0);                        // an empty input, or room for the zero token alone: takes nothing
-        } else {
-            // (one call site: the encoder is inlined, and its scalar operands stay scalar)
-            c = encode_block_wave<uint16_t, false, false, true, false, true>(src + pos, min(rem, 65536), dst, y.accel, table, nullptr, 0,
-                                                                             nullptr, T, &used);
-            wave_fence();                                               // the next page zeroes the table this one read
-        }
-        if (lane == 0) {
-            if (x.headerKind >= 4) store_le32(page, c);
-            if (x.headerKind == 8) store_le32(page + 4, used);
-            x.pageCompLen[first + (uint64_t)k] = c;
-            x.pageSrcLen[first + (uint64_t)k] = used;
-        }
-        k++;
-        pos += used;
-        if (pos >= n || used == 0) break;
-    }
-    if (lane == 0) { x.nPages[i] = k; x.consumed[i] = pos; }
+    pages_walk<true>(y.p, (int)blockIdx.x, lane, [&](const uint8_t *from, int rem, uint8_t *dst, int T, int &used) -> int {
+        // (one call site: the encoder is inlined, and its scalar operands stay scalar)
+        const int c = encode_block_wave<uint16_t, false, false, true, false, true>(from, min(rem, 65536), dst, y.accel, table, nullptr, 0,
+                                                                                   nullptr, T, &used);
+        wave_fence();                                                   // the next page zeroes the table this one read
+        return c;
+    });
 }
 
 void launch_pages_fast(const PagesFastArgs &a, hipStream_t s)
@@ -815,71 +833,34 @@ void launch_pages_fast(const PagesFastArgs &a, hipStream_t s)
 
 // ---------------------------------------------------------------------------
 // K2, fast fixed-size output pages against a prepared dictionary (mi355lz4_compress_pages_fastdict_device, DESIGN.md 7n).
-// k_encode_fastdict's persistent grid of single waves, one window of y.stage per wave with the kept bytes ending at its byte 65536,
-// and k_pages_fast's walk per input.  A page of 13 input bytes and more copies the next min(rem, 65536) bytes behind the dictionary,
-// reloads the table image, replays the seam steps and runs encode_block_wave<.., DICT, PREP, BUDGET>: of the block that
-// compress_fastdict_device writes for those bytes it holds the leading sequences whose cuts are all valid, closed by the literal run
-// that fills the page.  Shorter remainders, and every page of an empty dictionary, are encoded where they lie.  Nothing of the
-// object is written.
+// The persistent grid of single waves and the windows of k_encode_fastdict (enc_window_*), and pages_walk per input.  A page of 13
+// input bytes and more has the next min(rem, 65536) bytes prepared in the window and runs encode_block_wave<.., DICT, PREP, BUDGET>:
+// of the block that compress_fastdict_device writes for those bytes it holds the leading sequences whose cuts are all valid, closed
+// by the literal run that fills the page.  Shorter remainders, and every page of an empty dictionary, are encoded where they lie.
+// Nothing of the object is written.
 // ---------------------------------------------------------------------------
 __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(ENC_WAVES_PER_EU, ENC_WAVES_PER_EU))) void k_pages_fastdict(PagesFastDictArgs y)
 {
     __shared__ __attribute__((aligned(16))) uint16_t table[ENC_TABLE_ENTRIES + ENC_LDS_PAD + (ENC_STAGE ? 128 : 0)];
-    const PagesArgs x = y.p;
     const int lane = lane_id();
-    const LZ4_GLOBAL uint32_t *hdr = as_global((const uint32_t *)(y.fast + FASTDICT_KEEP_OFF));
-    const int keep = (int)min(ex_uni(hdr[0]), 65536u);
-    const int seam0 = (int)min(ex_uni(hdr[1]), 65536u);
-    uint8_t *blockAt = y.stage + (uint64_t)blockIdx.x * (uint64_t)y.stageStride + 65536;
-    if (keep > 0) wave_copy_bytes(blockAt - keep, y.image + HCDICT_DICT_OFF, (uint32_t)keep);
+    const int keep = enc_window_header(y.fast, 0), seam0 = enc_window_header(y.fast, 1);
+    uint8_t *blockAt = enc_window_block_at(y.stage, y.stageStride);
+    enc_window_dict(blockAt, y.image, keep);
     dev_v4 *tab4 = (dev_v4 *)table;
-    for (int i = (int)blockIdx.x; i < x.nInputs; i += (int)gridDim.x) {
-        const int n = uni(x.srcLen[i]);
-        const int T = uni(x.pageSize[i]);
-        if (n < 0 || n > PAGES_MAX_INPUT || (T > 0 && (uint64_t)x.headerKind + (uint64_t)T > (uint64_t)x.pageStride)) {
-            if (lane == 0) x.nPages[i] = 0;
-            continue;
-        }
-        const uint8_t *src = x.src + uni64((int64_t)x.srcOff[i]);
-        const uint64_t first = (uint64_t)i * (uint64_t)x.maxPages;
-        int pos = 0, k = 0;
-        while (k < x.maxPages && T >= 1) {                              // T < 1: no page
-            const int rem = n - pos;
-            uint8_t *page = x.pages + (first + (uint64_t)k) * (uint64_t)x.pageStride;
-            uint8_t *dst = page + x.headerKind;
-            int c, used = 0;
-            if (rem == 0 || T == 1) {
-                c = enc_empty_block(dst, lane == 0);                    // an empty input, or room for the zero token alone: takes nothing
-            } else {
-                const int m = min(rem, 65536);
-                const uint8_t *from = src + pos;
-                int dictLen = 0;
-                if (m >= LZ4_MFLIMIT + 1 && keep > 0) {
-                    wave_copy_bytes(blockAt, from, (uint32_t)m);
-                    for (int j = lane; j < (int)(FASTDICT_TABLE_BYTES / 16); j += LZ4_WAVE) tab4[j] = as_global((const dev_v4 *)y.fast)[j];
-                    // the slice's bytes are read back by other lanes than wrote them, and the steps below enter into the loaded table
-                    wave_fence();
-                    for (int q0 = seam0; q0 < keep; q0 += ENC_SEED_SPAN) enc_seed_step<false>(table, blockAt - keep, q0, keep);
-                    from = blockAt;
-                    dictLen = keep;
-                } else if (m >= LZ4_MFLIMIT + 1) {                      // no dictionary: from an empty table, where the bytes lie
-                    for (int j = lane; j < (int)(FASTDICT_TABLE_BYTES / 16); j += LZ4_WAVE) tab4[j] = dev_v4{0u, 0u, 0u, 0u};
-                }                                                       // (shorter remainders are literals: no window, no table)
-                // (one call site: the encoder is inlined, and its scalar operands stay scalar)
-                c = encode_block_wave<uint16_t, true, false, true, true, true>(from, m, dst, y.accel, table, nullptr, dictLen, nullptr, T, &used);
-                wave_fence();                                           // the next page reloads the table and the window this one read
-            }
-            if (lane == 0) {
-                if (x.headerKind >= 4) store_le32(page, c);
-                if (x.headerKind == 8) store_le32(page + 4, used);
-                x.pageCompLen[first + (uint64_t)k] = c;
-                x.pageSrcLen[first + (uint64_t)k] = used;
-            }
-            k++;
-            pos += used;
-            if (pos >= n || used == 0) break;
-        }
-        if (lane == 0) { x.nPages[i] = k; x.consumed[i] = pos; }
+    for (int i = (int)blockIdx.x; i < y.p.nInputs; i += (int)gridDim.x) {
+        pages_walk<true>(y.p, i, lane, [&](const uint8_t *from, int rem, uint8_t *dst, int T, int &used) -> int {
+            const int m = min(rem, 65536);
+            int dictLen = 0;
+            if (m >= LZ4_MFLIMIT + 1 && keep > 0) {
+                enc_window_prepare(table, tab4, lane, blockAt, y.fast, from, m, keep, seam0);
+                from = blockAt;
+                dictLen = keep;
+            } else if (m >= LZ4_MFLIMIT + 1) enc_window_clear(tab4, lane);
+            // (one call site: the encoder is inlined, and its scalar operands stay scalar)
+            const int c = encode_block_wave<uint16_t, true, false, true, true, true>(from, m, dst, y.accel, table, nullptr, dictLen, nullptr, T, &used);
+            wave_fence();                                               // the next page reloads the table and the window this one read
+            return c;
+        });
     }
 }
 
@@ -956,7 +937,7 @@ void launch_dictset_group(const FastDictMultiArgs &a, int grid, hipStream_t s)
     hipLaunchKernelGGL(k_dictset_scatter, dim3(perBlock), dim3(256), 0, s, a);
 }
 
-// k_encode_fastdict's grid, occupancy, window and call site.  Wave w takes order[w * nBlocks / grid, (w + 1) * nBlocks / grid) (x.range) and
+// The grid, occupancy and windows of k_encode_fastdict (enc_window_*), and a call site of its own.  Wave w takes order[w * nBlocks / grid, (w + 1) * nBlocks / grid) (x.range) and
 // remembers which member its window holds (`held`; -1: none, which needs no window; -2: nothing yet).  When the next block names another member the
 // wave reads that member's {keep, seam0} and copies its kept bytes so that they end at byte 65536 of the window -- in front of the
 // block copy and of the fence that orders both against the reads.  A shorter dictionary behind a longer one leaves stale bytes in
@@ -970,7 +951,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(ENC_WAVES_PE
     const int lane = lane_id();
     const EncodeArgs a = x.e;
     const int j0 = min(max(uni(x.range[blockIdx.x]), 0), a.nBlocks), j1 = min(max(uni(x.range[blockIdx.x + 1u]), j0), a.nBlocks);
-    uint8_t *blockAt = x.stage + (uint64_t)blockIdx.x * (uint64_t)x.stageStride + 65536;
+    uint8_t *blockAt = enc_window_block_at(x.stage, x.stageStride);
     int held = -2, keep = 0, seam0 = 0;                                 // (-2: nothing yet, so the first block counts as a staging)
     const uint8_t *fast = nullptr;
     dev_v4 *tab4 = (dev_v4 *)table;
@@ -994,10 +975,8 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(ENC_WAVES_PE
                 const DictSetEntry m = x.set[k];
                 fast = (const uint8_t *)(uintptr_t)uni64((int64_t)(uintptr_t)m.fast);
                 const uint8_t *image = (const uint8_t *)(uintptr_t)uni64((int64_t)(uintptr_t)m.image);
-                const LZ4_GLOBAL uint32_t *hdr = as_global((const uint32_t *)(fast + FASTDICT_KEEP_OFF));
-                keep = (int)min(ex_uni(hdr[0]), 65536u);
-                seam0 = (int)min(ex_uni(hdr[1]), 65536u);
-                if (keep > 0) wave_copy_bytes(blockAt - keep, image + HCDICT_DICT_OFF, (uint32_t)keep);
+                keep = enc_window_header(fast, 0); seam0 = enc_window_header(fast, 1);
+                enc_window_dict(blockAt, image, keep);
             }
             held = k;
             if (lane == 0) atomicAdd(&x.last[0], 1u);
@@ -1006,17 +985,10 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(ENC_WAVES_PE
         uint8_t *slot = a.slots + (size_t)blk * a.slotStride;
         int dictLen = 0;
         if (n >= LZ4_MFLIMIT + 1 && keep > 0) {
-            wave_copy_bytes(blockAt, src, (uint32_t)n);
-            for (int i = lane; i < (int)(FASTDICT_TABLE_BYTES / 16); i += LZ4_WAVE) tab4[i] = as_global((const dev_v4 *)fast)[i];
-            // the block's bytes -- and, behind a restaging, the dictionary's -- are read back by other lanes than wrote them, and the
-            // steps below enter into the loaded table
-            wave_fence();
-            for (int q0 = seam0; q0 < keep; q0 += ENC_SEED_SPAN) enc_seed_step<false>(table, blockAt - keep, q0, keep);
+            enc_window_prepare(table, tab4, lane, blockAt, fast, src, n, keep, seam0);
             src = blockAt;
             dictLen = keep;
-        } else if (n >= LZ4_MFLIMIT + 1) {                              // no dictionary: the block of a one-block linked call, where it lies
-            for (int i = lane; i < (int)(FASTDICT_TABLE_BYTES / 16); i += LZ4_WAVE) tab4[i] = dev_v4{0u, 0u, 0u, 0u};
-        }                                                               // (shorter blocks are literals: no window, no table)
+        } else if (n >= LZ4_MFLIMIT + 1) enc_window_clear(tab4, lane);
         // (one call site of an instantiation of its own -- SITE 1, encode_wave.hpp: the encoder is inlined, and its scalar operands
         // stay scalar, here and in k_encode_fastdict)
         const int c = encode_block_wave<uint16_t, true, false, PAIR, true, false, 1>(src, n, slot + a.headerKind, a.accel, table, a.stats, dictLen);
@@ -1061,7 +1033,7 @@ __global__ __launch_bounds__(LZ4_WAVE) void k_fstreams_plan(FStreamsArgs x)
     if (lane == 0) x.good[w] = good;
 }
 
-// k_encode_fastdict's persistent grid of single waves, occupancy and windows, over all blocks of the call.  A block at or behind
+// The persistent grid of single waves, occupancy and windows of k_encode_fastdict (enc_window_block_at), over all blocks of the call.  A block at or behind
 // its stream's good[] gets framedLen 0 and nothing else.  A block under 13 bytes is literals, and one with an empty D is the block
 // of a one-block linked call: both are encoded where they lie.  So is a block whose D ends exactly where it starts -- the block
 // before it in the call, when the caller's arrays are contiguous.  Every other block is staged: D so that it ends at byte 65536 of
@@ -1073,7 +1045,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(ENC_WAVES_PE
     __shared__ __attribute__((aligned(16))) uint16_t table[ENC_TABLE_ENTRIES + ENC_LDS_PAD + ((PAIR && ENC_STAGE) ? 128 : 0)];
     const int lane = lane_id();
     const EncodeArgs a = x.e;
-    uint8_t *blockAt = x.stage + (uint64_t)blockIdx.x * (uint64_t)x.stageStride + 65536;
+    uint8_t *blockAt = enc_window_block_at(x.stage, x.stageStride);
     for (int blk = (int)blockIdx.x; blk < a.nBlocks; blk += (int)gridDim.x) {
         const int w = min(max(uni(x.blockStream[blk]), 0), x.nWork - 1);
         const int32_t *e = x.work + 3 * (size_t)w;
