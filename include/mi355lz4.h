@@ -152,6 +152,26 @@ int mi355lz4_device_count(void);
  * are synchronous and use, besides the engine's stream, two copy streams and two compute streams created on first
  * use, plus a small pool of host threads for staging pageable memory (MI355LZ4_COPY_THREADS, default 8); for the
  * duration of such a call the engine's stream is one of its own.
+ * Which *_device call is in which class (tests/test_stream_order_gpu.py holds every one to it on a non-blocking stream:
+ * the enqueue-only ones return before work queued in front of them on the stream has run):
+ *   wait on the host, by design: mi355lz4_decompress_batch_device with linked != 0 (unless mi355lz4_set_linked_async),
+ *     mi355lz4_decompress_streams_device, mi355lz4_decompress_linked_begin / _end / _end_last, and
+ *     mi355lz4_compress_batch_device in reference-exact mode (mi355lz4_set_compress_exact: it reads the lengths back);
+ *   only enqueue: every other one -- mi355lz4_compress_batch_device at level 0 (segments or not, linked or not, block
+ *     checksums or not) and at levels 1..9, _compact_device, _decompress_batch_device with linked == 0 or with
+ *     mi355lz4_set_linked_async, _decompress_partial_device, _index_device, _decoded_size_device, _xxh32_device,
+ *     _generate_device, _interleave_device, _compress_streams_device, _compress_dict_device, _decompress_dict_device,
+ *     _compress_hcdict_device, _compress_fastdict_device, _compress_fastdict_multi_device, _decompress_dict_multi_device,
+ *     the three _compress_pages*_device calls, _decompress_dstreams_device, _compress_streams_fast_device, and the calls
+ *     that prepare their state on the stream (_cstreams_reset, _cstreams_load_dict, _hcdict_load, _dstreams_reset,
+ *     _dstreams_set_dict, _fstreams_reset, _fstreams_set_dict).
+ *   An enqueue-only call may still wait in three cases, none of which reads the caller's data early: the first use of a
+ *   scratch and a scratch that has to grow (hipMalloc / hipFree; the calls that stage dictionary windows -- _compress_hcdict_device,
+ *   _compress_fastdict_device, _compress_fastdict_multi_device, _compress_pages_fastdict_device, _compress_streams_fast_device --
+ *   synchronise the stream before their staging grows), a fifth stream taking over one of
+ *   the four per-stream scratches (segments, dictionary staging: the engine waits for the stream that used it), and the
+ *   fifth of five _compress_streams_device / _compress_streams_fast_device / _decompress_dstreams_device calls in flight
+ *   on one set (the stream table goes through a ring of four).
  *
  * Process environment: the library sets no environment variable; the HIP runtime's settings (GPU_MAX_HW_QUEUES
  * among them) are the process's. */
@@ -521,6 +541,8 @@ int mi355lz4_set_block_checksum(mi355lz4_ctx *ctx, int on);
  *          one-step lazy parse; smaller output, slower; `accel` is ignored.  Deterministic, plain LZ4 blocks that
  *          every decoder reads; linked compression uses the same dictionary as level 0;
  *   10..12 accepted, searched as 9 (mi355lz4_get_compression_level then returns 9).
+ * At every level mi355lz4_compress_batch_device only enqueues: the hash-chain encoder is one launch on the engine's stream and
+ * reads no length on the host.
  * Anything else, or a null ctx: MI355LZ4_E_ARG.  The multi handle's compress call needs its engines to agree. */
 int mi355lz4_set_compression_level(mi355lz4_ctx *ctx, int level);
 /* The effective level (0..9), or MI355LZ4_E_ARG for a null ctx. */
