@@ -79,6 +79,8 @@ module Streamly.Internal.LZ4.GPU
     , freeFastStreams
     , resetFastStreams
     , fastStreamsSetDict
+    , setFastStreamsLevel
+    , fastStreamsLevel
     , c_compressStreamsFastDevice
     , compressChunksManyFast
     , DecompressStreams
@@ -352,6 +354,11 @@ foreign import ccall safe "mi355lz4.h mi355lz4_fstreams_reset"
     c_fstreamsReset :: Ptr C_Engine -> Ptr C_FStreams -> Ptr Int32 -> CInt -> IO CInt
 foreign import ccall safe "mi355lz4.h mi355lz4_fstreams_set_dict"
     c_fstreamsSetDict :: Ptr C_Engine -> Ptr C_FStreams -> CInt -> Ptr Word8 -> CInt -> IO CInt
+-- the set's compression level: a host-side attribute, no device work
+foreign import ccall unsafe "mi355lz4.h mi355lz4_fstreams_set_level"
+    c_fstreamsSetLevel :: Ptr C_FStreams -> CInt -> IO CInt
+foreign import ccall unsafe "mi355lz4.h mi355lz4_fstreams_get_level"
+    c_fstreamsGetLevel :: Ptr C_FStreams -> IO CInt
 -- device pointers in, device pointers out; only enqueues
 foreign import ccall safe "mi355lz4.h mi355lz4_compress_streams_fast_device"
     c_compressStreamsFastDevice
@@ -540,6 +547,16 @@ fastStreamsSetDict :: Engine -> FastStreams -> Int -> Ptr Word8 -> Int -> IO ()
 fastStreamsSetDict (Engine p) (FastStreams fs) slot dict len = do
     rc <- c_fstreamsSetDict p fs (fromIntegral slot) dict (fromIntegral len)
     when (rc /= 0) $ error "mi355lz4_fstreams_set_dict failed"
+
+-- | The set's compression level for the calls made after this one: 0 the wave encoder (the default), 1..12 the hash-chain
+-- encoder (@LZ4_streamHC_t@'s level: it belongs to the streams, not to a call).  Nothing is enqueued.
+setFastStreamsLevel :: FastStreams -> Int -> IO ()
+setFastStreamsLevel (FastStreams fs) level = do
+    rc <- c_fstreamsSetLevel fs (fromIntegral level)
+    when (rc /= 0) $ error "mi355lz4_fstreams_set_level: level outside 0..12"
+
+fastStreamsLevel :: FastStreams -> IO Int
+fastStreamsLevel (FastStreams fs) = fromIntegral <$> c_fstreamsGetLevel fs
 
 newDecompressStreams :: Engine -> Int -> IO DecompressStreams
 newDecompressStreams (Engine p) n = alloca $ \pp -> do

@@ -1134,6 +1134,29 @@ int mi355lz4_compress_streams_fast(mi355lz4_ctx *ctx, mi355lz4_fstreams *fs, con
                                    const int32_t *srcLen, int nBlocks, const int32_t *streamFirst,
                                    const int32_t *streamSlot, int nStreams, int accel, int headerKind, uint8_t *framedOut,
                                    size_t cap, size_t *outLen, int32_t *blockFramedLen, int32_t *status);
+/* High-compression levels of the two calls above: a property of the set, as LZ4_streamHC_t carries its level.  "Only level 0
+ * accepted" above speaks of the ENGINE's level (mi355lz4_set_compression_level), which selects the encoder of the batch calls
+ * and stays 0 for the fast stream calls whatever the set's level is; the set's own level selects theirs.  _set_level(fs, L):
+ * L in 0..12, 0 (the default after _create) is the wave encoder and everything above holds byte for byte; 1..12 is the
+ * hash-chain encoder of mi355lz4_set_compression_level (10..12 search as 9).  A host-side attribute: it needs no device and
+ * enqueues nothing, and it applies to the calls made after it -- a call already enqueued keeps the level it was made at.  A
+ * NULL set is MI355LZ4_E_ARG; a level outside 0..12 is MI355LZ4_E_ARG and leaves the level as it was.  _get_level returns the
+ * level (MI355LZ4_E_ARG for a NULL set).
+ * At set level L in 1..12: the dictionary rule, the stream table rules, the bad-length rule, the empty-stream and empty-block
+ * rules, the enqueue-only behaviour, what the call may write and block checksums are exactly those of level 0; accel is ignored,
+ * as every high-compression call ignores it.  Bytes: block k is, byte for byte, what mi355lz4_compress_batch_device with the
+ * linked switch on and the engine at level L writes for the second block of the contiguous two-block call [D, B_k] with
+ * maxBlockLen = max(|D|, maxBlockLen); with an empty D, the block of the one-block linked call.  So a stream's bytes depend
+ * neither on how it is cut into calls nor on where its blocks lie: they equal one linked mi355lz4_compress_batch_device call at
+ * level L over the stream laid out contiguously.  The level may change between calls of one stream: a slot is the last 64 KiB
+ * of the stream whatever encoder wrote the block, so the stream stays one valid linked stream, read by the same four readers.
+ * mi355lz4_compress_streams_fast follows the set's level the same way, group seams included.  One workgroup per block on a
+ * grid of one per CU (MI355LZ4_HSTREAMS_GROUPS, read per call: that many workgroups, clamped to 1..CUs).  Rates (profiles/hstreams_rate.json,
+ * scripts/hstreams_rate.py; text): 16 streams of 160 blocks of 64 KiB at level 9 in 78.5 ms and 0.790 of level 0's bytes, where
+ * one linked mi355lz4_compress_batch_device call per stream -- the same bytes -- takes 124.4 ms and level 0 1.54 ms; 2560 streams
+ * of one such block in 53.2 ms against 13.6 s. */
+int mi355lz4_fstreams_set_level(mi355lz4_fstreams *fs, int level);   /* 0..12; 0: the wave encoder (default) */
+int mi355lz4_fstreams_get_level(const mi355lz4_fstreams *fs);
 
 /* mi355lz4_slot_stride with room for the trailer when blockChecksum != 0. */
 size_t mi355lz4_slot_stride_ex(int blockLen, int headerKind, int blockChecksum);

@@ -201,6 +201,10 @@ public:
     // mi355lz4_fstreams_set_dict: the slot becomes the last 64 KiB of dictDevice[0, len) (DEVICE memory; len 0 equals a
     // reset); enqueued, the slot keeps its own copy
     void setDict(int slot, const uint8_t *dictDevice, int len);
+    // mi355lz4_fstreams_set_level: the set's compression level for the calls made after it -- 0 the wave encoder (default), 1..12
+    // the hash-chain encoder; a host-side attribute, nothing is enqueued.  Throws Error outside 0..12 (the level stays).
+    void setLevel(int level);
+    int level() const;
 private:
     Engine &eng_;
     mi355lz4_fstreams *fs_ = nullptr;

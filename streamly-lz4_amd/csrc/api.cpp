@@ -1385,6 +1385,22 @@ extern "C" int mi355lz4_fstreams_create(mi355lz4_ctx *c, int nSlots, mi355lz4_fs
 extern "C" void mi355lz4_fstreams_destroy(mi355lz4_fstreams *fs) { slots_destroy(fs); }
 extern "C" int mi355lz4_fstreams_count(const mi355lz4_fstreams *fs) { return slots_count(fs, "fstreams_count"); }
 
+// The set's level: LZ4's level belongs to the stream, here to the set.  0: the wave encoder; 1..12: the hash-chain
+// encoder over the same plan, windows and slots (k_encode_hc_fstreams; 10..12 search as 9).  A host-side attribute: no device,
+// nothing enqueued; a call reads it when it enqueues, so a call already made keeps its level.
+extern "C" int mi355lz4_fstreams_set_level(mi355lz4_fstreams *fs, int level)
+{
+    if (!fs) return fail(MI355LZ4_E_ARG, "fstreams_set_level: null set");
+    if (level < 0 || level > 12) return fail(MI355LZ4_E_ARG, "fstreams_set_level: level %d outside 0..12", level);
+    fs->level = level;
+    return MI355LZ4_OK;
+}
+extern "C" int mi355lz4_fstreams_get_level(const mi355lz4_fstreams *fs)
+{
+    if (!fs) return fail(MI355LZ4_E_ARG, "fstreams_get_level: null set");
+    return fs->level;
+}
+
 extern "C" int mi355lz4_fstreams_reset(mi355lz4_ctx *c, mi355lz4_fstreams *fs, const int32_t *slots, int n)
 {
     if (int r = slots_reset_check(c, fs, slots, n, "fstreams_reset")) return r;
@@ -1438,12 +1454,15 @@ int mi355lz4_detail::fstreams_enqueue(mi355lz4_ctx *c, mi355lz4_fstreams *fs, co
     x.e.linked = 0; x.e.lookBack = 0;
     x.state = fs->state;
     x.stageStride = fastdict_window_stride(a.uniformLen);
-    const int grid = encode_fastdict_grid(a.nBlocks, env_int("MI355LZ4_FSTREAMS_WAVES", 0), x.stageStride);
+    const int level = fs->level;                                // (the set's, as it is now: the chain depth is a launch argument)
+    const int grid = level > 0 ? encode_hc_fstreams_grid(a.nBlocks, env_int("MI355LZ4_HSTREAMS_GROUPS", 0), x.stageStride)
+                               : encode_fastdict_grid(a.nBlocks, env_int("MI355LZ4_FSTREAMS_WAVES", 0), x.stageStride);
     const size_t windows = (size_t)grid * x.stageStride;
     if ((rc = hcdict_stage(c, windows + ((size_t)x.nWork + (size_t)a.nBlocks) * 4, &x.stage))) return rc;
     x.good = (int32_t *)(x.stage + windows);
     x.blockStream = x.good + x.nWork;
-    launch_fstreams(x, grid, c->stream);
+    if (level > 0) launch_fstreams_hc(x, grid, level, c->stream);
+    else launch_fstreams(x, grid, c->stream);
     if ((rc = check_launch("fast streams launch"))) return rc;
     if ((rc = stream_table_launched(c, used))) return rc;       // (the ring entry is busy from here on, whatever the trailers do)
     return encode_trailers(c, x.e);

@@ -142,7 +142,9 @@ struct SlotSet {
 };
 struct mi355lz4_cstreams : SlotSet {};
 struct mi355lz4_dstreams : SlotSet {};
-struct mi355lz4_fstreams : SlotSet {};      // (the fast compress side's set: a slot is the decode side's, FSTREAM_SLOT_BYTES)
+struct mi355lz4_fstreams : SlotSet {        // (the fast compress side's set: a slot is the decode side's, FSTREAM_SLOT_BYTES)
+    int level = 0;                          // 0: the wave encoder; 1..12: the hash-chain encoder (mi355lz4_fstreams_set_level)
+};
 
 namespace mi355lz4_detail {
 

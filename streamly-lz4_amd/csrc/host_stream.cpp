@@ -228,6 +228,12 @@ void FastCompressStreams::setDict(int slot, const uint8_t *dictDevice, int len)
     if (mi355lz4_fstreams_set_dict(eng_.ctx(), fs_, slot, dictDevice, len) != MI355LZ4_OK)
         throw Error(std::string("streamly_lz4::FastCompressStreams::setDict: ") + mi355lz4_last_error());
 }
+void FastCompressStreams::setLevel(int level)
+{
+    if (mi355lz4_fstreams_set_level(fs_, level) != MI355LZ4_OK)
+        throw Error(std::string("streamly_lz4::FastCompressStreams::setLevel: ") + mi355lz4_last_error());
+}
+int FastCompressStreams::level() const { return mi355lz4_fstreams_get_level(fs_); }
 
 std::vector<std::vector<Array>> Engine::compressStreamsFast(const BlockConfig &cfg, int speed, const std::vector<std::vector<Array>> &streams,
                                                         FastCompressStreams &fs, const std::vector<int32_t> &slots)

@@ -418,6 +418,13 @@ void launch_encode_fastdict_multi(const FastDictMultiArgs &a, int grid, hipStrea
 // single waves over all blocks of all streams (the slots only read), then the slots' new tails (one workgroup per entry of
 // a.work), one behind the other on s.  Nothing is read on the host.
 void launch_fstreams(const FStreamsArgs &a, int grid, hipStream_t s);
+// ... of a set whose level is 1..12 (mi355lz4_fstreams_set_level): the same plan and the same save around k_encode_hc_fstreams, a
+// persistent grid of encode_hc_fstreams_grid(..) workgroups of the hash-chain encoder, one window of a.stage each -- the smallest
+// of the blocks, the CUs and the windows FASTDICT_SCRATCH_MAX holds.  knob: MI355LZ4_HSTREAMS_GROUPS, that many workgroups,
+// clamped to 1..CUs (0: not set)
+int encode_hc_fstreams_grid(int nBlocks, int knob, size_t stageStride);
+void launch_fstreams_hc(const FStreamsArgs &a, int grid, int level, hipStream_t s);
+void launch_encode_hc_fstreams(const FStreamsArgs &a, int grid, int depth, hipStream_t s);     // (its middle launch: kernels_hstreams.hip)
 // independent blocks against one external dictionary (a.dict0, a.dict0Len; a.linked is not used): one wave per block
 void launch_decode_dict(const DecodeArgs &a, hipStream_t s);
 // ... each against the member of a set that it names: one wave per block

@@ -16,6 +16,8 @@
 //                          k_pages_fastdict: such pages against a prepared dictionary         encode_wave.hpp, DICT + PREP + BUDGET
 //                          k_dictset_zero / _hist / _scan / _scatter, k_encode_fastdict_multi<PAIR>: a dictionary per block
 //                          k_fstreams_plan, k_encode_fstreams<PAIR>, k_fstreams_save: linked streams continued across calls
+//                          (k_encode_hc_fstreams, those streams at a set's level 1..12, is a second caller of encode_block_hc<false>
+//                          and for that reason NOT of this unit: kernels_hstreams.hip; its launcher is here)
 //   compact.inc            k_scan_u64, k_copy_slots, k_interleave, k_header_sizes, k_decoded_size       size_walk.hpp
 //   checksum.inc           k_xxh32_ranges / _append / _verify: four lanes per range          checksum.hpp
 //   generate.inc           k_generate: synthetic inputs (bench and test support)

@@ -147,6 +147,8 @@ def _load():
     sig("mi355lz4_fstreams_count", C.c_int, vp)
     sig("mi355lz4_fstreams_reset", C.c_int, vp, vp, _i32p, C.c_int)
     sig("mi355lz4_fstreams_set_dict", C.c_int, vp, vp, C.c_int, vp, C.c_int)
+    sig("mi355lz4_fstreams_set_level", C.c_int, vp, C.c_int)
+    sig("mi355lz4_fstreams_get_level", C.c_int, vp)
     sig("mi355lz4_debug_fstreams_peek", C.c_int, vp, C.c_int, _u8p, C.POINTER(C.c_int))
     sig("mi355lz4_compress_streams_fast_device", C.c_int, vp, vp, vp, vp, vp, C.c_uint64, C.c_int, C.c_int, _i32p, _i32p,
         C.c_int, C.c_int, C.c_int, vp, C.c_size_t, vp)
@@ -268,6 +270,7 @@ DECLARED_SYMBOLS = [
     "mi355lz4_compress_streams_device", "mi355lz4_compress_streams",
     "mi355lz4_fstreams_create", "mi355lz4_fstreams_destroy", "mi355lz4_fstreams_count", "mi355lz4_fstreams_reset",
     "mi355lz4_fstreams_set_dict", "mi355lz4_compress_streams_fast_device", "mi355lz4_compress_streams_fast",
+    "mi355lz4_fstreams_set_level", "mi355lz4_fstreams_get_level",
     "mi355lz4_decoded_size_device", "mi355lz4_decoded_sizes_host",
     "mi355lz4_decompress_partial_device", "mi355lz4_decompress_partial",
     "mi355lz4_dstreams_create", "mi355lz4_dstreams_destroy", "mi355lz4_dstreams_count", "mi355lz4_dstreams_reset",
@@ -1443,6 +1446,17 @@ class FastCompressStreams:
         n = int(dict_device.numel() if length is None else length) if dict_device is not None else 0
         _check(lib.mi355lz4_fstreams_set_dict(self._engine.ctx, self._h, int(slot), _dptr(dict_device) if n else None, n),
                "fstreams_set_dict")
+
+    def set_level(self, level):
+        """The set's compression level for the calls made after this one (mi355lz4_fstreams_set_level): 0 the wave encoder
+        (default), 1..12 the hash-chain encoder.  A host-side attribute: nothing is enqueued."""
+        _check(lib.mi355lz4_fstreams_set_level(self._h, int(level)), "fstreams_set_level")
+
+    @property
+    def level(self):
+        r = int(lib.mi355lz4_fstreams_get_level(self._h))
+        _check(min(r, 0), "fstreams_get_level")
+        return r
 
     def peek(self, slot):
         """Diagnostics: (dictionary bytes held, those bytes), after the device is idle."""
