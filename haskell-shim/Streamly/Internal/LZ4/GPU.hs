@@ -90,6 +90,12 @@ module Streamly.Internal.LZ4.GPU
     , c_dstreamsSetDict
     , c_decompressDStreamsDevice
     , decompressChunksMany
+    , Frames
+    , newFrames
+    , freeFrames
+    , loadFrames
+    , decodeFrames
+    , decompressFramesMany
     , MultiEngine
     , newMultiEngine
     , freeMultiEngine
@@ -102,9 +108,9 @@ where
 
 import Control.Monad (forM, forM_, when)
 import Control.Monad.IO.Class (MonadIO(..))
-import Data.Int (Int32)
+import Data.Int (Int32, Int64)
 import Data.Word (Word8, Word64)
-import Foreign.C (CInt(..), CSize(..))
+import Foreign.C (CInt(..), CSize(..), CUInt(..))
 import Foreign.Marshal.Alloc (alloca)
 import Foreign.Marshal.Array (allocaArray, peekArray, pokeArray, withArrayLen)
 import Foreign.Marshal.Utils (copyBytes)
@@ -557,6 +563,86 @@ setFastStreamsLevel (FastStreams fs) level = do
 
 fastStreamsLevel :: FastStreams -> IO Int
 fastStreamsLevel (FastStreams fs) = fromIntegral <$> c_fstreamsGetLevel fs
+
+-- Batches of standard LZ4 frames (include/mi355lz4.h, "batches of standard LZ4 frames"): a parsed batch on the device.
+data C_Frames
+newtype Frames = Frames (Ptr C_Frames)
+
+foreign import ccall safe "mi355lz4.h mi355lz4_frames_create"
+    c_framesCreate :: Ptr C_Engine -> Ptr (Ptr C_Frames) -> IO CInt
+foreign import ccall safe "mi355lz4.h mi355lz4_frames_destroy"
+    c_framesDestroy :: Ptr C_Frames -> IO ()
+foreign import ccall safe "mi355lz4.h mi355lz4_frames_load"
+    c_framesLoad
+        :: Ptr C_Engine -> Ptr C_Frames -> Ptr Word8 -> Word64 -> Ptr Word64 -> Ptr Word64 -> CInt -> CUInt -> IO CInt
+foreign import ccall unsafe "mi355lz4.h mi355lz4_frames_inputs"
+    c_framesInputs :: Ptr C_Frames -> IO CInt
+foreign import ccall unsafe "mi355lz4.h mi355lz4_frames_blocks"
+    c_framesBlocks :: Ptr C_Frames -> IO CInt
+foreign import ccall unsafe "mi355lz4.h mi355lz4_frames_total"
+    c_framesTotal :: Ptr C_Frames -> IO Word64
+foreign import ccall unsafe "mi355lz4.h mi355lz4_frames_sizes"
+    c_framesSizes :: Ptr C_Frames -> IO (Ptr Int64)
+foreign import ccall unsafe "mi355lz4.h mi355lz4_frames_get_sizes"
+    c_framesGetSizes :: Ptr C_Frames -> Ptr Int64 -> IO CInt
+foreign import ccall safe "mi355lz4.h mi355lz4_frames_decode"
+    c_framesDecode :: Ptr C_Engine -> Ptr C_Frames -> Ptr Word8 -> Ptr Word64 -> Ptr Int64 -> IO CInt
+foreign import ccall safe "mi355lz4.h mi355lz4_decompress_frames"
+    c_decompressFrames
+        :: Ptr C_Engine -> Ptr (Ptr Word8) -> Ptr CSize -> CInt -> CUInt -> Ptr Word8 -> CSize -> Ptr CSize -> Ptr Int64
+        -> IO CInt
+
+newFrames :: Engine -> IO Frames
+newFrames (Engine p) = alloca $ \pp -> do
+    rc <- c_framesCreate p pp
+    when (rc /= 0) $ error "mi355lz4_frames_create failed"
+    Frames <$> peek pp
+
+freeFrames :: Frames -> IO ()
+freeFrames (Frames p) = c_framesDestroy p
+
+-- | Parse @n@ inputs that lie in DEVICE memory (input i is @buf[inOff[i], inOff[i] + inLen[i])@); the exact decoded size of
+-- every input, or its negative @MI355LZ4_FRM_E_*@ code.  Waits for the engine's stream; @buf@ is borrowed until the decodes
+-- that use it have run.
+loadFrames :: Engine -> Frames -> Ptr Word8 -> Word64 -> Ptr Word64 -> Ptr Word64 -> Int -> Int -> IO [Int64]
+loadFrames (Engine p) (Frames fr) buf bufLen inOff inLen n flags = do
+    rc <- c_framesLoad p fr buf bufLen inOff inLen (fromIntegral n) (fromIntegral flags)
+    when (rc /= 0) $ error "mi355lz4_frames_load failed"
+    allocaArray (max n 1) $ \ps -> do
+        _ <- c_framesGetSizes fr ps
+        peekArray n ps
+
+-- | Decode the loaded inputs into DEVICE memory: input i with a size goes to @out[outOff[i], ..)@, @result[i]@ is its size or
+-- a code.  Only enqueues on the engine's stream.
+decodeFrames :: Engine -> Frames -> Ptr Word8 -> Ptr Word64 -> Ptr Int64 -> IO ()
+decodeFrames (Engine p) (Frames fr) out outOff result = do
+    rc <- c_framesDecode p fr out outOff result
+    when (rc /= 0) $ error "mi355lz4_frames_decode failed"
+
+-- | Many inputs of standard LZ4 frames (each what @lz4 -d@ accepts) decoded in one GPU call: per input its content, or
+-- 'Left' its @MI355LZ4_FRM_E_*@ code.  The first call only sizes the output (the C ABI answers a capacity of 0 with the total).
+decompressFramesMany :: Engine -> [Array.Array Word8] -> IO [Either Int64 (Array.Array Word8)]
+decompressFramesMany (Engine eng) inputs = do
+    let n = length inputs
+        lens = map Array.byteLength inputs
+        offs = scanl (+) 0 lens
+    packed <- concatArrays inputs
+    allocaArray (max n 1) $ \pIn -> allocaArray (max n 1) $ \pLen -> allocaArray (max n 1) $ \pRes -> alloca $ \pOutLen ->
+      Array.asPtrUnsafe (Array.unsafeCast packed) $ \pBytes -> do
+        pokeArray pIn [ (pBytes :: Ptr Word8) `plusPtr` o | o <- take n offs ]
+        pokeArray pLen (map fromIntegral lens)
+        rc0 <- c_decompressFrames eng pIn pLen (fromIntegral n) 0 nullPtr 0 pOutLen pRes
+        total <- if rc0 == (-4) then fromIntegral <$> peek pOutLen else return (0 :: Int)
+        (MArray.Array cont _ b _) <- MArray.newArray (max total 1)
+        rc <- if rc0 == (-4)
+                then c_decompressFrames eng pIn pLen (fromIntegral n) 0 b (fromIntegral total) pOutLen pRes
+                else return rc0
+        when (rc /= 0 && rc /= (-5)) $ error "decompressFramesMany: mi355lz4_decompress_frames failed"
+        res <- peekArray n pRes
+        let sizes = map (\r -> if r > 0 then fromIntegral r else 0) res
+            starts = scanl (+) 0 sizes
+        return [ if r < 0 then Left r else Right (Array.Array cont (b `plusPtr` o) (b `plusPtr` (o + l)))
+               | (r, o, l) <- zip3 res starts sizes ]
 
 newDecompressStreams :: Engine -> Int -> IO DecompressStreams
 newDecompressStreams (Engine p) n = alloca $ \pp -> do

@@ -62,6 +62,18 @@ extern "C" {
 #define MI355LZ4_BLK_E_SIZE_UNKNOWN (-0x7F000005) /* mi355lz4_decoded_size_device: the token chain gives no size the call vouches for */
 #define MI355LZ4_BLK_E_DICT (-0x7F000006)       /* mi355lz4_decompress_dict_multi_device: dictIdx[i] names no member of the set */
 
+/* per-input codes of the frame batches (mi355lz4_frames: sizes[] and result[]); an input reports the error with the smallest
+ * byte position in it */
+#define MI355LZ4_FRM_E_MAGIC            (-0x7F000101)  /* no frame begins here (trailing bytes too) */
+#define MI355LZ4_FRM_E_HEADER           (-0x7F000102)  /* version, reserved bits, BD code, DictID */
+#define MI355LZ4_FRM_E_HEADER_CHECKSUM  (-0x7F000103)
+#define MI355LZ4_FRM_E_TRUNCATED        (-0x7F000104)  /* the input ends inside a frame */
+#define MI355LZ4_FRM_E_BLOCK_SIZE       (-0x7F000105)  /* a block word above the frame's block maximum */
+#define MI355LZ4_FRM_E_BLOCK_CHECKSUM   (-0x7F000106)
+#define MI355LZ4_FRM_E_BLOCK            (-0x7F000107)  /* no size to vouch for, or the decode does not give that size */
+#define MI355LZ4_FRM_E_CONTENT_SIZE     (-0x7F000108)
+#define MI355LZ4_FRM_E_CONTENT_CHECKSUM (-0x7F000109)
+
 #define MI355LZ4_MAX_INPUT_SIZE 0x7E000000      /* = LZ4_MAX_INPUT_SIZE, cbits/lz4.h:170 */
 
 typedef struct mi355lz4_ctx mi355lz4_ctx;
@@ -130,6 +142,11 @@ typedef struct mi355lz4_ctx mi355lz4_ctx;
  *   _decompress_dict_multi_device: the ranges of _decompress_dict_device, and nothing of `out` for a block whose index names no
  *   member (result[i] = MI355LZ4_BLK_E_DICT); never a member, dictIdx, framed, blockOff, outOff or outCap.  Of the set itself the
  *   compress call writes two diagnostic words.  _compress_fastdict_multi and _decompress_dict_multi are host-buffer calls as above.
+ * Frame batches: _frames_load writes the object it is handed and nothing else (never buf, inOff or inLen).  _frames_decode: no
+ *   byte of `out` outside the union of [outOff[i], outOff[i] + sizes[i]) over the inputs with sizes[i] >= 0 -- whatever `buf` holds
+ *   at decode time, for an input that decodes and one that fails at decode time alike -- nothing at all for an input whose size is
+ *   a code; result[] only in [0, nInputs); never buf or outOff; of the object only its decode scratch.  _decompress_frames is a
+ *   host-buffer call as above (result only in [0, nInputs)).
  * Scratch that a call needs is the engine's own. */
 
 /* ---- engine lifecycle ------------------------------------------------ */
@@ -172,6 +189,9 @@ int mi355lz4_device_count(void);
  *   the four per-stream scratches (segments, dictionary staging: the engine waits for the stream that used it), and the
  *   fifth of five _compress_streams_device / _compress_streams_fast_device / _decompress_dstreams_device calls in flight
  *   on one set (the stream table goes through a ring of four).
+ *   The frame batches are methods of an object and carry no suffix: mi355lz4_frames_load waits on the host by design (twice:
+ *   for the counts that size its tables, and for the sizes), mi355lz4_frames_decode only enqueues
+ *   (tests/test_frames_stream_gpu.py holds it to the same protocol).
  *
  * Process environment: the library sets no environment variable; the HIP runtime's settings (GPU_MAX_HW_QUEUES
  * among them) are the process's. */
@@ -1169,6 +1189,70 @@ int mi355lz4_index_host_ex(const uint8_t *framedIn, size_t inLen, int headerKind
  * checksums. */
 int mi355lz4_xxh32_device(mi355lz4_ctx *ctx, const uint8_t *base, const uint64_t *off, const int32_t *len, int n,
                           uint32_t seed, uint32_t *out);
+
+/* ---- batches of standard LZ4 frames ------------------------------------
+ * The LZ4 frame format (what the `lz4` tool and liblz4's LZ4F_* write) as a batched, device-resident call.  A caller-owned
+ * object holds a parsed batch: _frames_load parses many inputs on the device and reports their exact decoded sizes,
+ * _frames_decode decodes them all.  An input is what `lz4 -d` accepts: any sequence of LZ4 frames and skippable frames; it may
+ * be empty (size 0).  The device-pointer calls carry no _device suffix: they are methods of an object, as mi355lz4_hcdict_load.
+ *
+ * Format: magic 0x184D2204; skippable frames 0x184D2A50..5F are skipped; version 01; reserved FLG and BD bits and DictID frames
+ * are rejected; BD codes 4..7; the optional 8-byte content size; the header checksum byte; in a block word the high bit marks a
+ * stored block, n <= the frame's block maximum, 0 is the end mark; a stored block of 0 bytes is skipped; optional block
+ * checksums over the block's bytes as stored; the optional content checksum behind the end mark; trailing bytes that begin no
+ * frame are MI355LZ4_FRM_E_MAGIC (fewer than four of them: _TRUNCATED).  A linked frame's window is the last 64 KiB of that
+ * frame's output, across stored and short blocks.
+ * A compressed block's size is read off its token chain by the rule of mi355lz4_decoded_size_device without the last clause of
+ * its rule 4 (a long match from the window that ends near the block's end is legitimate in a linked frame), and it is bounded by
+ * the frame's block maximum.  Rule 2 stays: a block that breaks the format's end-of-block rules (no match in a block under 13
+ * bytes, the last match at least 12 bytes before the end, five literals last) is refused with MI355LZ4_FRM_E_BLOCK where
+ * liblz4, given spare capacity, might accept it.  No conforming encoder writes such a block.
+ *
+ * Codes: sizes[i] / result[i] is the input's decoded size or the MI355LZ4_FRM_E_* code of the error with the smallest byte
+ * position in the input: a header error sits at the frame's magic, a block error at the block's size word, content size and
+ * content checksum errors at the end mark.  The scan stops at the first structural error (MAGIC, HEADER, HEADER_CHECKSUM,
+ * TRUNCATED, BLOCK_SIZE): nothing behind it exists, block errors in front of it win.  MAGIC .. BLOCK_CHECKSUM, CONTENT_SIZE
+ * and BLOCK for a chain without a size are known at _load; BLOCK from decoding and CONTENT_CHECKSUM appear in _decode's result.
+ * The two flags switch the respective verification off; the fields must still be present and inside the input.
+ *
+ * _frames_load: buf, inOff, inLen are DEVICE memory; input i is buf[inOff[i], inOff[i] + inLen[i]), full 64-bit quantities, any
+ * alignment (an input that leaves [0, bufLen) is _TRUNCATED).  It parses on the engine's stream and WAITS for it, twice: for the
+ * frame and block counts that size the tables, and for the sizes.  The tables cost a fixed number of bytes per input, frame
+ * and block that is really there; nothing is sized by a declared content size or by blocks x maximum block size.  The object
+ * keeps its own copy of inOff and inLen and borrows buf, which must hold the same bytes until the decodes that use it have
+ * run.  A second _load on the same object replaces the first.  The frames and the blocks of a call must each number below
+ * INT_MAX (MI355LZ4_E_ARG otherwise).
+ * _frames_inputs / _blocks / _total (sum of the sizes >= 0) / _sizes (device array, nInputs entries) / _get_sizes (the host
+ * copy that _load read back) describe the last _load.
+ * _frames_decode: out, outOff, result are DEVICE memory.  Enqueue only, on the engine's stream; mi355lz4_set_block_checksum is
+ * ignored (a frame's block checksums are its own).  Input i with sizes[i] >= 0 is written to out[outOff[i], outOff[i] +
+ * sizes[i]); result[i] = its size or a code; an input whose size is a code gets that code and nothing of `out` is touched for
+ * it; an input that fails at decode time leaves unspecified bytes inside its own range and nowhere else.  The object's decode
+ * scratch is written: two decodes of ONE object go on the same stream, or the caller orders them.  Compressed blocks of
+ * independent frames take the engine's own decode paths in one internal call; a linked frame is one wavefront's work.
+ * MI355LZ4_E_ARG: a null ctx or fr, nInputs < 0, a null array with nInputs > 0, unknown flag bits, an object created on
+ * another device's engine, _decode before any _load, a null out with bytes to write.  nInputs == 0 is MI355LZ4_OK.
+ * mi355lz4_decompress_frames: host buffers, synchronous: the inputs go to the device, _load, _decode into a dense layout (input
+ * i at the scan of the sizes >= 0), outputs and result[] come back: input i lies at the scan of the results >= 0 (an input
+ * that failed at decode time is closed up on the host), *outLen = their sum.  cap below the total of the sizes:
+ * MI355LZ4_E_CAPACITY with *outLen = that total and nothing written to out, so one failed call sizes the buffer.
+ * MI355LZ4_E_BLOCK when some input has a negative result; the others are delivered. */
+typedef struct mi355lz4_frames mi355lz4_frames;
+#define MI355LZ4_FRAMES_SKIP_CONTENT_CHECKSUM 1u
+#define MI355LZ4_FRAMES_SKIP_BLOCK_CHECKSUM   2u
+int mi355lz4_frames_create(mi355lz4_ctx *ctx, mi355lz4_frames **out);
+void mi355lz4_frames_destroy(mi355lz4_frames *fr);
+int mi355lz4_frames_load(mi355lz4_ctx *ctx, mi355lz4_frames *fr, const uint8_t *buf, uint64_t bufLen,
+                         const uint64_t *inOff, const uint64_t *inLen, int nInputs, unsigned flags);
+int mi355lz4_frames_inputs(const mi355lz4_frames *fr);
+int mi355lz4_frames_blocks(const mi355lz4_frames *fr);
+uint64_t mi355lz4_frames_total(const mi355lz4_frames *fr);
+const int64_t *mi355lz4_frames_sizes(const mi355lz4_frames *fr);
+int mi355lz4_frames_get_sizes(const mi355lz4_frames *fr, int64_t *sizesHost);
+int mi355lz4_frames_decode(mi355lz4_ctx *ctx, const mi355lz4_frames *fr, uint8_t *out, const uint64_t *outOff,
+                           int64_t *result);
+int mi355lz4_decompress_frames(mi355lz4_ctx *ctx, const uint8_t *const *in, const size_t *inLen, int nInputs,
+                               unsigned flags, uint8_t *out, size_t cap, size_t *outLen, int64_t *result);
 
 /* ---- timing support: HIP events on the engine's own stream ------------- */
 int mi355lz4_event_create(void **ev);

@@ -28,6 +28,7 @@ struct mi355lz4_hcdict;
 struct mi355lz4_dictset;
 struct mi355lz4_dstreams;
 struct mi355lz4_fstreams;
+struct mi355lz4_frames;
 
 namespace streamly_lz4 {
 
@@ -160,10 +161,39 @@ public:
     std::vector<std::vector<Array>> compressPagesWithDictFast(const BlockConfig &cfg, const std::vector<Array> &arrays, const class HcDict &hd,
                                                               int pageSize, int maxPages, std::vector<int32_t> *consumed = nullptr,
                                                               int accel = 1);
+    // Many inputs of standard LZ4 frames in one call (mi355lz4_decompress_frames): each input is what `lz4 -d` accepts -- any
+    // sequence of LZ4 frames and skippable frames, or nothing -- and comes back decoded.  The batched counterpart of
+    // lz4FrameDecompress below, parsed, sized and decoded on the device.  When some input fails, throws Error; with `result`
+    // given it does not: result[i] is then input i's size or its MI355LZ4_FRM_E_* code, and a failed input's array is empty.
+    std::vector<Array> decompressFrames(const std::vector<Array> &inputs, unsigned flags = 0, std::vector<int64_t> *result = nullptr);
 private:
     mi355lz4_ctx *ctx_ = nullptr;
     size_t batch_;
     bool linked_ = false;
+};
+
+// A parsed batch of standard LZ4 frames on the engine's device (mi355lz4_frames), for callers whose data is device-resident:
+// load() parses many inputs and returns their exact decoded sizes (it waits for the engine's stream), decode() decodes them all
+// and only enqueues.  All pointers are DEVICE memory; buf is borrowed until the decodes that use it have run.
+class Frames {
+public:
+    explicit Frames(Engine &eng);                       // throws Error
+    ~Frames();
+    Frames(const Frames &) = delete;
+    Frames &operator=(const Frames &) = delete;
+    mi355lz4_frames *handle() const { return fr_; }
+    // input i is buf[inOff[i], inOff[i] + inLen[i]); the sizes or MI355LZ4_FRM_E_* codes, one per input; replaces the last load
+    std::vector<int64_t> load(const uint8_t *buf, uint64_t bufLen, const uint64_t *inOff, const uint64_t *inLen, int nInputs,
+                              unsigned flags = 0);
+    int inputs() const;
+    int blocks() const;
+    uint64_t total() const;                             // sum of the sizes >= 0
+    const int64_t *sizesDevice() const;
+    // input i with a size goes to out[outOff[i], outOff[i] + size); result[i] = its size or a code
+    void decode(uint8_t *out, const uint64_t *outOff, int64_t *result);
+private:
+    Engine &eng_;
+    mi355lz4_frames *fr_ = nullptr;
 };
 
 // A set of nSlots device-resident reference-exact compress streams (mi355lz4_cstreams: about 80 KiB a slot), one per

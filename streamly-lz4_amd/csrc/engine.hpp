@@ -146,6 +146,20 @@ struct mi355lz4_fstreams : SlotSet {        // (the fast compress side's set: a 
     int level = 0;                          // 0: the wave encoder; 1..12: the hash-chain encoder (mi355lz4_fstreams_set_level)
 };
 
+// A parsed batch of standard LZ4 frames (frames.cpp, kernels/frames.inc): the tables of the last _load on the
+// device -- a fixed number of bytes per input, per frame and per block -- the counts the load read back, and the host copy of the
+// sizes.  buf is borrowed; inOff and inLen are the object's own copies.
+struct mi355lz4_frames {
+    using DevBuf = mi355lz4_detail::DevBuf;
+    int device = 0;
+    bool loaded = false;
+    FramesArgs a{};                        // what the kernels are handed (the decode fills in out, outOff, result)
+    uint64_t total = 0;
+    DevBuf perInput, perFrame, perBlock;   // the tables
+    DevBuf pin;                            // pinned: {frames, blocks}, then {indep, linked}, then the sizes
+    int64_t *sizesHost() const { return (int64_t *)((uint8_t *)pin.p + 64); }
+};
+
 namespace mi355lz4_detail {
 
 // pageable host memory <-> device through pinned staging, on the engine's stream (api.cpp)

@@ -479,6 +479,57 @@ std::vector<Array> Engine::decompressWithDict(const BlockConfig &cfg, const std:
     return res;
 }
 
+Frames::Frames(Engine &eng) : eng_(eng)
+{
+    if (mi355lz4_frames_create(eng.ctx(), &fr_) != MI355LZ4_OK) throw Error(std::string("streamly_lz4::Frames: ") + mi355lz4_last_error());
+}
+Frames::~Frames() { mi355lz4_frames_destroy(fr_); }
+int Frames::inputs() const { return mi355lz4_frames_inputs(fr_); }
+int Frames::blocks() const { return mi355lz4_frames_blocks(fr_); }
+uint64_t Frames::total() const { return mi355lz4_frames_total(fr_); }
+const int64_t *Frames::sizesDevice() const { return mi355lz4_frames_sizes(fr_); }
+std::vector<int64_t> Frames::load(const uint8_t *buf, uint64_t bufLen, const uint64_t *inOff, const uint64_t *inLen, int nInputs,
+                                  unsigned flags)
+{
+    if (mi355lz4_frames_load(eng_.ctx(), fr_, buf, bufLen, inOff, inLen, nInputs, flags) != MI355LZ4_OK)
+        throw Error(std::string("Frames::load: ") + mi355lz4_last_error());
+    std::vector<int64_t> sizes((size_t)nInputs);
+    mi355lz4_frames_get_sizes(fr_, sizes.data());
+    return sizes;
+}
+void Frames::decode(uint8_t *out, const uint64_t *outOff, int64_t *result)
+{
+    if (mi355lz4_frames_decode(eng_.ctx(), fr_, out, outOff, result) != MI355LZ4_OK)
+        throw Error(std::string("Frames::decode: ") + mi355lz4_last_error());
+}
+
+std::vector<Array> Engine::decompressFrames(const std::vector<Array> &inputs, unsigned flags, std::vector<int64_t> *result)
+{
+    const int n = (int)inputs.size();
+    std::vector<const uint8_t *> ptrs;
+    std::vector<size_t> lens;
+    for (const Array &a : inputs) { ptrs.push_back(a.data()); lens.push_back(a.size()); }
+    ptrs.push_back(nullptr);
+    lens.push_back(0);
+    std::vector<int64_t> res((size_t)n + 1);
+    size_t outLen = 0;
+    // one call that fails for its capacity sizes the buffer (the C ABI's own way), the second decodes
+    int rc = mi355lz4_decompress_frames(ctx_, ptrs.data(), lens.data(), n, flags, nullptr, 0, &outLen, res.data());
+    Array out(outLen);
+    if (rc == MI355LZ4_E_CAPACITY)
+        rc = mi355lz4_decompress_frames(ctx_, ptrs.data(), lens.data(), n, flags, out.data(), out.size(), &outLen, res.data());
+    if (rc != MI355LZ4_OK && !(rc == MI355LZ4_E_BLOCK && result)) throw Error(std::string("decompressFrames: ") + mi355lz4_last_error());
+    std::vector<Array> parts;
+    size_t pos = 0;
+    for (int k = 0; k < n; k++) {
+        const size_t len = res[(size_t)k] > 0 ? (size_t)res[(size_t)k] : 0;
+        parts.emplace_back(out.begin() + (long)pos, out.begin() + (long)(pos + len));
+        pos += len;
+    }
+    if (result) result->assign(res.begin(), res.begin() + n);
+    return parts;
+}
+
 DictSet::DictSet(Engine &eng, const std::vector<const HcDict *> &members)
 {
     std::vector<const mi355lz4_hcdict *> h;

@@ -451,5 +451,66 @@ void launch_xxh32_ranges(const uint8_t *base, const uint64_t *off, const int32_t
                          hipStream_t s);
 void launch_xxh32_append(uint8_t *slots, size_t slotStride, int headerKind, int32_t *framedLen, int n, hipStream_t s);
 void launch_xxh32_verify(const DecodeArgs &a, int32_t *fail, hipStream_t s);
+// batches of standard LZ4 frames (mi355lz4_frames; kernels/frames.inc).  Input i is buf[inOff[i], inOff[i] + inLen[i]):
+// any sequence of LZ4 frames and skippable frames.  The tables cost a fixed number of bytes per input, per frame and per block.
+#define FRM_E_MAGIC            (-0x7F000101)   // = MI355LZ4_FRM_E_* (include/mi355lz4.h)
+#define FRM_E_HEADER           (-0x7F000102)
+#define FRM_E_HEADER_CHECKSUM  (-0x7F000103)
+#define FRM_E_TRUNCATED        (-0x7F000104)
+#define FRM_E_BLOCK_SIZE       (-0x7F000105)
+#define FRM_E_BLOCK_CHECKSUM   (-0x7F000106)
+#define FRM_E_BLOCK            (-0x7F000107)
+#define FRM_E_CONTENT_SIZE     (-0x7F000108)
+#define FRM_E_CONTENT_CHECKSUM (-0x7F000109)
+#define FRM_SKIP_CONTENT_CHECKSUM 1u
+#define FRM_SKIP_BLOCK_CHECKSUM   2u
+// a frame's flags word: the FLG byte of its descriptor, and
+#define FRM_F_BROKEN 0x100u                    // a structural error ended the frame: it has no end mark, size or checksum to check
+// what the decode does with a block (FramesArgs::kind)
+enum { FRM_K_NONE = 0, FRM_K_COMP = 1, FRM_K_STORED = 2, FRM_K_LINKED = 3 };
+
+struct FrmFrame {
+    uint64_t endPos;         // position of the end mark in buf (of the structural error: a broken frame)
+    uint64_t declared;       // content size of the descriptor
+    uint64_t outRel;         // where the frame's content starts in its input's output (k_frames_layout)
+    uint64_t size;           // the frame's content size (k_frames_layout)
+    int32_t input, firstBlock, nBlocks;
+    uint32_t flags;          // FLG | FRM_F_*
+    uint32_t blockMax;
+    uint32_t checksum;       // the content checksum word
+};
+struct FrmBlock {
+    uint64_t payOff;         // the block's bytes in buf; its size word lies 4 bytes in front
+    uint64_t outRel;         // where it decodes to in its input's output (k_frames_layout)
+    uint32_t n;              // stored bytes; bit 31: the block is stored, not compressed
+    int32_t frame;
+    int32_t size;            // what it decodes to, or SIZE_E_UNKNOWN (k_frames_sizes)
+    int32_t kind;            // FRM_K_* (k_frames_layout)
+};
+struct FramesArgs {
+    const uint8_t *buf; uint64_t bufLen;
+    const uint64_t *inOff, *inLen;      // the object's copies
+    int nInputs; uint32_t flags;
+    // per input
+    int32_t *nFrames, *nBlocks;         // k_frames_scan's counts
+    int32_t *err; uint64_t *errPos;     // ... the first structural error (0: none) and its position in buf
+    uint64_t *frameFirst, *blockFirst;  // exclusive scans of the counts, nInputs + 1 entries
+    int64_t *sizes;                     // the decoded size, or the load-time code
+    uint64_t *errKey;                   // decode: the smallest (position << 4 | code) of the decode-time errors
+    // per frame, per block
+    FrmFrame *frames; FrmBlock *blocks;
+    int nFramesAll, nBlocksAll;
+    int32_t *bsumFail;                  // per block: its checksum does not match (k_frames_bsum)
+    // lists made by k_frames_layout: counts[0] compressed blocks of independent frames, counts[1] linked frames
+    uint32_t *counts; int32_t *indep; int32_t *linked;
+    // decode: the engine's call over the indep list
+    uint64_t *decOff, *decOut; int32_t *decCap, *decRes;
+    int nIndep, nLinked;
+    uint8_t *out; const uint64_t *outOff; int64_t *result;
+};
+void launch_frames_scan(const FramesArgs &a, hipStream_t s);      // counts, first structural error, the scans of the counts
+void launch_frames_load(const FramesArgs &a, hipStream_t s);      // fill, block checksums, sizes, layout
+void launch_frames_place(const FramesArgs &a, hipStream_t s);     // decode: errKey reset, the engine call's arrays from outOff
+void launch_frames_decode(const FramesArgs &a, hipStream_t s);    // decode: stored blocks, linked frames, verdicts, checksums, result
 void launch_generate(int kind, uint8_t *dst, int blockLen, int nBlocks, uint64_t firstBlock,
                      uint64_t blockStep, uint32_t litMax, uint32_t offMax, hipStream_t s);

@@ -33,6 +33,8 @@
 //   linked_tolerant.inc    k_decode_tolerant: deferred lists; k_decode_fixup_regions: their replay      linked_replay.hpp
 //   linked_ptr.inc         k_ptr_expand / _jump / _fetch<CHASE> / _finish: the pointer passes           linked_ptr.hpp
 //                          k_longest_stream, k_dict_share; launch_linked_resolve_a / _b / _fetch_block
+//   frames.inc             k_frames_scan / _fill / _bsum / _sizes / _layout: a batch of standard LZ4 frames parsed and sized;
+//                          k_frames_place / _stored / _check / _finish / _result, k_decode_frames_linked: its decode     size_walk.hpp, checksum.hpp
 //   kernel_info.inc        (no kernel) decode_kernel_info: resident workgroups per CU and static LDS of the decode_par.hpp kernels
 //
 // Everything is HBM/LDS byte work; there is deliberately no MFMA anywhere.
@@ -67,4 +69,5 @@ using namespace lz4dev;
 #include "kernels/runin.inc"
 #include "kernels/linked_tolerant.inc"
 #include "kernels/linked_ptr.inc"
+#include "kernels/frames.inc"
 #include "kernels/kernel_info.inc"

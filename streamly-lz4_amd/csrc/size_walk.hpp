@@ -183,6 +183,10 @@ __device__ __forceinline__ int sw_step(SizeWalk &w, const uint8_t *src, int iend
 }
 
 // Decoded size of the block src[0, srcLen), or SIZE_E_UNKNOWN (the rule at the top of this file).  [lo, hi) bounds every read.
+// WINDOW: the block of a standard LZ4 frame (kernels/frames.inc).  Only the last clause of rule 4 is dropped: in a linked frame a
+// long match from the window that ends near the block's end is legitimate, and a frame promises no particular code for a bad
+// offset -- the decode into exactly s bytes says whether the source exists.  Rule 2 stays.
+template <bool WINDOW = false>
 __device__ __forceinline__ int decoded_size_block(const uint8_t *src, int srcLen, int maxUncomp, const uint8_t *lo,
                                                   const uint8_t *hi, SizeLds &L)
 {
@@ -302,7 +306,7 @@ __device__ __forceinline__ int decoded_size_block(const uint8_t *src, int srcLen
     if (w.anyMatch && (s < LZ4_MFLIMIT + 1 || lastLit < LZ4_LASTLITERALS || lastLit + w.lastMl < LZ4_MFLIMIT)) return SIZE_E_UNKNOWN;
     if (w.zeroOff) return SIZE_E_UNKNOWN;
     if (s == 0 && (srcLen != 1 || as_global(src)[0] != 0)) return SIZE_E_UNKNOWN;
-    if (w.risk && w.riskEnd + SW_TAIL >= s) return SIZE_E_UNKNOWN;
+    if (!WINDOW && w.risk && w.riskEnd + SW_TAIL >= s) return SIZE_E_UNKNOWN;
     return (int)s;
 }
 

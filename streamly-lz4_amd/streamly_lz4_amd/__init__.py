@@ -247,6 +247,18 @@ def _load():
     sig("slz4_xxh32", C.c_uint32, _u8p, C.c_size_t, C.c_uint32)
     sig("slz4_lz4frame_compress", C.c_int, vp, C.c_int, C.c_int, C.c_int, _u8p, C.c_size_t, C.POINTER(vp))
     sig("slz4_lz4frame_decompress", C.c_int, vp, _u8p, C.c_size_t, C.POINTER(vp))
+    # batches of standard LZ4 frames on the device
+    sig("mi355lz4_frames_create", C.c_int, vp, C.POINTER(vp))
+    sig("mi355lz4_frames_destroy", None, vp)
+    sig("mi355lz4_frames_load", C.c_int, vp, vp, vp, C.c_uint64, vp, vp, C.c_int, C.c_uint)
+    sig("mi355lz4_frames_inputs", C.c_int, vp)
+    sig("mi355lz4_frames_blocks", C.c_int, vp)
+    sig("mi355lz4_frames_total", C.c_uint64, vp)
+    sig("mi355lz4_frames_sizes", vp, vp)
+    sig("mi355lz4_frames_get_sizes", C.c_int, vp, C.POINTER(C.c_int64))
+    sig("mi355lz4_frames_decode", C.c_int, vp, vp, vp, vp, vp)
+    sig("mi355lz4_decompress_frames", C.c_int, vp, C.POINTER(_u8p), C.POINTER(C.c_size_t), C.c_int, C.c_uint, _u8p,
+        C.c_size_t, C.POINTER(C.c_size_t), C.POINTER(C.c_int64))
     return L
 
 
@@ -286,6 +298,9 @@ DECLARED_SYMBOLS = [
     "mi355lz4_compress_pages_device", "mi355lz4_compress_pages",
     "mi355lz4_compress_pages_fast_device", "mi355lz4_compress_pages_fast",
     "mi355lz4_compress_pages_fastdict_device", "mi355lz4_compress_pages_fastdict",
+    "mi355lz4_frames_create", "mi355lz4_frames_destroy", "mi355lz4_frames_load", "mi355lz4_frames_inputs",
+    "mi355lz4_frames_blocks", "mi355lz4_frames_total", "mi355lz4_frames_sizes", "mi355lz4_frames_get_sizes",
+    "mi355lz4_frames_decode", "mi355lz4_decompress_frames",
     "LZ4_createStream", "LZ4_freeStream", "LZ4_createStreamDecode", "LZ4_freeStreamDecode", "LZ4_compressBound",
     "LZ4_compress_fast_continue", "LZ4_decompress_safe_continue",
 ]
@@ -1263,6 +1278,36 @@ class Engine:
             _check(rc, "decompress_dict_multi")
         return out[: out_len.value].tobytes(), blen[: got.value].tolist()
 
+    def decompress_frames(self, inputs, flags=0, cap=None, raise_on_error=True):
+        """Many inputs of standard LZ4 frames in host memory (each what `lz4 -d` accepts), decoded in one call
+        (mi355lz4_decompress_frames).  Returns ([decoded bytes per input; b"" for a failed one], [size or MI355LZ4_FRM_E_*
+        code per input]).  cap: the output capacity; None sizes it with one failed call, as the C ABI lets a caller do."""
+        inputs = [bytes(a) for a in inputs]
+        n = len(inputs)
+        arrs = [np.frombuffer(a, dtype=np.uint8) for a in inputs]
+        ptrs = (_u8p * max(n, 1))(*[a.ctypes.data_as(_u8p) if a.size else None for a in arrs])
+        lens = (C.c_size_t * max(n, 1))(*[a.size for a in arrs])
+        result = (C.c_int64 * max(n, 1))()
+        out_len = C.c_size_t()
+        if cap is None:
+            rc = lib.mi355lz4_decompress_frames(self.ctx, ptrs, lens, n, int(flags), None, 0, C.byref(out_len), result)
+            if rc != -4:
+                if rc != 0 and (raise_on_error or rc != -5):
+                    _check(rc, "decompress_frames")
+                return [b""] * n, [int(result[i]) for i in range(n)]
+            cap = int(out_len.value)
+        out = np.empty(max(int(cap), 1), dtype=np.uint8)
+        rc = lib.mi355lz4_decompress_frames(self.ctx, ptrs, lens, n, int(flags), out.ctypes.data_as(_u8p), int(cap),
+                                            C.byref(out_len), result)
+        if rc != 0 and (raise_on_error or rc != -5):
+            _check(rc, "decompress_frames")
+        res = [int(result[i]) for i in range(n)]
+        parts, at = [], 0
+        for r in res:
+            parts.append(out[at: at + r].tobytes() if r >= 0 else b"")
+            at += max(r, 0)
+        return parts, res
+
 
 class HcDict:
     """A prepared high-compression dictionary on the engine's device (mi355lz4_hcdict, about 216 KiB): the dictionary's last
@@ -1527,6 +1572,72 @@ class DecompressStreams:
         if self._h:
             lib.mi355lz4_dstreams_destroy(self._h)
             self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+FRAMES_SKIP_CONTENT_CHECKSUM = 1
+FRAMES_SKIP_BLOCK_CHECKSUM = 2
+FRM_E_MAGIC, FRM_E_HEADER, FRM_E_HEADER_CHECKSUM, FRM_E_TRUNCATED, FRM_E_BLOCK_SIZE, FRM_E_BLOCK_CHECKSUM, FRM_E_BLOCK, \
+    FRM_E_CONTENT_SIZE, FRM_E_CONTENT_CHECKSUM = [-0x7F000100 - k for k in range(1, 10)]
+
+
+class Frames:
+    """A parsed batch of standard LZ4 frames on the engine's device (mi355lz4_frames).  load() parses many inputs and
+    reports their exact decoded sizes (it waits for the engine's stream); decode() decodes them all and only enqueues."""
+
+    def __init__(self, engine):
+        self._h = C.c_void_p()
+        self._engine = engine
+        self._buf = None
+        _check(lib.mi355lz4_frames_create(engine.ctx, C.byref(self._h)), "frames_create")
+
+    def load(self, buf, in_off, in_len, n_inputs=None, flags=0, buf_len=None):
+        """buf: uint8 device tensor (borrowed until the decodes have run); in_off, in_len: uint64-valued int64 device
+        tensors; input i is buf[in_off[i] : in_off[i] + in_len[i]].  Returns the sizes (list of ints: size or code)."""
+        self._engine._follow_torch()
+        n = int(in_off.numel() if n_inputs is None else n_inputs)
+        blen = int(buf.numel() if buf_len is None else buf_len) if buf is not None else 0
+        _check(lib.mi355lz4_frames_load(self._engine.ctx, self._h, _dptr(buf), blen, _dptr(in_off), _dptr(in_len), n,
+                                        int(flags)), "frames_load")
+        self._buf = buf
+        return self.sizes()
+
+    def sizes(self):
+        n = int(lib.mi355lz4_frames_inputs(self._h))
+        if n < 0:
+            raise LZ4Error("frames_inputs failed: %s" % _err())
+        a = (C.c_int64 * max(n, 1))()
+        _check(lib.mi355lz4_frames_get_sizes(self._h, a), "frames_get_sizes")
+        return [int(a[i]) for i in range(n)]
+
+    def sizes_device_ptr(self):
+        return lib.mi355lz4_frames_sizes(self._h)
+
+    def total(self):
+        return int(lib.mi355lz4_frames_total(self._h))
+
+    def blocks(self):
+        n = int(lib.mi355lz4_frames_blocks(self._h))
+        if n < 0:
+            raise LZ4Error("frames_blocks failed: %s" % _err())
+        return n
+
+    def decode(self, out, out_off, result):
+        """out: uint8 device tensor; out_off: int64 device tensor (uint64 values); result: int64 device tensor.  Enqueued."""
+        self._engine._follow_torch()
+        _check(lib.mi355lz4_frames_decode(self._engine.ctx, self._h, _dptr(out), _dptr(out_off), _dptr(result)),
+               "frames_decode")
+
+    def close(self):
+        if self._h:
+            lib.mi355lz4_frames_destroy(self._h)
+            self._h = C.c_void_p()
+        self._buf = None
 
     def __del__(self):
         try:
