@@ -161,7 +161,11 @@ __global__ __launch_bounds__(LZ4_WAVE) void k_frames_sizes(FramesArgs a)
         int r = n;
         if (!(word & 0x80000000u)) {
             const int bmax = uni((int)a.frames[uni(a.blocks[b].frame)].blockMax);
-            r = decoded_size_block<true>(a.buf + payOff, n, bmax, a.buf, a.buf + a.bufLen, lds);
+            // A block of one byte is a token alone: the empty block 0x00 (size 0, size_walk.hpp rule 4), or a field that leaves the
+            // block.  It is answered here: in this instantiation the compiler folded the walk's own `s == 0` exit into "no size"
+            // whatever the byte, and every frame with such a block was refused at load.
+            if (n == 1) r = (frm_rd8(a.buf + payOff) == 0u) ? 0 : SIZE_E_UNKNOWN;
+            else r = decoded_size_block<true>(a.buf + payOff, n, bmax, a.buf, a.buf + a.bufLen, lds);
         }
         if (lane == 0) a.blocks[b].size = r;
     }

@@ -679,9 +679,11 @@ _SEAM, _SEAM_DICTS = {}, {}
 
 
 def seam_dictionary(dict_len):
-    """the seam family's dictionary of dict_len bytes (any byte value, from a seed of its own)"""
+    """the seam family's dictionary of dict_len bytes (any byte value, from a seed of its own; ONE generator for all its bytes:
+    a generator per byte made every dictionary one repeated byte, which a match read from the wrong place also yields)"""
     if dict_len not in _SEAM_DICTS:
-        _SEAM_DICTS[dict_len] = bytes(random.Random(7000 + dict_len).getrandbits(8) for _ in range(dict_len))
+        rng = random.Random(7000 + dict_len)
+        _SEAM_DICTS[dict_len] = bytes(rng.getrandbits(8) for _ in range(dict_len))
     return _SEAM_DICTS[dict_len]
 
 

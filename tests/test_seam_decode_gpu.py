@@ -14,6 +14,10 @@ runs the full sets: none was given seam_cuts_small() (which equals seam_cuts() a
 PAR_FAR_WIDE is 0, so `spos + 16 <= 0` is compiled out, and a 16-bit offset never puts spos below -65535, so
 dictLo = -min(dictLen, 65535) and -min(dictLen, 65536) accept the same matches.  The probes stay on both sides of both for
 the day PAR_FAR_WIDE is switched on.
+
+Later (with tests/test_frames_corpus_gpu.py): lz4_synth.seam_dictionary had made every dictionary of the seam family ONE
+repeated byte, which a match read from the wrong place of the dictionary yields as well.  With dictionaries of all byte values
+every test of this file gave the oracle's results again, unchanged.
 """
 import random
 
