@@ -11,16 +11,16 @@ CSRC  := $(PKG)/csrc
 LIB   := $(PKG)/lib/libmi355lz4.so
 HIPFLAGS ?= -O3 -std=c++17 -fPIC --offload-arch=$(ARCH) -Wall -Wno-unused-function -Wno-unused-value -Wno-unused-result
 
-SRCS := $(CSRC)/kernels.hip $(CSRC)/kernels_hstreams.hip $(CSRC)/api.cpp $(CSRC)/host_batch.cpp $(CSRC)/legacy.cpp $(CSRC)/host_stream.cpp $(CSRC)/lz4_frame.cpp $(CSRC)/multi_device.cpp $(CSRC)/frames.cpp
+SRCS := $(CSRC)/kernels.hip $(CSRC)/kernels_hstreams.hip $(CSRC)/kernels_cframes.hip $(CSRC)/api.cpp $(CSRC)/host_batch.cpp $(CSRC)/legacy.cpp $(CSRC)/host_stream.cpp $(CSRC)/lz4_frame.cpp $(CSRC)/multi_device.cpp $(CSRC)/frames.cpp $(CSRC)/cframes.cpp
 # kernels/*.inc are the parts of kernels.hip (its one translation unit), not sources of their own; kernels_hstreams.hip is the one
-# kernel compiled apart from it (the file says why)
+# encoder kernel compiled apart from it and kernels_cframes.hip the frame writer's kernels (the files say why)
 HDRS := $(wildcard $(CSRC)/*.hpp $(CSRC)/*.h $(CSRC)/kernels/*.inc include/*.h)
 OBJS    := $(patsubst $(CSRC)/%,build/obj/%.o,$(SRCS))
 OBJSEXP := $(patsubst $(CSRC)/%,build/obj-exp/%.o,$(SRCS))
 
 all: lib oracle
 
-# One object per source, then the link: `make -j8 lib lib-exp` compiles them side by side (a fixed count: the sources are nine,
+# One object per source, then the link: `make -j8 lib lib-exp` compiles them side by side (a fixed count: the sources are eleven,
 # and a count taken from the machine oversubscribes a shared one).
 lib: $(LIB)
 
@@ -49,8 +49,8 @@ oracle:
 	$(MAKE) -C oracle
 
 # Host-side sanitizer builds (CPU only; GPU ASan is not available on this pool): the host sources (api.cpp, host_batch.cpp,
-# legacy.cpp, host_stream.cpp, lz4_frame.cpp, multi_device.cpp, frames.cpp) compiled by g++ against the HIP host API, kernel launchers stubbed, driven by tests/native/host_san_test.cpp.
-SAN_SRCS := $(CSRC)/api.cpp $(CSRC)/host_batch.cpp $(CSRC)/legacy.cpp $(CSRC)/host_stream.cpp $(CSRC)/lz4_frame.cpp $(CSRC)/multi_device.cpp $(CSRC)/frames.cpp tests/native/san_stubs_frames.cpp tests/native/san_stubs.cpp tests/native/san_stubs_dict.cpp tests/native/san_stubs_hcdict.cpp tests/native/san_stubs_fastdict.cpp tests/native/san_stubs_dictset.cpp tests/native/san_stubs_fstreams.cpp tests/native/san_stubs_hstreams.cpp tests/native/san_stubs_pages.cpp tests/native/san_stubs_fastpages.cpp tests/native/san_stubs_dictpages.cpp tests/native/san_stubs_info.cpp tests/native/host_san_test.cpp
+# legacy.cpp, host_stream.cpp, lz4_frame.cpp, multi_device.cpp, frames.cpp, cframes.cpp) compiled by g++ against the HIP host API, kernel launchers stubbed, driven by tests/native/host_san_test.cpp.
+SAN_SRCS := $(CSRC)/api.cpp $(CSRC)/host_batch.cpp $(CSRC)/legacy.cpp $(CSRC)/host_stream.cpp $(CSRC)/lz4_frame.cpp $(CSRC)/multi_device.cpp $(CSRC)/frames.cpp $(CSRC)/cframes.cpp tests/native/san_stubs_frames.cpp tests/native/san_stubs_cframes.cpp tests/native/san_stubs.cpp tests/native/san_stubs_dict.cpp tests/native/san_stubs_hcdict.cpp tests/native/san_stubs_fastdict.cpp tests/native/san_stubs_dictset.cpp tests/native/san_stubs_fstreams.cpp tests/native/san_stubs_hstreams.cpp tests/native/san_stubs_pages.cpp tests/native/san_stubs_fastpages.cpp tests/native/san_stubs_dictpages.cpp tests/native/san_stubs_info.cpp tests/native/host_san_test.cpp
 SAN_FLAGS := -std=c++17 -O1 -g -fno-omit-frame-pointer -D__HIP_PLATFORM_AMD__ -I/opt/rocm/include -Wall -Wno-unused-function -Wno-unused-result
 SAN_LIBS := -L/opt/rocm/lib -Wl,-rpath,/opt/rocm/lib -lamdhip64 -lpthread
 
@@ -153,7 +153,16 @@ build/san/frames_args_asan: $(FRAMES_SAN_SRCS) $(HDRS)
 asan-frames: build/san/frames_args_asan
 	ASAN_OPTIONS=detect_leaks=1:abort_on_error=0 LSAN_OPTIONS=suppressions=tests/native/lsan.supp ./build/san/frames_args_asan
 
-asan: build/san/host_asan asan-fstreams asan-hstreams
+# The frame writer's argument checks, the same way (tests/native/cframes_args_main.cpp; cframes.cpp is the layer under test).
+CFRAMES_SAN_SRCS := $(CSRC)/api.cpp $(CSRC)/host_batch.cpp $(CSRC)/cframes.cpp tests/native/san_stubs.cpp tests/native/san_stubs_dict.cpp tests/native/san_stubs_hcdict.cpp tests/native/san_stubs_fastdict.cpp tests/native/san_stubs_dictset.cpp tests/native/san_stubs_fstreams.cpp tests/native/san_stubs_hstreams.cpp tests/native/san_stubs_pages.cpp tests/native/san_stubs_fastpages.cpp tests/native/san_stubs_dictpages.cpp tests/native/san_stubs_info.cpp tests/native/san_stubs_cframes.cpp tests/native/cframes_args_main.cpp
+build/san/cframes_args_asan: $(CFRAMES_SAN_SRCS) $(HDRS)
+	@mkdir -p build/san
+	g++ $(SAN_FLAGS) -fsanitize=address,undefined -fno-sanitize-recover=undefined -o $@ $(CFRAMES_SAN_SRCS) $(SAN_LIBS)
+
+asan-cframes: build/san/cframes_args_asan
+	ASAN_OPTIONS=detect_leaks=1:abort_on_error=0 LSAN_OPTIONS=suppressions=tests/native/lsan.supp ./build/san/cframes_args_asan
+
+asan: build/san/host_asan asan-fstreams asan-hstreams asan-cframes
 	ASAN_OPTIONS=detect_leaks=1:abort_on_error=0 LSAN_OPTIONS=suppressions=tests/native/lsan.supp ./build/san/host_asan
 
 tsan: build/san/host_tsan
@@ -164,4 +173,4 @@ clean:
 	rm -f $(LIB) $(LIBEXP)
 	$(MAKE) -C oracle clean
 
-.PHONY: all lib lib-exp oracle clean asan asan-frames asan-dict asan-hcdict asan-fastdict asan-pages asan-fastpages asan-dictpages asan-dictset asan-fstreams asan-hstreams tsan
+.PHONY: all lib lib-exp oracle clean asan asan-frames asan-cframes asan-dict asan-hcdict asan-fastdict asan-pages asan-fastpages asan-dictpages asan-dictset asan-fstreams asan-hstreams tsan

@@ -96,6 +96,13 @@ module Streamly.Internal.LZ4.GPU
     , loadFrames
     , decodeFrames
     , decompressFramesMany
+    , FrameWriter
+    , newFrameWriter
+    , freeFrameWriter
+    , frameBound
+    , reserveFrameWriter
+    , compressFramesDevice
+    , compressFramesMany
     , MultiEngine
     , newMultiEngine
     , freeMultiEngine
@@ -643,6 +650,80 @@ decompressFramesMany (Engine eng) inputs = do
             starts = scanl (+) 0 sizes
         return [ if r < 0 then Left r else Right (Array.Array cont (b `plusPtr` o) (b `plusPtr` (o + l)))
                | (r, o, l) <- zip3 res starts sizes ]
+
+-- Writing batches of standard LZ4 frames (include/mi355lz4.h, "writing batches of standard LZ4 frames"): a frame writer holds
+-- the block table and the slots of its calls on the device.
+data C_FrameWriter
+newtype FrameWriter = FrameWriter (Ptr C_FrameWriter)
+
+foreign import ccall unsafe "mi355lz4.h mi355lz4_cframes_bound"
+    c_cframesBound :: Word64 -> CInt -> CUInt -> IO Word64
+foreign import ccall safe "mi355lz4.h mi355lz4_cframes_create"
+    c_cframesCreate :: Ptr C_Engine -> Ptr (Ptr C_FrameWriter) -> IO CInt
+foreign import ccall safe "mi355lz4.h mi355lz4_cframes_destroy"
+    c_cframesDestroy :: Ptr C_FrameWriter -> IO ()
+foreign import ccall safe "mi355lz4.h mi355lz4_cframes_reserve"
+    c_cframesReserve :: Ptr C_Engine -> Ptr C_FrameWriter -> CInt -> Word64 -> Word64 -> CInt -> IO CInt
+foreign import ccall safe "mi355lz4.h mi355lz4_cframes_compress"
+    c_cframesCompress
+        :: Ptr C_Engine -> Ptr C_FrameWriter -> Ptr Word8 -> Word64 -> Ptr Word64 -> Ptr Word64 -> CInt -> Word64 -> Word64
+        -> CInt -> CUInt -> CInt -> Ptr Word8 -> Ptr Word64 -> Ptr Word64 -> Ptr Int64 -> IO CInt
+foreign import ccall safe "mi355lz4.h mi355lz4_compress_frames"
+    c_compressFrames
+        :: Ptr C_Engine -> Ptr (Ptr Word8) -> Ptr CSize -> CInt -> CInt -> CUInt -> CInt -> Ptr Word8 -> CSize -> Ptr CSize
+        -> Ptr Int64 -> IO CInt
+
+newFrameWriter :: Engine -> IO FrameWriter
+newFrameWriter (Engine p) = alloca $ \pp -> do
+    rc <- c_cframesCreate p pp
+    when (rc /= 0) $ error "mi355lz4_cframes_create failed"
+    FrameWriter <$> peek pp
+
+freeFrameWriter :: FrameWriter -> IO ()
+freeFrameWriter (FrameWriter p) = c_cframesDestroy p
+
+-- | The exact worst case of one frame of @len@ bytes at block size id 4..7 with the given @MI355LZ4_CFRAMES_*@ flags.
+frameBound :: Word64 -> Int -> Int -> IO Word64
+frameBound len bsid flags = c_cframesBound len (fromIntegral bsid) (fromIntegral flags)
+
+-- | Size the writer's scratch for calls of at most @n@ inputs, none longer than @maxLen@, @total@ bytes in all.
+reserveFrameWriter :: Engine -> FrameWriter -> Int -> Word64 -> Word64 -> Int -> IO ()
+reserveFrameWriter (Engine p) (FrameWriter w) n maxLen total bsid = do
+    rc <- c_cframesReserve p w (fromIntegral n) maxLen total (fromIntegral bsid)
+    when (rc /= 0) $ error "mi355lz4_cframes_reserve failed"
+
+-- | @n@ inputs in DEVICE memory (input i is @src[inOff[i], inOff[i] + inLen[i])@), one frame each at @dst + dstOff[i]@;
+-- @frameLen[i]@ is the frame's length or a negative @MI355LZ4_FRW_E_*@ code.  Only enqueues on the engine's stream.
+compressFramesDevice
+    :: Engine -> FrameWriter -> Ptr Word8 -> Word64 -> Ptr Word64 -> Ptr Word64 -> Int -> Word64 -> Word64 -> Int -> Int -> Int
+    -> Ptr Word8 -> Ptr Word64 -> Ptr Word64 -> Ptr Int64 -> IO ()
+compressFramesDevice (Engine p) (FrameWriter w) src srcLen inOff inLen n maxLen total bsid flags accel dst dstOff dstCap frameLen = do
+    rc <- c_cframesCompress p w src srcLen inOff inLen (fromIntegral n) maxLen total (fromIntegral bsid) (fromIntegral flags)
+                            (fromIntegral accel) dst dstOff dstCap frameLen
+    when (rc /= 0) $ error "mi355lz4_cframes_compress failed"
+
+-- | Many inputs, one standard LZ4 frame each, in one GPU call (block size id 4..7, @MI355LZ4_CFRAMES_*@ flags): the frames in
+-- input order.  The output is sized by the bound, which never fails.
+compressFramesMany :: Engine -> Int -> Int -> Int -> [Array.Array Word8] -> IO [Array.Array Word8]
+compressFramesMany (Engine eng) bsid flags accel inputs = do
+    let n = length inputs
+        lens = map Array.byteLength inputs
+        offs = scanl (+) 0 lens
+    bounds <- mapM (\l -> fromIntegral <$> frameBound (fromIntegral l) bsid flags) lens
+    let cap = sum bounds :: Int
+    packed <- concatArrays inputs
+    allocaArray (max n 1) $ \pIn -> allocaArray (max n 1) $ \pLen -> allocaArray (max n 1) $ \pRes -> alloca $ \pOutLen ->
+      Array.asPtrUnsafe (Array.unsafeCast packed) $ \pBytes -> do
+        pokeArray pIn [ (pBytes :: Ptr Word8) `plusPtr` o | o <- take n offs ]
+        pokeArray pLen (map fromIntegral lens)
+        (MArray.Array cont _ b _) <- MArray.newArray (max cap 1)
+        rc <- c_compressFrames eng pIn pLen (fromIntegral n) (fromIntegral bsid) (fromIntegral flags) (fromIntegral accel) b
+                               (fromIntegral cap) pOutLen pRes
+        when (rc /= 0) $ error "compressFramesMany: mi355lz4_compress_frames failed"
+        res <- peekArray n pRes
+        let sizes = map fromIntegral res :: [Int]
+            starts = scanl (+) 0 sizes
+        return [ Array.Array cont (b `plusPtr` o) (b `plusPtr` (o + l)) | (o, l) <- zip starts sizes ]
 
 newDecompressStreams :: Engine -> Int -> IO DecompressStreams
 newDecompressStreams (Engine p) n = alloca $ \pp -> do

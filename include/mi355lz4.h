@@ -147,6 +147,10 @@ typedef struct mi355lz4_ctx mi355lz4_ctx;
  *   at decode time, for an input that decodes and one that fails at decode time alike -- nothing at all for an input whose size is
  *   a code; result[] only in [0, nInputs); never buf or outOff; of the object only its decode scratch.  _decompress_frames is a
  *   host-buffer call as above (result only in [0, nInputs)).
+ * Frame writer: _cframes_compress: dst[dstOff[i], dstOff[i] + frameLen[i]) for the inputs with frameLen[i] >= 0 -- nothing behind
+ *   a frame's end inside its capacity -- nothing of dst for an input that gets a code; frameLen[] only in [0, nInputs); the
+ *   object's scratch; never src, inOff, inLen, dstOff or dstCap.  _cframes_reserve writes nothing but the object.
+ *   _compress_frames is a host-buffer call as above (frameLen only in [0, nInputs); nothing of out with MI355LZ4_E_CAPACITY).
  * Scratch that a call needs is the engine's own. */
 
 /* ---- engine lifecycle ------------------------------------------------ */
@@ -191,7 +195,9 @@ int mi355lz4_device_count(void);
  *   on one set (the stream table goes through a ring of four).
  *   The frame batches are methods of an object and carry no suffix: mi355lz4_frames_load waits on the host by design (twice:
  *   for the counts that size its tables, and for the sizes), mi355lz4_frames_decode only enqueues
- *   (tests/test_frames_stream_gpu.py holds it to the same protocol).
+ *   (tests/test_frames_stream_gpu.py holds it to the same protocol).  So do the frame writer's: mi355lz4_cframes_compress only
+ *   enqueues once the object's scratch is large enough (mi355lz4_cframes_reserve, or an earlier call of the shape;
+ *   tests/test_cframes_stream_gpu.py).
  *
  * Process environment: the library sets no environment variable; the HIP runtime's settings (GPU_MAX_HW_QUEUES
  * among them) are the process's. */
@@ -1253,6 +1259,69 @@ int mi355lz4_frames_decode(mi355lz4_ctx *ctx, const mi355lz4_frames *fr, uint8_t
                            int64_t *result);
 int mi355lz4_decompress_frames(mi355lz4_ctx *ctx, const uint8_t *const *in, const size_t *inLen, int nInputs,
                                unsigned flags, uint8_t *out, size_t cap, size_t *outLen, int64_t *result);
+
+/* ---- writing batches of standard LZ4 frames ------------------------------
+ * The write side of the frame batches: many device-resident inputs become one standard LZ4 frame each -- what the `lz4` tool,
+ * LZ4F_decompress and mi355lz4_frames_load read -- in one call that only enqueues.  A caller-owned object, the frame writer,
+ * holds the call's block table and the slots its blocks are compressed into.  The device-pointer calls carry no _device
+ * suffix: they are methods of an object, as those of mi355lz4_frames.
+ *
+ * _cframes_compress: src, inOff, inLen, dst, dstOff, dstCap, frameLen are DEVICE memory.  Input i is src[inOff[i], inOff[i] +
+ * inLen[i]), full 64-bit quantities, any alignment; it may be empty.  It becomes exactly one frame at dst + dstOff[i]:
+ * frameLen[i] = the frame's length, or MI355LZ4_FRW_E_CAPACITY (the frame does not fit dstCap[i]) or MI355LZ4_FRW_E_INPUT (the
+ * input leaves [0, srcBufLen), is longer than maxInputLen, or its blocks end behind the call's block bound), and then nothing
+ * is written for the input; the other inputs are unaffected, except that the blocks are counted in input order, so every
+ * input with blocks behind one that passes the block bound gets _INPUT too.
+ * The frame: magic; FLG (version 01, B.Indep unless MI355LZ4_CFRAMES_LINKED, the three option bits); BD (blockSizeId 4..7: 64 KiB,
+ * 256 KiB, 1 MiB, 4 MiB); the 8-byte content size when asked for; the header checksum byte; ceil(len / block size) blocks, of
+ * which only the last may be short (an empty input has none); the end mark; the content checksum when asked for.  A block
+ * whose compressed size c >= its n bytes is stored (word n | 0x80000000, the input's bytes: lz4FrameCompress's rule); a block
+ * checksum covers the payload as stored.
+ * The bytes of a compressed block are exactly what one mi355lz4_compress_batch_device call (headerKind 4, maxBlockLen =
+ * min(block size, maxInputLen), the engine at its current compression level 0..12, mi355lz4_set_linked_compress = the LINKED
+ * flag, the same accel) over the blocks of input i
+ * alone, where they lie in src, writes as block k's data -- at level 0 whenever the segment path makes the same choice in both
+ * calls (mi355lz4_set_segments(0) fixes that), always at levels 1..12 and with LINKED.  Reference-exact mode and
+ * mi355lz4_set_block_checksum do not apply (a frame is its own stream and its block checksums are its own); the engine's linked
+ * switch is left as it was.  A linked frame's first block never sees the input in front of it, even where the two lie back
+ * to back in src.
+ * Host-side bounds: the call cannot read inLen, so the caller states maxInputLen >= every inLen[i] (it gives the largest block,
+ * min(block size, maxInputLen), and so the slots' stride) and totalLen >= their sum (the block table holds totalLen / block
+ * size + nInputs blocks).  _cframes_reserve sizes the object's scratch for such a shape ahead of time (for LINKED, the larger
+ * one); a _compress that finds it too small waits for the engine's stream and grows it.  A warm call only enqueues on the
+ * engine's stream (tests/test_cframes_stream_gpu.py).  The scratch is the tables (some 40 bytes per table entry) and one slot of
+ * mi355lz4_slot_stride(largest block, 4) bytes per table entry -- with LINKED the table has one more entry per input, which
+ * keeps inputs apart.  Two calls on ONE object go on the same stream, or the caller orders them.
+ * mi355lz4_cframes_bound (host only): the exact worst case, (7 or 15) + blocks * (4 + 4 with block checksums) + len + 4 + 4 with a
+ * content checksum; a dstCap[i] of it never gives _CAPACITY.  0 for a blockSizeId outside 4..7 or unknown flag bits.
+ * The content checksum of an input is computed by four lanes (xxh32 is four serial chains): one huge input with
+ * MI355LZ4_CFRAMES_CONTENT_CHECKSUM is hashed at well under 1 GB/s, as on the decode side.
+ * MI355LZ4_E_ARG: a null ctx or object, an object created on another device's engine, nInputs < 0, a null array with nInputs >
+ * 0, blockSizeId outside 4..7, unknown flag bits, totalLen / block size + nInputs (+ nInputs with LINKED) at or above INT_MAX.
+ * nInputs == 0 is MI355LZ4_OK.
+ * mi355lz4_compress_frames: host buffers, synchronous.  The inputs go to the device in groups under a device-memory budget
+ * (MI355LZ4_CFRAMES_BUDGET_MB, default 1024; one input is never split), each group is compressed into a bound-spaced layout, a
+ * gather kernel packs its frames densely and one copy brings them back: frame i lies in `out` at the sum of frameLen[0, i),
+ * *outLen = their sum.  When they do not fit cap: MI355LZ4_E_CAPACITY with *outLen = that sum, frameLen[] filled and nothing
+ * written to out, so one failed call sizes the buffer. */
+typedef struct mi355lz4_cframes mi355lz4_cframes;
+#define MI355LZ4_CFRAMES_LINKED            1u   /* block-dependent frames (what `lz4` writes by default) */
+#define MI355LZ4_CFRAMES_BLOCK_CHECKSUM    2u
+#define MI355LZ4_CFRAMES_CONTENT_SIZE      4u
+#define MI355LZ4_CFRAMES_CONTENT_CHECKSUM  8u
+#define MI355LZ4_FRW_E_CAPACITY (-0x7F000201)   /* the frame does not fit dstCap[i]; nothing written for the input */
+#define MI355LZ4_FRW_E_INPUT    (-0x7F000202)   /* the input leaves [0, srcBufLen), exceeds maxInputLen, or its blocks do not fit the call's block bound */
+uint64_t mi355lz4_cframes_bound(uint64_t len, int blockSizeId, unsigned flags);
+int mi355lz4_cframes_create(mi355lz4_ctx *ctx, mi355lz4_cframes **out);
+void mi355lz4_cframes_destroy(mi355lz4_cframes *w);
+int mi355lz4_cframes_reserve(mi355lz4_ctx *ctx, mi355lz4_cframes *w, int nInputs, uint64_t maxInputLen, uint64_t totalLen,
+                             int blockSizeId);
+int mi355lz4_cframes_compress(mi355lz4_ctx *ctx, mi355lz4_cframes *w, const uint8_t *src, uint64_t srcBufLen,
+                              const uint64_t *inOff, const uint64_t *inLen, int nInputs, uint64_t maxInputLen, uint64_t totalLen,
+                              int blockSizeId, unsigned flags, int accel, uint8_t *dst, const uint64_t *dstOff,
+                              const uint64_t *dstCap, int64_t *frameLen);
+int mi355lz4_compress_frames(mi355lz4_ctx *ctx, const uint8_t *const *in, const size_t *inLen, int nInputs, int blockSizeId,
+                             unsigned flags, int accel, uint8_t *out, size_t cap, size_t *outLen, int64_t *frameLen);
 
 /* ---- timing support: HIP events on the engine's own stream ------------- */
 int mi355lz4_event_create(void **ev);

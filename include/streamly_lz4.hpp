@@ -29,6 +29,7 @@ struct mi355lz4_dictset;
 struct mi355lz4_dstreams;
 struct mi355lz4_fstreams;
 struct mi355lz4_frames;
+struct mi355lz4_cframes;
 
 namespace streamly_lz4 {
 
@@ -166,6 +167,10 @@ public:
     // lz4FrameDecompress below, parsed, sized and decoded on the device.  When some input fails, throws Error; with `result`
     // given it does not: result[i] is then input i's size or its MI355LZ4_FRM_E_* code, and a failed input's array is empty.
     std::vector<Array> decompressFrames(const std::vector<Array> &inputs, unsigned flags = 0, std::vector<int64_t> *result = nullptr);
+    // Many inputs, one standard LZ4 frame each, in one call (mi355lz4_compress_frames): the batched counterpart of
+    // lz4FrameCompress below, cut into blocks, compressed and laid out on the device.  blockSizeId 4..7 (64 KiB .. 4 MiB), flags
+    // MI355LZ4_CFRAMES_*; the engine's compression level applies.  Throws Error.
+    std::vector<Array> compressFrames(const std::vector<Array> &inputs, int blockSizeId = 4, unsigned flags = 0, int accel = 1);
 private:
     mi355lz4_ctx *ctx_ = nullptr;
     size_t batch_;
@@ -194,6 +199,27 @@ public:
 private:
     Engine &eng_;
     mi355lz4_frames *fr_ = nullptr;
+};
+
+// A frame writer on the engine's device (mi355lz4_cframes), for callers whose data is device-resident: compress() turns many
+// inputs into one standard LZ4 frame each and only enqueues once the scratch is there (reserve(), or an earlier call of the
+// shape).  All pointers are DEVICE memory; frameLen[i] is frame i's length or an MI355LZ4_FRW_E_* code.
+class FrameWriter {
+public:
+    explicit FrameWriter(Engine &eng);                  // throws Error
+    ~FrameWriter();
+    FrameWriter(const FrameWriter &) = delete;
+    FrameWriter &operator=(const FrameWriter &) = delete;
+    mi355lz4_cframes *handle() const { return w_; }
+    static uint64_t bound(uint64_t len, int blockSizeId, unsigned flags);     // the exact worst case of one frame
+    void reserve(int nInputs, uint64_t maxInputLen, uint64_t totalLen, int blockSizeId);
+    // input i is src[inOff[i], inOff[i] + inLen[i]) and becomes one frame at dst + dstOff[i], dstCap[i] bytes at the most
+    void compress(const uint8_t *src, uint64_t srcBufLen, const uint64_t *inOff, const uint64_t *inLen, int nInputs, uint64_t maxInputLen,
+                  uint64_t totalLen, int blockSizeId, unsigned flags, int accel, uint8_t *dst, const uint64_t *dstOff,
+                  const uint64_t *dstCap, int64_t *frameLen);
+private:
+    Engine &eng_;
+    mi355lz4_cframes *w_ = nullptr;
 };
 
 // A set of nSlots device-resident reference-exact compress streams (mi355lz4_cstreams: about 80 KiB a slot), one per

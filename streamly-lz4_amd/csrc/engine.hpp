@@ -160,6 +160,15 @@ struct mi355lz4_frames {
     int64_t *sizesHost() const { return (int64_t *)((uint8_t *)pin.p + 64); }
 };
 
+// A frame writer (cframes.cpp, kernels_cframes.hip): the scratch of its calls on the device -- a fixed number of
+// bytes per input and per entry of the block table, and the slots the engine's internal call compresses into.  Grown on demand
+// (mi355lz4_cframes_reserve ahead of time); nothing of a call is kept in it.
+struct mi355lz4_cframes {
+    using DevBuf = mi355lz4_detail::DevBuf;
+    int device = 0;
+    DevBuf perInput, perEntry, slots;
+};
+
 namespace mi355lz4_detail {
 
 // pageable host memory <-> device through pinned staging, on the engine's stream (api.cpp)

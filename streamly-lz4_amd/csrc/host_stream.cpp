@@ -503,6 +503,52 @@ void Frames::decode(uint8_t *out, const uint64_t *outOff, int64_t *result)
         throw Error(std::string("Frames::decode: ") + mi355lz4_last_error());
 }
 
+FrameWriter::FrameWriter(Engine &eng) : eng_(eng)
+{
+    if (mi355lz4_cframes_create(eng.ctx(), &w_) != MI355LZ4_OK) throw Error(std::string("streamly_lz4::FrameWriter: ") + mi355lz4_last_error());
+}
+FrameWriter::~FrameWriter() { mi355lz4_cframes_destroy(w_); }
+uint64_t FrameWriter::bound(uint64_t len, int blockSizeId, unsigned flags) { return mi355lz4_cframes_bound(len, blockSizeId, flags); }
+void FrameWriter::reserve(int nInputs, uint64_t maxInputLen, uint64_t totalLen, int blockSizeId)
+{
+    if (mi355lz4_cframes_reserve(eng_.ctx(), w_, nInputs, maxInputLen, totalLen, blockSizeId) != MI355LZ4_OK)
+        throw Error(std::string("FrameWriter::reserve: ") + mi355lz4_last_error());
+}
+void FrameWriter::compress(const uint8_t *src, uint64_t srcBufLen, const uint64_t *inOff, const uint64_t *inLen, int nInputs,
+                           uint64_t maxInputLen, uint64_t totalLen, int blockSizeId, unsigned flags, int accel, uint8_t *dst,
+                           const uint64_t *dstOff, const uint64_t *dstCap, int64_t *frameLen)
+{
+    if (mi355lz4_cframes_compress(eng_.ctx(), w_, src, srcBufLen, inOff, inLen, nInputs, maxInputLen, totalLen, blockSizeId, flags, accel,
+                                  dst, dstOff, dstCap, frameLen) != MI355LZ4_OK)
+        throw Error(std::string("FrameWriter::compress: ") + mi355lz4_last_error());
+}
+
+std::vector<Array> Engine::compressFrames(const std::vector<Array> &inputs, int blockSizeId, unsigned flags, int accel)
+{
+    const int n = (int)inputs.size();
+    std::vector<const uint8_t *> ptrs;
+    std::vector<size_t> lens;
+    size_t cap = 0;
+    for (const Array &a : inputs) {
+        ptrs.push_back(a.data()); lens.push_back(a.size());
+        cap += (size_t)mi355lz4_cframes_bound(a.size(), blockSizeId, flags);
+    }
+    ptrs.push_back(nullptr);
+    lens.push_back(0);
+    std::vector<int64_t> flen((size_t)n + 1);
+    Array out(cap + 1);
+    size_t outLen = 0;
+    if (mi355lz4_compress_frames(ctx_, ptrs.data(), lens.data(), n, blockSizeId, flags, accel, out.data(), cap, &outLen, flen.data()) != MI355LZ4_OK)
+        throw Error(std::string("compressFrames: ") + mi355lz4_last_error());
+    std::vector<Array> res;
+    size_t pos = 0;
+    for (int k = 0; k < n; k++) {
+        res.emplace_back(out.begin() + (long)pos, out.begin() + (long)(pos + (size_t)flen[(size_t)k]));
+        pos += (size_t)flen[(size_t)k];
+    }
+    return res;
+}
+
 std::vector<Array> Engine::decompressFrames(const std::vector<Array> &inputs, unsigned flags, std::vector<int64_t> *result)
 {
     const int n = (int)inputs.size();

@@ -512,5 +512,45 @@ void launch_frames_scan(const FramesArgs &a, hipStream_t s);      // counts, fir
 void launch_frames_load(const FramesArgs &a, hipStream_t s);      // fill, block checksums, sizes, layout
 void launch_frames_place(const FramesArgs &a, hipStream_t s);     // decode: errKey reset, the engine call's arrays from outOff
 void launch_frames_decode(const FramesArgs &a, hipStream_t s);    // decode: stored blocks, linked frames, verdicts, checksums, result
+// writing batches of standard LZ4 frames (mi355lz4_cframes; kernels_cframes.hip).  Input i is src[inOff[i], inOff[i] +
+// inLen[i]) and becomes one frame at dst + dstOff[i].  The block table of a call has tabCap entries: realCap real blocks at the
+// most, and with CFRM_LINKED one zero-length spacer behind every input's blocks -- block k of input i is entry blockFirst[i] + k
+// (+ i with spacers).  An entry past the real ones, a spacer and an entry of a refused input have length 0 and blockInput -1.
+#define FRW_E_CAPACITY (-0x7F000201)           // = MI355LZ4_FRW_E_* (include/mi355lz4.h)
+#define FRW_E_INPUT    (-0x7F000202)
+#define CFRM_LINKED            1u              // = MI355LZ4_CFRAMES_*
+#define CFRM_BLOCK_CHECKSUM    2u
+#define CFRM_CONTENT_SIZE      4u
+#define CFRM_CONTENT_CHECKSUM  8u
+#define CFRM_PIECE 16384u                      // k_cframes_pack: bytes of a block's payload one wave copies
+struct CFramesArgs {
+    const uint8_t *src; uint64_t srcBufLen;
+    const uint64_t *inOff, *inLen;
+    int nInputs;
+    uint64_t maxInputLen;
+    uint32_t bmax;                             // the frames' block maximum, 1 << (8 + 2 * bsid)
+    int bsid;
+    uint32_t flags;                            // CFRM_*
+    int realCap, tabCap;
+    int maxBlockLen;                           // min(bmax, maxInputLen): what the engine's call is told
+    uint8_t *dst; const uint64_t *dstOff, *dstCap; int64_t *frameLen;
+    // per input
+    int32_t *nb;                               // blocks of the input, -1: refused by its range or its length (k_cframes_count)
+    uint64_t *blockFirst;                      // exclusive scan of nb, nInputs + 1 entries
+    int64_t *verdict;                          // what frameLen[i] gets (k_cframes_layout)
+    uint64_t *base;                            // dstOff[i] + header bytes - pieceOff[the input's first entry]
+    // per entry of the table: the engine call's arrays, and what the frame layer makes of its results
+    uint64_t *srcOff; int32_t *srcLen; int32_t *blockInput; int32_t *framedLen;
+    int32_t *piece;                            // 4 + payload + 4 with block checksums; 0 for an entry that is no block
+    uint64_t *pieceOff;                        // exclusive scan of piece, tabCap + 1 entries
+    uint8_t *slots; size_t slotStride;
+};
+void launch_scan_u64(const int32_t *sizes, int n, uint64_t *offs, hipStream_t s);   // k_scan_u64 (kernels/compact.inc), n + 1 offsets
+void launch_cframes_plan(const CFramesArgs &a, hipStream_t s);    // k_cframes_count, the scan, k_cframes_plan
+void launch_cframes_finish(const CFramesArgs &a, hipStream_t s);  // behind the engine's call: sizes, the scan, layout, pack, head
+// dense[run, run + frameLen[i]) = dst[dstOff[i], ..) for the inputs with frameLen[i] >= 0, run = the scan of those lengths (host
+// form: scanOff is scratch of nInputs + 1 entries; scanOff[nInputs] = the total); nothing is copied when the total is above denseCap
+void launch_cframes_gather(const uint8_t *dst, const uint64_t *dstOff, const int64_t *frameLen, int nInputs, uint64_t *scanOff,
+                           uint8_t *dense, uint64_t denseCap, hipStream_t s);
 void launch_generate(int kind, uint8_t *dst, int blockLen, int nBlocks, uint64_t firstBlock,
                      uint64_t blockStep, uint32_t litMax, uint32_t offMax, hipStream_t s);

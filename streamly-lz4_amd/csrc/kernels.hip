@@ -35,6 +35,7 @@
 //                          k_longest_stream, k_dict_share; launch_linked_resolve_a / _b / _fetch_block
 //   frames.inc             k_frames_scan / _fill / _bsum / _sizes / _layout: a batch of standard LZ4 frames parsed and sized;
 //                          k_frames_place / _stored / _check / _finish / _result, k_decode_frames_linked: its decode     size_walk.hpp, checksum.hpp
+//                          (the write side of the frame batches, k_cframes_*, is a unit of its own: kernels_cframes.hip)
 //   kernel_info.inc        (no kernel) decode_kernel_info: resident workgroups per CU and static LDS of the decode_par.hpp kernels
 //
 // Everything is HBM/LDS byte work; there is deliberately no MFMA anywhere.

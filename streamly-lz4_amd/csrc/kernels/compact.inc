@@ -27,6 +27,12 @@ __global__ __launch_bounds__(1024) void k_scan_u64(const int32_t *sizes, int n, 
     if (t == 1023) offs[n] = part[1023];
 }
 
+// (for the translation units that hold no copy of the kernel: kernels_cframes.hip)
+void launch_scan_u64(const int32_t *sizes, int n, uint64_t *offs, hipStream_t s)
+{
+    hipLaunchKernelGGL(k_scan_u64, dim3(1), dim3(1024), 0, s, sizes, n, offs);
+}
+
 // Copy n bytes with a 256-thread workgroup; dst gets 16-byte aligned stores in
 // the body, src is read with (possibly unaligned) 16-byte loads.
 __device__ __forceinline__ void wg_copy_bytes(uint8_t *dst, const uint8_t *src, uint64_t n)

@@ -259,6 +259,15 @@ def _load():
     sig("mi355lz4_frames_decode", C.c_int, vp, vp, vp, vp, vp)
     sig("mi355lz4_decompress_frames", C.c_int, vp, C.POINTER(_u8p), C.POINTER(C.c_size_t), C.c_int, C.c_uint, _u8p,
         C.c_size_t, C.POINTER(C.c_size_t), C.POINTER(C.c_int64))
+    # writing batches of standard LZ4 frames on the device
+    sig("mi355lz4_cframes_bound", C.c_uint64, C.c_uint64, C.c_int, C.c_uint)
+    sig("mi355lz4_cframes_create", C.c_int, vp, C.POINTER(vp))
+    sig("mi355lz4_cframes_destroy", None, vp)
+    sig("mi355lz4_cframes_reserve", C.c_int, vp, vp, C.c_int, C.c_uint64, C.c_uint64, C.c_int)
+    sig("mi355lz4_cframes_compress", C.c_int, vp, vp, vp, C.c_uint64, vp, vp, C.c_int, C.c_uint64, C.c_uint64, C.c_int, C.c_uint,
+        C.c_int, vp, vp, vp, vp)
+    sig("mi355lz4_compress_frames", C.c_int, vp, C.POINTER(_u8p), C.POINTER(C.c_size_t), C.c_int, C.c_int, C.c_uint, C.c_int, _u8p,
+        C.c_size_t, C.POINTER(C.c_size_t), C.POINTER(C.c_int64))
     return L
 
 
@@ -301,6 +310,8 @@ DECLARED_SYMBOLS = [
     "mi355lz4_frames_create", "mi355lz4_frames_destroy", "mi355lz4_frames_load", "mi355lz4_frames_inputs",
     "mi355lz4_frames_blocks", "mi355lz4_frames_total", "mi355lz4_frames_sizes", "mi355lz4_frames_get_sizes",
     "mi355lz4_frames_decode", "mi355lz4_decompress_frames",
+    "mi355lz4_cframes_bound", "mi355lz4_cframes_create", "mi355lz4_cframes_destroy", "mi355lz4_cframes_reserve",
+    "mi355lz4_cframes_compress", "mi355lz4_compress_frames",
     "LZ4_createStream", "LZ4_freeStream", "LZ4_createStreamDecode", "LZ4_freeStreamDecode", "LZ4_compressBound",
     "LZ4_compress_fast_continue", "LZ4_decompress_safe_continue",
 ]
@@ -1278,6 +1289,29 @@ class Engine:
             _check(rc, "decompress_dict_multi")
         return out[: out_len.value].tobytes(), blen[: got.value].tolist()
 
+    def compress_frames(self, inputs, block_size_id=4, flags=0, accel=1, cap=None):
+        """Many inputs in host memory, one standard LZ4 frame each, in one call (mi355lz4_compress_frames).  flags:
+        CFRAMES_LINKED | CFRAMES_BLOCK_CHECKSUM | CFRAMES_CONTENT_SIZE | CFRAMES_CONTENT_CHECKSUM.  Returns ([frame bytes per
+        input], [frame length per input]).  cap: the output capacity; None takes the sum of cframes_bound, which never fails."""
+        inputs = [bytes(a) for a in inputs]
+        n = len(inputs)
+        arrs = [np.frombuffer(a, dtype=np.uint8) for a in inputs]
+        ptrs = (_u8p * max(n, 1))(*[a.ctypes.data_as(_u8p) if a.size else None for a in arrs])
+        lens = (C.c_size_t * max(n, 1))(*[a.size for a in arrs])
+        flen = (C.c_int64 * max(n, 1))()
+        out_len = C.c_size_t()
+        if cap is None:
+            cap = sum(cframes_bound(a.size, block_size_id, flags) for a in arrs)
+        out = np.empty(max(int(cap), 1), dtype=np.uint8)
+        _check(lib.mi355lz4_compress_frames(self.ctx, ptrs, lens, n, int(block_size_id), int(flags), int(accel),
+                                            out.ctypes.data_as(_u8p), int(cap), C.byref(out_len), flen), "compress_frames")
+        res = [int(flen[i]) for i in range(n)]
+        parts, at = [], 0
+        for r in res:
+            parts.append(out[at: at + r].tobytes())
+            at += r
+        return parts, res
+
     def decompress_frames(self, inputs, flags=0, cap=None, raise_on_error=True):
         """Many inputs of standard LZ4 frames in host memory (each what `lz4 -d` accepts), decoded in one call
         (mi355lz4_decompress_frames).  Returns ([decoded bytes per input; b"" for a failed one], [size or MI355LZ4_FRM_E_*
@@ -1638,6 +1672,53 @@ class Frames:
             lib.mi355lz4_frames_destroy(self._h)
             self._h = C.c_void_p()
         self._buf = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+CFRAMES_LINKED, CFRAMES_BLOCK_CHECKSUM, CFRAMES_CONTENT_SIZE, CFRAMES_CONTENT_CHECKSUM = 1, 2, 4, 8
+FRW_E_CAPACITY, FRW_E_INPUT = -0x7F000201, -0x7F000202
+
+
+def cframes_bound(n, block_size_id=4, flags=0):
+    """The exact worst case of one frame of n input bytes (mi355lz4_cframes_bound); 0 for a bad block size id or flag."""
+    return int(lib.mi355lz4_cframes_bound(int(n), int(block_size_id), int(flags)))
+
+
+class FrameWriter:
+    """A frame writer on the engine's device (mi355lz4_cframes): the block table and the slots of its calls.  compress() turns
+    many device-resident inputs into one standard LZ4 frame each and only enqueues once the scratch is there (reserve())."""
+
+    def __init__(self, engine):
+        self._h = C.c_void_p()
+        self._engine = engine
+        _check(lib.mi355lz4_cframes_create(engine.ctx, C.byref(self._h)), "cframes_create")
+
+    def reserve(self, n_inputs, max_input_len, total_len, block_size_id=4):
+        """Size the scratch for calls of at most this shape (either linked setting) ahead of time."""
+        _check(lib.mi355lz4_cframes_reserve(self._engine.ctx, self._h, int(n_inputs), int(max_input_len), int(total_len),
+                                            int(block_size_id)), "cframes_reserve")
+
+    def compress(self, src, in_off, in_len, max_input_len, total_len, dst, dst_off, dst_cap, frame_len, block_size_id=4, flags=0,
+                 accel=1, n_inputs=None, src_len=None):
+        """src, dst: uint8 device tensors; in_off, in_len, dst_off, dst_cap: uint64-valued int64 device tensors; frame_len:
+        int64 device tensor (a length or FRW_E_* per input).  max_input_len, total_len: host-side bounds of in_len and of
+        its sum.  Enqueued on the engine's stream."""
+        self._engine._follow_torch()
+        n = int(in_off.numel() if n_inputs is None else n_inputs)
+        slen = int(src.numel() if src_len is None else src_len) if src is not None else 0
+        _check(lib.mi355lz4_cframes_compress(self._engine.ctx, self._h, _dptr(src), slen, _dptr(in_off), _dptr(in_len), n,
+                                             int(max_input_len), int(total_len), int(block_size_id), int(flags), int(accel),
+                                             _dptr(dst), _dptr(dst_off), _dptr(dst_cap), _dptr(frame_len)), "cframes_compress")
+
+    def close(self):
+        if self._h:
+            lib.mi355lz4_cframes_destroy(self._h)
+            self._h = C.c_void_p()
 
     def __del__(self):
         try:
